@@ -30,6 +30,9 @@ full size, c2 / c4 at B = 4, c3 / c5 at B = 2 (scaled linearly in B, labelled), 
 With several ranks the line carries `collectives`: bytes of each gradient bucket, its stand-alone all-reduce time, the step
 time without any collective, and the fraction of the collective time that backward hid (`overlap_frac`).
 `--self-check N` appends N more timed steps and reports whether the K-step mean holds over them.
+`--dump-outputs DIR` writes what the last timed step computed (rank 0) as DIR/<name>.npy, float32: `loss` (what
+train_step returned), `params` (the flat parameter buffer after that step's update) and `grads` (the flat gradient the
+update consumed).  The inputs and initial weights are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -81,7 +84,11 @@ def parse_args():
                     help="bf16: the separately named PERFORMANCE VARIANT of the PointNet encoder (csrc/pointnet_bf16.hip: "
                          "bf16 activations and matrix-core GEMMs, fp32 statistics; transformer, pose head, losses and "
                          "optimiser stay fp32) - a second line beside the fp32 parity run, never the default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's loss, parameters and gradient as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     args.config = CONFIG_ALIASES.get(args.config, args.config)
     return args
 
@@ -459,6 +466,24 @@ def chamfer_standalone(dev, reps=20):
             "cases": rows}
 
 
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all files together
+
+
+def dump_outputs(out_dir, tensors, budget=DUMP_BUDGET_BYTES):
+    """Write each tensor as out_dir/<name>.npy, float32, flattened to 1-d.  One larger than its equal share of `budget` is
+    replaced by a fixed sample of its elements (indices drawn from a generator seeded with 0, sorted): every run and every
+    build of the same workload dumps the same elements."""
+    import numpy as np
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    share = budget // len(tensors)
+    for name, t in tensors.items():
+        a = t.detach().float().reshape(-1).cpu().numpy()
+        if a.nbytes > share:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))]
+        np.save(out / f"{name}.npy", a)
+
+
 def main():
     global N_BATCHES
     args = parse_args()
@@ -548,6 +573,8 @@ def main():
     gc.enable()
     _lib.KernelTimer.active = None
     final_loss = float(loss)
+    if args.dump_outputs and rank == 0:  # now: the self-check and the per-phase pass below step the model further
+        dump_outputs(args.dump_outputs, {"loss": loss, "params": trainer.flat.flat_param, "grads": trainer.flat.flat_grad})
     self_check = None
     if args.self_check > 0:  # does the K-step mean hold over a longer run?  (same fences, same batch)
         gc.collect()

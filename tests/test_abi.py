@@ -139,3 +139,28 @@ def test_bench_batches_have_representative_part_counts():
             assert parts == bench.representative_parts(preset, seed)  # a function of (preset, seed) only
     lo, hi = 2, 20
     assert all(lo <= p <= hi for p in bench.representative_parts("everyday", 7))
+
+
+def test_bench_dump_outputs_keeps_its_budget_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: one float32 .npy per output; a tensor over its share of the budget is cut to the same
+    seeded sample of its elements in every run, and one within it is written whole."""
+    import importlib.util
+    import pathlib
+
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench", pathlib.Path(__file__).resolve().parents[1] / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    big = torch.arange(10000, dtype=torch.float32)
+    outs = {"loss": torch.tensor(1.5, dtype=torch.float64), "big": big, "small": torch.ones(3, 4)}
+    for run in ("a", "b"):
+        bench.dump_outputs(tmp_path / run, outs, budget=3 * 4096)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["big.npy", "loss.npy", "small.npy"]
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) <= 3 * 4096 + 3 * 128  # (+ the .npy headers)
+    a, b = (np.load(tmp_path / r / "big.npy") for r in ("a", "b"))
+    assert a.dtype == np.float32 and a.size == 1024 and np.array_equal(a, b)
+    assert (np.diff(a) > 0).all() and np.isin(a, big.numpy()).all()  # sorted, distinct elements of the tensor
+    assert np.array_equal(np.load(tmp_path / "a" / "loss.npy"), np.float32([1.5]))
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), np.ones(12, np.float32))

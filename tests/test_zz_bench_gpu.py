@@ -158,6 +158,29 @@ def test_self_check_leg_reports_the_ratio(cuda_device, capsys):
         print(f"\n  BENCH c2 self-check: {d['ms_per_step']:.3f} ms/step timed; {sc}", end="")
 
 
+def test_dump_outputs_of_the_last_timed_step(cuda_device, tmp_path):
+    """`--dump-outputs DIR`: the last timed step's loss, parameters and gradient as float32 .npy files within 64 MB, the loss
+    the one the line reports, and two runs with the same arguments dump the same outputs (same seeded inputs and weights;
+    compared by relative norm: the kernels' float atomics leave the order of some sums open)."""
+    import numpy as np
+    flags = ("--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-chamfer-standalone", "--dump-outputs")
+    runs = []
+    for r in ("a", "b"):
+        d = _run(*flags, str(tmp_path / r))
+        assert d["steps"] == 2 and d["ms_per_step"] > 0
+        files = sorted(p.name for p in (tmp_path / r).iterdir())
+        assert files == ["grads.npy", "loss.npy", "params.npy"], files
+        assert sum((tmp_path / r / f).stat().st_size for f in files) <= 64 << 20
+        z = {f[:-4]: np.load(tmp_path / r / f) for f in files}
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in z.values())
+        assert z["loss"].shape == (1,) and float(z["loss"][0]) == d["final_loss"]
+        assert z["params"].shape == z["grads"].shape and z["params"].size > 10 ** 6 and np.abs(z["grads"]).max() > 0
+        runs.append(z)
+    for k in ("loss", "params", "grads"):
+        a, b = runs[0][k].astype(np.float64), runs[1][k].astype(np.float64)
+        assert np.linalg.norm(a - b) <= 1e-5 * np.linalg.norm(a), k
+
+
 def test_kernel_timer_scope(cuda_device):
     from multi_part_assembly_amd import _lib
 
