@@ -5,7 +5,8 @@
 // element — the size of ONE fp32 rounding of the product — so the result differs from an fp32 GEMM by no more than a
 // different summation order does (tests hold the encoder to 1e-4 / 2e-4 of float64 as before).  Six bf16 MFMAs of K = 16
 // take 6 x 32 = 192 cycles per SIMD where the eight v_mfma_f32_32x32x2_f32 of the same 16 k-values take 512.
-// Same tiles, grids and calling conventions as dg_gemm.h.
+// R = (valid parts) x N point rows is only known on the device, so every kernel takes `hdr` (hdr[1] = R; or NULL and
+// the row count by value) and is launched for the worst case: tiles past R exit at once.
 //
 //   gemm_nt_split :  C[r, n] (+)= sum_k A[r, k] * W[n, k]
 //   gemm_tn_split :  P[chunk][n, k] = sum_{r in chunk} Y[r, n] * X[r, k]
@@ -14,10 +15,10 @@
 // bytes + 16 of padding (208 = 13 x 16: the 16-byte fragment reads of 16 consecutive rows fall on 16 different bank
 // quads).  The split is computed while the operands are staged (13 VALU operations per pair of elements).
 //
-// Block = kGsT threads.  tools/probes/gemm_split.hip takes the kernels apart at the encoder's shapes: the three phases of
-// a K step — global loads, split + LDS stores, MFMAs — cost about 100 + 145 + 200 us of a 470 us weight gradient and
-// add up rather than overlap, with four waves per block (two blocks per CU) or eight (DG_GS_WAVES: 64 x 32 wave tiles,
-// four waves per SIMD), with one K step of loads in flight or two: the time is the same within 3 %.  The loads of the
+// Block = kGsT threads.  Taken apart at the encoder's shapes (LABBOOK r1-4 §4), the three phases of a K step — global loads,
+// split + LDS stores, MFMAs — cost about 100 + 145 + 200 us of a 470 us weight gradient and add up rather than overlap,
+// with four waves per block (two blocks per CU) or eight (DG_GS_WAVES: 64 x 32 wave tiles, four waves per SIMD), with
+// one K step of loads in flight or two: the time is the same within 3 %.  The loads of the
 // big shapes move 1.4 GB at ~4.6 TB/s when they run alone; the MFMAs alone run at 240 TFLOP/s fp32-equivalent (the
 // bf16 pipe's sustained 1.85 PFLOP/s over six products).  Four waves are the default.
 #pragma once
@@ -31,38 +32,20 @@ namespace dg {
 typedef __bf16 gs_bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 gs_bf16x4 __attribute__((ext_vector_type(4)));
 
-#ifndef DG_GS_WAVES  // A/B knob: waves per block (4: the 2 x 2 arrangement of dg_gemm.h; 8: 2 x 4 / 4 x 2)
+#ifndef DG_GS_WAVES  // A/B knob: waves per block (4: 2 x 2; 8: 2 x 4 / 4 x 2)
 #define DG_GS_WAVES 4
-#endif
-#ifndef DG_GS_ROWPERM  // 1: staging threads take panel rows four apart (conflict-free stores); 0: consecutive rows (rounds 3-5a)
-#define DG_GS_ROWPERM 1
 #endif
 constexpr int kGsT = 64 * DG_GS_WAVES;  // threads per block
 constexpr int kGsRow = 208;             // bytes per LDS row: 3 planes x 32 bf16 + 16 pad
 
-// probe knobs (tools/probes/gemm_split.hip): which of the three phases of a K step the kernels execute
-#ifdef GS_PROBE_NO_STASH
-#define GS_STASH_ON (hdr[0] == -12345)
-#else
-#define GS_STASH_ON true
-#endif
-#ifdef GS_PROBE_NO_LOAD
-#define GS_LOAD_ON (hdr[0] == -12345)
-#else
-#define GS_LOAD_ON true
-#endif
-
 struct Split4 {
   gs_bf16x4 h, m, l;
 };
-#ifndef DG_GS_SPLIT_PK  // 1: the split on register pairs (v_cvt_pk_bf16_f32 + v_pk_add_f32: ~4.5 VALU operations per element,
-#define DG_GS_SPLIT_PK 1  // the same bits); 0: element by element (~8; rounds 3-5)
-#endif
 typedef float gs_f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 gs_bf16x2 __attribute__((ext_vector_type(2)));
+// the split on register pairs: v_cvt_pk_bf16_f32 + v_pk_add_f32, ~4.5 VALU operations per element
 __device__ __forceinline__ Split4 gs_split(const float4 v) {
   Split4 s;
-#if DG_GS_SPLIT_PK
   auto split2 = [](gs_f32x2 x, gs_bf16x2& h, gs_bf16x2& m, gs_bf16x2& l) {
     h = __builtin_convertvector(x, gs_bf16x2);
     const gs_f32x2 r = x - __builtin_convertvector(h, gs_f32x2);
@@ -76,16 +59,6 @@ __device__ __forceinline__ Split4 gs_split(const float4 v) {
   s.h = gs_bf16x4{h0[0], h0[1], h1[0], h1[1]};
   s.m = gs_bf16x4{m0[0], m0[1], m1[0], m1[1]};
   s.l = gs_bf16x4{l0[0], l0[1], l1[0], l1[1]};
-#else
-  const float f[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    s.h[u] = (__bf16)f[u];
-    const float r1 = f[u] - (float)s.h[u];
-    s.m[u] = (__bf16)r1;
-    s.l[u] = (__bf16)(r1 - (float)s.m[u]);
-  }
-#endif
   return s;
 }
 // one thread's float4 (columns 4 c4 .. 4 c4 + 3 of the chunk) -> the three planes of LDS row `row`
@@ -108,9 +81,6 @@ __device__ __forceinline__ Frag3 gs_frag(const unsigned char* panel, int row, in
   f.l = *reinterpret_cast<const gs_bf16x8*>(p + 128);
   return f;
 }
-#ifdef GS_PROBE_NO_MMA  // probe knob: staging without the matrix products
-#define GS_MMA6(acc, a, b) acc[0] += (float)(a).h[0] * (float)(b).l[0];
-#else
 #define GS_MMA6(acc, a, b)                                                          \
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16((a).h, (b).h, acc, 0, 0, 0);        \
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16((a).h, (b).m, acc, 0, 0, 0);        \
@@ -118,7 +88,6 @@ __device__ __forceinline__ Frag3 gs_frag(const unsigned char* panel, int row, in
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16((a).m, (b).m, acc, 0, 0, 0);        \
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16((a).h, (b).l, acc, 0, 0, 0);        \
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16((a).l, (b).h, acc, 0, 0, 0);
-#endif
 
 // 4 x 4 transpose of bf16 values inside a lane quad: lane t holds (row t; columns 0..3) and receives (column t; rows
 // 0..3) — two exchange stages (lane ^ 1, lane ^ 2), each one DPP move and one byte permute / select per dword.
@@ -156,10 +125,12 @@ struct GsEpi {
 };
 
 // ---- C[r, n] (+)= A[r, :] . W[n, :] -----------------------------------------------------------------------------------
-// Arguments, tiles and the XCD-aware block -> tile mapping exactly as gemm_nt_kernel (dg_gemm.h); block = kGsT threads.
+// A [R, K] row-major with leading dimension lda (a column slice of a wider buffer is fine), W [Nout, K] row-major,
+// C [R, Nout] with leading dimension ldc.  K % 32 == 0, Nout % BN == 0.  grid = (DG_GEMM_GRID_X(Rmax), Nout / BN),
+// block = kGsT threads, block tile 128 rows x BN columns, K walked in chunks of 32.
 // WT: the second operand is given TRANSPOSED, Wt [K][Nout] with leading dimension ldwt (the
 // input-gradient GEMM dX = dY . W reads the layer's weight as it is stored): its panel is staged through the 4 x 4
-// quad transpose of gemm_tn_split_kernel.
+// quad transpose gs_quad_transpose.
 template <int BN, bool ACCUM, int EPI = 0, bool WT = false>
 __global__ __launch_bounds__(kGsT, DG_GS_WAVES == 8 ? 4 : 2) void gemm_nt_split_kernel(const float* __restrict__ A, int lda,
                                                             const float* __restrict__ W, int K, float* __restrict__ C,
@@ -174,6 +145,10 @@ __global__ __launch_bounds__(kGsT, DG_GS_WAVES == 8 ? 4 : 2) void gemm_nt_split_
   __shared__ __attribute__((aligned(16))) unsigned char Bs[BN * kGsRow];
   const int R = hdr != nullptr ? hdr[1] : epi.rows;
   if (EPI != 0 && epi.zero != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 64) epi.zero[threadIdx.x] = 0u;
+  // block -> (row tile, column tile).  The column tiles of one row tile all read the same A rows; workgroups go to the
+  // 8 XCDs round-robin, so they are given consecutive slots of ONE XCD (linear id L: XCD L % 8, row tile
+  // (L / 8 / gy) * 8 + L % 8, column tile (L / 8) % gy): the A tile is fetched from HBM once instead of gy times.
+  // gridDim.x is a multiple of 8 (DG_GEMM_GRID_X); tiles past R exit.
   long long r0;
   int n0;
   {
@@ -189,7 +164,7 @@ __global__ __launch_bounds__(kGsT, DG_GS_WAVES == 8 ? 4 : 2) void gemm_nt_split_
   // on every plane's store (a third of the kernel's LDS cycles: profiles/r05b_c3_pmc_lds_counters.txt).  Rows four apart
   // start 16 banks apart — four disjoint runs — so slot g of a pass takes row 4 (g % 4) + (g / 4) % 4 + 16 (g / 16).
   const int c4 = threadIdx.x & 7, rg = threadIdx.x >> 3;
-  const int rl = DG_GS_ROWPERM ? ((rg & 3) << 2) + ((rg >> 2) & 3) + (rg & ~15) : rg;
+  const int rl = ((rg & 3) << 2) + ((rg >> 2) & 3) + (rg & ~15);
   float4 ra[A4], rb[B4];
   const float* ap_[A4];
 #pragma unroll
@@ -234,14 +209,12 @@ __global__ __launch_bounds__(kGsT, DG_GS_WAVES == 8 ? 4 : 2) void gemm_nt_split_
   const int chunks = K / kKC;
   for (int c = 0; c < chunks; ++c) {
     if (c > 0) __syncthreads();  // the previous chunk's fragment reads are done
-    if (GS_STASH_ON) {
 #pragma unroll
-      for (int i = 0; i < A4; ++i) gs_stash(As, rl + RS * i, c4, ra[i]);
+    for (int i = 0; i < A4; ++i) gs_stash(As, rl + RS * i, c4, ra[i]);
 #pragma unroll
-      for (int i = 0; i < B4; ++i) stash_w(i);
-    }
+    for (int i = 0; i < B4; ++i) stash_w(i);
     __syncthreads();
-    if (c + 1 < chunks && GS_LOAD_ON) fetch((c + 1) * kKC);
+    if (c + 1 < chunks) fetch((c + 1) * kKC);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       Frag3 fa[TM], fb[TN];
@@ -313,21 +286,13 @@ __global__ __launch_bounds__(kGsT, DG_GS_WAVES == 8 ? 4 : 2) void gemm_nt_split_
 }
 
 // ---- P[chunk][n, k] = sum over the chunk's rows of Y[r, n] * X[r, k] ----------------------------------------------------
-// Arguments and grid as gemm_tn_kernel; block = kGsT threads.  The MFMA reduction index is the point row, so both operands
-// are TRANSPOSED while they are staged into the rows [column][row] of the panels.  The four lanes of a quad load four
-// consecutive rows of the same four columns, transpose the 4 x 4 block of every bf16 plane in registers
-// (gs_quad_transpose) and store 8 bytes (one column, four rows) each: 3 ds_write_b64 per float4 where element-wise
-// stores take 12 ds_write_b16.  A 16-lane store group is 8 columns x 2 row groups = 32 different banks.  The four 8-row
-// groups of a panel row are XOR-swizzled by (column >> 4) & 3 (a fragment = 8 consecutive rows = one aligned 16-byte
-// group).
-#ifndef DG_GS_TN_TR  // 1: row-major panels + transposed fragment reads (ds_read_b64_tr_b16, round 6); 0: the quad-transpose staging
-#define DG_GS_TN_TR 1
-#endif
-#if DG_GS_TN_TR
-// Round 6: the panels hold the step's 32 rows AS THEY ARE LOADED — row = [h | m | l] planes of the tile's columns — and the
-// fragments come out transposed from the LDS (ds_read_b64_tr_b16: two reads per plane and k-step, pn_bwd_q.h's lane map).  The
-// 4 x 4 quad transposes of the staging (two DPP moves, two byte permutes and a select per plane and float4, on top of the
-// split) are gone: the staging waves' VALU issue is what bounds these kernels (LABBOOK 6.3).
+// Y [R, Nout] (ldy), X [R, K] (ldx).  Block tile 128 (n) x BK (k) outputs, the rows of chunk blockIdx.z in steps of 32
+// through LDS; block = kGsT threads.  grid = (Nout / 128 rounded up, K / BK, row chunks); part [chunks][Nout][K].  Chunks
+// entirely past R write zeros (the second stage, launch_tn_reduce, adds all chunks in order).
+// The MFMA reduction index is the point row.  The panels hold the step's 32 rows AS THEY ARE LOADED — row = [h | m | l]
+// planes of the tile's columns — and the fragments come out transposed from the LDS (ds_read_b64_tr_b16: two reads per
+// plane and k-step, pn_bwd_q.h's lane map): no transposes in the staging, whose VALU issue is what bounds these kernels
+// (LABBOOK 6.3).
 template <int BK>
 __global__ __launch_bounds__(kGsT, DG_GS_WAVES == 8 ? 4 : 2) void gemm_tn_split_kernel(const float* __restrict__ Y, int ldy, int Nout,
                                                             const float* __restrict__ X, int ldx, int K,
@@ -416,20 +381,18 @@ __global__ __launch_bounds__(kGsT, DG_GS_WAVES == 8 ? 4 : 2) void gemm_tn_split_
     fetch(rb);
     for (long long r = rb; r < re; r += RC) {
       if (r > rb) __syncthreads();  // the previous step's fragment reads are done
-      if (GS_STASH_ON) {
 #pragma unroll
-        for (int i = 0; i < Y4; ++i) {
-          const int rl = yr + YP * i;
-          put(Ys + rl * YROW, 2 * BNT, yc4, ry[i], ycol_ok && r + rl < re);
-        }
+      for (int i = 0; i < Y4; ++i) {
+        const int rl = yr + YP * i;
+        put(Ys + rl * YROW, 2 * BNT, yc4, ry[i], ycol_ok && r + rl < re);
+      }
 #pragma unroll
-        for (int i = 0; i < X4; ++i) {
-          const int rl = xr + XP * i;
-          put(Xs + rl * XROW, 2 * BK, xc4, rx[i], r + rl < re);
-        }
+      for (int i = 0; i < X4; ++i) {
+        const int rl = xr + XP * i;
+        put(Xs + rl * XROW, 2 * BK, xc4, rx[i], r + rl < re);
       }
       __syncthreads();
-      if (r + RC < re && GS_LOAD_ON) fetch(r + RC);
+      if (r + RC < re) fetch(r + RC);
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         Frag3 fy[TNn], fx[TK];
@@ -458,135 +421,5 @@ __global__ __launch_bounds__(kGsT, DG_GS_WAVES == 8 ? 4 : 2) void gemm_tn_split_
       }
     }
 }
-#else
-template <int BK>
-__global__ __launch_bounds__(kGsT, DG_GS_WAVES == 8 ? 4 : 2) void gemm_tn_split_kernel(const float* __restrict__ Y, int ldy, int Nout,
-                                                            const float* __restrict__ X, int ldx, int K,
-                                                            float* __restrict__ part, int rows_per_chunk,
-                                                            const int* __restrict__ hdr, int rows) {
-  constexpr int BNT = 128, RC = 32;
-  // waves as WNW x WKW over the 128 x BK tile of the gradient
-  constexpr int WKW = DG_GS_WAVES == 4 ? 2 : (BK == 128 ? 4 : 2), WNW = DG_GS_WAVES / WKW;
-  constexpr int TNn = BNT / WNW / 32, TK = BK / WKW / 32;
-  constexpr int YC = BNT / 4, XC = BK / 4;           // column quads per row
-  constexpr int YS = 2 * (kGsT / 8) / YC, XS = 2 * (kGsT / 8) / XC;  // 4-row groups staged per pass of the block
-  constexpr int Y4 = 8 / YS, X4 = 8 / XS;            // float4 per thread and step
-  static_assert(YS >= 1 && XS >= 1 && YS <= 8 && XS <= 8, "staging layout");
-  __shared__ __attribute__((aligned(16))) unsigned char Ys[BNT * kGsRow];
-  __shared__ __attribute__((aligned(16))) unsigned char Xs[BK * kGsRow];
-  const int R = hdr != nullptr ? hdr[1] : rows;  // `rows`: the row count for callers that know it on the host
-  // block -> (n tile, k tile, row chunk).  The tiles of one row chunk read the same rows of Y and X; workgroups go to
-  // the 8 XCDs round-robin (linear id L runs on XCD L % 8) and every XCD has its own L2, so a chunk's tiles are given
-  // consecutive slots of ONE XCD (chunks a multiple of 8): its rows come from HBM once instead of once per tile.
-  int bx = (int)blockIdx.x, by = (int)blockIdx.y, bz = (int)blockIdx.z;
-  if (gridDim.z % 8 == 0) {
-    const int gx = (int)gridDim.x, tiles = gx * (int)gridDim.y, L = (bz * (int)gridDim.y + by) * gx + bx;
-    const int q = L >> 3, t = q % tiles;
-    bz = (q / tiles) * 8 + (L & 7);
-    bx = t % gx;
-    by = t / gx;
-  }
-  const int n0 = bx * BNT, k0 = by * BK;
-  // rows_per_chunk == 0: the valid rows (known on the device only) are dealt evenly to the grid's chunks
-  const int rpc = rows_per_chunk > 0 ? rows_per_chunk : (int)((((long long)R + gridDim.z - 1) / gridDim.z + 31) / 32 * 32);
-  const long long rb = (long long)bz * rpc;
-  long long re = rb + rpc;
-  if (re > R) re = R;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
-  const int wn = wave / WKW, wk = wave % WKW;
-  float4 ry[Y4], rx[X4];
-  // thread -> (row 4 g + qt, column quad c4):  qt = tid & 3, g = (tid >> 2 & 1) + 2 ((tid >> 3) / C) + S i,  c4 = (tid >> 3) % C
-  const int qt = threadIdx.x & 3, t8 = threadIdx.x >> 3;
-  const int yc4 = t8 % YC, yg = ((threadIdx.x >> 2) & 1) + 2 * (t8 / YC);
-  const int xc4 = t8 % XC, xg = ((threadIdx.x >> 2) & 1) + 2 * (t8 / XC);
-  const unsigned sel1 = (qt & 1) ? 0x03020706u : 0x05040100u;
-  const bool qlow = (qt & 2) == 0;
-  const bool ycol_ok = n0 + 4 * yc4 < Nout;
-  const float* ybase = Y + (ycol_ok ? n0 + 4 * yc4 : 0);
-  const float* xbase = X + k0 + 4 * xc4;
-  // loads are unconditional (rows clamped to the chunk's last one); what lies past the chunk is zeroed when it is staged
-  auto fetch = [&](long long r) {
-#pragma unroll
-    for (int i = 0; i < Y4; ++i) {
-      const long long row = r + 4 * (yg + YS * i) + qt;
-      ry[i] = *reinterpret_cast<const float4*>(ybase + (row < re ? row : re - 1) * ldy);
-    }
-#pragma unroll
-    for (int i = 0; i < X4; ++i) {
-      const long long row = r + 4 * (xg + XS * i) + qt;
-      rx[i] = *reinterpret_cast<const float4*>(xbase + (row < re ? row : re - 1) * ldx);
-    }
-  };
-  // the quad's 4 x 4 block (rows 4 g .. 4 g + 3, columns 4 c4 .. 4 c4 + 3): this lane stores column 4 c4 + qt
-  auto put = [&](unsigned char* panel, int c4, int g, const float4 v0, bool ok) {
-    const float4 v = make_float4(ok ? v0.x : 0.f, ok ? v0.y : 0.f, ok ? v0.z : 0.f, ok ? v0.w : 0.f);
-    const Split4 s = gs_split(v);
-    const int col = 4 * c4 + qt;
-    unsigned char* p = panel + col * kGsRow + 16 * ((g >> 1) ^ ((col >> 4) & 3)) + 8 * (g & 1);
-    *reinterpret_cast<uint2*>(p) = gs_quad_transpose(s.h, sel1, qlow);
-    *reinterpret_cast<uint2*>(p + 64) = gs_quad_transpose(s.m, sel1, qlow);
-    *reinterpret_cast<uint2*>(p + 128) = gs_quad_transpose(s.l, sel1, qlow);
-  };
-  auto frag = [&](const unsigned char* panel, int col, int s) {  // rows 16 s + 8 h .. + 7 of column `col`
-    const unsigned char* p = panel + col * kGsRow + 16 * ((2 * s + h) ^ ((col >> 4) & 3));
-    Frag3 f;
-    f.h = *reinterpret_cast<const gs_bf16x8*>(p);
-    f.m = *reinterpret_cast<const gs_bf16x8*>(p + 64);
-    f.l = *reinterpret_cast<const gs_bf16x8*>(p + 128);
-    return f;
-  };
-  f32x16 acc[TNn][TK];
-#pragma unroll
-  for (int a = 0; a < TNn; ++a)
-#pragma unroll
-    for (int b = 0; b < TK; ++b) acc[a][b] = f32x16{0};
-  if (rb < re) {
-    fetch(rb);
-    for (long long r = rb; r < re; r += RC) {
-      if (r > rb) __syncthreads();  // the previous step's fragment reads are done
-      if (GS_STASH_ON) {
-#pragma unroll
-        for (int i = 0; i < Y4; ++i) {
-          const int g = yg + YS * i;
-          put(Ys, yc4, g, ry[i], ycol_ok && r + 4 * g + qt < re);
-        }
-#pragma unroll
-        for (int i = 0; i < X4; ++i) {
-          const int g = xg + XS * i;
-          put(Xs, xc4, g, rx[i], r + 4 * g + qt < re);
-        }
-      }
-      __syncthreads();
-      if (r + RC < re && GS_LOAD_ON) fetch(r + RC);
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        Frag3 fy[TNn], fx[TK];
-#pragma unroll
-        for (int a = 0; a < TNn; ++a) fy[a] = frag(Ys, wn * (32 * TNn) + 32 * a + j, s);
-#pragma unroll
-        for (int b = 0; b < TK; ++b) fx[b] = frag(Xs, wk * (32 * TK) + 32 * b + j, s);
-#pragma unroll
-        for (int a = 0; a < TNn; ++a)
-#pragma unroll
-          for (int b = 0; b < TK; ++b) {
-            GS_MMA6(acc[a][b], fy[a], fx[b])
-          }
-      }
-    }
-  }
-  float* out = part + (long long)bz * Nout * K;
-#pragma unroll
-  for (int a = 0; a < TNn; ++a)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int n = n0 + wn * (32 * TNn) + a * 32 + acc_row(r, h);
-      if (n < Nout) {
-#pragma unroll
-        for (int b = 0; b < TK; ++b) out[(long long)n * K + k0 + wk * (32 * TK) + 32 * b + j] = acc[a][b][r];
-      }
-    }
-}
-
-#endif  // DG_GS_TN_TR
 
 }  // namespace dg

@@ -11,7 +11,7 @@
 // tensor (13 GB at C = 128, n = 640).  None of them exists here:
 //   * kNN: Gram tiles on the matrix cores, top-20 kept in registers (dg_knn.h; index-exact, arithmetic pinned);
 //   * the 1x1 convolution is linear in the edge feature:  W [x_j - x_i ; x_i] = Wa x_j + (Wb - Wa) x_i = U_j + V_i, so
-//     ONE exact-fp32 MFMA GEMM per POINT (X -> [U | V], dg_gemm.h) replaces the GEMM per EDGE (20x fewer FLOPs);
+//     ONE fp32-grade matrix-core GEMM per POINT (X -> [U | V], dg_gemm_split.h) replaces the GEMM per EDGE (20x fewer FLOPs);
 //   * BatchNorm + LeakyReLU is a monotone per-channel map whose direction is the sign of gamma, so
 //     max_j act(bn(U_j + V_i)) = act(bn(ext_j U_j + V_i)) with ext = max (gamma >= 0) or min: the aggregation kernel
 //     keeps a 32-channel slice of the part's U in LDS (128 KB), gathers the 20 neighbour rows from there (LDS, not
@@ -28,20 +28,6 @@
 #include "coop_reduce.h"
 #include "dg_gemm.h"
 #include "dg_gemm_split.h"
-#ifndef DG_GEMM_SPLIT  // 1: fp32-grade GEMMs on the bf16 matrix cores (dg_gemm_split.h); 0: v_mfma_f32_32x32x2_f32 (dg_gemm.h)
-#define DG_GEMM_SPLIT 1
-#endif
-#if DG_GEMM_SPLIT
-#define DG_NT_KERNEL gemm_nt_split_kernel
-#define DG_TN_KERNEL gemm_tn_split_kernel
-#define DG_GEMM_THREADS kGsT
-#define DG_NT_TAIL , GsEpi{}, 0
-#else
-#define DG_NT_KERNEL gemm_nt_kernel
-#define DG_TN_KERNEL gemm_tn_kernel
-#define DG_GEMM_THREADS kGT
-#define DG_NT_TAIL
-#endif
 #include <cstdio>
 #include <type_traits>
 #include <vector>
@@ -1503,16 +1489,16 @@ inline void launch_agg_bwd(dim3 grid, hipStream_t s, const float* uv, int CO, co
                      coef, M, N, guv, hdr);
 }
 
-// C (+)= A . W^T on the matrix cores (see dg_gemm.h); Nout a multiple of 64
+// C (+)= A . W^T on the matrix cores (see dg_gemm_split.h); Nout a multiple of 64
 void gemm_nt(const float* A, int lda, const float* W, int K, float* C, int ldc, int Nout, bool accum, int64_t Rmax,
              const int* hdr, hipStream_t s) {
   const unsigned gx = DG_GEMM_GRID_X(Rmax);
   if (Nout % 128 == 0) {
-    if (accum) launch(DG_NT_KERNEL<128, true>, dim3(gx, Nout / 128), dim3(DG_GEMM_THREADS), s, A, lda, W, K, C, ldc, hdr DG_NT_TAIL);
-    else launch(DG_NT_KERNEL<128, false>, dim3(gx, Nout / 128), dim3(DG_GEMM_THREADS), s, A, lda, W, K, C, ldc, hdr DG_NT_TAIL);
+    if (accum) launch(gemm_nt_split_kernel<128, true>, dim3(gx, Nout / 128), dim3(kGsT), s, A, lda, W, K, C, ldc, hdr, GsEpi{}, 0);
+    else launch(gemm_nt_split_kernel<128, false>, dim3(gx, Nout / 128), dim3(kGsT), s, A, lda, W, K, C, ldc, hdr, GsEpi{}, 0);
   } else {
-    if (accum) launch(DG_NT_KERNEL<64, true>, dim3(gx, Nout / 64), dim3(DG_GEMM_THREADS), s, A, lda, W, K, C, ldc, hdr DG_NT_TAIL);
-    else launch(DG_NT_KERNEL<64, false>, dim3(gx, Nout / 64), dim3(DG_GEMM_THREADS), s, A, lda, W, K, C, ldc, hdr DG_NT_TAIL);
+    if (accum) launch(gemm_nt_split_kernel<64, true>, dim3(gx, Nout / 64), dim3(kGsT), s, A, lda, W, K, C, ldc, hdr, GsEpi{}, 0);
+    else launch(gemm_nt_split_kernel<64, false>, dim3(gx, Nout / 64), dim3(kGsT), s, A, lda, W, K, C, ldc, hdr, GsEpi{}, 0);
   }
 }
 
@@ -1524,8 +1510,8 @@ void gemm_tn(const float* Y, int ldy, int Nout, const float* X, int ldx, int K, 
   const int chunks = tn * tk >= 4 ? kTnChunks : (int)(4 * kTnChunks / (tn * tk));
   const int rows_per_chunk = 0;  // cut the VALID rows (hdr[1], at most Rmax) evenly: every chunk has work
   const dim3 grid(tn, tk, (unsigned)chunks);
-  if (K % 128 == 0) launch(DG_TN_KERNEL<128>, grid, dim3(DG_GEMM_THREADS), s, Y, ldy, Nout, X, ldx, K, part, rows_per_chunk, hdr, 0);
-  else launch(DG_TN_KERNEL<64>, grid, dim3(DG_GEMM_THREADS), s, Y, ldy, Nout, X, ldx, K, part, rows_per_chunk, hdr, 0);
+  if (K % 128 == 0) launch(gemm_tn_split_kernel<128>, grid, dim3(kGsT), s, Y, ldy, Nout, X, ldx, K, part, rows_per_chunk, hdr, 0);
+  else launch(gemm_tn_split_kernel<64>, grid, dim3(kGsT), s, Y, ldy, Nout, X, ldx, K, part, rows_per_chunk, hdr, 0);
   const long long elems = (long long)Nout * K;
   launch_tn_reduce(part, chunks, elems, out, s);
 }

@@ -4,8 +4,9 @@
 // Replaces the Conv1d(k=1) + BatchNorm1d + ReLU layers of the reference's MLP3 / MLP4 / MLP5 and the Linear + ReLU
 // layers of RelationNet (multi_part_assembly/models/dgl/modules.py:5-73, models/rgl_net/modules.py:5-30): the P x P edge
 // MLP runs them over B*P*P = 12 800 pair rows three times per training step (dgl/network.py:135-152), the node MLP
-// over B*P rows.  The GEMMs are the exact-fp32 matrix-core kernels of dg_gemm.h (weights [Nout, K] as PyTorch stores
-// them); BatchNorm statistics are fixed-order two-stage sums in double; the backward is the affine map
+// over B*P rows.  The GEMMs are the fp32-grade matrix-core kernels of dg_gemm_split.h above kSmallRows rows and those of
+// tf_gemm.h below (weights [Nout, K] as PyTorch stores them); BatchNorm statistics are fixed-order two-stage sums in
+// double; the backward is the affine map
 //   dY = alpha * dz + gammap * Y + betap,  dz = dOut * [out > 0]
 // followed by dW = dY^T X (row-chunked, fixed order), db = column sums of dY, dX = dY W.  No atomics: bit-reproducible.
 // Padded pairs are rows like any other (the reference's BatchNorm sees them too, dgl/network.py:139-144).
@@ -16,18 +17,6 @@
 #include "dg_gemm.h"
 #include "dg_gemm_split.h"
 #include "tf_gemm.h"
-#ifndef DG_GEMM_SPLIT  // 1: fp32-grade GEMMs on the bf16 matrix cores (dg_gemm_split.h); 0: v_mfma_f32_32x32x2_f32 (dg_gemm.h)
-#define DG_GEMM_SPLIT 1
-#endif
-#if DG_GEMM_SPLIT
-#define DG_NT_KERNEL gemm_nt_split_kernel
-#define DG_TN_KERNEL gemm_tn_split_kernel
-#define DG_GEMM_THREADS kGsT
-#else
-#define DG_NT_KERNEL gemm_nt_kernel
-#define DG_TN_KERNEL gemm_tn_kernel
-#define DG_GEMM_THREADS kGT
-#endif
 
 namespace {
 
@@ -47,33 +36,6 @@ constexpr int kRT = 16;          // rows per block of the row-tiled kernels
 #endif
 constexpr int kSmallRows = MPA_ML_SMALL_ROWS;
 constexpr int kChunks = 64;      // most row chunks of the weight-gradient GEMM (fewer for few rows: >= 256 rows each)
-
-__global__ void ml_set_hdr_kernel(int* hdr, int R, unsigned* tickets) {
-  hdr[0] = 1;
-  hdr[1] = R;
-  for (int t = threadIdx.x; t < 64; t += blockDim.x) tickets[t] = 0u;
-}
-
-// y[r][c] += bias[c] (in place) and the per-tile column sums (sum y, sum y^2).  grid = tiles, block = 256 (channels in
-// chunks of 256).
-__global__ __launch_bounds__(256) void ml_bias_stats_kernel(float* __restrict__ y, const float* __restrict__ bias, int R,
-                                                            int C, float* __restrict__ partial) {
-  const long long r0 = (long long)blockIdx.x * kRT;
-  const int rows = R - r0 < kRT ? (int)(R - r0) : kRT;
-  for (int c = threadIdx.x; c < C; c += 256) {
-    const float b = bias != nullptr ? bias[c] : 0.0f;
-    float s = 0.0f, ss = 0.0f;
-    for (int i = 0; i < rows; ++i) {
-      const float t = y[(r0 + i) * C + c] + b;
-      y[(r0 + i) * C + c] = t;
-      s += t;
-      ss = __builtin_fmaf(t, t, ss);
-    }
-    float* d = partial + ((long long)blockIdx.x * C + c) * 2;
-    d[0] = s;
-    d[1] = ss;
-  }
-}
 
 __global__ __launch_bounds__(64 * kSlices) void ml_bn_finalize_kernel(
     const float* __restrict__ partial, int rows, int C, double count, const float* __restrict__ gamma,
@@ -398,17 +360,11 @@ __global__ __launch_bounds__(kSbT) void ml_small_bn_bwd_kernel(
   }
 }
 
-__global__ void ml_transpose_kernel(const float* __restrict__ w, int rows, int cols, float* __restrict__ wt) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= rows * cols) return;
-  wt[(e % cols) * rows + e / cols] = w[e];
-}
-
 // ---- first layer of the P x P edge MLP without the pair tensor --------------------------------------------------------------
 // The layer's input row (b, i, j) is [a_i ; b_j], so  x w^T = pa[(b, i)] + pb[(b, j)]  with  pa = a Wa^T + bias,
 // pb = b Wb^T  (Wa | Wb = the column halves of w): two GEMMs over the B*P part rows instead of one over the B*P*P pair rows.
-// ypre[(b,i,j)][c] = pa[(b,i)][c] + pb[(b,j)][c] and the per-tile column sums (sum, sum of squares; rows ascending) of
-// ml_bias_stats_kernel.  grid = tiles of kRT rows, block 256.
+// ypre[(b,i,j)][c] = pa[(b,i)][c] + pb[(b,j)][c] and the per-tile column sums (sum, sum of squares; rows ascending) of kRT
+// rows.  grid = tiles of kRT rows, block 256.
 __global__ __launch_bounds__(256) void pair_sum_stats_kernel(const float* __restrict__ pa, const float* __restrict__ pb, int P,
                                                              int R, int C, float* __restrict__ ypre,
                                                              float* __restrict__ partial) {
@@ -480,9 +436,8 @@ __global__ __launch_bounds__(256) void ml_reduce_strided_kernel(const float* __r
 }
 
 struct MlWs {
-  int* hdr;
   unsigned* tickets;
-  float *ypre, *bn, *coef, *partial, *wt, *tnpart, *dy;
+  float *ypre, *bn, *coef, *partial, *tnpart, *dy;
   double* stage;
   int64_t total;
 };
@@ -496,13 +451,12 @@ MlWs ml_carve(char* base, int64_t R, int64_t K, int64_t N) {
     return r;
   };
   const int64_t tiles = (R + kRT - 1) / kRT;
-  w.hdr = reinterpret_cast<int*>(take(64));
+  take(64);  // (unused: keeps the layout and size of the workspace)
   w.tickets = reinterpret_cast<unsigned*>(take(256));
   w.ypre = reinterpret_cast<float*>(take(4 * R * N));
   w.bn = reinterpret_cast<float*>(take(4 * 4 * N));
   w.coef = reinterpret_cast<float*>(take(4 * 3 * N));
   w.partial = reinterpret_cast<float*>(take(4 * tiles * N * 2));
-  w.wt = reinterpret_cast<float*>(take(4 * K * N));
   w.tnpart = reinterpret_cast<float*>(take(4 * (int64_t)kChunks * N * K));
   w.dy = reinterpret_cast<float*>(take(4 * R * N));
   w.stage = reinterpret_cast<double*>(take(8 * 2 * N * ((tiles + kEB - 1) / kEB)));
@@ -528,7 +482,6 @@ void launch(Kern kern, dim3 grid, dim3 block, hipStream_t s, Args... args) {
   hipLaunchKernelGGL(kern, grid, block, 0, s, args...);
 }
 
-#if DG_GEMM_SPLIT
 // C = A W^T with the output pass of `EPI` (dg_gemm_split.h); WT: W is given as [K][Nout].  The row count travels by value.
 template <int EPI, bool WT>
 void ml_gemm(const float* A, int lda, const float* W, int K, float* C, int ldc, int Nout, int64_t R, GsEpi epi, int ldwt,
@@ -542,14 +495,6 @@ void ml_gemm(const float* A, int lda, const float* W, int K, float* C, int ldc, 
     launch(gemm_nt_split_kernel<64, false, EPI, WT>, dim3(gx, Nout / 64), dim3(kGsT), s, A, lda, W, K, C, ldc,
            (const int*)nullptr, epi, ldwt);
 }
-#else
-void ml_gemm_nt(const float* A, int lda, const float* W, int K, float* C, int ldc, int Nout, int64_t R, const int* hdr,
-                hipStream_t s) {
-  const unsigned gx = DG_GEMM_GRID_X(R);
-  if (Nout % 128 == 0) launch(DG_NT_KERNEL<128, false>, dim3(gx, Nout / 128), dim3(DG_GEMM_THREADS), s, A, lda, W, K, C, ldc, hdr);
-  else launch(DG_NT_KERNEL<64, false>, dim3(gx, Nout / 64), dim3(DG_GEMM_THREADS), s, A, lda, W, K, C, ldc, hdr);
-}
-#endif
 
 }  // namespace
 
@@ -570,7 +515,6 @@ extern "C" int mpa_mlp_layer_forward(const float* x, int64_t ldx, const float* w
   MPA_REQUIRE((uintptr_t)ws % 256 == 0, "mlp_layer_forward: workspace must be 256-byte aligned");
   hipStream_t s = mpa::as_stream(stream);
   const MlWs m = ml_carve(static_cast<char*>(ws), R, K, N);
-  const int tiles = (int)((R + kRT - 1) / kRT);
   const long long total4 = R * N / 4;
   const CoopWs cw{m.stage, m.tickets};
   if (R <= kSmallRows) {
@@ -612,7 +556,6 @@ extern "C" int mpa_mlp_layer_forward(const float* x, int64_t ldx, const float* w
            (const float*)m.bn, (const float*)nullptr, total4, (int)N, relu, out);
     return mpa::check_launch("mlp_layer_forward");
   }
-#if DG_GEMM_SPLIT
   // bias, BatchNorm statistics / activation in the GEMM's output pass: 3 launches with BatchNorm, 1 without
   GsEpi epi;
   epi.bias = bias;
@@ -635,29 +578,6 @@ extern "C" int mpa_mlp_layer_forward(const float* x, int64_t ldx, const float* w
     launch(ml_bn_from_running_kernel, dim3((unsigned)(N / 64)), dim3(64), s, (int)N, gamma, beta,
            (const float*)running_mean, (const float*)running_var, eps, m.bn);
   }
-  (void)tiles;
-#else
-  launch(ml_set_hdr_kernel, dim3(1), dim3(64), s, m.hdr, (int)R, m.tickets);
-  if (gamma == nullptr) {
-    ml_gemm_nt(x, (int)ldx, w, (int)K, out, (int)N, (int)N, R, m.hdr, s);
-    launch(ml_apply_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), s, (const float*)out, (const float*)nullptr,
-           bias, total4, (int)N, relu, out);
-    return mpa::check_launch("mlp_layer_forward");
-  }
-  ml_gemm_nt(x, (int)ldx, w, (int)K, m.ypre, (int)N, (int)N, R, m.hdr, s);
-  if (training) {
-    launch(ml_bias_stats_kernel, dim3((unsigned)tiles), dim3(256), s, m.ypre, bias, (int)R, (int)N, m.partial);
-    launch(ml_bn_finalize_kernel, dim3((unsigned)(N / 64), (unsigned)((tiles + kEB - 1) / kEB)), dim3(64 * kSlices), s,
-           (const float*)m.partial, tiles, (int)N, (double)R, gamma, beta, running_mean, running_var, momentum, eps, m.bn,
-           cw);
-  } else {
-    if (bias != nullptr)
-      launch(ml_apply_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), s, (const float*)m.ypre,
-             (const float*)nullptr, bias, total4, (int)N, 0, m.ypre);
-    launch(ml_bn_from_running_kernel, dim3((unsigned)(N / 64)), dim3(64), s, (int)N, gamma, beta,
-           (const float*)running_mean, (const float*)running_var, eps, m.bn);
-  }
-#endif
   launch(ml_apply_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), s, (const float*)m.ypre, (const float*)m.bn,
          (const float*)nullptr, total4, (int)N, relu, out);
   return mpa::check_launch("mlp_layer_forward");
@@ -702,14 +622,13 @@ extern "C" int mpa_mlp_layer_backward(const float* grad_out, const float* x, int
     if (chunks >= 8) chunks = chunks / 8 * 8;  // (a multiple of 8 gets the kernel's XCD-aware chunk mapping)
     const int rows_per_chunk = (int)(((R + chunks - 1) / chunks + 31) / 32 * 32);
     const dim3 grid((unsigned)((N + 127) / 128), (unsigned)(K % 128 == 0 ? K / 128 : K / 64), (unsigned)chunks);
-    // the row count travels by value in both builds (both kernels take `rows` when hdr is null): the forward's
-    // small-row path never writes the header
+    // the row count travels by value (`rows`, with hdr null)
     const int* hdr = nullptr;
     if (K % 128 == 0)
-      launch(DG_TN_KERNEL<128>, grid, dim3(DG_GEMM_THREADS), s, (const float*)m.dy, (int)N, (int)N, x, (int)ldx, (int)K, m.tnpart,
+      launch(gemm_tn_split_kernel<128>, grid, dim3(kGsT), s, (const float*)m.dy, (int)N, (int)N, x, (int)ldx, (int)K, m.tnpart,
              rows_per_chunk, hdr, (int)R);
     else
-      launch(DG_TN_KERNEL<64>, grid, dim3(DG_GEMM_THREADS), s, (const float*)m.dy, (int)N, (int)N, x, (int)ldx, (int)K, m.tnpart,
+      launch(gemm_tn_split_kernel<64>, grid, dim3(kGsT), s, (const float*)m.dy, (int)N, (int)N, x, (int)ldx, (int)K, m.tnpart,
              rows_per_chunk, hdr, (int)R);
     const long long elems = (long long)N * K;
     if (grad_b != nullptr) {
@@ -730,12 +649,7 @@ extern "C" int mpa_mlp_layer_backward(const float* grad_out, const float* x, int
     g.K = (int)N;
     tfg::launch_gemm<tfg::EPI_NONE, true>(g, s);
   } else if (grad_x != nullptr) {  // dX [R][K] = dY [R][N] . W [N][K]
-#if DG_GEMM_SPLIT
     ml_gemm<0, true>(m.dy, (int)N, w, (int)N, grad_x, (int)K, (int)K, R, GsEpi{}, (int)K, s);
-#else
-    launch(ml_transpose_kernel, dim3((unsigned)((N * K + 255) / 256)), dim3(256), s, w, (int)N, (int)K, m.wt);
-    ml_gemm_nt(m.dy, (int)N, m.wt, (int)N, grad_x, (int)K, (int)K, R, m.hdr, s);
-#endif
   }
   return mpa::check_launch("mlp_layer_backward");
 }

@@ -5,9 +5,9 @@
 // A = relu(bn_prev(Yprev)) the layer's input, so both gradients can be written WITHOUT the layer's own output Y:
 //     dA      = dZ (alpha.W) + A Q + c0,          Q = W^T diag(gammap) W  [CIN x CIN],  c0 = betap W
 //     dW      = alpha.(dZ^T A) + gammap.(W G) + betap (x) asum,      G = A^T A,  asum = column sums of A
-// (the form the never-stored last layer always used: pn_dgrad_split_kernel).  The kernel therefore reads dZ_l and
+// (the form the never-stored last layer uses: pn_bwd_top_q_kernel below).  The kernel therefore reads dZ_l and
 // Yprev ONCE and writes dZ_{l-1}: 360 / 270 MB per launch for the 64 -> 128 / 64 -> 64 layers instead of the 540 / 360 MB
-// of pn_bwd_fused_kernel (which also read Y_l), and every product runs on v_mfma_f32_32x32x16_bf16 with both operands
+// a kernel that also reads Y_l moves (LABBOOK 6.1), and every product runs on v_mfma_f32_32x32x16_bf16 with both operands
 // split into three bf16 terms (six products of order <= 2; csrc/dg_gemm_split.h has the error analysis) instead of the
 // 2.67 x slower exact-fp32 MFMA.  T = dZ^T A, G and asum leave the kernel as per-block partial tables; the final
 // combination with the coefficients is a tiny kernel at the end of the pass (pn_bwd_finish_kernel).
@@ -16,7 +16,7 @@
 // and dZ_1 is not written either: the only consumers of dZ_1 are conv1's weight gradient and bn1's coefficients, and
 //     dW1 = alpha1.(dZ1^T P) + gammap1.(W1 P^T P) + betap1 (x) psum
 // needs dZ1 only through S = dZ1^T P [64 x 3], which the input-gradient epilogue accumulates in registers (3 FMAs per
-// element) — 90 MB less written, 90 MB less read and one kernel (pn_wgrad_mfma_kernel<WG_FIRST>, 47 us) less per step.
+// element) — 90 MB less written, 90 MB less read and one kernel (conv1's own weight gradient, 47 us) less per step.
 //
 // One block per CU, persistent over RB-row units of the valid parts, three kinds of waves that meet at ONE barrier per unit:
 //   * NS stager waves: fetch the unit after next (coalesced 16-byte loads, a whole unit in flight per CU), apply the
@@ -28,7 +28,7 @@
 //     their reduction index is the point row, so both operands are TRANSPOSED reads of the row-major panels —
 //     ds_read_b64_tr_b16, two per fragment and plane (tools/probes/tr_read.hip pins the lane layout).
 // So staging (VALU + memory), the matrix pipe and the epilogues of a CU overlap by construction instead of taking turns
-// within every wave (the stash -> barrier -> MFMA -> epilogue cycle that bound pn_bwd_fused_kernel: LABBOOK round 4).
+// within every wave (the stash -> barrier -> MFMA -> epilogue cycle that bound the round-4 fused kernel: LABBOOK r1-4 §6).
 
 // -DPN_TIMING: every wave of block 5 adds up the cycles it spends between barriers (busy) and prints them at the end
 #ifdef PN_TIMING
@@ -627,8 +627,8 @@ __global__ __launch_bounds__(64 * (NS + ND + NW), (NS + ND + NW + 3) / 4) void p
 // ---- the never-stored last layer in the same form ---------------------------------------------------------------------------
 // conv5's output Y5 is never stored (pointnet.hip: top-2 records), so its backward always was  dA4 = A4 Q + c0 + S W5  with S the
 // sparse arg-max gradient (CSR by 32-row tile: erow, ech, eval, tptr) and  dW5  from the Gram matrix G = A4^T A4.  This kernel
-// does the input gradient AND the Gram matrix in one pass over Y4 (pn_dgrad_split_kernel + pn_gram_split_kernel read it once
-// each: 139 + 79 us) with the wave roles of pn_bwd_q_kernel: stagers convert Y4 rows into the A panel and stage the unit's
+// does the input gradient AND the Gram matrix in one pass over Y4 (two kernels that read it once each took 139 + 79 us:
+// LABBOOK 6.1) with the wave roles of pn_bwd_q_kernel: stagers convert Y4 rows into the A panel and stage the unit's
 // CSR entries (three-stage request pipeline: tile offsets, entries, LDS); four input-gradient waves (one 32-column tile each,
 // Q register-resident) leave A Q + c0 raw in LDS; four weight-gradient waves accumulate the ten upper tiles of G; both kinds
 // then finish the previous unit: sparse rows added from the staged entries, ReLU mask, dZ4 stores, BatchNorm-backward sums.

@@ -12,7 +12,7 @@
 //   * hidden layers, 4 store waves: one barrier later they write the previous unit's tile as coalesced 16-byte stores and
 //     take BatchNorm's column sums (sum, sum of squares) from it;
 //   * last layer (TOP: Y5 is never stored): the GEMM waves keep, per channel, the top-2 records of sign(gamma) * y and the
-//     column sums in their accumulator layout (pn_fwd_split_kernel's epilogue).
+//     column sums in their accumulator layout.
 // Per block: one (sum, sum) row of `partial` per channel (fixed order), reduced by pn_bn_finalize_kernel.
 
 template <int CIN, int COUT, int RB, bool FIRST, int BPC = 1>

@@ -586,11 +586,11 @@ def test_pn_transformer_step_at_the_benchmark_part_size_against_float64(cuda_dev
     per-part Chamfer term, 6e-5 for BOTH float32 evaluations (nearest-neighbour near-ties resolve differently in float64).
     The predicted poses themselves differ from float64 by 3e-6 (HIP) / 2e-6 (oracle), and which near-ties those shifts
     flip decides the offset; evaluating the pose head's normalisation backward in double changes nothing.
-    A/B, round 5: is it the fp32-grade split-bf16 products (the 128 / 256-wide PointNet layers)?  The same test against a
-    build with every PointNet GEMM on `v_mfma_f32_32x32x2_f32` (tools/build_variant.sh pn_exact pointnet.hip
-    -DMPA_PN_SPLIT=0; the transformer and the pose head are exact-fp32 matrix products in both builds): median ratio
-    5.49 (split: 6.70), 64 of 73 tensors beyond twice the oracle's deviation (66), largest 8.00e-4 (8.02e-4) on the same
-    tensor.  The split products account for a fifth of the ratio; the offset is there without them."""
+    A/B, round 5: was it the fp32-grade split-bf16 products (the 128 / 256-wide PointNet layers)?  The same test was run
+    against a build, since retired, that had every PointNet GEMM on `v_mfma_f32_32x32x2_f32` (the transformer and the pose
+    head were exact-fp32 matrix products in both builds): median ratio 5.49 (split: 6.70), 64 of 73 tensors beyond twice
+    the oracle's deviation (66), largest 8.00e-4 (8.02e-4) on the same tensor.  The split products accounted for a fifth
+    of the ratio; the offset was there without them."""
     from oracle import nets as on
     cfg = config.pn_transformer_everyday()
     _against_float64(cuda_device, capsys, cfg, "PNTransformer + PointNet",
