@@ -25,7 +25,7 @@ extern "C" {
 #define MPA_ELAUNCH (-2) /* hipGetLastError() reported a launch failure */
 
 /* ABI version of this header; bumped whenever a signature changes. */
-#define MPA_ABI_VERSION 8
+#define MPA_ABI_VERSION 9
 int mpa_abi_version(void);
 
 /* Thread-local, NUL-terminated description of the last failure on this thread ("" if none). */
@@ -434,6 +434,28 @@ int mpa_gru_forward(const float* gi, const float* h0, const float* whh, const fl
 int mpa_gru_backward(const float* grad_out, const float* h0, const float* whh, const float* out, int64_t D, int64_t B,
                      int64_t T, int64_t H, float* ws, float* grad_gi, float* grad_whh, float* grad_bhh, int32_t* status,
                      void* stream);
+/* ------------------------------------------------------------------------------------------------
+ * B-LSTM seq2seq decoder (live layer 0 of nn.GRU(128, 528, 2 layers) + its output head) — replaces the per-part loop of
+ *   Seq2Seq.infer_decoder / DecoderRNN.forward : multi_part_assembly/models/b_lstm/seq2seq.py:106-137,165-191
+ * All T steps in ONE launch per pass (same exchange, status word and co-residency rules as mpa_gru_*):
+ *   h_t = GRU(gi_t, h_{t-1}) (torch.nn.GRU's equations, H = 528),  z1_t = W1 h_t + b1 [256],  y_t = W2 z1_t + b2 [128].
+ * gi [T,B,3H] = W_ih x_t + b_ih of the teacher-forced inputs (one GEMM by the caller), or NULL for free running: then
+ * x_0 = 0 and x_t = mask[t] * y_{t-1} (mask [T,B,128] holds the caller's scaled dropout mask, NULL = none), with y_{t-1}
+ * exactly the y the launch returns.  h0 [B,H]; wih [3H,128], bih, whh [3H,H], bhh, w1 [256,H], b1, w2 [128,256], b2.
+ * Outputs hs [T,B,H], z1 [T,B,256], y [T,B,128]; `ws` (mpa_seq2seq_decoder_workspace floats, 8-byte aligned) carries the
+ * gates to backward.  backward: dh [T,B,H] (the head's gradient w.r.t. h_t) -> dgi [T,B,3H] (w.r.t. gi), dwhh, dbhh
+ * (overwritten) and dh0 [B,H]; deterministic (partials summed in block order).  B <= 64.
+ * ---------------------------------------------------------------------------------------------- */
+int mpa_seq2seq_decoder_workspace(int64_t B, int64_t T, int64_t* float_elems);
+/* *ok = 1 iff the current device can hold the whole grid of both decoder kernels at once. */
+int mpa_seq2seq_decoder_resident(int64_t B, int* ok);
+int mpa_seq2seq_decoder_forward(const float* gi, const float* mask, const float* h0, const float* wih, const float* bih,
+                                const float* whh, const float* bhh, const float* w1, const float* b1, const float* w2,
+                                const float* b2, int64_t B, int64_t T, float* ws, float* hs, float* z1, float* y,
+                                int32_t* status, void* stream);
+int mpa_seq2seq_decoder_backward(const float* dh, const float* h0, const float* whh, const float* hs, int64_t B,
+                                 int64_t T, float* ws, float* dgi, float* dwhh, float* dbhh, float* dh0, int32_t* status,
+                                 void* stream);
 /* Test support: `blocks` workgroups that each hold `lds_bytes` of LDS and do nothing for `usec` microseconds — CUs no other
  * stream can use meanwhile (how tests/test_gru_gpu.py provokes the co-residency failure above). */
 int mpa_debug_occupy(int64_t blocks, int64_t lds_bytes, int64_t usec, void* stream);

@@ -83,6 +83,10 @@ SIGNATURES: dict[str, tuple] = {
     "mpa_gru_resident": (_INT, [_I64, _I64, _I64, _P]),
     "mpa_gru_forward": (_INT, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
     "mpa_gru_backward": (_INT, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P]),
+    "mpa_seq2seq_decoder_workspace": (_INT, [_I64, _I64, _P]),
+    "mpa_seq2seq_decoder_resident": (_INT, [_I64, _P]),
+    "mpa_seq2seq_decoder_forward": (_INT, [_P] * 11 + [_I64, _I64] + [_P] * 6),
+    "mpa_seq2seq_decoder_backward": (_INT, [_P] * 4 + [_I64, _I64] + [_P] * 7),
     "mpa_debug_occupy": (_INT, [_I64, _I64, _I64, _P]),
     "mpa_transformer_workspace": (_INT, [_I64] * 6 + [_P]),
     "mpa_transformer_forward": (_INT, [_P, _P, _P] + [_I64] * 6 + [_F32, _U64, _P, _P, _P, _P]),
@@ -96,7 +100,7 @@ SIGNATURES: dict[str, tuple] = {
     "mpa_grad_clip_coef": (_INT, [_P, _I64, _F32, _P, _F32, _P, _P, _P]),
 }
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 _lib = None
 
 

@@ -150,3 +150,33 @@ def pn_transformer_refine_everyday():
     opt.warmup_ratio = 0.05
     return Config(exp=_exp(400), data=breaking_bad_everyday(), optimizer=opt, model=pn_transformer_refine_model(),
                   loss=geometric_loss())
+
+
+def lstm_model():
+    """configs/_base_/models/lstm.py:5-13."""
+    return Config(name="lstm", rot_type="quat", pc_feat_dim=128, encoder="pointnet", lstm_hidden_size=256)
+
+
+def breaking_bad_artifact():
+    """configs/_base_/datasets/breaking_bad/artifact.py: the keys and sizes of everyday, another data list."""
+    return breaking_bad_everyday()
+
+
+def lstm_everyday():
+    """configs/lstm/lstm-32x1-cosine_200e-everyday.py."""
+    return Config(exp=_exp(200), data=breaking_bad_everyday(), optimizer=adam_cosine(), model=lstm_model(),
+                  loss=geometric_loss())
+
+
+def lstm_artifact():
+    """configs/lstm/lstm-32x1-cosine_200e-artifact.py."""
+    return Config(exp=_exp(200), data=breaking_bad_artifact(), optimizer=adam_cosine(), model=lstm_model(),
+                  loss=geometric_loss())
+
+
+def lstm_partnet_chair():
+    """configs/lstm/lstm-32x1-cosine_200e-partnet_chair.py (semantic data: matching + min-of-N; the parts are shuffled
+    to avoid part-label leakage from their order)."""
+    data = partnet_chair()
+    data.shuffle_parts = True
+    return Config(exp=_exp(200), data=data, optimizer=adam_cosine(), model=lstm_model(), loss=semantic_loss())

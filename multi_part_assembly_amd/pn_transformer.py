@@ -166,7 +166,7 @@ class PNTransformerRefine(PNTransformer):
 
 
 def build_model(cfg):
-    """Registry of reference models/__init__.py:10-26 (the LSTM / identity baselines are out of scope)."""
+    """Registry of reference models/__init__.py:10-26 (the identity baseline is out of scope)."""
     model = _build_model(cfg)
     TransformerEncoder.assign_dropout_salts(model)  # sibling encoders draw different masks, reproducibly
     return model
@@ -186,4 +186,7 @@ def _build_model(cfg):
     if cfg.model.name == "rgl_net":
         from .gnn import RGLNet
         return RGLNet(cfg)
+    if cfg.model.name == "lstm":
+        from .lstm import LSTMModel
+        return LSTMModel(cfg)
     raise NotImplementedError(f"Model {cfg.model.name} not supported")

@@ -43,6 +43,13 @@ class Trainer:
             warnings.warn("Trainer: use_graph=True is not available for models with semantic part matching (the matching's "
                           "point sample is drawn on the host every step); running eager launches")
             use_graph = False
+        if use_graph and getattr(model, "host_draws_per_forward", False):
+            # B-LSTM draws its teacher-forcing coin and its decoder noise on the host in every forward (lstm.py; reference
+            # b_lstm/seq2seq.py:177-178,212-220): a captured step would replay ONE draw for ever.  Eager launches instead.
+            import warnings
+            warnings.warn(f"Trainer: use_graph=True is not available for {type(model).__name__} (its teacher-forcing coin "
+                          "and decoder noise are drawn on the host every forward); running eager launches")
+            use_graph = False
         self.use_graph, self.graph_warmup = use_graph, graph_warmup
         self._graph, self._static_batch, self._static_loss, self._eager_steps = None, None, None, 0
         cfg = cfg if cfg is not None else model.cfg
