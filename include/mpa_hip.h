@@ -25,7 +25,7 @@ extern "C" {
 #define MPA_ELAUNCH (-2) /* hipGetLastError() reported a launch failure */
 
 /* ABI version of this header; bumped whenever a signature changes. */
-#define MPA_ABI_VERSION 9
+#define MPA_ABI_VERSION 10
 int mpa_abi_version(void);
 
 /* Thread-local, NUL-terminated description of the last failure on this thread ("" if none). */
@@ -564,6 +564,12 @@ int mpa_match_parts(const float* part_pcs, const float* pred_trans, const float*
                     const float* gt_quat, const int32_t* match_ids, const int32_t* sample_idx, int64_t B, int64_t P,
                     int64_t N, int64_t G, int64_t n, float* cost_ws, int32_t* col4row_ws, float* new_trans,
                     float* new_quat, int32_t* perm, void* stream);
+/* mpa_match_parts_rmat: mpa_match_parts with rotation matrices [B,P,3,3] (rot_type='rmat') in place of quaternions: the
+ *   clouds of the cost matrices are transformed as in mpa_pose_apply_rmat_forward; new_rmat [B,P,3,3]. */
+int mpa_match_parts_rmat(const float* part_pcs, const float* pred_trans, const float* pred_rmat, const float* gt_trans,
+                         const float* gt_rmat, const int32_t* match_ids, const int32_t* sample_idx, int64_t B, int64_t P,
+                         int64_t N, int64_t G, int64_t n, float* cost_ws, int32_t* col4row_ws, float* new_trans,
+                         float* new_rmat, int32_t* perm, void* stream);
 
 /* ---- batch producer (device side) -------------------------------------------------------------------------
  * Replaces the per-part numpy work of GeometryPartDataset.__getitem__ (multi_part_assembly/datasets/
@@ -573,6 +579,62 @@ int mpa_match_parts(const float* part_pcs, const float* pred_trans, const float*
  * slots are zero-filled.  float64 arithmetic like the reference, fixed summation order. */
 int mpa_part_batch_transform(const double* raw, const double* rot, const int32_t* perm, const float* valids,
                              int64_t M, int64_t N, float* part_pcs, float* part_trans, void* stream);
+
+/* ---- rotation matrices (rot_type='rmat'; csrc/rmat.hip, the 6D pose head in csrc/transformer.hip) -------------------------
+ * Replaces the rmat half of multi_part_assembly/utils/rotation.py:134-167 and utils/transforms.py:126-244, and the 6D
+ * branch of models/modules/regressor.py:6-27,33-69.  Matrices are [.., 3, 3] row-major fp32.
+ *
+ * mpa_quat_to_rmat: pytorch3d quaternion_to_matrix of quat [count, 4] (real part first; |q|^2 summed left to right) ->
+ *   rmat [count, 9].  No backward (it converts ground-truth poses).
+ * mpa_rot6d_to_rmat_forward: pytorch3d rotation_6d_to_matrix of rot6d [count, 6] -> rmat [count, 9]: rows b1 =
+ *   normalize(a1), b2 = normalize(a2 - (b1.a2) b1) (F.normalize: x / max(|x|, 1e-12)), b3 = b1 x b2.
+ *   _backward: grad_rmat [count, 9] -> grad_rot6d [count, 6].
+ * mpa_pose_apply_rmat_forward / _backward: the contract of mpa_pose_apply_* with rmat [num_parts, 9] in place of quat:
+ *   out_i = (r_i0 x + r_i1 y) + r_i2 z (+ t_i), left to right, no FMA (the reference's `r @ v[..., None]`).  Backward:
+ *   grad_rmat [num_parts, 9] = sum_n g p^T, grad_trans (NULL: skipped), grad_pc = R^T g (NULL: skipped; zero where
+ *   masked).  Deterministic (fixed reduction tree, no atomics).
+ * mpa_pose_head6_*: mpa_pose_head_* with the 6D rotation head: params[4] = rot.w [6,128], params[5] = rot.b [6];
+ *   rot6d [M, 6] = normalize_rot6d(h . Wr^T + br) (reference regressor.py:6-27), trans [M, 3].  Its own workspace size. */
+int mpa_quat_to_rmat(const float* quat, int64_t count, float* rmat, void* stream);
+
+/* The fused assembly loss (mpa_assembly_loss_*) with rotation matrices: rmat_pred / rmat_gt [B,P,3,3] row-major in place
+ * of the quaternions, same workspace (mpa_assembly_loss_workspace), same searches and routes, same outputs.  The clouds
+ * are transformed as in mpa_pose_apply_rmat_forward; rot_loss = mean over the nine entries of (I - R1^T R2)^2
+ * (utils/loss.py:76-82); the backward writes grad_rmat [B,P,3,3] as fixed-order sums dL/dR = sum g p^T plus the closed
+ * form of rot_loss (no atomics, deterministic). */
+int mpa_assembly_loss_forward_rmat(const float* part_pcs, const float* valids, const float* rmat_pred,
+                                   const float* trans_pred, const float* rmat_gt, const float* trans_gt, int64_t B,
+                                   int64_t P, int64_t N, int training, int fill_pad_points, float* float_ws,
+                                   int32_t* int_ws, float* losses, void* stream);
+int mpa_assembly_loss_forward_rmat_timed(const float* part_pcs, const float* valids, const float* rmat_pred,
+                                         const float* trans_pred, const float* rmat_gt, const float* trans_gt,
+                                         int64_t B, int64_t P, int64_t N, int training, int fill_pad_points,
+                                         float* float_ws, int32_t* int_ws, float* losses, void* const* events,
+                                         void* stream);
+int mpa_assembly_loss_forward_rmat_ordered(const float* part_pcs, const float* valids, const float* rmat_pred,
+                                           const float* trans_pred, const float* rmat_gt, const float* trans_gt,
+                                           int64_t B, int64_t P, int64_t N, int training, int fill_pad_points,
+                                           const float* order, int search, float* float_ws, int32_t* int_ws,
+                                           float* losses, void* const* events, void* stream);
+int mpa_assembly_loss_backward_rmat(const float* grad_losses, const float* part_pcs, const float* valids,
+                                    const float* rmat_pred, const float* trans_pred, const float* rmat_gt,
+                                    const float* trans_gt, int64_t B, int64_t P, int64_t N, int training,
+                                    const float* float_ws, const int32_t* int_ws, float* grad_rmat, float* grad_trans,
+                                    void* stream);
+int mpa_rot6d_to_rmat_forward(const float* rot6d, int64_t count, float* rmat, void* stream);
+int mpa_rot6d_to_rmat_backward(const float* rot6d, const float* grad_rmat, int64_t count, float* grad_rot6d,
+                               void* stream);
+int mpa_pose_apply_rmat_forward(const float* pc, const float* rmat, const float* trans, const float* mask, float fill,
+                                int64_t num_parts, int64_t num_points, float* out, void* stream);
+int mpa_pose_apply_rmat_backward(const float* grad_out, const float* pc, const float* rmat, const float* mask,
+                                 float fill, int64_t num_parts, int64_t num_points, float* grad_rmat,
+                                 float* grad_trans, float* grad_pc, void* stream);
+int mpa_pose_head6_workspace(int64_t M, int64_t F, int64_t* float_elems);
+int mpa_pose_head6_forward(const float* x, const float* const* params, int64_t M, int64_t F, float* ws,
+                           float* rot6d, float* trans, void* stream);
+int mpa_pose_head6_backward(const float* grad_rot6d, const float* grad_trans, const float* x,
+                            const float* const* params, int64_t M, int64_t F, float* ws, float* grad_x,
+                            float* const* grad_params, void* stream);
 
 #ifdef __cplusplus
 }

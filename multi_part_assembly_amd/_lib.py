@@ -40,6 +40,7 @@ SIGNATURES: dict[str, tuple] = {
     "mpa_assembly_loss_workspace": (_INT, [_I64, _I64, _I64, _P, _P]),
     "mpa_linear_sum_assignment": (_INT, [_P, _P, _I64, _I64, _P, _P]),
     "mpa_match_parts": (_INT, [_P] * 7 + [_I64] * 5 + [_P] * 6),
+    "mpa_match_parts_rmat": (_INT, [_P] * 7 + [_I64] * 5 + [_P] * 6),
     "mpa_quat_sanitize": (_INT, [_P, _I64, _P, _P, _P]),
     "mpa_loss_reduce_forward": (_INT, [_P, _P, _I64, _I64, _P, _P, _P]),
     "mpa_loss_reduce_backward": (_INT, [_P, _P, _P, _I64, _I64, _P, _P]),
@@ -98,9 +99,21 @@ SIGNATURES: dict[str, tuple] = {
     "mpa_adam_step_dev": (_INT, [_P, _P, _P, _P, _I64, _P, _F32, _F32, _F32, _F32, _INT, _P, _P]),
     "mpa_grad_clip_workspace": (_INT, [_P]),
     "mpa_grad_clip_coef": (_INT, [_P, _I64, _F32, _P, _F32, _P, _P, _P]),
+    "mpa_quat_to_rmat": (_INT, [_P, _I64, _P, _P]),
+    "mpa_assembly_loss_forward_rmat": (_INT, [_P] * 6 + [_I64, _I64, _I64, _INT, _INT, _P, _P, _P, _P]),
+    "mpa_assembly_loss_forward_rmat_timed": (_INT, [_P] * 6 + [_I64, _I64, _I64, _INT, _INT, _P, _P, _P, _P, _P]),
+    "mpa_assembly_loss_forward_rmat_ordered": (_INT, [_P] * 6 + [_I64, _I64, _I64, _INT, _INT, _P, _INT, _P, _P, _P, _P, _P]),
+    "mpa_assembly_loss_backward_rmat": (_INT, [_P] * 7 + [_I64, _I64, _I64, _INT, _P, _P, _P, _P, _P]),
+    "mpa_rot6d_to_rmat_forward": (_INT, [_P, _I64, _P, _P]),
+    "mpa_rot6d_to_rmat_backward": (_INT, [_P, _P, _I64, _P, _P]),
+    "mpa_pose_apply_rmat_forward": (_INT, [_P, _P, _P, _P, _F32, _I64, _I64, _P, _P]),
+    "mpa_pose_apply_rmat_backward": (_INT, [_P, _P, _P, _P, _F32, _I64, _I64, _P, _P, _P, _P]),
+    "mpa_pose_head6_workspace": (_INT, [_I64, _I64, _P]),
+    "mpa_pose_head6_forward": (_INT, [_P, _P, _I64, _I64, _P, _P, _P, _P]),
+    "mpa_pose_head6_backward": (_INT, [_P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P]),
 }
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 _lib = None
 
 

@@ -31,9 +31,20 @@ class BaseModel(nn.Module):
         super().__init__()
         self.cfg = cfg
         self.rot_type = cfg.model.rot_type
-        if self.rot_type != "quat":
+        # pose = (rotation, translation): a quaternion or the 6D rotation form (base_model.py:29-43 of the reference)
+        if self.rot_type == "quat":
+            self.pose_dim = 3 + 4
+        elif self.rot_type == "rmat":
+            self.pose_dim = 3 + 6
+        else:
             raise NotImplementedError(f"rotation {self.rot_type} is not supported")
-        self.pose_dim = 7
+        zero_pose = torch.zeros(1, 1, self.pose_dim)
+        zero_pose[..., 0] = 1.0  # identity quaternion, or the first two rows of the identity matrix; zero translation
+        if self.rot_type == "rmat":
+            zero_pose[..., 4] = 1.0
+        # a plain attribute upstream; a non-persistent buffer here (same state_dict keys) so that it lives on the
+        # module's device: a host-to-device copy inside forward cannot be captured into a HIP graph
+        self.register_buffer("zero_pose", zero_pose, persistent=False)
         self.semantic = cfg.data.dataset != "geometry"
         self.max_num_part = cfg.data.max_num_part
         self.pc_feat_dim = cfg.model.pc_feat_dim
@@ -41,7 +52,7 @@ class BaseModel(nn.Module):
         self.sample_iter = cfg.loss.get("sample_iter", 1)
         # fused HIP loss path for geometric data (csrc/assembly_loss.hip); the per-function path is
         # kept for the semantic datasets and as a cross-check.  keep_pts: also return the transformed
-        # clouds (only visualisation needs them).
+        # clouds (only visualisation needs them).  Quaternions and rotation matrices alike.
         self.fused_loss = True
         self.keep_pts = False
 
@@ -59,7 +70,8 @@ class BaseModel(nn.Module):
         wrapped into `part_rot` here, like base_model.py:128-132 (non-destructively)."""
         data_dict = dict(data_dict)
         if "part_rot" not in data_dict:
-            data_dict["part_rot"] = Rotation3D(data_dict.pop("part_quat"), rot_type="quat")
+            part_rot = Rotation3D(data_dict.pop("part_quat"), rot_type="quat")
+            data_dict["part_rot"] = part_rot if self.rot_type == "quat" else part_rot.convert(self.rot_type)
         return self.loss_function(data_dict, optimizer_idx=optimizer_idx)
 
     # ---- GT <-> prediction matching (semantic datasets only) --------------------------------------
@@ -102,8 +114,8 @@ class BaseModel(nn.Module):
                 if (ids_host[b] == group).any():
                     idx[b, group - 1] = torch.randperm(N)[:n].to(torch.int32)
         idx = idx.pin_memory().to(part_pcs.device, non_blocking=True)
-        new_trans, new_q = match_parts(part_pcs, pred_trans, pred_rot.rot, gt_trans, gt_rot.rot, match_ids, idx)
-        return new_trans, Rotation3D(new_q, rot_type=self.rot_type)
+        new_trans, new_rot = match_parts(part_pcs, pred_trans, pred_rot.rot, gt_trans, gt_rot.rot, match_ids, idx)
+        return new_trans, Rotation3D(new_rot, rot_type=self.rot_type)
 
     # ---- loss assembly ------------------------------------------------------------------------------
     def _calc_loss(self, out_dict, data_dict):

@@ -30,6 +30,7 @@
 #include "assembly_internal.h"
 #include "chamfer_core.h"
 #include "common.h"
+#include "mat3.h"
 
 namespace {
 
@@ -73,6 +74,27 @@ __device__ __forceinline__ void quat_apply(const Quat q, float px, float py, flo
 
 __device__ __forceinline__ Quat load_quat(const float* q) { return Quat{q[0], q[1], q[2], q[3]}; }
 
+// The rotation of part m in the forms the loss takes: RW = 4 quaternions [B*P][4] (w, x, y, z), RW = 9 row-major rotation
+// matrices [B*P][9] (rot_type='rmat'; mat3.h arithmetic, the reference's `r @ v[..., None]`).
+template <int RW>
+struct PartRot;
+template <>
+struct PartRot<4> {
+  Quat q;
+  __device__ __forceinline__ PartRot(const float* r, int m) : q(load_quat(r + 4 * m)) {}
+  __device__ __forceinline__ void apply(float px, float py, float pz, float& ox, float& oy, float& oz) const {
+    quat_apply(q, px, py, pz, ox, oy, oz);
+  }
+};
+template <>
+struct PartRot<9> {
+  mpa::Mat3 r;
+  __device__ __forceinline__ PartRot(const float* p, int m) : r(mpa::load_mat3(p + 9LL * m)) {}
+  __device__ __forceinline__ void apply(float px, float py, float pz, float& ox, float& oy, float& oz) const {
+    mpa::mat3_rotate(r, px, py, pz, ox, oy, oz);
+  }
+};
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -96,6 +118,7 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
 
 // ---- pose kernel ----------------------------------------------------------------------------------
 // grid = B*P blocks.  partial layout: [B*P][5] = {l2sum, cd1sum, cd2sum, scd1sum, scd2sum}.
+template <int RW>
 __global__ __launch_bounds__(kThreads) void assembly_pose_kernel(
     const float* __restrict__ pcs, const float* __restrict__ valids, const float* __restrict__ q1,
     const float* __restrict__ t1, const float* __restrict__ q2, const float* __restrict__ t2, int N,
@@ -106,7 +129,7 @@ __global__ __launch_bounds__(kThreads) void assembly_pose_kernel(
   __shared__ float box[kThreads / 64][12];
   const int m = blockIdx.x;
   if (m == 0 && threadIdx.x == 0 && ticket != nullptr) *ticket = 0u;  // of the grid sorts' "last block" election
-  const Quat qa = load_quat(q1 + 4 * m), qb = load_quat(q2 + 4 * m);
+  const PartRot<RW> qa(q1, m), qb(q2, m);
   const float ta0 = t1[3 * m], ta1 = t1[3 * m + 1], ta2 = t1[3 * m + 2];
   const float tb0 = t2[3 * m], tb1 = t2[3 * m + 1], tb2 = t2[3 * m + 2];
   const long long base = 3LL * m * N;
@@ -115,8 +138,8 @@ __global__ __launch_bounds__(kThreads) void assembly_pose_kernel(
     const int count = fill_pads ? N : 1;
     for (int n = threadIdx.x; n < count; n += kThreads) {
       float ax, ay, az, bx, by, bz;
-      quat_apply(qa, kPadFill, kPadFill, kPadFill, ax, ay, az);
-      quat_apply(qb, kPadFill, kPadFill, kPadFill, bx, by, bz);
+      qa.apply(kPadFill, kPadFill, kPadFill, ax, ay, az);
+      qb.apply(kPadFill, kPadFill, kPadFill, bx, by, bz);
       const long long o = base + 3LL * n;
       S1[o] = ax + ta0; S1[o + 1] = ay + ta1; S1[o + 2] = az + ta2;
       S2[o] = bx + tb0; S2[o + 1] = by + tb1; S2[o + 2] = bz + tb2;
@@ -132,8 +155,8 @@ __global__ __launch_bounds__(kThreads) void assembly_pose_kernel(
     const long long o = base + 3LL * n;
     const float px = pcs[o], py = pcs[o + 1], pz = pcs[o + 2];
     float ax, ay, az, bx, by, bz;
-    quat_apply(qa, px, py, pz, ax, ay, az);
-    quat_apply(qb, px, py, pz, bx, by, bz);
+    qa.apply(px, py, pz, ax, ay, az);
+    qb.apply(px, py, pz, bx, by, bz);
     R1[o] = ax; R1[o + 1] = ay; R1[o + 2] = az;
     R2[o] = bx; R2[o + 1] = by; R2[o + 2] = bz;
     const float s1[3] = {ax + ta0, ay + ta1, az + ta2}, s2[3] = {bx + tb0, by + tb1, bz + tb2};
@@ -187,6 +210,7 @@ struct LeafOut {
   float* part[4];
 };
 
+template <int RW>
 __global__ __launch_bounds__(kThreads) void assembly_pose_leaf_kernel(
     const float4* __restrict__ sorted, const float* __restrict__ valids, const float* __restrict__ q1,
     const float* __restrict__ t1, const float* __restrict__ q2, const float* __restrict__ t2, int P, int N, int Npad,
@@ -198,7 +222,7 @@ __global__ __launch_bounds__(kThreads) void assembly_pose_leaf_kernel(
   const int m = blockIdx.x, p = m % P;
   if (m == 0 && threadIdx.x < 2) heavy_counters[threadIdx.x] = 0;  // of the two searches' second passes
   if (m == 0 && threadIdx.x == 0 && ticket != nullptr) *ticket = 0u;  // of the grid sorts' "last block" election
-  const Quat qa = load_quat(q1 + 4 * m), qb = load_quat(q2 + 4 * m);
+  const PartRot<RW> qa(q1, m), qb(q2, m);
   const float ta[3] = {t1[3 * m], t1[3 * m + 1], t1[3 * m + 2]};
   const float tb[3] = {t2[3 * m], t2[3 * m + 1], t2[3 * m + 2]};
   const long long base = 3LL * m * N;
@@ -206,8 +230,8 @@ __global__ __launch_bounds__(kThreads) void assembly_pose_leaf_kernel(
     const int count = fill_pads ? N : 1;
     for (int n = threadIdx.x; n < count; n += kThreads) {
       float ax, ay, az, bx, by, bz;
-      quat_apply(qa, kPadFill, kPadFill, kPadFill, ax, ay, az);
-      quat_apply(qb, kPadFill, kPadFill, kPadFill, bx, by, bz);
+      qa.apply(kPadFill, kPadFill, kPadFill, ax, ay, az);
+      qb.apply(kPadFill, kPadFill, kPadFill, bx, by, bz);
       const long long o = base + 3LL * n;
       S1[o] = ax + ta[0]; S1[o + 1] = ay + ta[1]; S1[o + 2] = az + ta[2];
       S2[o] = bx + tb[0]; S2[o + 1] = by + tb[1]; S2[o + 2] = bz + tb[2];
@@ -226,8 +250,8 @@ __global__ __launch_bounds__(kThreads) void assembly_pose_leaf_kernel(
     const int n = __float_as_int(r.w);
     const bool real = in && n >= 0;
     float ax, ay, az, bx, by, bz;
-    quat_apply(qa, r.x, r.y, r.z, ax, ay, az);
-    quat_apply(qb, r.x, r.y, r.z, bx, by, bz);
+    qa.apply(r.x, r.y, r.z, ax, ay, az);
+    qb.apply(r.x, r.y, r.z, bx, by, bz);
     const float s1[3] = {ax + ta[0], ay + ta[1], az + ta[2]}, s2[3] = {bx + tb[0], by + tb[1], bz + tb[2]};
     if (real) {
       const long long o = base + 3LL * n;
@@ -412,7 +436,23 @@ __global__ __launch_bounds__(kThreads) void assembly_nn_kernel(
 }
 
 // ---- finalize ---------------------------------------------------------------------------------------
+// rot_loss of one part, matrix form (loss.py:76-82): mean over the nine entries of (I - R1^T R2)^2
+__device__ __forceinline__ float rmat_rot_loss(const float* __restrict__ r1, const float* __restrict__ r2) {
+  float s = 0.0f;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const float mij = (r1[i] * r2[j] + r1[3 + i] * r2[3 + j]) + r1[6 + i] * r2[6 + j];  // (R1^T R2)_ij
+      const float d = (i == j ? 1.0f : 0.0f) - mij;
+      s += d * d;
+    }
+  }
+  return s / 9.0f;
+}
+
 // grid = B blocks of 64 threads.  losses [5][B].
+template <int RW>
 __global__ __launch_bounds__(64) void assembly_finalize_kernel(
     const float* __restrict__ valids, const float* __restrict__ q1, const float* __restrict__ t1,
     const float* __restrict__ q2, const float* __restrict__ t2, const float* __restrict__ partial,
@@ -427,9 +467,13 @@ __global__ __launch_bounds__(64) void assembly_finalize_kernel(
     if (v != 0.0f) {
       const float dx = t1[3 * m] - t2[3 * m], dy = t1[3 * m + 1] - t2[3 * m + 1], dz = t1[3 * m + 2] - t2[3 * m + 2];
       trans = ((dx * dx + dy * dy) + dz * dz) * v;
-      const float dot = q1[4 * m] * q2[4 * m] + q1[4 * m + 1] * q2[4 * m + 1] + q1[4 * m + 2] * q2[4 * m + 2] +
-                        q1[4 * m + 3] * q2[4 * m + 3];
-      cosine = (1.0f - __builtin_fabsf(dot)) * v;
+      if constexpr (RW == 4) {
+        const float dot = q1[4 * m] * q2[4 * m] + q1[4 * m + 1] * q2[4 * m + 1] + q1[4 * m + 2] * q2[4 * m + 2] +
+                          q1[4 * m + 3] * q2[4 * m + 3];
+        cosine = (1.0f - __builtin_fabsf(dot)) * v;
+      } else {
+        cosine = rmat_rot_loss(q1 + 9LL * m, q2 + 9LL * m) * v;
+      }
       float c1 = 0.0f, c2 = 0.0f, s1 = 0.0f, s2 = 0.0f;
       // (the two searches may cut a part into different numbers of tiles: brute force / grid vs leaf search)
       const long long nblk_p = (long long)B * P * tiles_p, nblk_s = (long long)B * P * tiles_s;
@@ -493,7 +537,9 @@ __device__ __forceinline__ void accumulate(PoseGrad& a, float w, float ux, float
   }
 }
 
-// closed-form terms of pose component k (0..3 quaternion, 4..6 translation) of part m: translation L2, quaternion cosine
+// closed-form terms of pose component k (0..RW-1 rotation, RW..RW+2 translation) of part m: translation L2, rotation term.
+// Matrix form: L = (1/9) sum_ij (d_ij - M_ij)^2, M = R1^T R2  ->  dL/dR1[a][i] = (2/9) sum_j (M_ij - d_ij) R2[a][j].
+template <int RW>
 __device__ __forceinline__ float pose_closed_form(const float* __restrict__ go, const float* __restrict__ valids,
                                                   const float* __restrict__ q1, const float* __restrict__ t1,
                                                   const float* __restrict__ q2, const float* __restrict__ t2, int B,
@@ -503,12 +549,62 @@ __device__ __forceinline__ float pose_closed_form(const float* __restrict__ go, 
   if (vb[m % P] == 0.0f) return 0.0f;
   float nv = 0.0f;
   for (int i = 0; i < P; ++i) nv += vb[i];
-  if (k >= 4) return (go[0 * B + b] / nv) * 2.0f * (t1[3 * m + (k - 4)] - t2[3 * m + (k - 4)]);
+  if (k >= RW) return (go[0 * B + b] / nv) * 2.0f * (t1[3 * m + (k - RW)] - t2[3 * m + (k - RW)]);
+  if constexpr (RW == 9) {
+    const float* r1 = q1 + 9LL * m;
+    const float* r2 = q2 + 9LL * m;
+    const int a = k / 3, i = k % 3;
+    float g = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const float mij = (r1[i] * r2[j] + r1[3 + i] * r2[3 + j]) + r1[6 + i] * r2[6 + j];
+      g += (mij - (i == j ? 1.0f : 0.0f)) * r2[3 * a + j];
+    }
+    return (go[3 * B + b] / nv) * (2.0f / 9.0f) * g;
+  }
   const float dot = q1[4 * m] * q2[4 * m] + q1[4 * m + 1] * q2[4 * m + 1] + q1[4 * m + 2] * q2[4 * m + 2] +
                     q1[4 * m + 3] * q2[4 * m + 3];
   const float sgn = dot > 0.0f ? 1.0f : (dot < 0.0f ? -1.0f : 0.0f);
   return (go[3 * B + b] / nv) * (-sgn) * q2[4 * m + k];
 }
+
+// Per-thread sums of one part's pose gradient: RW = 4 through the quaternion Jacobian (7 sums: w, x, y, z, t), RW = 9 as
+// dL/dR_ij = sum g_i p_j and dL/dt = sum g (12 sums).  KS: stride of a slice's partial sums in psum.
+template <int RW>
+struct GradAcc;
+template <>
+struct GradAcc<4> {
+  static constexpr int K = 7, KS = 8;
+  float w, ux, uy, uz;
+  PoseGrad acc{0, 0, 0, 0, 0, 0, 0};
+  __device__ __forceinline__ GradAcc(const float* q1, int m)
+      : w(q1[4 * m]), ux(q1[4 * m + 1]), uy(q1[4 * m + 2]), uz(q1[4 * m + 3]) {}
+  __device__ __forceinline__ void add(float px, float py, float pz, float gx, float gy, float gz, bool with_trans) {
+    accumulate(acc, w, ux, uy, uz, px, py, pz, gx, gy, gz, with_trans);
+  }
+  __device__ __forceinline__ void values(float* v) const {
+    v[0] = acc.w, v[1] = acc.x, v[2] = acc.y, v[3] = acc.z, v[4] = acc.tx, v[5] = acc.ty, v[6] = acc.tz;
+  }
+};
+template <>
+struct GradAcc<9> {
+  static constexpr int K = 12, KS = 16;
+  float a[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  __device__ __forceinline__ GradAcc(const float*, int) {}
+  __device__ __forceinline__ void add(float px, float py, float pz, float gx, float gy, float gz, bool with_trans) {
+    const float p[3] = {px, py, pz}, g[3] = {gx, gy, gz};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) a[3 * i + j] += g[i] * p[j];
+      if (with_trans) a[9 + i] += g[i];
+    }
+  }
+  __device__ __forceinline__ void values(float* v) const {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) v[k] = a[k];
+  }
+};
 
 // grid = B*P blocks.  go [5][B] = d(total)/d(loss term).  Writes gq [B*P][4], gt [B*P][3] (pred pose).
 __global__ __launch_bounds__(kThreads) void assembly_backward_kernel(
@@ -617,27 +713,159 @@ __global__ __launch_bounds__(kThreads) void assembly_backward_kernel(
       psum[((long long)m * S + sl) * 8 + k] = s;
       return;
     }
-    s += pose_closed_form(go, valids, q1, t1, q2, t2, B, P, m, k);
+    s += pose_closed_form<4>(go, valids, q1, t1, q2, t2, B, P, m, k);
     if (k < 4) gq[4 * m + k] = s;
     else gt[3 * m + (k - 4)] = s;
   }
 }
 
+// The same for rotation matrices (rot_type='rmat'): dL/dR as nine fixed-order sums instead of the quaternion Jacobian.
+// (The quaternion kernel above is kept as it was rather than instantiated from this template: it compiles to the same
+// instructions as before.)
+// grid = B*P blocks.  go [5][B] = d(total)/d(loss term).  Writes gq [B*P][RW], gt [B*P][3] (pred pose).
+template <int RW>
+__global__ __launch_bounds__(kThreads) void assembly_backward_mat_kernel(
+    const float* __restrict__ go, const float* __restrict__ pcs, const float* __restrict__ valids,
+    const float* __restrict__ q1, const float* __restrict__ t1, const float* __restrict__ q2,
+    const float* __restrict__ t2, const float* __restrict__ R1, const float* __restrict__ R2,
+    const float* __restrict__ S1, const float* __restrict__ S2, const int* __restrict__ ip1,
+    const int* __restrict__ ip2, const int* __restrict__ is1, const int* __restrict__ is2, int B,
+    int P, int N, int training, float* __restrict__ gq, float* __restrict__ gt, float* __restrict__ psum) {
+  // gridDim.y = S slices of the point range per part (the scans below are chains of L2 latencies: one 4-wave block
+  // per part leaves the chip at ~5 waves per CU); S > 1: the 7 partial sums of a slice go to psum[(m * S + s) * 8 + k]
+  // and assembly_backward_finish_kernel adds them in slice order.
+  constexpr int K = GradAcc<RW>::K, KS = GradAcc<RW>::KS;
+  __shared__ float red[kThreads / 64][K];
+  const int m = blockIdx.x, b = m / P, p = m % P;
+  const int S = (int)gridDim.y, sl = (int)blockIdx.y;
+  const int n_lo = (int)((long long)sl * N / S), n_hi = (int)((long long)(sl + 1) * N / S);
+  const float* vb = valids + (long long)b * P;
+  float nv = 0.0f;
+  for (int k = 0; k < P; ++k) nv += vb[k];
+  const bool valid = vb[p] != 0.0f;
+  GradAcc<RW> acc(q1, m);
+  const float inv_n = 1.0f / (float)N;
+  const float c_cd = 2.0f * go[1 * B + b] * inv_n / nv;
+  const float c_l2 = 2.0f * go[4 * B + b] * inv_n / nv;
+  const float c_s = 2.0f * (training ? go[2 * B + b] / (float)(P * N) : go[2 * B + b] * inv_n / nv);
+  const long long base = 3LL * m * N, sbase = 3LL * b * P * N;
+
+  if (valid) {
+    // A. this part's own points as QUERIES (part-CD dir 1, point-wise L2, shape-CD dir 1)
+    for (int n = n_lo + threadIdx.x; n < n_hi; n += kThreads) {
+      const long long o = base + 3LL * n;
+      const float px = pcs[o], py = pcs[o + 1], pz = pcs[o + 2];
+      const float ax = R1[o], ay = R1[o + 1], az = R1[o + 2];
+      // a stored index of -1 (no candidate below 1e32: NaN / inf poses of a diverged step) contributes nothing,
+      // like chamfer_kernel.cu:199-208 for idx = -1 — and must not be used as an address
+      const int i1 = ip1[(long long)m * N + n], i2 = is1[(long long)m * N + n];
+      const float k_cd = i1 >= 0 ? c_cd : 0.0f, k_s = i2 >= 0 ? c_s : 0.0f;
+      const long long j = base + 3LL * (i1 >= 0 ? i1 : 0);
+      float gx = k_cd * (ax - R2[j]) + c_l2 * (ax - R2[o]);
+      float gy = k_cd * (ay - R2[j + 1]) + c_l2 * (ay - R2[o + 1]);
+      float gz = k_cd * (az - R2[j + 2]) + c_l2 * (az - R2[o + 2]);
+      acc.add(px, py, pz, gx, gy, gz, false);
+      const long long js = sbase + 3LL * (i2 >= 0 ? i2 : 0);
+      gx = k_s * (S1[o] - S2[js]);
+      gy = k_s * (S1[o + 1] - S2[js + 1]);
+      gz = k_s * (S1[o + 2] - S2[js + 2]);
+      acc.add(px, py, pz, gx, gy, gz, true);
+    }
+    // B. this part's points as matched TARGETS of its GT copy (part-CD dir 2)
+    for (int k = n_lo + threadIdx.x; k < n_hi; k += kThreads) {
+      const int jraw = ip2[(long long)m * N + k], jn = jraw >= 0 ? jraw : 0;
+      const float k_cd = jraw >= 0 ? c_cd : 0.0f;
+      const long long o = base + 3LL * k, j = base + 3LL * jn;
+      const float gx = -k_cd * (R2[o] - R1[j]), gy = -k_cd * (R2[o + 1] - R1[j + 1]),
+                  gz = -k_cd * (R2[o + 2] - R1[j + 2]);
+      acc.add(pcs[j], pcs[j + 1], pcs[j + 2], gx, gy, gz, false);
+    }
+  }
+  // C. this part's points as matched TARGETS of any valid GT point of the sample (shape-CD dir 2).
+  //    Also runs for padded parts: their representative could, in principle, be somebody's nearest.
+  //    The scan is a chain of L2 latencies (one index per thread and GT part, a match is rare): the indices of UP parts
+  //    are requested together.
+  constexpr int UP = 4;
+  for (int pp0 = 0; pp0 < P; pp0 += UP) {
+    for (int k = n_lo + threadIdx.x; k < n_hi; k += kThreads) {
+      int jj[UP];
+#pragma unroll
+      for (int u = 0; u < UP; ++u) {
+        const int pp = pp0 + u < P ? pp0 + u : P - 1;
+        jj[u] = is2[((long long)b * P + pp) * N + k];
+      }
+#pragma unroll
+      for (int u = 0; u < UP; ++u) {
+        const int pp = pp0 + u, j = jj[u];
+        if (pp >= P || vb[pp] == 0.0f) continue;
+        if (j < p * N || j >= (p + 1) * N) continue;  // not a point of this part (a range test, not an integer division)
+        const long long o = 3LL * (((long long)b * P + pp) * N + k), jt = sbase + 3LL * j;
+        const float gx = -c_s * (S2[o] - S1[jt]), gy = -c_s * (S2[o + 1] - S1[jt + 1]),
+                    gz = -c_s * (S2[o + 2] - S1[jt + 2]);
+        float px = kPadFill, py = kPadFill, pz = kPadFill;
+        if (valid) {
+          px = pcs[jt];
+          py = pcs[jt + 1];
+          pz = pcs[jt + 2];
+        }
+        acc.add(px, py, pz, gx, gy, gz, true);
+      }
+    }
+  }
+
+  float vals[K];
+  acc.values(vals);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const float s = wave_sum(vals[k]);
+    if (lane == 0) red[wave][k] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < K) {
+    float s = 0.0f;
+#pragma unroll
+    for (int v = 0; v < kThreads / 64; ++v) s += red[v][threadIdx.x];
+    const int k = threadIdx.x;
+    if (S > 1) {
+      psum[((long long)m * S + sl) * KS + k] = s;
+      return;
+    }
+    s += pose_closed_form<RW>(go, valids, q1, t1, q2, t2, B, P, m, k);
+    if (k < RW) gq[RW * m + k] = s;
+    else gt[3 * m + (k - RW)] = s;
+  }
+}
+
+template <int RW>
+constexpr auto backward_kernel() {
+  if constexpr (RW == 4)
+    return &assembly_backward_kernel;
+  else
+    return &assembly_backward_mat_kernel<RW>;
+}
+
 // S > 1: one thread per (part, pose component)
+template <int RW>
 __global__ void assembly_backward_finish_kernel(const float* __restrict__ go, const float* __restrict__ valids,
                                                 const float* __restrict__ q1, const float* __restrict__ t1,
                                                 const float* __restrict__ q2, const float* __restrict__ t2,
                                                 const float* __restrict__ psum, int B, int P, int S,
                                                 float* __restrict__ gq, float* __restrict__ gt) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= B * P * 8) return;
-  const int m = e >> 3, k = e & 7;
-  if (k == 7) return;
+  constexpr int KS = GradAcc<RW>::KS, SH = RW == 4 ? 3 : 4;
+  if (e >= B * P * KS) return;
+  const int m = e >> SH, k = e & (KS - 1);
+  if constexpr (RW == 4) {
+    if (k == 7) return;
+  } else {
+    if (k >= GradAcc<RW>::K) return;
+  }
   float s = 0.0f;
-  for (int q = 0; q < S; ++q) s += psum[((long long)m * S + q) * 8 + k];  // slice order: deterministic
-  s += pose_closed_form(go, valids, q1, t1, q2, t2, B, P, m, k);
-  if (k < 4) gq[4 * m + k] = s;
-  else gt[3 * m + (k - 4)] = s;
+  for (int q = 0; q < S; ++q) s += psum[((long long)m * S + q) * KS + k];  // slice order: deterministic
+  s += pose_closed_form<RW>(go, valids, q1, t1, q2, t2, B, P, m, k);
+  if (k < RW) gq[RW * m + k] = s;
+  else gt[3 * m + (k - RW)] = s;
 }
 
 // floats the leaf search adds to the workspace: order + 4 record arrays (float4 per slot), 4 x leaf boxes, 4 x part boxes
@@ -794,12 +1022,14 @@ extern "C" int mpa_assembly_loss_forward_timed(const float* part_pcs, const floa
 // `search`: -1 = MPA_SHAPE_SEARCH or the default (see search_mode), 0 brute, 1 grid, 2 leaf, 3 auto.
 // `order` (nullable): the k-d order of this batch's parts from mpa_assembly_order — a function of part_pcs and valids
 // only, so one ordering serves every loss evaluation of a step (GNN iterations, min-of-N samples); null: computed here.
-extern "C" int mpa_assembly_loss_forward_ordered(const float* part_pcs, const float* valids,
-                                                 const float* quat_pred, const float* trans_pred,
-                                                 const float* quat_gt, const float* trans_gt, int64_t B,
-                                                 int64_t P, int64_t N, int training, int fill_pad_points,
-                                                 const float* order, int search, float* float_ws, int32_t* int_ws,
-                                                 float* losses, void* const* events, void* stream) {
+namespace {
+// RW = 4: quaternion poses, RW = 9: rotation matrices (the same launches; only the pose, finalize and backward kernels
+// read the rotation)
+template <int RW>
+int loss_forward(const float* part_pcs, const float* valids, const float* quat_pred, const float* trans_pred,
+                 const float* quat_gt, const float* trans_gt, int64_t B, int64_t P, int64_t N, int training,
+                 int fill_pad_points, const float* order, int search, float* float_ws, int32_t* int_ws, float* losses,
+                 void* const* events, void* stream) {
   auto mark = [&](int k) {
     if (events != nullptr && events[k] != nullptr)  // (entries may be null: time only some of the phases)
       (void)hipEventRecord(reinterpret_cast<hipEvent_t>(events[k]), mpa::as_stream(stream));
@@ -834,7 +1064,7 @@ extern "C" int mpa_assembly_loss_forward_ordered(const float* part_pcs, const fl
       lo.leaf[c] = w.leaf[c];
       lo.part[c] = w.pbox[c];
     }
-    hipLaunchKernelGGL(assembly_pose_leaf_kernel, dim3(parts), dim3(kThreads), 0, s,
+    hipLaunchKernelGGL(assembly_pose_leaf_kernel<RW>, dim3(parts), dim3(kThreads), 0, s,
                        reinterpret_cast<const float4*>(order), valids, quat_pred, trans_pred, quat_gt, trans_gt, (int)P,
                        (int)N, npad, fill_pad_points, w.R1, w.R2, w.S1, w.S2, w.partial, lo,
                        mpa::leaf_heavy_counters(w.scratch), mode == 3 ? mpa::grid_bbox(w.grid_f, B, P, N) : (float*)nullptr,
@@ -867,14 +1097,14 @@ extern "C" int mpa_assembly_loss_forward_ordered(const float* part_pcs, const fl
                                     w.shape_tiles, nullptr, nullptr, s, route, 4);
     mark(3);
     const int nw = npad >= 64 ? npad / 64 : 1;  // every wave of a valid part leaves its distance sum
-    hipLaunchKernelGGL(assembly_finalize_kernel, dim3((unsigned)B), dim3(64), 0, s, valids, quat_pred,
+    hipLaunchKernelGGL(assembly_finalize_kernel<RW>, dim3((unsigned)B), dim3(64), 0, s, valids, quat_pred,
                        trans_pred, quat_gt, trans_gt, w.partial, part_gate ? (const float*)w.part_tiles : (const float*)w.wsum_part,
                        (const float*)w.wsum_shape, (int)B, (int)P, (int)N, part_gate ? mpa::gate_tiles(N, N) : nw, nw, training, losses,
                        (const float*)w.shape_tiles, w.tiles, (const int*)route);
     mark(4);
     return mpa::check_launch("assembly_loss_forward");
   }
-  hipLaunchKernelGGL(assembly_pose_kernel, dim3(parts), dim3(kThreads), 0, s, part_pcs, valids,
+  hipLaunchKernelGGL(assembly_pose_kernel<RW>, dim3(parts), dim3(kThreads), 0, s, part_pcs, valids,
                      quat_pred, trans_pred, quat_gt, trans_gt, (int)N, fill_pad_points, w.R1, w.R2,
                      w.S1, w.S2, w.partial, mpa::grid_bbox(w.grid_f, B, P, N), mpa::grid_ticket(w.grid_i, B));
   mark(1);
@@ -907,11 +1137,49 @@ extern "C" int mpa_assembly_loss_forward_ordered(const float* part_pcs, const fl
     hipLaunchKernelGGL((assembly_nn_kernel<2, mpa::kChunkMin, true>), grid, dim3(kThreads), 0, s, valids,
                        w.S1, w.S2, (int)B, (int)P, (int)N, w.tiles, remap, w.is1, w.is2, w.shape_tiles);
   mark(3);
-  hipLaunchKernelGGL(assembly_finalize_kernel, dim3((unsigned)B), dim3(64), 0, s, valids, quat_pred,
+  hipLaunchKernelGGL(assembly_finalize_kernel<RW>, dim3((unsigned)B), dim3(64), 0, s, valids, quat_pred,
                      trans_pred, quat_gt, trans_gt, w.partial, w.part_tiles, w.shape_tiles, (int)B,
                      (int)P, (int)N, tiles_part, w.tiles, training, losses, (const float*)nullptr, 0, (const int*)nullptr);
   mark(4);
   return mpa::check_launch("assembly_loss_forward");
+}
+
+template <int RW>
+int loss_backward(const float* grad_losses, const float* part_pcs, const float* valids, const float* quat_pred,
+                  const float* trans_pred, const float* quat_gt, const float* trans_gt, int64_t B, int64_t P, int64_t N,
+                  int training, const float* float_ws, const int32_t* int_ws, float* grad_quat, float* grad_trans,
+                  void* stream) {
+  MPA_REQUIRE(B >= 0 && P >= 0 && N >= 0, "assembly_loss_backward: negative size");
+  if (B == 0) return MPA_OK;
+  MPA_REQUIRE(P >= 1 && P <= 64 && N >= 1, "assembly_loss_backward: need 1 <= P <= 64 and N >= 1");
+  MPA_REQUIRE(grad_losses && part_pcs && valids && quat_pred && trans_pred && quat_gt && trans_gt &&
+                  float_ws && int_ws && grad_quat && grad_trans, "assembly_loss_backward: null pointer");
+  const Workspace w = carve(const_cast<float*>(float_ws), const_cast<int32_t*>(int_ws), B, P, N,
+                            pick_q(B, P, N));
+  // four slices of the point range per part when the (forward-only) tile-sum area (4 * B*P * tiles floats) is big enough
+  // for their partials (KS per slice: 8 quaternion, 16 matrix)
+  const int S = RW == 4 ? (w.tiles >= 8 ? 4 : 1) : (w.tiles >= 16 ? 4 : (w.tiles >= 8 ? 2 : 1));
+  auto* kernel = backward_kernel<RW>();
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(B * P), (unsigned)S), dim3(kThreads), 0,
+                     mpa::as_stream(stream), grad_losses, part_pcs, valids, quat_pred, trans_pred,
+                     quat_gt, trans_gt, w.R1, w.R2, w.S1, w.S2, w.ip1, w.ip2, w.is1, w.is2, (int)B,
+                     (int)P, (int)N, training, grad_quat, grad_trans, w.part_tiles);
+  if (S > 1)
+    hipLaunchKernelGGL(assembly_backward_finish_kernel<RW>, dim3((unsigned)((B * P * GradAcc<RW>::KS + 255) / 256)), dim3(256), 0,
+                       mpa::as_stream(stream), grad_losses, valids, quat_pred, trans_pred, quat_gt, trans_gt,
+                       (const float*)w.part_tiles, (int)B, (int)P, S, grad_quat, grad_trans);
+  return mpa::check_launch("assembly_loss_backward");
+}
+}  // namespace
+
+extern "C" int mpa_assembly_loss_forward_ordered(const float* part_pcs, const float* valids,
+                                                 const float* quat_pred, const float* trans_pred,
+                                                 const float* quat_gt, const float* trans_gt, int64_t B,
+                                                 int64_t P, int64_t N, int training, int fill_pad_points,
+                                                 const float* order, int search, float* float_ws, int32_t* int_ws,
+                                                 float* losses, void* const* events, void* stream) {
+  return loss_forward<4>(part_pcs, valids, quat_pred, trans_pred, quat_gt, trans_gt, B, P, N, training, fill_pad_points,
+                         order, search, float_ws, int_ws, losses, events, stream);
 }
 
 extern "C" int mpa_assembly_loss_backward(const float* grad_losses, const float* part_pcs,
@@ -920,22 +1188,42 @@ extern "C" int mpa_assembly_loss_backward(const float* grad_losses, const float*
                                           const float* trans_gt, int64_t B, int64_t P, int64_t N,
                                           int training, const float* float_ws, const int32_t* int_ws,
                                           float* grad_quat, float* grad_trans, void* stream) {
-  MPA_REQUIRE(B >= 0 && P >= 0 && N >= 0, "assembly_loss_backward: negative size");
-  if (B == 0) return MPA_OK;
-  MPA_REQUIRE(P >= 1 && P <= 64 && N >= 1, "assembly_loss_backward: need 1 <= P <= 64 and N >= 1");
-  MPA_REQUIRE(grad_losses && part_pcs && valids && quat_pred && trans_pred && quat_gt && trans_gt &&
-                  float_ws && int_ws && grad_quat && grad_trans, "assembly_loss_backward: null pointer");
-  const Workspace w = carve(const_cast<float*>(float_ws), const_cast<int32_t*>(int_ws), B, P, N,
-                            pick_q(B, P, N));
-  // four slices of the point range per part when the (forward-only) tile-sum area is big enough for their partials
-  const int S = w.tiles >= 8 ? 4 : 1;
-  hipLaunchKernelGGL(assembly_backward_kernel, dim3((unsigned)(B * P), (unsigned)S), dim3(kThreads), 0,
-                     mpa::as_stream(stream), grad_losses, part_pcs, valids, quat_pred, trans_pred,
-                     quat_gt, trans_gt, w.R1, w.R2, w.S1, w.S2, w.ip1, w.ip2, w.is1, w.is2, (int)B,
-                     (int)P, (int)N, training, grad_quat, grad_trans, w.part_tiles);
-  if (S > 1)
-    hipLaunchKernelGGL(assembly_backward_finish_kernel, dim3((unsigned)((B * P * 8 + 255) / 256)), dim3(256), 0,
-                       mpa::as_stream(stream), grad_losses, valids, quat_pred, trans_pred, quat_gt, trans_gt,
-                       (const float*)w.part_tiles, (int)B, (int)P, S, grad_quat, grad_trans);
-  return mpa::check_launch("assembly_loss_backward");
+  return loss_backward<4>(grad_losses, part_pcs, valids, quat_pred, trans_pred, quat_gt, trans_gt, B, P, N, training,
+                          float_ws, int_ws, grad_quat, grad_trans, stream);
+}
+
+// ---- matrix form (rot_type='rmat'): rmat_pred / rmat_gt [B,P,3,3] in place of the quaternions ------------------------------------
+extern "C" int mpa_assembly_loss_forward_rmat_ordered(const float* part_pcs, const float* valids, const float* rmat_pred,
+                                                      const float* trans_pred, const float* rmat_gt, const float* trans_gt,
+                                                      int64_t B, int64_t P, int64_t N, int training, int fill_pad_points,
+                                                      const float* order, int search, float* float_ws, int32_t* int_ws,
+                                                      float* losses, void* const* events, void* stream) {
+  return loss_forward<9>(part_pcs, valids, rmat_pred, trans_pred, rmat_gt, trans_gt, B, P, N, training, fill_pad_points,
+                         order, search, float_ws, int_ws, losses, events, stream);
+}
+
+extern "C" int mpa_assembly_loss_forward_rmat(const float* part_pcs, const float* valids, const float* rmat_pred,
+                                              const float* trans_pred, const float* rmat_gt, const float* trans_gt,
+                                              int64_t B, int64_t P, int64_t N, int training, int fill_pad_points,
+                                              float* float_ws, int32_t* int_ws, float* losses, void* stream) {
+  return loss_forward<9>(part_pcs, valids, rmat_pred, trans_pred, rmat_gt, trans_gt, B, P, N, training, fill_pad_points,
+                         nullptr, -1, float_ws, int_ws, losses, nullptr, stream);
+}
+
+extern "C" int mpa_assembly_loss_forward_rmat_timed(const float* part_pcs, const float* valids, const float* rmat_pred,
+                                                    const float* trans_pred, const float* rmat_gt, const float* trans_gt,
+                                                    int64_t B, int64_t P, int64_t N, int training, int fill_pad_points,
+                                                    float* float_ws, int32_t* int_ws, float* losses, void* const* events,
+                                                    void* stream) {
+  return loss_forward<9>(part_pcs, valids, rmat_pred, trans_pred, rmat_gt, trans_gt, B, P, N, training, fill_pad_points,
+                         nullptr, -1, float_ws, int_ws, losses, events, stream);
+}
+
+extern "C" int mpa_assembly_loss_backward_rmat(const float* grad_losses, const float* part_pcs, const float* valids,
+                                               const float* rmat_pred, const float* trans_pred, const float* rmat_gt,
+                                               const float* trans_gt, int64_t B, int64_t P, int64_t N, int training,
+                                               const float* float_ws, const int32_t* int_ws, float* grad_rmat,
+                                               float* grad_trans, void* stream) {
+  return loss_backward<9>(grad_losses, part_pcs, valids, rmat_pred, trans_pred, rmat_gt, trans_gt, B, P, N, training,
+                          float_ws, int_ws, grad_rmat, grad_trans, stream);
 }

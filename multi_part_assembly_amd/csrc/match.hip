@@ -14,6 +14,7 @@
 //                       (p <= 20 here: a few thousand steps);
 //   match_apply_kernel  new_gt[slot] = gt[member[col4row[rank(slot)]]] for grouped slots, identity elsewhere.
 #include "common.h"
+#include "mat3.h"
 #include "quat.h"
 
 namespace {
@@ -30,7 +31,9 @@ __device__ __forceinline__ int group_members(const int* __restrict__ ids, int P,
   return c;
 }
 
-// grid = (B*G, P*P) blocks of 128 threads; cost [B*G][P][P]
+// grid = (B*G, P*P) blocks of 128 threads; cost [B*G][P][P].  RW = 4: quaternions (w, x, y, z); RW = 9: row-major
+// rotation matrices (rot_type='rmat', mat3.h arithmetic)
+template <int RW>
 __global__ __launch_bounds__(kCostT) void match_cost_kernel(
     const float* __restrict__ pcs, const float* __restrict__ t1, const float* __restrict__ q1,
     const float* __restrict__ t2, const float* __restrict__ q2, const int* __restrict__ match_ids,
@@ -50,11 +53,17 @@ __global__ __launch_bounds__(kCostT) void match_cost_kernel(
     const float* a = pcs + (mi * N + s) * 3;
     const float* c = pcs + (mj * N + s) * 3;
     float x, y, z;
-    mpa::quat_rotate(mpa::Quat{q1[4 * mi], q1[4 * mi + 1], q1[4 * mi + 2], q1[4 * mi + 3]}, a[0], a[1], a[2], x, y, z);
+    if constexpr (RW == 4)
+      mpa::quat_rotate(mpa::Quat{q1[4 * mi], q1[4 * mi + 1], q1[4 * mi + 2], q1[4 * mi + 3]}, a[0], a[1], a[2], x, y, z);
+    else
+      mpa::mat3_rotate(mpa::load_mat3(q1 + 9 * mi), a[0], a[1], a[2], x, y, z);
     A[t][0] = x + t1[3 * mi];
     A[t][1] = y + t1[3 * mi + 1];
     A[t][2] = z + t1[3 * mi + 2];
-    mpa::quat_rotate(mpa::Quat{q2[4 * mj], q2[4 * mj + 1], q2[4 * mj + 2], q2[4 * mj + 3]}, c[0], c[1], c[2], x, y, z);
+    if constexpr (RW == 4)
+      mpa::quat_rotate(mpa::Quat{q2[4 * mj], q2[4 * mj + 1], q2[4 * mj + 2], q2[4 * mj + 3]}, c[0], c[1], c[2], x, y, z);
+    else
+      mpa::mat3_rotate(mpa::load_mat3(q2 + 9 * mj), c[0], c[1], c[2], x, y, z);
     Bc[t][0] = x + t2[3 * mj];
     Bc[t][1] = y + t2[3 * mj + 1];
     Bc[t][2] = z + t2[3 * mj + 2];
@@ -176,6 +185,7 @@ __global__ __launch_bounds__(64) void lsap_kernel(const float* __restrict__ cost
 
 // grid = B blocks of 64 threads (thread = slot).  Rows of a group are its members in ascending slot order (the
 // reference indexes with the sorted member list), so member rank r receives the GT pose of member col4row[r].
+template <int RW>
 __global__ __launch_bounds__(64) void match_apply_kernel(const float* __restrict__ gt_t, const float* __restrict__ gt_q,
                                                          const int* __restrict__ match_ids,
                                                          const int* __restrict__ col4row, int P, int G,
@@ -207,7 +217,7 @@ __global__ __launch_bounds__(64) void match_apply_kernel(const float* __restrict
 #pragma unroll
   for (int k = 0; k < 3; ++k) new_t[3 * o + k] = gt_t[3 * s + k];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) new_q[4 * o + k] = gt_q[4 * s + k];
+  for (int k = 0; k < RW; ++k) new_q[RW * o + k] = gt_q[RW * s + k];
 }
 
 }  // namespace
@@ -222,23 +232,44 @@ extern "C" int mpa_linear_sum_assignment(const float* cost, const int32_t* sizes
   return mpa::check_launch("linear_sum_assignment");
 }
 
-extern "C" int mpa_match_parts(const float* part_pcs, const float* pred_trans, const float* pred_quat,
-                               const float* gt_trans, const float* gt_quat, const int32_t* match_ids,
-                               const int32_t* sample_idx, int64_t B, int64_t P, int64_t N, int64_t G, int64_t n,
-                               float* cost_ws, int32_t* col4row_ws, float* new_trans, float* new_quat,
-                               int32_t* perm, void* stream) {
+namespace {
+template <int RW>
+int match_parts(const float* part_pcs, const float* pred_trans, const float* pred_quat, const float* gt_trans,
+                const float* gt_quat, const int32_t* match_ids, const int32_t* sample_idx, int64_t B, int64_t P,
+                int64_t N, int64_t G, int64_t n, float* cost_ws, int32_t* col4row_ws, float* new_trans,
+                float* new_quat, int32_t* perm, void* stream) {
   MPA_REQUIRE(B >= 0 && P >= 1 && P <= kMaxP && N >= 1 && G >= 1 && G <= P && n >= 1 && n <= kMaxN && n <= N,
               "match_parts: need 1 <= P <= 64, 1 <= G <= P, 1 <= n <= min(N, 128)");
   if (B == 0) return MPA_OK;
   MPA_REQUIRE(part_pcs && pred_trans && pred_quat && gt_trans && gt_quat && match_ids && sample_idx && cost_ws &&
                   col4row_ws && new_trans && new_quat && perm, "match_parts: null pointer");
   hipStream_t s = mpa::as_stream(stream);
-  hipLaunchKernelGGL(match_cost_kernel, dim3((unsigned)(B * G), (unsigned)(P * P)), dim3(kCostT), 0, s, part_pcs,
+  hipLaunchKernelGGL(match_cost_kernel<RW>, dim3((unsigned)(B * G), (unsigned)(P * P)), dim3(kCostT), 0, s, part_pcs,
                      pred_trans, pred_quat, gt_trans, gt_quat, match_ids, sample_idx, (int)P, (int)N, (int)G, (int)n,
                      cost_ws);
   hipLaunchKernelGGL(lsap_kernel, dim3((unsigned)(B * G)), dim3(64), 0, s, cost_ws, (const int*)nullptr, match_ids,
                      (int)P, (int)G, (int)P, col4row_ws);
-  hipLaunchKernelGGL(match_apply_kernel, dim3((unsigned)B), dim3(64), 0, s, gt_trans, gt_quat, match_ids, col4row_ws,
+  hipLaunchKernelGGL(match_apply_kernel<RW>, dim3((unsigned)B), dim3(64), 0, s, gt_trans, gt_quat, match_ids, col4row_ws,
                      (int)P, (int)G, new_trans, new_quat, perm);
   return mpa::check_launch("match_parts");
+}
+}  // namespace
+
+extern "C" int mpa_match_parts(const float* part_pcs, const float* pred_trans, const float* pred_quat,
+                               const float* gt_trans, const float* gt_quat, const int32_t* match_ids,
+                               const int32_t* sample_idx, int64_t B, int64_t P, int64_t N, int64_t G, int64_t n,
+                               float* cost_ws, int32_t* col4row_ws, float* new_trans, float* new_quat,
+                               int32_t* perm, void* stream) {
+  return match_parts<4>(part_pcs, pred_trans, pred_quat, gt_trans, gt_quat, match_ids, sample_idx, B, P, N, G, n,
+                        cost_ws, col4row_ws, new_trans, new_quat, perm, stream);
+}
+
+// the same with rotation matrices [B,P,3,3] (rot_type='rmat'): mat3.h arithmetic, 9-wide gather of the GT rotations
+extern "C" int mpa_match_parts_rmat(const float* part_pcs, const float* pred_trans, const float* pred_rmat,
+                                    const float* gt_trans, const float* gt_rmat, const int32_t* match_ids,
+                                    const int32_t* sample_idx, int64_t B, int64_t P, int64_t N, int64_t G, int64_t n,
+                                    float* cost_ws, int32_t* col4row_ws, float* new_trans, float* new_rmat,
+                                    int32_t* perm, void* stream) {
+  return match_parts<9>(part_pcs, pred_trans, pred_rmat, gt_trans, gt_rmat, match_ids, sample_idx, B, P, N, G, n,
+                        cost_ws, col4row_ws, new_trans, new_rmat, perm, stream);
 }

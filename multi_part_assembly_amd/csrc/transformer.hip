@@ -16,6 +16,7 @@
 //   * dropout masks come from a counter-based hash of (seed, site, element) and are REGENERATED in backward.
 // All reductions are fixed-order (no atomics): the step stays bit-reproducible.
 #include "common.h"
+#include "mat3.h"
 #include "tf_gemm.h"
 
 namespace {
@@ -1400,6 +1401,138 @@ __global__ __launch_bounds__(1024) void head_wgrad_kernel(const float* __restric
   }
 }
 
+// ---- pose head tail, 6D rotation (rot_type='rmat'): rot = normalize_rot6d(h . Wr^T + br) (reference regressor.py:6-27) ------
+__global__ __launch_bounds__(kT) void head6_fwd_kernel(const float* __restrict__ hfeat,
+                                                       const float* __restrict__ wr, const float* __restrict__ br,
+                                                       const float* __restrict__ wt, const float* __restrict__ bt,
+                                                       int M, int K, float* __restrict__ rot_raw,
+                                                       float* __restrict__ rot, float* __restrict__ trans) {
+  const int row = blockIdx.x * (kT / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= M) return;
+  float a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int k = lane; k < K; k += 64) {
+    const float x = hfeat[(long long)row * K + k];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) a[c] = __builtin_fmaf(x, wr[c * K + k], a[c]);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) a[6 + c] = __builtin_fmaf(x, wt[c * K + k], a[6 + c]);
+  }
+#pragma unroll
+  for (int c = 0; c < 9; ++c) a[c] = wave_sum(a[c]);
+  if (lane == 0) {
+    float r6[6], b[6], n[2];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+      r6[c] = a[c] + br[c];
+      rot_raw[6 * row + c] = r6[c];
+    }
+    mpa::gram_schmidt6(r6, b, n);
+#pragma unroll
+    for (int c = 0; c < 6; ++c) rot[6 * row + c] = b[c];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) trans[3 * row + c] = a[6 + c] + bt[c];
+  }
+}
+
+// backward of the 6D tail: d(rot_raw) through normalize_rot6d, dh = dr . Wr + dt . Wt, raw-gradient rows
+// dqt [M, 16] = (dr0..5, dt0..2, 0 ...) for head6_wgrad_kernel
+__global__ __launch_bounds__(kT) void head6_bwd_kernel(const float* __restrict__ rot_raw,
+                                                       const float* __restrict__ grot,
+                                                       const float* __restrict__ gtrans,
+                                                       const float* __restrict__ wr, const float* __restrict__ wt,
+                                                       const float* __restrict__ act, int M, int K,
+                                                       float* __restrict__ dqt, float* __restrict__ dh) {
+  const int row = blockIdx.x * (kT / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= M) return;
+  float r6[6], g[6], dr[6], dt[3];
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    r6[c] = rot_raw[6 * row + c];
+    g[c] = grot[6 * row + c];
+  }
+  mpa::gram_schmidt6_backward(r6, g, dr);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) dt[c] = gtrans[3 * row + c];
+  if (lane < 16) {
+    float v = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) v = lane == c ? dr[c] : v;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v = lane == 6 + c ? dt[c] : v;
+    dqt[16 * row + lane] = v;
+  }
+  for (int k = lane; k < K; k += 64) {
+    float a = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) a = __builtin_fmaf(dr[c], wr[c * K + k], a);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) a = __builtin_fmaf(dt[c], wt[c * K + k], a);
+    dh[(long long)row * K + k] = act[(long long)row * K + k] > 0.0f ? a : 0.2f * a;  // LeakyReLU(0.2) gate
+  }
+}
+
+// dWr[c][k] = sum_rows dqt[row][c] * h[row][k] (c < 6), dWt likewise (c = 6..8), biases = column sums of dqt.
+// As head_wgrad_kernel with 16-wide rows, staged 256 rows per tile (LDS: 16 KB of rows + 40 KB of partials).
+__global__ __launch_bounds__(1024) void head6_wgrad_kernel(const float* __restrict__ dqt,
+                                                           const float* __restrict__ hfeat, int M, int K,
+                                                           float* __restrict__ dwr, float* __restrict__ dbr,
+                                                           float* __restrict__ dwt, float* __restrict__ dbt) {
+  __shared__ float sm[16][10][64];
+  __shared__ float4 dq[256][4];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, k = blockIdx.x * 64 + lane;
+  float a[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  constexpr int U = 16;  // 256 rows per tile -> 16 rows per wave, all loads in flight
+  for (int t0 = 0; t0 < M; t0 += 256) {
+    const int trows = M - t0 < 256 ? M - t0 : 256;
+    __syncthreads();
+    if ((int)threadIdx.x < 4 * trows)
+      dq[threadIdx.x >> 2][threadIdx.x & 3] = reinterpret_cast<const float4*>(dqt + 16LL * t0)[threadIdx.x];
+    __syncthreads();
+    for (int r0 = wave; r0 < trows; r0 += 16 * U) {
+      float xs[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int row = r0 + 16 * u;
+        xs[u] = (row < trows && k < K) ? hfeat[(long long)(t0 + row) * K + k] : 0.0f;
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int row = r0 + 16 * u;
+        if (row < trows) {  // wave-uniform: broadcast LDS reads
+          const float x = xs[u];
+          const float4 d0 = dq[row][0], d1 = dq[row][1], d2 = dq[row][2];
+          a[0] = __builtin_fmaf(d0.x, x, a[0]);
+          a[1] = __builtin_fmaf(d0.y, x, a[1]);
+          a[2] = __builtin_fmaf(d0.z, x, a[2]);
+          a[3] = __builtin_fmaf(d0.w, x, a[3]);
+          a[4] = __builtin_fmaf(d1.x, x, a[4]);
+          a[5] = __builtin_fmaf(d1.y, x, a[5]);
+          a[6] = __builtin_fmaf(d1.z, x, a[6]);
+          a[7] = __builtin_fmaf(d1.w, x, a[7]);
+          a[8] = __builtin_fmaf(d2.x, x, a[8]);
+          if (lane < 9) a[9] += reinterpret_cast<const float*>(&dq[row][0])[lane];  // bias gradients, lane = output
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 10; ++c) sm[wave][c][lane] = a[c];
+  __syncthreads();
+  if (wave < 10) {  // wave c reduces channel c over the 16 partials
+    float s = 0.0f;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) s += sm[w][wave][lane];
+    if (wave < 6) {
+      if (k < K) dwr[wave * K + k] = s;
+    } else if (wave < 9) {
+      if (k < K) dwt[(wave - 6) * K + k] = s;
+    } else if (blockIdx.x == 0 && lane < 9) {
+      if (lane < 6) dbr[lane] = s;
+      else dbt[lane - 6] = s;
+    }
+  }
+}
+
 // ---- host helpers ---------------------------------------------------------------------------------------------------------------
 // C = epi(LayerNorm(x) . W^T + bias) for K = 2 x kKP: the LayerNorm rides in the GEMM's operand load (g.ln_* set)
 template <int EPI>
@@ -1959,4 +2092,85 @@ extern "C" int mpa_pose_head_backward(const float* grad_rot, const float* grad_t
   launch_wgrad_group(wl, 2, s);  // both weight gradients in one launch, off the path to grad_x
   if (padded) launch_pad2(gx, grad_x, M, gw1, grad_params[0], 256, hp.Fp, F, s);  // drop the padding columns
   return mpa::check_launch("pose_head_backward");
+}
+
+// ---- pose head with the 6D rotation head (rot_type='rmat') ---------------------------------------------------------------------
+// params as mpa_pose_head_* with rot.w [6,128], rot.b [6].  ws: h1 [M,256] | h2 [M,128] | rot_raw [M,8] (6 used) | dqt [M,16] | d2 [M,128]
+// | d1 [M,256] | 64, then the padded copies as in head_pad.  The two GEMMs each way are the quaternion head's.
+static HeadPad head6_pad(float* ws, int64_t M, int64_t F) {
+  HeadPad h;
+  h.Fp = (F + 63) / 64 * 64;
+  h.x = ws + M * (256 + 128 + 8 + 16 + 128 + 256) + 64;
+  h.w = h.x + M * h.Fp;
+  h.dx = h.w + 256 * h.Fp;
+  h.dw = h.dx + M * h.Fp;
+  return h;
+}
+
+extern "C" int mpa_pose_head6_workspace(int64_t M, int64_t F, int64_t* float_elems) {
+  MPA_REQUIRE(M >= 0 && F >= 1 && F <= 4096 && float_elems, "pose_head6_workspace: need 1 <= F <= 4096");
+  *float_elems = M * (256 + 128 + 8 + 16 + 128 + 256) + 64;
+  if (F % 64 != 0) *float_elems += 2 * (M + 256) * ((F + 63) / 64 * 64);
+  return MPA_OK;
+}
+
+extern "C" int mpa_pose_head6_forward(const float* x, const float* const* params, int64_t M, int64_t F, float* ws,
+                                      float* rot6d, float* trans, void* stream) {
+  MPA_REQUIRE(M >= 0 && F >= 1 && F <= 4096, "pose_head6_forward: need 1 <= F <= 4096");
+  if (M == 0) return MPA_OK;
+  MPA_REQUIRE(M < (1LL << 31), "pose_head6_forward: too many rows");
+  MPA_REQUIRE(x && params && ws && rot6d && trans, "pose_head6_forward: null pointer");
+  hipStream_t s = mpa::as_stream(stream);
+  float* h1 = ws;
+  float* h2 = h1 + M * 256;
+  float* rot_raw = h2 + M * 128;
+  const float* w1 = params[0];
+  if (F % 64 != 0) {
+    const HeadPad hp = head6_pad(ws, M, F);
+    launch_pad2(x, hp.x, M, w1, hp.w, 256, F, hp.Fp, s);
+    x = hp.x, w1 = hp.w, F = hp.Fp;
+  }
+  launch_gemm<EPI_LEAKY>(gemm_args(x, w1, params[1], h1, (int)M, 256, (int)F), s);
+  launch_gemm<EPI_LEAKY>(gemm_args(h1, params[2], params[3], h2, (int)M, 128, 256), s);
+  hipLaunchKernelGGL(head6_fwd_kernel, dim3((unsigned)((M + 3) / 4)), dim3(kT), 0, s, h2, params[4], params[5],
+                     params[6], params[7], (int)M, 128, rot_raw, rot6d, trans);
+  return mpa::check_launch("pose_head6_forward");
+}
+
+extern "C" int mpa_pose_head6_backward(const float* grad_rot6d, const float* grad_trans, const float* x,
+                                       const float* const* params, int64_t M, int64_t F, float* ws, float* grad_x,
+                                       float* const* grad_params, void* stream) {
+  MPA_REQUIRE(M >= 0 && F >= 1 && F <= 4096, "pose_head6_backward: need 1 <= F <= 4096");
+  if (M == 0) return MPA_OK;
+  MPA_REQUIRE(M < (1LL << 31), "pose_head6_backward: too many rows");
+  MPA_REQUIRE(grad_rot6d && grad_trans && x && params && ws && grad_x && grad_params,
+              "pose_head6_backward: null pointer");
+  hipStream_t s = mpa::as_stream(stream);
+  float* h1 = ws;
+  float* h2 = h1 + M * 256;
+  float* rot_raw = h2 + M * 128;
+  float* dqt = rot_raw + M * 8;  // (rows of 8: every region stays 16-byte aligned for odd M)
+  float* d2 = dqt + M * 16;
+  float* d1 = d2 + M * 128;
+  const int Mi = (int)M;
+  const bool padded = F % 64 != 0;
+  const HeadPad hp = head6_pad(ws, M, F);  // (the forward call left x' and w' there; fc1.w has not changed since)
+  const float* w1 = padded ? hp.w : params[0];
+  const float* xin = padded ? hp.x : x;
+  float* gx = padded ? hp.dx : grad_x;
+  float* gw1 = padded ? hp.dw : grad_params[0];
+  const int Fi = (int)(padded ? hp.Fp : F);
+  hipLaunchKernelGGL(head6_bwd_kernel, dim3((unsigned)((M + 3) / 4)), dim3(kT), 0, s, rot_raw, grad_rot6d, grad_trans,
+                     params[4], params[6], h2, Mi, 128, dqt, d2);  // d2 = gradient at fc2's pre-activation
+  hipLaunchKernelGGL(head6_wgrad_kernel, dim3(2), dim3(1024), 0, s, dqt, h2, Mi, 128, grad_params[4], grad_params[5],
+                     grad_params[6], grad_params[7]);
+  GemmArgs ga = gemm_args(d2, params[2], nullptr, d1, Mi, 256, 128);  // fc2.weight is [128, 256] = [K, N]
+  ga.resid = h1;
+  launch_gemm<EPI_LEAKY_MASK, true>(ga, s);
+  launch_gemm<EPI_NONE, true>(gemm_args(d1, w1, nullptr, gx, Mi, Fi, 256), s);
+  const WgradArgs wl[2] = {wgrad_args(d2, h1, grad_params[2], grad_params[3], Mi, 128, 256),
+                           wgrad_args(d1, xin, gw1, grad_params[1], Mi, 256, Fi)};
+  launch_wgrad_group(wl, 2, s);
+  if (padded) launch_pad2(gx, grad_x, M, gw1, grad_params[0], 256, hp.Fp, F, s);  // drop the padding columns
+  return mpa::check_launch("pose_head6_backward");
 }

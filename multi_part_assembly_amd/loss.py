@@ -3,7 +3,7 @@
 
 The heavy parts run on the HIP library: pose application (csrc/pose.hip) and the Chamfer searches
 (csrc/chamfer.hip).  The O(B*P) reductions around them are a handful of torch ops on tiny tensors.
-`rot1/rot2` are `Rotation3D` (quaternion) objects.
+`rot1/rot2` are `Rotation3D` objects (quaternions or rotation matrices; the fused path takes quaternions).
 """
 from __future__ import annotations
 
@@ -13,7 +13,7 @@ import ctypes
 
 from . import _lib
 from .chamfer import chamfer_distance
-from .transforms import pose_apply, rot_pc
+from .transforms import pose_apply, pose_apply_rmat, rot_pc
 
 __all__ = ["geometric_assembly_loss", "part_order", "search_mode", "SEARCH_MODES", "LOSS_TERMS", "trans_l2_loss", "rot_l2_loss", "rot_cosine_loss", "rot_points_l2_loss",
            "rot_points_cd_loss", "shape_cd_loss", "repulsion_cd_loss"]
@@ -33,6 +33,12 @@ def _quat(rot):
     return rot.rot
 
 
+def _pose_apply(pts, rot, trans, mask, fill):
+    if rot.rot_type == "rmat":
+        return pose_apply_rmat(pts, rot.rot, trans, mask=mask, fill=fill)
+    return pose_apply(pts, _quat(rot), trans, mask=mask, fill=fill)
+
+
 def trans_l2_loss(trans1, trans2, valids):
     """Squared L2 between translations, [B, P, 3] x2 -> [B]."""
     return _valid_mean((trans1 - trans2).square().sum(-1), valids)
@@ -46,7 +52,15 @@ def rot_l2_loss(rot1, rot2, valids):
 
 
 def rot_cosine_loss(rot1, rot2, valids):
-    """1 - |<q1, q2>| per part."""
+    """1 - |<q1, q2>| per part; for rotation matrices the mean of the squared entries of I - R1^T R2 (loss.py:76-82)."""
+    if rot1.rot_type != rot2.rot_type:
+        raise ValueError(f"rotation types differ: {rot1.rot_type} vs {rot2.rot_type}")
+    if rot1.rot_type == "rmat":
+        B = rot1.shape[0]
+        r1, r2 = rot1.rot.reshape(-1, 3, 3), rot2.rot.reshape(-1, 3, 3)
+        iden = torch.eye(3, dtype=r1.dtype, device=r1.device).unsqueeze(0)
+        per_part = (iden - torch.bmm(r1.transpose(1, 2), r2)).pow(2).mean(dim=[-1, -2]).view(B, -1)
+        return _valid_mean(per_part, valids)
     q1, q2 = _quat(rot1), _quat(rot2)
     return _valid_mean(1.0 - (q1 * q2).sum(-1).abs(), valids)
 
@@ -78,8 +92,8 @@ def shape_cd_loss(pts, trans1, trans2, rot1, rot2, valids, ret_pts=False, traini
     """
     B, P, N, _ = pts.shape
     pts = pts.detach()
-    pts1 = pose_apply(pts, _quat(rot1), trans1, mask=valids, fill=PAD_FILL)
-    pts2 = pose_apply(pts, _quat(rot2), trans2, mask=valids, fill=PAD_FILL)
+    pts1 = _pose_apply(pts, rot1, trans1, mask=valids, fill=PAD_FILL)
+    pts2 = _pose_apply(pts, rot2, trans2, mask=valids, fill=PAD_FILL)
     dist1, dist2 = chamfer_distance(pts1.flatten(1, 2), pts2.flatten(1, 2))
     v = valids.float().detach()
     if training:
@@ -137,7 +151,8 @@ def part_order(part_pcs, valids):
 
 
 class _AssemblyLoss(torch.autograd.Function):
-    """All five geometric loss terms in 5 launches forward / 1 launch backward (csrc/assembly_loss.hip)."""
+    """All five geometric loss terms in 5 launches forward / 1 launch backward (csrc/assembly_loss.hip).  The rotations are
+    quaternions [B,P,4] or rotation matrices [B,P,3,3] (the `_rmat` entry points)."""
 
     @staticmethod
     def forward(ctx, part_pcs, valids, quat_pred, trans_pred, quat_gt, trans_gt, training, fill_pads, order=None,
@@ -161,7 +176,8 @@ class _AssemblyLoss(torch.autograd.Function):
             both = None
             if evs is not None or gs is not None:
                 both = (evs if evs is not None else [None] * 5) + (gs if gs is not None else [None] * 2)
-            st = L.mpa_assembly_loss_forward_ordered(
+            fwd = L.mpa_assembly_loss_forward_rmat_ordered if quat_pred.dim() == 4 else L.mpa_assembly_loss_forward_ordered
+            st = fwd(
                 _lib.ptr(part_pcs), _lib.ptr(valids), _lib.ptr(quat_pred), _lib.ptr(trans_pred),
                 _lib.ptr(quat_gt), _lib.ptr(trans_gt), B, P, N, int(training), int(fill_pads),
                 _lib.ptr(order) if order is not None else None, int(search),
@@ -193,7 +209,9 @@ class _AssemblyLoss(torch.autograd.Function):
         gt = torch.empty_like(trans_pred)
         grad_losses = grad_losses.contiguous()
         with torch.cuda.device(dev):
-            st = _lib.lib().mpa_assembly_loss_backward(
+            L = _lib.lib()
+            bwd = L.mpa_assembly_loss_backward_rmat if quat_pred.dim() == 4 else L.mpa_assembly_loss_backward
+            st = bwd(
                 _lib.ptr(grad_losses), _lib.ptr(part_pcs), _lib.ptr(valids), _lib.ptr(quat_pred),
                 _lib.ptr(trans_pred), _lib.ptr(quat_gt), _lib.ptr(trans_gt), B, P, N, ctx.training,
                 _lib.ptr(fws), _lib.ptr(iws), _lib.ptr(gq), _lib.ptr(gt), _lib.current_stream(dev))
@@ -262,7 +280,8 @@ def geometric_assembly_loss(part_pcs, pred_trans, pred_rot, gt_trans, gt_rot, va
 
     Returns ({name: [B]} for LOSS_TERMS, pts) where pts is None or, with ret_pts,
     (pred_trans_pts, gt_trans_pts) [B,P,N,3] as shape_cd_loss(..., ret_pts=True) returns them.
-    Gradients flow to pred_trans and pred_rot only (the GT pose is detached, as in the reference).
+    Gradients flow to pred_trans and pred_rot only (the GT pose is detached, as in the reference).  `pred_rot` and
+    `gt_rot` are quaternions or rotation matrices (both of the same type; rot_loss in the matching form, loss.py:59-84).
     `search`: "brute" | "grid" | "leaf" | "auto" (None: MPA_SHAPE_SEARCH, else "grid"): which exact searches run the two
     Chamfer terms — identical results.  `order`: `part_order(part_pcs, valids)` of this batch for "leaf" / "auto" when the
     caller evaluates the loss more than once per batch (computed by the call itself when None).
@@ -271,9 +290,12 @@ def geometric_assembly_loss(part_pcs, pred_trans, pred_rot, gt_trans, gt_rot, va
         raise RuntimeError("geometric_assembly_loss: only CUDA (HIP) tensors are supported")
     B, P, N, _ = part_pcs.shape
     f = lambda t: t.detach().to(torch.float32).contiguous()
+    if pred_rot.rot_type != gt_rot.rot_type:
+        raise ValueError(f"rotation types differ: {pred_rot.rot_type} vs {gt_rot.rot_type}")
+    rot = (lambda r: r.rot) if pred_rot.rot_type == "rmat" else _quat
     losses, pts = _AssemblyLoss.apply(
-        f(part_pcs), f(valids), _quat(pred_rot).to(torch.float32).contiguous(),
-        pred_trans.to(torch.float32).contiguous(), f(_quat(gt_rot)), f(gt_trans), bool(training),
+        f(part_pcs), f(valids), rot(pred_rot).to(torch.float32).contiguous(),
+        pred_trans.to(torch.float32).contiguous(), f(rot(gt_rot)), f(gt_trans), bool(training),
         bool(ret_pts), order, search_mode(search))
     terms = LossTerms((name, losses[i]) for i, name in enumerate(LOSS_TERMS))
     terms.stacked = (LOSS_TERMS, losses)

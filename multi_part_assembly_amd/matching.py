@@ -35,7 +35,8 @@ def linear_sum_assignment(cost: torch.Tensor, sizes: torch.Tensor | None = None)
 def match_parts(part_pcs, pred_trans, pred_quat, gt_trans, gt_quat, match_ids, sample_idx, ret_aux=False):
     """GT poses rearranged inside every group of equivalent parts so that they line up with the predictions at
     minimum Chamfer cost.  match_ids [B,P] (0 = unique / padded, g >= 1 = group g), sample_idx [B,G,n] point
-    indices per group slot.  Returns (new_trans [B,P,3], new_quat [B,P,4]) and, with ret_aux, also
+    indices per group slot; the rotations are quaternions [B,P,4] or rotation matrices [B,P,3,3].  Returns
+    (new_trans [B,P,3], new_rot in the rotations' shape) and, with ret_aux, also
     (perm [B,P], cost [B,G,P,P], col4row [B,G,P])."""
     if not part_pcs.is_cuda:
         raise RuntimeError("match_parts: only CUDA (HIP) tensors are supported")
@@ -48,12 +49,13 @@ def match_parts(part_pcs, pred_trans, pred_quat, gt_trans, gt_quat, match_ids, s
     cost = torch.empty((B, G, P, P), dtype=torch.float32, device=dev)
     col4row = torch.empty((B, G, P), dtype=torch.int32, device=dev)
     new_t = torch.empty((B, P, 3), dtype=torch.float32, device=dev)
-    new_q = torch.empty((B, P, 4), dtype=torch.float32, device=dev)
+    rmat = pred_quat.shape[-2:] == (3, 3)  # rotation matrices (rot_type='rmat') instead of quaternions
+    new_q = torch.empty((B, P) + tuple(pred_quat.shape[2:]), dtype=torch.float32, device=dev)
     perm = torch.empty((B, P), dtype=torch.int32, device=dev)
     args = [f(part_pcs), f(pred_trans), f(pred_quat), f(gt_trans), f(gt_quat), i32(match_ids), sample_idx]
     with torch.cuda.device(dev):
-        st = _lib.lib().mpa_match_parts(*[_lib.ptr(a) for a in args], B, P, N, G, n, _lib.ptr(cost),
-                                        _lib.ptr(col4row), _lib.ptr(new_t), _lib.ptr(new_q), _lib.ptr(perm),
-                                        _lib.current_stream(dev))
-    _lib.check(st, "mpa_match_parts")
+        fn = _lib.lib().mpa_match_parts_rmat if rmat else _lib.lib().mpa_match_parts
+        st = fn(*[_lib.ptr(a) for a in args], B, P, N, G, n, _lib.ptr(cost), _lib.ptr(col4row), _lib.ptr(new_t),
+                _lib.ptr(new_q), _lib.ptr(perm), _lib.current_stream(dev))
+    _lib.check(st, "mpa_match_parts_rmat" if rmat else "mpa_match_parts")
     return (new_t, new_q, perm, cost, col4row) if ret_aux else (new_t, new_q)

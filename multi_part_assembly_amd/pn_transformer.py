@@ -89,15 +89,12 @@ class PNTransformerRefine(PNTransformer):
     [pose -> positional encoding, added to the part tokens -> that round's transformer -> that round's pose head];
     the loss is summed over the rounds.  Same sub-module names (`corr_module.{i}`, `pose_predictor.{i}`,
     `corr_pos_enc.layers.*`).  Each round's transformer and every loss evaluation run on the HIP path; the pose
-    heads' odd input widths (features + 7 pose values) use the library-op fallback of `PoseRegressor`."""
+    heads' odd input widths (features + 7 or 9 pose values) use the library-op fallback of `PoseRegressor`."""
 
     def __init__(self, cfg):
         self.refine_steps = cfg.model.refine_steps
         self.pose_pc_feat = cfg.model.pose_pc_feat
-        super().__init__(cfg)
-        zero_pose = torch.zeros(1, 1, self.pose_dim)
-        zero_pose[..., 0] = 1.0
-        self.register_buffer("zero_pose", zero_pose, persistent=False)  # on the module's device: graph-capturable
+        super().__init__(cfg)  # (BaseModel registers `zero_pose`, the identity pose of cfg.model.rot_type)
         self.corr_pos_enc = PosEncoder([self.pose_dim, *cfg.model.transformer_pos_enc])
 
     def _init_corr_module(self):

@@ -1,9 +1,10 @@
 """Pose head — mirror of the reference's PoseRegressor / StocasticPoseRegressor
 (multi_part_assembly/models/modules/regressor.py:30-84); identical state_dict keys
-(`fc_layers.{0,2}.*`, `rot_head.*`, `trans_head.*`).  Quaternion output only.
+(`fc_layers.{0,2}.*`, `rot_head.*`, `trans_head.*`).  rot_type 'quat' (a unit quaternion) or 'rmat' (the 6D form
+of Zhou et al., made orthonormal by `normalize_rot6d`; `Rotation3D` turns it into a matrix).
 
-Compute: csrc/transformer.hip (`mpa_pose_head_*`): two fp32-MFMA GEMMs with the LeakyReLU fused, one
-kernel for both heads + the quaternion normalisation, deterministic backward.
+Compute: csrc/transformer.hip (`mpa_pose_head_*`, `mpa_pose_head6_*`): two fp32-MFMA GEMMs with the LeakyReLU fused,
+one kernel for both heads + the rotation's normalisation, deterministic backward.
 """
 from __future__ import annotations
 
@@ -15,26 +16,31 @@ import torch.nn.functional as F
 
 from . import _lib
 from .gradsink import GradSink
+from .rotation import normalize_rot6d
+
+# rot_type -> (width of the rotation head, C-ABI prefix)
+_HEADS = {"quat": (4, "mpa_pose_head"), "rmat": (6, "mpa_pose_head6")}
 
 
 class _PoseHeadFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, *params):
+    def forward(ctx, x, rot_type, *params):
         M, Fdim = x.shape
         dev = x.device
         lib = _lib.lib()
+        width, name = _HEADS[rot_type]
         n = ctypes.c_int64()
-        _lib.check(lib.mpa_pose_head_workspace(M, Fdim, ctypes.byref(n)), "mpa_pose_head_workspace")
+        _lib.check(getattr(lib, name + "_workspace")(M, Fdim, ctypes.byref(n)), name + "_workspace")
         ws = torch.empty(n.value, dtype=torch.float32, device=dev)
-        rot = torch.empty((M, 4), dtype=torch.float32, device=dev)
+        rot = torch.empty((M, width), dtype=torch.float32, device=dev)
         trans = torch.empty((M, 3), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             tok = _lib.KernelTimer.start(f"pose_head_forward[{M}x{Fdim}]")
-            st = lib.mpa_pose_head_forward(_lib.ptr(x), _lib.ptr_array(params), M, Fdim, _lib.ptr(ws),
-                                           _lib.ptr(rot), _lib.ptr(trans), _lib.current_stream(dev))
+            st = getattr(lib, name + "_forward")(_lib.ptr(x), _lib.ptr_array(params), M, Fdim, _lib.ptr(ws),
+                                                 _lib.ptr(rot), _lib.ptr(trans), _lib.current_stream(dev))
             _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_pose_head_forward")
-        ctx.params = params
+        _lib.check(st, name + "_forward")
+        ctx.params, ctx.name = params, name
         GradSink.note_use(params)
         ctx.save_for_backward(x, ws)
         return rot, trans
@@ -49,46 +55,47 @@ class _PoseHeadFn(torch.autograd.Function):
         grads, direct = GradSink.outputs(params)
         with torch.cuda.device(dev):
             tok = _lib.KernelTimer.start(f"pose_head_backward[{M}x{Fdim}]")
-            st = _lib.lib().mpa_pose_head_backward(
+            st = getattr(_lib.lib(), ctx.name + "_backward")(
                 _lib.ptr(grad_rot.contiguous()), _lib.ptr(grad_trans.contiguous()), _lib.ptr(x),
                 _lib.ptr_array(params), M, Fdim, _lib.ptr(ws), _lib.ptr(grad_x), _lib.ptr_array(grads),
                 _lib.current_stream(dev))
             _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_pose_head_backward")
+        _lib.check(st, ctx.name + "_backward")
         if direct:
             GradSink.delivered(params)
-            return (grad_x, *([None] * len(params)))
-        return (grad_x, *grads)
+            return (grad_x, None, *([None] * len(params)))
+        return (grad_x, None, *grads)
 
 
 class PoseRegressor(nn.Module):
     def __init__(self, feat_dim, rot_type="quat", norm_rot=True):
         super().__init__()
-        if rot_type != "quat":
+        if rot_type not in _HEADS:
             raise NotImplementedError(f"rotation {rot_type} is not supported")
         self.rot_type, self.norm_rot = rot_type, norm_rot
+        rot_dim = _HEADS[rot_type][0]
         self.fc_layers = nn.Sequential(nn.Linear(feat_dim, 256), nn.LeakyReLU(0.2),
                                        nn.Linear(256, 128), nn.LeakyReLU(0.2))
-        self.rot_head = nn.Linear(128, 4)
+        self.rot_head = nn.Linear(128, rot_dim)
         self.trans_head = nn.Linear(128, 3)
-        self.native = norm_rot  # csrc/transformer.hip normalises the quaternion in its head kernel
+        self.native = norm_rot  # csrc/transformer.hip normalises the rotation in its head kernel
 
     def forward(self, x):
-        """x [B, C] or [B, P, C] -> (rot [.., 4] unit-normalised, trans [.., 3])."""
+        """x [B, C] or [B, P, C] -> (rot [.., 4] unit-normalised or [.., 6] orthonormalised, trans [.., 3])."""
         if not x.is_cuda:
             raise RuntimeError("PoseRegressor: only CUDA (HIP) tensors are supported — no CPU fallback")
         if self.native:
             lead = x.shape[:-1]
             # (any input width: the library zero-pads odd widths — labels / noise appended — to its 64-column GEMM panels)
             rot, trans = _PoseHeadFn.apply(
-                x.reshape(-1, x.shape[-1]).float().contiguous(), self.fc_layers[0].weight,
+                x.reshape(-1, x.shape[-1]).float().contiguous(), self.rot_type, self.fc_layers[0].weight,
                 self.fc_layers[0].bias, self.fc_layers[2].weight, self.fc_layers[2].bias, self.rot_head.weight,
                 self.rot_head.bias, self.trans_head.weight, self.trans_head.bias)
-            return rot.view(*lead, 4), trans.view(*lead, 3)
-        hidden = self.fc_layers(x)  # un-normalised quaternions (no shipped config): library ops
+            return rot.view(*lead, rot.shape[-1]), trans.view(*lead, 3)
+        hidden = self.fc_layers(x)  # un-normalised rotations (no shipped config): library ops
         rot = self.rot_head(hidden)
         if self.norm_rot:
-            rot = F.normalize(rot, p=2, dim=-1)
+            rot = F.normalize(rot, p=2, dim=-1) if self.rot_type == "quat" else normalize_rot6d(rot)
         return rot, self.trans_head(hidden)
 
 
