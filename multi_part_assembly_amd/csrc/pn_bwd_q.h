@@ -626,12 +626,13 @@ __global__ __launch_bounds__(64 * (NS + ND + NW), (NS + ND + NW + 3) / 4) void p
 
 // ---- the never-stored last layer in the same form ---------------------------------------------------------------------------
 // conv5's output Y5 is never stored (pointnet.hip: top-2 records), so its backward always was  dA4 = A4 Q + c0 + S W5  with S the
-// sparse arg-max gradient (CSR by 32-row tile: erow, ech, eval, tptr) and  dW5  from the Gram matrix G = A4^T A4.  This kernel
+// sparse arg-max gradient and  dW5  from the Gram matrix G = A4^T A4.  S W5 arrives as finished rows: pn_top_csr_kernel sums
+// every distinct arg-max row once (rsum) and leaves one record per 32-row tile (rtile).  This kernel
 // does the input gradient AND the Gram matrix in one pass over Y4 (two kernels that read it once each took 139 + 79 us:
 // LABBOOK 6.1) with the wave roles of pn_bwd_q_kernel: stagers convert Y4 rows into the A panel and stage the unit's
-// CSR entries (three-stage request pipeline: tile offsets, entries, LDS); four input-gradient waves (one 32-column tile each,
+// sparse rows (three-stage request pipeline: tile record, row sums, LDS); four input-gradient waves (one 32-column tile each,
 // Q register-resident) leave A Q + c0 raw in LDS; four weight-gradient waves accumulate the ten upper tiles of G; both kinds
-// then finish the previous unit: sparse rows added from the staged entries, ReLU mask, dZ4 stores, BatchNorm-backward sums.
+// then finish the previous unit: sparse rows added from the staged sums, ReLU mask, dZ4 stores, BatchNorm-backward sums.
 struct PnGTile {
   signed char a, b;  // column tiles of A: row tile and column tile of G (a <= b)
 };
@@ -644,14 +645,12 @@ struct PnGPlan {
     return false;
   }
 };
-constexpr int kTopES = 32;  // CSR entries of a 32-row tile staged in LDS (more: read from memory by the epilogue, rare)
 
 template <int CIN, int NS, int ND, int NW>
 __global__ __launch_bounds__(64 * (NS + ND + NW), (NS + ND + NW + 3) / 4) void pn_bwd_top_q_kernel(
     const float* __restrict__ y_prev, const float* __restrict__ bn_prev, const float* __restrict__ q,
     const int* __restrict__ vlist, int N, float* __restrict__ dz_prev, float* __restrict__ partial,
-    float* __restrict__ dwpart, const int* __restrict__ erow, const int* __restrict__ ech,
-    const float* __restrict__ eval, const int* __restrict__ tptr, const float* __restrict__ w5, int F) {
+    float* __restrict__ dwpart, const int2* __restrict__ rtile, const float* __restrict__ rsum, int F) {
   constexpr int K = 0;  // (PN_T_REPORT prints them)
   constexpr bool FIRST = false;
   constexpr int RB = 32, SA = 6 * CIN + 16, CT = CIN / 32, KA = CIN / 16, KW = RB / 16;
@@ -772,85 +771,58 @@ __global__ __launch_bounds__(64 * (NS + ND + NW), (NS + ND + NW + 3) / 4) void p
         *reinterpret_cast<pn_bf16x4*>(p + 4 * CIN) = pl;
       }
     };
-    // S W5 of a unit, per row: request pipeline inside every stager wave (no cross-wave hand-over): tile offsets of unit u at
-    // iteration u - 3, its entries at u - 2 (lane l holds entry l & 31: row, channel, alpha * grad), the row sums at u - 1 —
-    // entry e is broadcast with v_readlane, a matching row costs one weight-row load from the L2, here, in the waves that wait
-    // for memory anyway.  Entry order = channel order, fixed.  The epilogue reads the sums at u + 1: three slots.
-    int tp0 = 0, tp1 = 0, e_row = 0, e_ch = 0, e_cnt = 0, e_pb = 0;
-    float e_val = 0.0f;
-    auto tp_fetch = [&](int it, int m) {
-      const int st = n0_of(it) >> 5;
-      tp0 = tptr[(long long)m * T1 + st];
-      tp1 = tptr[(long long)m * T1 + st + 1];
-    };
-    auto ent_fetch = [&](int it, int m) {  // uses the offsets of this unit (tp0 / tp1 hold them now)
-      e_cnt = tp1 - tp0;
-      e_pb = tp0;
-      const int l = lane & 31, e = l < e_cnt ? l : 0;
-      const long long g = (long long)m * F + tp0 + e;
-      const bool has = e_cnt > 0;
-      e_row = has ? erow[g] - n0_of(it) : -1;
-      e_ch = has ? ech[g] : 0;
-      e_val = has ? eval[g] : 0.0f;
-    };
-    auto rowsum_build = [&](int it, int m) {  // this thread's NLY rows x 4 columns (e_* hold this unit's entries now)
-      const int slot = it % 3, n0 = n0_of(it);
-      const int cnt = __builtin_amdgcn_readfirstlane(e_cnt), pb = __builtin_amdgcn_readfirstlane(e_pb);
-      float4 acc[NLY];
+    // S W5 of a unit, per row, from the table pn_top_csr_kernel built (rtile, rsum): the same request pipeline as the Y4 rows,
+    // one stage longer.  The tile record of unit u is requested at iteration u - 3; at u - 2 every thread requests its NLY rows
+    // x 4 columns of the finished sums (a row of the tile that has one is found by a popcount in the record's mask: no loop,
+    // no load that waits for another); at u - 1 they go to LDS, zeros for the rows without an arg-max.  The epilogue reads the
+    // sums at u + 1: three slots.
+    int2 rt = make_int2(0, 0);
+    float4 rv[NLY];
+    auto rt_fetch = [&](int it, int m) { rt = rtile[(long long)m * T1 + (n0_of(it) >> 5)]; };
+    auto rows_fetch = [&](int m) {  // uses the record of this unit (rt holds it now)
+      const float4* rs4 = reinterpret_cast<const float4*>(rsum) + (long long)m * F * QC + cy4;
 #pragma unroll
-      for (int i = 0; i < NLY; ++i) acc[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      for (int e = 0; e < cnt; ++e) {
-        int er, ec;
-        float ev;
-        if (e < kTopES) {
-          er = __builtin_amdgcn_readlane(e_row, e);
-          ec = __builtin_amdgcn_readlane(e_ch, e);
-          ev = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, e_val), e));
-        } else {  // unusually crowded tile
-          const long long g = (long long)m * F + pb + e;
-          er = erow[g] - n0;
-          ec = ech[g];
-          ev = eval[g];
-        }
-#pragma unroll
-        for (int i = 0; i < NLY; ++i)
-          if (er == ry0 + i * RG) {
-            const float4 wv = reinterpret_cast<const float4*>(w5 + (long long)ec * CIN)[cy4];
-            acc[i].x = __builtin_fmaf(ev, wv.x, acc[i].x);
-            acc[i].y = __builtin_fmaf(ev, wv.y, acc[i].y);
-            acc[i].z = __builtin_fmaf(ev, wv.z, acc[i].z);
-            acc[i].w = __builtin_fmaf(ev, wv.w, acc[i].w);
-          }
+      for (int i = 0; i < NLY; ++i) {
+        const int rl = ry0 + i * RG;
+        const unsigned mask = (unsigned)rt.y;
+        const int jr = rt.x + __builtin_popcount(mask & ((1u << rl) - 1u));
+        rv[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if ((mask >> rl) & 1u) rv[i] = rs4[(long long)jr * QC];
       }
+    };
+    auto rows_stash = [&](int it) {
+      const int slot = it % 3;
 #pragma unroll
-      for (int i = 0; i < NLY; ++i) *reinterpret_cast<float4*>(&rowsum[slot][(ry0 + i * RG) * CIN + 4 * cy4]) = acc[i];
+      for (int i = 0; i < NLY; ++i) *reinterpret_cast<float4*>(&rowsum[slot][(ry0 + i * RG) * CIN + 4 * cy4]) = rv[i];
     };
     int m1 = part_of(1), m2 = part_of(2), m3 = part_of(3);
     if (n_it > 0) {
       const int m0 = part_of(0);
-      tp_fetch(0, m0);
+      rt_fetch(0, m0);
       fetch(0, m0);
-      ent_fetch(0, m0);
-      if (n_it > 1) tp_fetch(1, m1);
-      rowsum_build(0, m0);
-      if (n_it > 1) ent_fetch(1, m1);
-      if (n_it > 2) tp_fetch(2, m2);
+      rows_fetch(m0);
+      if (n_it > 1) rt_fetch(1, m1);
+      rows_stash(0);
       stash(0, 0);
-      if (n_it > 1) fetch(1, m1);
+      if (n_it > 1) {
+        fetch(1, m1);
+        rows_fetch(m1);
+      }
+      if (n_it > 2) rt_fetch(2, m2);
     }
     __syncthreads();  // panel 0 and unit 0's sparse rows are complete
     PN_T_DECL
     for (int it = 0; it < n_it; ++it) {
       const int m4 = part_of(it + 4);
       if (it + 1 < n_it) {
-        rowsum_build(it + 1, m1);  // (its entries were requested an iteration ago, its offsets two)
+        rows_stash(it + 1);  // (requested an iteration ago, like the unit's Y4 rows)
         stash(it + 1, (it + 1) & 1);
       }
       if (it + 2 < n_it) {
-        ent_fetch(it + 2, m2);
         fetch(it + 2, m2);
+        rows_fetch(m2);  // (its tile record was requested an iteration ago)
       }
-      if (it + 3 < n_it) tp_fetch(it + 3, m3);
+      if (it + 3 < n_it) rt_fetch(it + 3, m3);
       m1 = m2;
       m2 = m3;
       m3 = m4;

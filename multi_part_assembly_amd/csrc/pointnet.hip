@@ -295,44 +295,133 @@ __global__ void pn_top_finalize_kernel(const float* __restrict__ topv, const int
   ybest[i] = y;
 }
 
-// Per part: the arg-max entries (row, channel, alpha*grad) sorted by 32-row tile (ties: channel order), and the
-// tile offsets — the sparse operand of the last layer's input gradient.  grid = M, block = F threads.
-// Blocks [M, M + C4 + 1) of the same launch compute Q and c0 (pn_top_q below): two small, independent, latency-bound jobs
-// that both wait for the coefficients of the last BatchNorm — side by side instead of one after the other.
+// Per part: the sparse operand of the last layer's input gradient, dA4 += S W5, as finished rows.  The arg-max entries
+// (row, channel, alpha * grad) are sorted by (row, channel) in LDS; every DISTINCT arg-max row gets its sum
+//     rsum[m][j][:] = sum over the row's entries, in channel order, of  val * W5[channel][:]
+// (from 0.0f, one __builtin_fmaf per entry and column: the order and the instruction are part of the result), and every
+// 32-row tile t a record rtile[m][t] = {j of its first distinct row, bit r set: row 32 t + r has a sum}.  Rows are numbered in
+// ascending order, so row 32 t + r of a tile is  j = rtile.x + popcount(rtile.y & ((1 << r) - 1)).
+// Blocks [0, C4 + 1) compute Q and c0 (pn_top_q below), blocks [C4 + 1, C4 + 1 + M) one part each: two independent, latency-bound
+// jobs that both wait for the coefficients of the last BatchNorm — side by side instead of one after the other (Q's chain of
+// F dependent FMAs is the longer one: its blocks go first).  block = 1024 threads: the first F sort (one counting scan of
+// single-word keys; leaders of the rows and their numbers from ballots), then sixteen lanes per row, two float4 columns each.
 __device__ __forceinline__ void pn_top_q_row(const float* __restrict__ w5, const float* __restrict__ coef, int F, int C4,
                                              float* __restrict__ q, int k);
-__global__ void pn_top_csr_kernel(const int* __restrict__ argmax, const float* __restrict__ gfeat,
-                                  const float* __restrict__ coef, const float* __restrict__ valids, int N, int F,
-                                  int* __restrict__ erow, int* __restrict__ ech, float* __restrict__ eval,
-                                  int* __restrict__ tptr, int M, const float* __restrict__ w5, int C4,
-                                  float* __restrict__ q) {
-  extern __shared__ int bins[];  // [F]
-  if ((int)blockIdx.x >= M) {
-    pn_top_q_row(w5, coef, F, C4, q, (int)blockIdx.x - M);
+constexpr int kTopRowsThreads = 1024;
+__host__ __device__ constexpr int pn_top_csr_lds_words(int F, int T) { return 4 * F + 12 + 2 * (T + 1); }
+__global__ __launch_bounds__(kTopRowsThreads) void pn_top_csr_kernel(
+    const int* __restrict__ argmax, const float* __restrict__ gfeat, const float* __restrict__ coef,
+    const float* __restrict__ valids, int N, int F, int2* __restrict__ rtile, float* __restrict__ rsum, int M,
+    const float* __restrict__ w5, float* __restrict__ q) {
+  constexpr int C4 = 128, QC = C4 / 4, LPR = 16;  // lanes per row
+  constexpr int kNone = 0x7fffffff;
+  // [F] keys (row << 8 | channel) | [F] keys, sorted | [F] values, sorted | [F + 1] row starts | [3] D, pad | [4] leaders of a
+  // wave | [4] entries of a wave | [T + 1] first row of a tile | [T + 1] row mask of a tile
+  extern __shared__ __attribute__((aligned(16))) int sm[];
+  if ((int)blockIdx.x <= C4) {
+    pn_top_q_row(w5, coef, F, C4, q, (int)blockIdx.x);
     return;
   }
-  const int m = blockIdx.x, c = threadIdx.x, T = (N + 31) / 32;
+  const int m = (int)blockIdx.x - (C4 + 1), c = threadIdx.x, T = (N + 31) / 32;
   if (valids[m] == 0.0f) return;
-  const int arg = argmax[(long long)m * F + c];
-  const int bin = arg >= 0 ? arg >> 5 : T;  // T: no entry
-  bins[c] = bin;
+  int* keys = sm;
+  int* skey = sm + F;
+  float* sval = reinterpret_cast<float*>(sm + 2 * F);
+  int* rs = sm + 3 * F;
+  int* wlead = sm + 4 * F + 4;
+  int* wcnt = wlead + 4;
+  int* toff = wcnt + 4;
+  int* tmask = toff + T + 1;
+  int key = kNone;
+  if (c < F) {
+    const int arg = argmax[(long long)m * F + c];
+    key = arg >= 0 ? (arg << 8 | c) : kNone;  // (F <= 256, rows < 32768)
+    keys[c] = key;
+    skey[c] = kNone;
+  }
+  for (int t = c; t < 2 * (T + 1); t += kTopRowsThreads) toff[t] = 0;
   __syncthreads();
-  int below = 0, rank = 0;
-  for (int k = 0; k < F; ++k) {
-    const int b = bins[k];
-    below += b < bin ? 1 : 0;
-    rank += (b == bin && k < c) ? 1 : 0;
+  if (c < F && key != kNone) {
+    const int4* keys4 = reinterpret_cast<const int4*>(keys);  // (four words a read, several reads in flight)
+    int pos = 0;
+#pragma unroll 4
+    for (int k4 = 0; k4 < F / 4; ++k4) {
+      const int4 v = keys4[k4];
+      pos += (v.x < key ? 1 : 0) + (v.y < key ? 1 : 0) + (v.z < key ? 1 : 0) + (v.w < key ? 1 : 0);
+    }
+    skey[pos] = key;
+    sval[pos] = coef[c] * gfeat[(long long)m * F + c];  // alpha_c * grad_feat[m, c]
   }
-  if (arg >= 0) {
-    const long long o = (long long)m * F + below + rank;
-    erow[o] = arg;
-    ech[o] = c;
-    eval[o] = coef[c] * gfeat[(long long)m * F + c];  // alpha_c * grad_feat[m, c]
+  __syncthreads();
+  // thread p takes the entry at sorted position p: the first entry of a row (its lowest channel) is the row's leader
+  int row = -1;
+  bool leader = false;
+  unsigned long long lb = 0;
+  if (c < F) {
+    const int k = skey[c];
+    const int prev = c > 0 ? skey[c - 1] >> 8 : -1;
+    row = k >> 8;
+    leader = k != kNone && row != prev;
+    lb = __ballot(leader);
+    const unsigned long long vb = __ballot(k != kNone);
+    if ((c & 63) == 0) {
+      wlead[c >> 6] = __builtin_popcountll(lb);
+      wcnt[c >> 6] = __builtin_popcountll(vb);
+    }
   }
-  for (int t = c; t <= T; t += blockDim.x) {
-    int cnt = 0;
-    for (int k = 0; k < F; ++k) cnt += bins[k] < t ? 1 : 0;
-    tptr[(long long)m * (T + 1) + t] = cnt;
+  __syncthreads();
+  if (c < F) {
+    int j = __builtin_popcountll(lb & ((1ull << (c & 63)) - 1ull)), D = 0, E = 0;
+    for (int w = 0; w < F / 64; ++w) {
+      j += w < (c >> 6) ? wlead[w] : 0;
+      D += wlead[w];
+      E += wcnt[w];
+    }
+    if (leader) {
+      rs[j] = c;
+      const int prev = c > 0 ? skey[c - 1] >> 8 : -1;
+      if ((prev >> 5) != (row >> 5)) toff[row >> 5] = j;
+      atomicOr(&tmask[row >> 5], (int)(1u << (row & 31)));
+    }
+    if (c == 0) {
+      rs[D] = E;
+      rs[F + 1] = D;
+    }
+  }
+  __syncthreads();
+  for (int t = c; t <= T; t += kTopRowsThreads) rtile[(long long)m * (T + 1) + t] = make_int2(toff[t], tmask[t]);
+  const int D = rs[F + 1], cq = c & (LPR - 1);
+  const float4* w4 = reinterpret_cast<const float4*>(w5);
+  for (int j = c / LPR; j < D; j += kTopRowsThreads / LPR) {
+    const int pb = rs[j], pe = rs[j + 1];
+    float4 a0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), a1 = a0;
+    for (int p = pb; p < pe; p += 4) {  // up to four entries' weight rows in flight, then their FMAs in entry order
+      float4 u0[4], u1[4];
+      float v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (p + u < pe) {
+          const int ch = skey[p + u] & 255;
+          v[u] = sval[p + u];
+          u0[u] = w4[(long long)ch * QC + cq];
+          u1[u] = w4[(long long)ch * QC + cq + LPR];
+        }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (p + u < pe) {
+          a0.x = __builtin_fmaf(v[u], u0[u].x, a0.x);
+          a0.y = __builtin_fmaf(v[u], u0[u].y, a0.y);
+          a0.z = __builtin_fmaf(v[u], u0[u].z, a0.z);
+          a0.w = __builtin_fmaf(v[u], u0[u].w, a0.w);
+          a1.x = __builtin_fmaf(v[u], u1[u].x, a1.x);
+          a1.y = __builtin_fmaf(v[u], u1[u].y, a1.y);
+          a1.z = __builtin_fmaf(v[u], u1[u].z, a1.z);
+          a1.w = __builtin_fmaf(v[u], u1[u].w, a1.w);
+        }
+    }
+    float4* o = reinterpret_cast<float4*>(rsum) + ((long long)m * F + j) * QC + cq;
+    o[0] = a0;
+    o[LPR] = a1;
   }
 }
 
@@ -608,21 +697,23 @@ struct PnWs {
   CoopWs coop;    // fp64 group sums + tickets of the cooperative reductions
   float* topv;    // [M*splits][F][2] top-2 records of the last layer (values)
   float* ybest;   // [M][F] pre-BatchNorm value at the arg-max
-  float* eval;    // [M][F] CSR values alpha*grad_feat
+  float* eval;    // [M][F] retired (the arg-max entries live in pn_top_csr_kernel's LDS); kept: the fields behind it stay put
   float* q;       // [129][128] Q then c0
   float* gram;    // [129][128] Gram matrix then column sums of A4
   float* ql[5];   // Q form of conv2..conv4: [CIN + 1][CIN] Q then c0 of layer l
   float* red[5];  // ... and the layer's reduced tables [T | G | asum | (S, P^T P, psum)]
+  float* rsum;    // [M][F][128] S W5 of part m's distinct arg-max row j (at most F of them), see pn_top_csr_kernel
   int64_t total;
 };
 
 struct PnIws {
   int* argmax;  // [M][F]
   int* topn;    // [M*splits][F][2]
-  int* erow;    // [M][F] CSR rows
-  int* ech;     // [M][F] CSR channels
-  int* tptr;    // [M][T+1] CSR tile offsets
+  int* erow;    // [M][F], [M][F], [M][T+1]: retired with `eval` (the CSR by 32-row tile that the last layer's backward
+  int* ech;     // pass walked entry by entry); kept so that the fields behind them stay put
+  int* tptr;
   int* vlist;   // [4 + M] number of valid parts, then (from [4]) their ids
+  int2* rtile;  // [M][T+1] {first distinct arg-max row, mask of the rows that have one} of part m's 32-row tile t
   int64_t total;
 };
 
@@ -668,6 +759,7 @@ PnWs carve(float* base, const Dims& d) {
   w.eval = take(d.M * d.F);
   w.q = take(129 * 128);
   w.gram = take(129 * 128);
+  w.rsum = take(d.M * d.F * 128);
   w.total = p - base;
   return w;
 }
@@ -686,6 +778,7 @@ PnIws carve_int(int32_t* base, const Dims& d) {
   w.ech = take(d.M * d.F);
   w.tptr = take(d.M * ((d.N + 31) / 32 + 1));
   w.vlist = take(d.M + 4);
+  w.rtile = reinterpret_cast<int2*>(take(2 * d.M * ((d.N + 31) / 32 + 1)));
   w.total = p - base;
   return w;
 }
@@ -790,11 +883,11 @@ extern "C" int mpa_pointnet_backward(const float* grad_feat, const float* points
   hipLaunchKernelGGL(pn_bwd_top_kernel, dim3((unsigned)(F / 64), (unsigned)((M + kEB - 1) / kEB)), dim3(64 * kSlices),
                      0, s, grad_feat, iw.argmax, w.ybest, valids, (int)M, (int)F, w.count, bn_w[4], w.bn[5],
                      w.coef[5], grad_bn_w[4], grad_bn_b[4], w.coop);
-  hipLaunchKernelGGL(pn_top_csr_kernel, dim3((unsigned)(M + C4 + 1)), dim3((unsigned)F), sizeof(int) * F, s, iw.argmax,
-                     grad_feat, w.coef[5], valids, (int)N, (int)F, iw.erow, iw.ech, w.eval, iw.tptr, (int)M, conv_w[4], C4,
-                     w.q);
+  hipLaunchKernelGGL(pn_top_csr_kernel, dim3((unsigned)(M + C4 + 1)), dim3(kTopRowsThreads),
+                     sizeof(int) * pn_top_csr_lds_words((int)F, (int)((N + 31) / 32)), s, iw.argmax, grad_feat, w.coef[5], valids, (int)N,
+                     (int)F, iw.rtile, w.rsum, (int)M, conv_w[4], w.q);
   hipLaunchKernelGGL((pn_bwd_top_q_kernel<128, 4, 4, 4>), dim3(256), dim3(768), 0, s, w.Y[4], w.bn[4], w.q, iw.vlist, (int)N,
-                     w.dZ[4], w.partial, w.dwpart, iw.erow, iw.ech, w.eval, iw.tptr, conv_w[4], (int)F);
+                     w.dZ[4], w.partial, w.dwpart, iw.rtile, w.rsum, (int)F);
   hipLaunchKernelGGL(pn_bwd_coef_kernel, dim3((unsigned)(C4 / 64), (unsigned)((256 + kEB - 1) / kEB)), dim3(64 * kSlices), 0, s,
                      w.partial, (const float*)nullptr, 256, 1, C4, w.count, bn_w[3], w.bn[4], w.coef[4], grad_bn_w[3],
                      grad_bn_b[3], w.coop);
