@@ -580,6 +580,32 @@ int mpa_match_parts_rmat(const float* part_pcs, const float* pred_trans, const f
 int mpa_part_batch_transform(const double* raw, const double* rot, const int32_t* perm, const float* valids,
                              int64_t M, int64_t N, float* part_pcs, float* part_trans, void* stream);
 
+/* Geometry batches sampled from device-resident meshes (csrc/mesh_sample.hip): one launch draws, for each of the M =
+ * B * max_num_part slots, N surface samples of part slot_part[m] and runs the transform of mpa_part_batch_transform on
+ * them without the float64 cloud leaving LDS (N <= 2048).  The mesh store: tri [F_total,9] float64 = per triangle
+ * (origin, e1 = v1 - v0, e2 = v2 - v0), cum_area [F_total] float64 = per part the running sum of its triangle areas,
+ * part_face_off [parts_total + 1] int64.  slot_part [M] int64; a negative entry is a padded slot, written as zeros.
+ * Per point i, from three uniforms (u0, u1, u2) in [0, 1): pick = u0 * cum[last]; face = first index of the part's
+ * segment with cum[face] >= pick; (a, b) = (u1, u2), replaced by (|a - 1|, |b - 1|) where a + b > 1; p = (e1 * a +
+ * e2 * b) + origin, each operation rounded once.  Outputs part_pcs [M,N,3], part_trans [M,3] float32 and, if raw_out is
+ * not NULL, the sampled float64 cloud raw_out [M,N,3].
+ *   Replay mode (uniforms != NULL): uniforms [M,N,3] float64, rot [M,9] float64, perm [M,N] int32 come from the caller;
+ * part_pcs and part_trans are bit-equal to mpa_part_batch_transform on the cloud numpy computes from the same uniforms.
+ * part_quat may be NULL (the caller knows its rotations); seed, stream_id and rot_range are ignored.
+ *   Device-random mode (uniforms, rot, perm all NULL): Philox4x32-10, stateless.  key = (seed low word, seed high word);
+ * counter = (i, purpose, stream_id[m] low word, high word).  purpose 0 and 1 are the point draws: u0 = words 0-1 and u1 =
+ * words 2-3 of call 0, u2 = words 0-1 of call 1; purpose 2 and 3 with i = 0 are the slot's rotation: r0 = words 0-1 and
+ * r1 = words 2-3 of call 2, r2 = words 0-1 of call 3.  A uniform from the word pair (hi, lo), hi the first word, is
+ * ((hi >> 5) * 2^26 + (lo >> 6)) * 2^-53.  rot_range <= 0: the rotation is the unit quaternion (x, y, z, w) =
+ * (sqrt(1-r0) sin 2 pi r1, sqrt(1-r0) cos 2 pi r1, sqrt(r0) sin 2 pi r2, sqrt(r0) cos 2 pi r2) (Shoemake: uniform);
+ * rot_range > 0: Euler angles (r - 0.5) * 2 * rot_range degrees, extrinsic xyz.  part_quat [M,4] float32 receives the
+ * scalar-first quaternion of the INVERSE rotation.  The points keep their draw order (no permutation).
+ *   MPA_EINVAL: negative sizes, N outside [1, 2048], a NULL pointer the mode needs, rot / perm without uniforms. */
+int mpa_mesh_sample_batch(const double* tri, const double* cum_area, const int64_t* part_face_off, int64_t parts_total,
+                          const int64_t* slot_part, int64_t M, int64_t N, const double* uniforms, const double* rot,
+                          const int32_t* perm, uint64_t seed, const int64_t* stream_id, double rot_range,
+                          float* part_pcs, float* part_trans, float* part_quat, double* raw_out, void* stream);
+
 /* ---- rotation matrices (rot_type='rmat'; csrc/rmat.hip, the 6D pose head in csrc/transformer.hip) -------------------------
  * Replaces the rmat half of multi_part_assembly/utils/rotation.py:134-167 and utils/transforms.py:126-244, and the 6D
  * branch of models/modules/regressor.py:6-27,33-69.  Matrices are [.., 3, 3] row-major fp32.

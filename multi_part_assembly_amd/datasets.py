@@ -15,6 +15,10 @@ the same keys, shapes and dtypes, batched `[B, ...]` and already on the device.
   coordinates, numpy's global RNG in the same call order).  trimesh is a third-party dependency that is neither vendored
   by the reference nor present in this image, so that piece is PARITY UNPINNED (its statistical properties are tested);
   without a sampler the producer raises.
+* Device-resident meshes: `MeshStore` parses every part mesh once and packs per-triangle (origin, e1, e2) and per-part
+  cumulative areas as float64 device arrays; `DeviceGeometryProducer.batch` then samples, recentres, rotates and casts a
+  whole batch in ONE launch (`mpa_mesh_sample_batch`, csrc/mesh_sample.hip) with counter-based Philox randomness on the
+  device — the host builds a few [B, P] integer tables per batch and nothing per part.  Same `data_dict`.
 * PartNet-style semantic data: the on-disk format is plain numpy (`{category}.{split}.npy` id lists,
   `shape_data/{id}_level3.npy` pickled dicts, `contact_points/pairs_with_contact_points_{id}_level3.npy`);
   the label derivations (`instance_label`, `match_ids`, one-hot `part_label`) are host integer logic.
@@ -56,24 +60,47 @@ def load_obj(path):
     return np.asarray(verts, dtype=np.float64).reshape(-1, 3), np.asarray(faces, dtype=np.int64).reshape(-1, 3)
 
 
+def triangle_table(vertices, faces):
+    """Per triangle: origin = v0, e1 = v1 - v0, e2 = v2 - v0 (float64 [F, 3] each) and area [F] — the quantities the
+    surface sampler works on.  `MeshStore` packs exactly these arrays, so a face pick on the device is bit-reproducible
+    against `sample_surface_from_uniforms`."""
+    tri = np.asarray(vertices, dtype=np.float64)[np.asarray(faces, dtype=np.int64)]   # [F, 3, 3]
+    e1, e2 = tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
+    area = 0.5 * np.linalg.norm(np.cross(e1, e2), axis=1)
+    return tri[:, 0], e1, e2, area
+
+
+def sample_surface_from_uniforms(vertices, faces, u):
+    """The surface sampling of `sample_surface` as a function of its uniforms `u` float64 [count, 3] in [0, 1): column 0
+    picks the face — `searchsorted(cumsum(area), u0 * total_area)`, probability proportional to area — and columns 1, 2
+    are the lengths (a, b) along the triangle's two edge vectors, reflected to (|a - 1|, |b - 1|) where a + b > 1; the
+    point is `(e1 * a + e2 * b) + origin`.  -> float64 [count, 3].  This is the yardstick of the device sampler
+    (csrc/mesh_sample.hip), which repeats these float64 operations one by one."""
+    u = np.asarray(u, dtype=np.float64)
+    if u.ndim != 2 or u.shape[1] != 3:
+        raise ValueError(f"sample_surface_from_uniforms: u must be [count, 3], got {u.shape}")
+    origin, e1, e2, area = triangle_table(vertices, faces)
+    weight_cum = np.cumsum(area)
+    face_pick = u[:, 0] * weight_cum[-1]
+    face_index = np.searchsorted(weight_cum, face_pick)
+    origins = origin[face_index]
+    vectors = np.stack([e1[face_index], e2[face_index]], axis=1)   # [count, 2, 3]
+    lengths = u[:, 1:, None].copy()                                # [count, 2, 1]
+    outside = lengths.sum(axis=1).reshape(-1) > 1.0
+    lengths[outside] -= 1.0
+    lengths = np.abs(lengths)
+    return (vectors * lengths).sum(axis=1) + origins
+
+
 def sample_surface(vertices, faces, count):
     """`trimesh.sample.sample_surface(mesh, count)[0]` restated from trimesh's published algorithm (trimesh is not in this
     image: parity unpinned): faces are picked with probability proportional to their area by inverting the cumulative
     area with `np.random.random(count)`, and a point inside the picked triangle is `origin + a * e1 + b * e2` with (a, b)
     = `np.random.random((count, 2, 1))`, reflected into the triangle where a + b > 1.  Uses numpy's GLOBAL generator,
     like trimesh, so that `np.random.seed` in the caller governs it."""
-    tri = vertices[faces]                                   # [F, 3, 3]
-    area = 0.5 * np.linalg.norm(np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]), axis=1)
-    weight_cum = np.cumsum(area)
-    face_pick = np.random.random(count) * weight_cum[-1]
-    face_index = np.searchsorted(weight_cum, face_pick)
-    origins = tri[face_index, 0]
-    vectors = tri[face_index, 1:] - origins[:, None, :]     # [count, 2, 3]
+    face_pick = np.random.random(count)
     lengths = np.random.random((count, 2, 1))
-    outside = lengths.sum(axis=1).reshape(-1) > 1.0
-    lengths[outside] -= 1.0
-    lengths = np.abs(lengths)
-    return (vectors * lengths).sum(axis=1) + origins
+    return sample_surface_from_uniforms(vertices, faces, np.concatenate([face_pick[:, None], lengths[:, :, 0]], axis=1))
 
 
 class ObjSurfaceSampler:
@@ -195,6 +222,267 @@ class GeometryBatchProducer:
     def batch(self, indices: Sequence[int]) -> dict:
         """Sample the fracture folders `data_list[i]` with the configured sampler and produce the batch."""
         return self.produce([self.sampler(self.data_list[i]) for i in indices], data_ids=indices)
+
+
+# ---- device-resident meshes ---------------------------------------------------------------------------------------
+class MeshStore:
+    """Every part mesh of a list of shapes, parsed once and packed into four flat arrays the device sampler reads
+    (csrc/mesh_sample.hip):
+
+    * `tri` float64 [F_total, 9]: per triangle (origin, e1, e2) of `triangle_table`;
+    * `cum_area` float64 [F_total]: per part, `np.cumsum` of that part's triangle areas;
+    * `part_face_off` int64 [parts_total + 1]: part k owns the faces `part_face_off[k]:part_face_off[k + 1]`;
+    * `shape_part_off` int64 [shapes + 1]: shape s owns the parts `shape_part_off[s]:shape_part_off[s + 1]`.
+
+    float64 like the reference pipeline up to its final cast: 80 B per face, `nbytes` in total; with `max_bytes` a store
+    that would be larger raises instead of exhausting device memory (stores larger than the device are out of scope).
+    Zero-area faces inside a part stay and are never picked (`searchsorted`), except a degenerate FIRST face at a pick of
+    exactly 0.  The arrays live on the host; `device_arrays(device)` uploads them once per device."""
+
+    def __init__(self, tri, cum_area, part_face_off, shape_part_off, max_bytes=None):
+        self.tri = np.ascontiguousarray(tri, dtype=np.float64).reshape(-1, 9)
+        self.cum_area = np.ascontiguousarray(cum_area, dtype=np.float64).reshape(-1)
+        self.part_face_off = np.ascontiguousarray(part_face_off, dtype=np.int64).reshape(-1)
+        self.shape_part_off = np.ascontiguousarray(shape_part_off, dtype=np.int64).reshape(-1)
+        pf, sp = self.part_face_off, self.shape_part_off
+        if (len(pf) < 1 or len(sp) < 1 or pf[0] != 0 or sp[0] != 0 or pf[-1] != len(self.tri)
+                or len(self.cum_area) != len(self.tri) or sp[-1] != len(pf) - 1
+                or (np.diff(pf) < 1).any() or (np.diff(sp) < 1).any()):
+            raise ValueError("MeshStore: inconsistent offsets (every part needs a face, every shape a part)")
+        last = self.cum_area[pf[1:] - 1]
+        if not (np.isfinite(last) & (last > 0.0)).all():
+            raise ValueError("MeshStore: a part with zero (or non-finite) total area cannot be sampled")
+        _check_store_bytes(self.nbytes, max_bytes)
+        self._device = {}
+
+    @property
+    def nbytes(self):
+        return self.tri.nbytes + self.cum_area.nbytes + self.part_face_off.nbytes + self.shape_part_off.nbytes
+
+    @property
+    def num_shapes(self):
+        return len(self.shape_part_off) - 1
+
+    @property
+    def num_parts(self):
+        return len(self.part_face_off) - 1
+
+    def __len__(self):
+        return self.num_shapes
+
+    @classmethod
+    def from_arrays(cls, shapes, min_num_part=2, max_num_part=20, max_bytes=None):
+        """shapes: per shape a list of `(vertices [V, 3], triangles [F, 3])`, one per part, in part order."""
+        shapes = [list(parts) for parts in shapes]
+        faces_total = sum(len(f) for parts in shapes for _, f in parts)
+        parts_total = sum(len(parts) for parts in shapes)
+        _check_store_bytes(80 * faces_total + 8 * (parts_total + 1) + 8 * (len(shapes) + 1), max_bytes)
+        tri, cum, pf, sp = [], [], [0], [0]
+        for s, parts in enumerate(shapes):
+            if not min_num_part <= len(parts) <= max_num_part:
+                raise ValueError(f"shape {s}: {len(parts)} parts outside [{min_num_part}, {max_num_part}]")
+            for k, (v, f) in enumerate(parts):
+                v, f = np.asarray(v, dtype=np.float64).reshape(-1, 3), np.asarray(f, dtype=np.int64).reshape(-1, 3)
+                if len(f) == 0:
+                    raise ValueError(f"shape {s} part {k}: a mesh without faces cannot be sampled")
+                if f.min() < 0 or f.max() >= len(v):
+                    raise ValueError(f"shape {s} part {k}: face index outside the {len(v)} vertices")
+                origin, e1, e2, area = triangle_table(v, f)
+                c = np.cumsum(area)
+                if not (np.isfinite(c[-1]) and c[-1] > 0.0):
+                    raise ValueError(f"shape {s} part {k}: zero (or non-finite) total area cannot be sampled")
+                tri.append(np.concatenate([origin, e1, e2], axis=1))
+                cum.append(c)
+                pf.append(pf[-1] + len(f))
+            sp.append(sp[-1] + len(parts))
+        if not shapes:
+            raise ValueError("MeshStore: no shapes")
+        return cls(np.concatenate(tri), np.concatenate(cum), pf, sp, max_bytes=max_bytes)
+
+    @classmethod
+    def from_folders(cls, data_dir, data_list, min_num_part=2, max_num_part=20, max_bytes=None):
+        """The fracture folders `data_dir/data_list[i]`, each holding one .obj per part: sorted file names and part-count
+        limits as `ObjSurfaceSampler`, every mesh parsed once with `load_obj`."""
+        shapes = []
+        for rel in data_list:
+            folder = os.path.join(data_dir, rel)
+            mesh_files = sorted(os.listdir(folder))
+            if not min_num_part <= len(mesh_files) <= max_num_part:
+                raise ValueError(f"{folder}: {len(mesh_files)} parts outside [{min_num_part}, {max_num_part}]")
+            shapes.append([load_obj(os.path.join(folder, name)) for name in mesh_files])
+        return cls.from_arrays(shapes, min_num_part, max_num_part, max_bytes)
+
+    def save(self, path):
+        """One .npz with the four arrays: the per-part parse is paid once per dataset."""
+        with open(path, "wb") as fh:
+            np.savez(fh, tri=self.tri, cum_area=self.cum_area, part_face_off=self.part_face_off,
+                     shape_part_off=self.shape_part_off)
+
+    @classmethod
+    def load(cls, path, max_bytes=None):
+        with np.load(path) as z:
+            return cls(z["tri"], z["cum_area"], z["part_face_off"], z["shape_part_off"], max_bytes=max_bytes)
+
+    def device_arrays(self, device):
+        """(tri, cum_area, part_face_off) as tensors on `device`, uploaded at the first call."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("MeshStore: the mesh sampler runs on the HIP device only (there is no CPU fallback)")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device not in self._device:
+            self._device[device] = tuple(torch.from_numpy(a).to(device)
+                                         for a in (self.tri, self.cum_area, self.part_face_off))
+        return self._device[device]
+
+
+def _check_store_bytes(nbytes, max_bytes):
+    if max_bytes is not None and nbytes > max_bytes:
+        raise ValueError(f"MeshStore: {nbytes} bytes of mesh data exceed max_bytes={max_bytes}")
+
+
+MAX_DEVICE_SAMPLE_POINTS = 2048  # the sampled float64 cloud of a part lives in LDS (csrc/mesh_sample.hip)
+
+
+class DeviceGeometryProducer:
+    """`GeometryBatchProducer.batch` + `ObjSurfaceSampler` with the per-part work on the device: the meshes sit in a
+    `MeshStore`, and ONE HIP launch per batch (`mpa_mesh_sample_batch`) samples every part's surface, recentres, rotates
+    and casts.  `.batch()` returns the `data_dict` of `GeometryBatchProducer.produce` — same keys, shapes and dtypes.
+    The host only builds the [B, P] integer tables from the store's offsets and sends them in one pinned copy.
+
+    Randomness (`.batch`) is Philox4x32-10 on the device, stateless: key = `seed`, and slot m of a batch uses the
+    64-bit stream `batch_counter * B * P + m` (include/mpa_hip.h has the counter layout), so the same (seed,
+    batch_counter, slot) gives the same bits in every run, whichever other shapes share the batch.  It reproduces the
+    reference's DISTRIBUTION, not numpy's streams.  The points of a part are NOT shuffled: the N samples are independent
+    and identically distributed, so a random permutation of them changes nothing a model can see.  `rot_range <= 0`: a
+    uniformly random rotation; `> 0`: Euler angles uniform in [-rot_range, rot_range] degrees, as the reference.
+    `shuffle_parts` permutes the parts of each shape with `random.shuffle`, like the reference.
+
+    `.replay` feeds host-drawn uniforms / rotations / point orders through the same kernel, for parity tests."""
+
+    def __init__(self, store: MeshStore, num_points=1000, min_num_part=2, max_num_part=20, rot_range=-1,
+                 data_keys=("part_ids",), seed=0, device="cuda", shuffle_parts=False):
+        if not 1 <= num_points <= MAX_DEVICE_SAMPLE_POINTS:
+            raise ValueError(f"DeviceGeometryProducer: num_points={num_points} outside [1, {MAX_DEVICE_SAMPLE_POINTS}]")
+        self.store = store
+        self.num_points, self.min_num_part, self.max_num_part = num_points, min_num_part, max_num_part
+        self.rot_range = float(rot_range)
+        self.data_keys = tuple(data_keys)
+        for key in self.data_keys:
+            if key not in ("part_ids", "valid_matrix"):
+                raise ValueError(f"ERROR: unknown data {key}")
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.device = torch.device(device)
+        self.shuffle_parts = shuffle_parts
+        self.batch_counter = 0  # the default `batch_counter` of the next batch() call
+
+    def __len__(self):
+        return self.store.num_shapes
+
+    def _slots(self, indices):
+        """indices -> slot_part int64 [B, P] (store part id, -1 in padded slots) and the valid mask [B, P]."""
+        off = self.store.shape_part_off
+        idx = np.asarray(list(indices), dtype=np.int64).reshape(-1)
+        if ((idx < 0) | (idx >= len(off) - 1)).any():
+            raise IndexError(f"DeviceGeometryProducer: shape index outside [0, {len(off) - 1})")
+        start, count = off[idx], off[idx + 1] - off[idx]
+        if ((count < self.min_num_part) | (count > self.max_num_part)).any():
+            raise ValueError(f"DeviceGeometryProducer: a shape has a part count outside "
+                             f"[{self.min_num_part}, {self.max_num_part}]")
+        ar = np.arange(self.max_num_part, dtype=np.int64)[None]
+        valid = ar < count[:, None]
+        slot = np.where(valid, start[:, None] + ar, -1)
+        if self.shuffle_parts:
+            for b, p in enumerate(count):
+                order = list(range(p))
+                random.shuffle(order)
+                slot[b, :p] = slot[b, order]
+        return slot, valid
+
+    def _run(self, indices, stream_ids=None, uniforms=None, rot=None, perm=None, quat=None, return_raw=False):
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError("DeviceGeometryProducer: the mesh sampler runs on the HIP device only "
+                               "(there is no CPU fallback)")
+        indices = list(indices)
+        slot, valid = self._slots(indices)
+        B, P, N = len(indices), self.max_num_part, self.num_points
+        M = B * P
+        replay = uniforms is not None
+        with torch.cuda.device(dev):
+            tri, cum, pf = self.store.device_arrays(dev)
+            # one pinned buffer, one asynchronous copy: int64 [2, M] (slot_part, stream) | float32 [2, M] (valids, ids)
+            host = torch.empty(24 * M, dtype=torch.uint8, pin_memory=True)
+            h64 = host[: 16 * M].view(torch.int64).view(2, B, P).numpy()
+            h32 = host[16 * M:].view(torch.float32).view(2, B, P).numpy()
+            h64[0] = slot
+            h64[1] = 0 if stream_ids is None else stream_ids
+            h32[0] = valid
+            h32[1] = np.arange(P)[None] * valid
+            buf = host.to(dev, non_blocking=True)
+            d64 = buf[: 16 * M].view(torch.int64).view(2, B, P)
+            d32 = buf[16 * M:].view(torch.float32).view(2, B, P)
+            part_pcs = torch.empty((B, P, N, 3), dtype=torch.float32, device=dev)
+            part_trans = torch.empty((B, P, 3), dtype=torch.float32, device=dev)
+            raw = torch.empty((B, P, N, 3), dtype=torch.float64, device=dev) if return_raw else None
+            if replay:
+                d_uni, d_rot, d_perm = (_to_device(a, dev) for a in (uniforms, rot, perm))
+                part_quat = _to_device(quat, dev)
+                args = (_lib.ptr(d_uni), _lib.ptr(d_rot), _lib.ptr(d_perm), 0, None, 0.0, _lib.ptr(part_pcs),
+                        _lib.ptr(part_trans), None)
+            else:
+                part_quat = torch.empty((B, P, 4), dtype=torch.float32, device=dev)
+                args = (None, None, None, self.seed, _lib.ptr(d64[1]), self.rot_range, _lib.ptr(part_pcs),
+                        _lib.ptr(part_trans), _lib.ptr(part_quat))
+            st = _lib.lib().mpa_mesh_sample_batch(_lib.ptr(tri), _lib.ptr(cum), _lib.ptr(pf), self.store.num_parts,
+                                                  _lib.ptr(d64[0]), M, N, *args, _lib.ptr(raw),
+                                                  _lib.current_stream(dev))
+        _lib.check(st, "mpa_mesh_sample_batch")
+        d_val = d32[0]
+        out = {
+            "part_pcs": part_pcs,
+            "part_quat": part_quat,
+            "part_trans": part_trans,
+            "part_valids": d_val,
+            "data_id": torch.as_tensor(indices, dtype=torch.int64),
+            "instance_label": torch.zeros((B, P, 0), dtype=torch.float32, device=dev),
+            "part_label": torch.zeros((B, P, 0), dtype=torch.float32, device=dev),
+        }
+        if "part_ids" in self.data_keys:
+            out["part_ids"] = d32[1]
+        if "valid_matrix" in self.data_keys:
+            out["valid_matrix"] = d_val[:, :, None] * d_val[:, None, :]
+        return (out, raw) if return_raw else out
+
+    def batch(self, indices: Sequence[int], batch_counter: int | None = None, return_raw=False):
+        """The `data_dict` of the shapes `indices`, sampled, rotated and cast on the device.  `batch_counter` selects the
+        random streams (default: the number of batches drawn so far); with `return_raw` also the sampled float64 cloud
+        [B, P, N, 3] before the transform, as a second result."""
+        indices = list(indices)
+        if batch_counter is None:
+            batch_counter = self.batch_counter
+            self.batch_counter += 1
+        M = len(indices) * self.max_num_part
+        streams = (int(batch_counter) * M + np.arange(M, dtype=np.int64)).reshape(len(indices), self.max_num_part)
+        return self._run(indices, stream_ids=streams, return_raw=return_raw)
+
+    def replay(self, indices: Sequence[int], uniforms, rot, perm, quat, return_raw=False):
+        """Replay mode: uniforms float64 [B, P, N, 3], rot float64 [B, P, 9], perm int32 [B, P, N] and quat float32
+        [B, P, 4] drawn by the caller (as `GeometryBatchProducer` draws rot / perm / quat).  `part_pcs` and `part_trans`
+        are bit-equal to `GeometryBatchProducer.produce` on the clouds `sample_surface_from_uniforms` computes."""
+        indices = list(indices)
+        B, P, N = len(indices), self.max_num_part, self.num_points
+        uniforms = np.ascontiguousarray(uniforms, dtype=np.float64)
+        rot = np.ascontiguousarray(rot, dtype=np.float64)
+        perm = np.ascontiguousarray(perm, dtype=np.int32)
+        quat = np.ascontiguousarray(quat, dtype=np.float32)
+        for name, arr, shape in (("uniforms", uniforms, (B, P, N, 3)), ("rot", rot, (B, P, 9)),
+                                 ("perm", perm, (B, P, N)), ("quat", quat, (B, P, 4))):
+            if arr.shape != shape:
+                raise ValueError(f"replay: {name} must be {shape}, got {arr.shape}")
+        if perm.size and (perm.min() < 0 or perm.max() >= N):
+            raise ValueError(f"replay: perm entries outside [0, {N})")
+        return self._run(indices, uniforms=uniforms, rot=rot, perm=perm, quat=quat, return_raw=return_raw)
 
 
 # ---- PartNet ---------------------------------------------------------------------------------------------------

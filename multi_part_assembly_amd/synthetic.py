@@ -11,6 +11,7 @@ and valid parts come first (:121-126,175-177).
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from .transforms import pose_apply
@@ -73,3 +74,49 @@ def make_semantic_batch(batch_size, max_parts=2, num_points=1000, seed=1234, dev
     batch["match_ids"] = torch.ones(B, P, dtype=torch.int64, device=dev)
     batch["instance_label"] = torch.eye(P, device=dev)[None].repeat(B, 1, 1)
     return batch
+
+
+def _uv_sphere(segments, rings):
+    """Closed latitude / longitude triangulation of the unit sphere: `segments * (rings - 1) + 2` vertices,
+    `2 * segments * (rings - 1)` triangles, outward orientation."""
+    theta = np.pi * np.arange(1, rings) / rings
+    phi = 2.0 * np.pi * np.arange(segments) / segments
+    ring = np.stack([np.sin(theta)[:, None] * np.cos(phi)[None], np.sin(theta)[:, None] * np.sin(phi)[None],
+                     np.broadcast_to(np.cos(theta)[:, None], (rings - 1, segments))], axis=-1).reshape(-1, 3)
+    verts = np.concatenate([[[0.0, 0.0, 1.0]], ring, [[0.0, 0.0, -1.0]]])
+    j = np.arange(segments)
+    jn = (j + 1) % segments
+    faces = [np.stack([np.zeros_like(j), 1 + j, 1 + jn], axis=1)]
+    for r in range(rings - 2):
+        a, b = 1 + r * segments, 1 + (r + 1) * segments
+        faces += [np.stack([a + j, b + j, b + jn], axis=1), np.stack([a + j, b + jn, a + jn], axis=1)]
+    last, south = 1 + (rings - 2) * segments, len(verts) - 1
+    faces.append(np.stack([last + j, np.full_like(j, south), last + jn], axis=1))
+    return verts, np.concatenate(faces).astype(np.int64)
+
+
+def make_fracture_meshes(seed, shapes, parts_per_shape, faces):
+    """Seeded stand-ins for the Breaking-Bad part meshes, without files: `shapes` lists of `(vertices float64 [V, 3],
+    triangles int64 [F, 3])`, one entry per part.  `parts_per_shape` is one count for every shape or one per shape.
+    Every part is a closed mesh of about `faces` triangles (`2 * s * max(1, faces // (2 * s))` with s = max(3,
+    round(sqrt(faces / 2))): 5000 -> exactly 5000): a sphere whose radius is perturbed per vertex by up to +-30 %,
+    scaled to the 'everyday' half-extents U(0.02, 0.3)^3 and moved to a centre ~ U(-0.4, 0.4)^3.  Uses a private
+    generator: numpy's global state is untouched."""
+    rng = np.random.RandomState(seed)
+    counts = [parts_per_shape] * shapes if np.isscalar(parts_per_shape) else list(parts_per_shape)
+    if len(counts) != shapes:
+        raise ValueError(f"make_fracture_meshes: {len(counts)} part counts for {shapes} shapes")
+    segments = max(3, int(round(np.sqrt(faces / 2.0))))
+    rings = max(1, faces // (2 * segments)) + 1
+    unit, tri = _uv_sphere(segments, rings)
+    lo, hi = PRESETS["everyday"]["half_extent"]
+    out = []
+    for count in counts:
+        parts = []
+        for _ in range(int(count)):
+            radius = 1.0 + 0.3 * (2.0 * rng.random_sample(len(unit)) - 1.0)
+            half = lo + (hi - lo) * rng.random_sample(3)
+            centre = 0.8 * rng.random_sample(3) - 0.4
+            parts.append((unit * radius[:, None] * half[None] + centre[None], tri.copy()))
+        out.append(parts)
+    return out
