@@ -662,6 +662,45 @@ int mpa_pose_head6_backward(const float* grad_rot6d, const float* grad_trans, co
                             const float* const* params, int64_t M, int64_t F, float* ws, float* grad_x,
                             float* const* grad_params, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Evaluation metrics of one batch (csrc/eval_metrics.hip) — replace the composition behind
+ *   BaseModel._calc_metrics : multi_part_assembly/models/modules/base_model.py:316-339
+ *   calc_part_acc, trans_metrics, rot_metrics, calc_connectivity_acc : multi_part_assembly/utils/eval_utils.py:12-199
+ *
+ * mpa_assembly_metrics[_rmat]: part_pcs [B, P, N, 3], trans_pred / trans_gt [B, P, 3], rotations as the Rotation3D
+ * value holds them — quaternions [B, P, 4] (real part first, not normalised) or row-major matrices [B, P, 3, 3] —
+ * valids [B, P] (1 = real part, 0 = padding), all contiguous fp32.  out [7, B] receives, in this order,
+ *   part_acc, trans_mse, trans_rmse, trans_mae, rot_mse, rot_rmse, rot_mae
+ * and per_part [B, P] (NULL to skip) the per-part Chamfer value mean_i dist1 + mean_j dist2 between the part posed by
+ * the predicted and by the ground-truth pose (0 for padded slots).  The posed coordinates are those of
+ * mpa_pose_apply[_rmat]_forward and the nearest-neighbour distances those of mpa_chamfer_forward, bit for bit; the
+ * two means are summed in a fixed shape of at most 20 fp32 roundings (relative error <= 1.2e-6).  part_acc counts the
+ * valid parts with per_part < 0.01 over the valid parts.  The translation / Euler-angle ('zyx', degrees, wrapped at
+ * 180) errors are evaluated in float64 from the fp32 inputs, weighted by valids and divided by their sum (the
+ * reference's `_valid_mean`; no valid part -> NaN, as the reference gives), rounded to fp32 once.
+ * Two launches, no atomics, fixed reduction order: bit-identical from run to run.  Padded slots (valids == 0) are
+ * never read: any values in their points and poses leave every output bit unchanged.
+ * Envelope: 1 <= N <= 2048 (both posed clouds of a part live in LDS, 24 N bytes), P >= 1, 7 * B * P < 2^31, finite
+ * inputs (a non-finite coordinate of a valid part makes its distances undefined).  Outside it the call is refused
+ * with MPA_EINVAL and the caller composes the metrics from the operators above.
+ * workspace: mpa_assembly_metrics_workspace() bytes, 8-byte aligned, contents irrelevant before and after.
+ *
+ * mpa_connectivity_acc: contact_points [B, P, P, 4] (flag, x, y, z), trans [B, P, 3], rot [B, P, 4] or [B, P, 3, 3]
+ * (is_rmat != 0).  For every (b, i, j) with flag == 1: the minimum squared distance between the 8 sign-flipped copies
+ * of contact_points[b, i, j, 1:] posed by part i and the 8 of contact_points[b, j, i, 1:] posed by part j; out [B] is
+ * (contacts with minimum < 0.01) / contacts in every element, NaN without contacts.  One launch of one block,
+ * integer counters only.  B * P * P < 2^31.
+ * ---------------------------------------------------------------------------------------------- */
+int mpa_assembly_metrics_workspace(int64_t B, int64_t P, int64_t* bytes);
+int mpa_assembly_metrics(const float* part_pcs, const float* trans_pred, const float* trans_gt, const float* quat_pred,
+                         const float* quat_gt, const float* valids, int64_t B, int64_t P, int64_t N, void* workspace,
+                         float* out, float* per_part, void* stream);
+int mpa_assembly_metrics_rmat(const float* part_pcs, const float* trans_pred, const float* trans_gt,
+                              const float* rmat_pred, const float* rmat_gt, const float* valids, int64_t B, int64_t P,
+                              int64_t N, void* workspace, float* out, float* per_part, void* stream);
+int mpa_connectivity_acc(const float* contact_points, const float* trans, const float* rot, int is_rmat, int64_t B,
+                         int64_t P, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

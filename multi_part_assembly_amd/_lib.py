@@ -112,6 +112,10 @@ SIGNATURES: dict[str, tuple] = {
     "mpa_pose_head6_workspace": (_INT, [_I64, _I64, _P]),
     "mpa_pose_head6_forward": (_INT, [_P, _P, _I64, _I64, _P, _P, _P, _P]),
     "mpa_pose_head6_backward": (_INT, [_P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P]),
+    "mpa_assembly_metrics_workspace": (_INT, [_I64, _I64, _P]),
+    "mpa_assembly_metrics": (_INT, [_P] * 6 + [_I64, _I64, _I64, _P, _P, _P, _P]),
+    "mpa_assembly_metrics_rmat": (_INT, [_P] * 6 + [_I64, _I64, _I64, _P, _P, _P, _P]),
+    "mpa_connectivity_acc": (_INT, [_P, _P, _P, _INT, _I64, _I64, _P, _P]),
 }
 
 ABI_VERSION = 10

@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from .chamfer import chamfer_distance
-from .eval_utils import calc_connectivity_acc, calc_part_acc, rot_metrics, trans_metrics
+from .eval_utils import assembly_metrics, calc_connectivity_acc, calc_part_acc, rot_metrics, trans_metrics
 from .matching import SUBSAMPLE, match_parts
 from .loss import (LossTerms, geometric_assembly_loss, part_order, search_mode, rot_cosine_loss, rot_points_cd_loss,
                    rot_points_l2_loss, shape_cd_loss, trans_l2_loss)
@@ -55,6 +55,9 @@ class BaseModel(nn.Module):
         # clouds (only visualisation needs them).  Quaternions and rotation matrices alike.
         self.fused_loss = True
         self.keep_pts = False
+        # evaluation metrics by csrc/eval_metrics.hip (two launches + one for the connectivity accuracy) instead of the
+        # per-function composition; off by default, `evaluate.Evaluator` switches it on for its run
+        self.fused_metrics = False
 
     # ---- hooks a trainer calls ---------------------------------------------------------------
     def training_step(self, data_dict, batch_idx=0, optimizer_idx=-1):
@@ -173,6 +176,17 @@ class BaseModel(nn.Module):
         semantic datasets that annotate contacts; translation / rotation MSE, RMSE, MAE for geometric data."""
         part_pcs, valids = data_dict["part_pcs"], data_dict["part_valids"]
         pred_trans, pred_rot = out_dict["trans"], out_dict["rot"]
+        if self.fused_metrics:
+            fused = assembly_metrics(part_pcs, pred_trans, gt_trans, pred_rot, gt_rot, valids)
+            metrics = {"part_acc": fused["part_acc"]}
+            if self.semantic and "contact_points" in data_dict:
+                metrics["connectivity_acc"] = calc_connectivity_acc(pred_trans, pred_rot, data_dict["contact_points"],
+                                                                    fused=True)
+            if not self.semantic:
+                for m in ("mse", "rmse", "mae"):  # (the key order of the composition below)
+                    metrics[f"trans_{m}"] = fused[f"trans_{m}"]
+                    metrics[f"rot_{m}"] = fused[f"rot_{m}"]
+            return metrics
         metrics = {"part_acc": calc_part_acc(part_pcs, pred_trans, gt_trans, pred_rot, gt_rot, valids)}
         if self.semantic and "contact_points" in data_dict:
             metrics["connectivity_acc"] = calc_connectivity_acc(pred_trans, pred_rot, data_dict["contact_points"])
@@ -264,11 +278,14 @@ class BaseModel(nn.Module):
                 terms = stacked[1]                                                            # [K, B] as computed
             else:
                 terms = torch.stack([sample_loss[k] for k in keys], dim=0)                   # [K, B]
-            cache = getattr(self, "_loss_weight_cache", None)
-            if cache is None or cache[0] != keys or cache[1].device != terms.device:
+            # one weight vector per key list, all kept: a captured training step reads its vector by address on every
+            # replay, so an evaluation between two replays (other keys: the metrics) must not free it
+            caches = self.__dict__.setdefault("_loss_weight_cache", {})
+            cache = caches.get((tuple(keys), terms.device))
+            if cache is None:
                 w = [float(self.cfg.loss[f"{k}_w"]) if k.endswith("_loss") else 0.0 for k in keys]
                 cache = (keys, torch.tensor(w, dtype=terms.dtype, device=terms.device))
-                self._loss_weight_cache = cache
+                caches[(tuple(keys), terms.device)] = cache
             # mean over the batch of sum_k w_k t_kb = sum_k w_k mean_b t_kb: one launch each way on the device the fused
             # loss runs on (mean + dot and their two backward kernels were 23 us of the 2.07 ms step)
             if terms.is_cuda and terms.dtype == torch.float32:

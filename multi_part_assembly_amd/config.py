@@ -180,3 +180,33 @@ def lstm_partnet_chair():
     data = partnet_chair()
     data.shuffle_parts = True
     return Config(exp=_exp(200), data=data, optimizer=adam_cosine(), model=lstm_model(), loss=semantic_loss())
+
+
+def identity_model():
+    """configs/_base_/models/identity.py:5-8."""
+    return Config(name="identity", rot_type="quat", pc_feat_dim=128)
+
+
+def identity_everyday():
+    """configs/identity/identity-32x1-cosine_200e-everyday.py (the shipped file pairs geometric data with the semantic
+    loss settings: five identical samples, no cosine / L2 rotation terms)."""
+    return Config(exp=_exp(200), data=breaking_bad_everyday(), optimizer=adam_cosine(), model=identity_model(),
+                  loss=semantic_loss())
+
+
+def identity_artifact():
+    """configs/identity/identity-32x1-cosine_200e-artifact.py."""
+    return Config(exp=_exp(200), data=breaking_bad_artifact(), optimizer=adam_cosine(), model=identity_model(),
+                  loss=semantic_loss())
+
+
+def identity_partnet_chair():
+    """configs/identity/identity-32x1-cosine_200e-partnet_chair.py."""
+    return Config(exp=_exp(200), data=partnet_chair(), optimizer=adam_cosine(), model=identity_model(),
+                  loss=semantic_loss())
+
+
+# the category lists scripts/test.py loops over with `--category all` (configs/_base_/datasets/breaking_bad/*.py)
+EVERYDAY_CATEGORIES = ("BeerBottle", "Bowl", "Cup", "DrinkingUtensil", "Mug", "Plate", "Spoon", "Teacup", "ToyFigure",
+                       "WineBottle", "Bottle", "Cookie", "DrinkBottle", "Mirror", "PillBottle", "Ring", "Statue", "Teapot",
+                       "Vase", "WineGlass")

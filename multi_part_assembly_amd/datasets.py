@@ -125,6 +125,30 @@ class ObjSurfaceSampler:
         return np.stack(pcs, axis=0)
 
 
+def read_fracture_list(data_dir, data_fn, category="", min_num_part=2, max_num_part=20):
+    """`GeometryPartDataset._read_data` (geometry_data.py:48-71): the lines of `data_dir/data_fn` name SHAPE folders
+    (`everyday/Bottle/<id>`); each is expanded into its `fractured_*` / `mode_*` sub-folders, and a fracture is kept
+    when its number of entries lies in [min_num_part, max_num_part] — the others are skipped, not an error.
+    `category` ('' or 'all': every shape) must be one path component of the line.  Returns fracture folders relative
+    to `data_dir`, in the reference's order (the list's, then `os.listdir`'s)."""
+    wanted = "" if category.lower() == "all" else category
+    with open(os.path.join(data_dir, data_fn)) as fh:
+        shapes = [line.strip() for line in fh]
+    fractures = []
+    for shape in shapes:
+        if not shape or (wanted and wanted not in shape.split("/")):
+            continue
+        if not os.path.isdir(os.path.join(data_dir, shape)):
+            print(f"{shape} does not exist")
+            continue
+        for sub in os.listdir(os.path.join(data_dir, shape)):
+            if "fractured" in sub or "mode" in sub:
+                count = len(os.listdir(os.path.join(data_dir, shape, sub)))
+                if min_num_part <= count <= max_num_part:
+                    fractures.append(os.path.join(shape, sub))
+    return fractures
+
+
 def _to_device(arr: np.ndarray, device) -> torch.Tensor:
     t = torch.from_numpy(np.ascontiguousarray(arr))
     if device is not None and torch.device(device).type == "cuda":

@@ -6,12 +6,27 @@ outputs.  Part accuracy runs the per-part Chamfer search on the HIP operator; th
 (eval_utils.py:84-96); the pair order — (b, i, j) ascending — is the same, and the result does not depend on it."""
 from __future__ import annotations
 
+import ctypes
 import math
+import warnings
 
 import torch
 
+from . import _lib
 from .chamfer import chamfer_distance
 from .transforms import transform_pc
+
+METRIC_KEYS = ("part_acc", "trans_mse", "trans_rmse", "trans_mae", "rot_mse", "rot_rmse", "rot_mae")
+FUSED_MAX_POINTS = 2048  # csrc/eval_metrics.hip keeps both posed clouds of a part in LDS (include/mpa_hip.h)
+_warned = set()
+
+
+def _warn_once(what, why):
+    """The package's single warning per reason when a call leaves the fused kernels for the composition.  (Modules keep
+    such a flag on themselves; these are free functions, so the flags live in one module-level set.)"""
+    if what not in _warned:
+        _warned.add(what)
+        warnings.warn(f"{what}: {why}; composing the result from the per-function operators")
 
 
 def _valid_mean(per_part, valids):
@@ -39,12 +54,17 @@ def _symmetric_copies(points):
 
 
 @torch.no_grad()
-def calc_connectivity_acc(trans, rot, contact_points):
+def calc_connectivity_acc(trans, rot, contact_points, fused=False):
     """Fraction of annotated contacts (contact_points[b, i, j, 0] == 1) whose two contact points, moved by the
     predicted poses of parts i and j, come closer than 0.01 (squared distance, minimum over the 8x8 symmetric
-    copies) -> the batch-wide value tiled to [B]."""
+    copies) -> the batch-wide value tiled to [B].  `fused=True`: one launch of csrc/eval_metrics.hip on CUDA tensors
+    (integer counters, no gather); on the CPU the composition below, with one warning."""
     B = trans.shape[0]
     rot_type, rot = rot.rot_type, rot.rot
+    if fused:
+        if trans.is_cuda and trans.dtype == torch.float32 and B * trans.shape[1] ** 2 < 2 ** 31:
+            return _connectivity_fused(trans, rot, rot_type, contact_points)
+        _warn_once("calc_connectivity_acc", "the fused kernel takes float32 CUDA tensors")
     b, i, j = torch.nonzero(contact_points[..., 0] == 1, as_tuple=True)
     p1 = _symmetric_copies(contact_points[b, i, j, 1:])
     p2 = _symmetric_copies(contact_points[b, j, i, 1:])
@@ -91,3 +111,70 @@ def rot_metrics(rot1, rot2, valids, metric):
         if metric == "rmse":
             per_part = per_part ** 0.5
     return _valid_mean(per_part, valids)
+
+
+def _connectivity_fused(trans, rot, rot_type, contact_points):
+    B, P = trans.shape[:2]
+    dev = trans.device
+    out = torch.empty(B, dtype=torch.float32, device=dev)
+    contact = contact_points.to(torch.float32).contiguous()
+    trans, rot = trans.contiguous(), rot.to(torch.float32).contiguous()
+    with torch.cuda.device(dev):
+        st = _lib.lib().mpa_connectivity_acc(_lib.ptr(contact), _lib.ptr(trans), _lib.ptr(rot), int(rot_type == "rmat"),
+                                             B, P, _lib.ptr(out), _lib.current_stream(dev))
+    _lib.check(st, "mpa_connectivity_acc")
+    return out
+
+
+def fused_metrics_supported(pts):
+    """The envelope of csrc/eval_metrics.hip (include/mpa_hip.h): float32 CUDA clouds of at most 2048 points per part."""
+    return (pts.is_cuda and pts.dtype == torch.float32 and pts.dim() == 4 and 1 <= pts.shape[2] <= FUSED_MAX_POINTS
+            and pts.shape[1] >= 1 and 7 * pts.shape[0] * pts.shape[1] < 2 ** 31)
+
+
+def _assembly_metrics_composed(pts, pred_trans, gt_trans, pred_rot, gt_rot, valids):
+    out = {"part_acc": calc_part_acc(pts, pred_trans, gt_trans, pred_rot, gt_rot, valids)}
+    for m in ("mse", "rmse", "mae"):
+        out[f"trans_{m}"] = trans_metrics(pred_trans, gt_trans, valids, metric=m)
+    for m in ("mse", "rmse", "mae"):
+        out[f"rot_{m}"] = rot_metrics(pred_rot, gt_rot, valids, metric=m)
+    return out
+
+
+@torch.no_grad()
+def assembly_metrics(pts, pred_trans, gt_trans, pred_rot, gt_rot, valids, ret_per_part=False):
+    """The seven per-batch-element metrics of the evaluation step in one call: {part_acc, trans_mse, trans_rmse,
+    trans_mae, rot_mse, rot_rmse, rot_mae}, each [B] — `calc_part_acc`, `trans_metrics` and `rot_metrics` of the same
+    arguments (pts [B,P,N,3], translations [B,P,3], rotations as Rotation3D of one kind, valids [B,P]).
+
+    Float32 CUDA inputs inside the kernels' envelope (N <= 2048, finite values) take two launches of
+    csrc/eval_metrics.hip; everything else — the CPU included — is composed from the seven functions, with one warning.
+    `ret_per_part` also returns the [B,P] per-part Chamfer values behind part_acc (fused path only; None otherwise)."""
+    if not fused_metrics_supported(pts) or pred_rot.rot_type != gt_rot.rot_type:
+        if fused_metrics_supported(pts):
+            _warn_once("assembly_metrics", f"a '{pred_rot.rot_type}' prediction against a '{gt_rot.rot_type}' ground truth: "
+                       "csrc/eval_metrics.hip takes both rotations in one form")
+        else:
+            _warn_once("assembly_metrics", f"{tuple(pts.shape)} {pts.dtype} {pts.device.type} clouds are outside "
+                       f"csrc/eval_metrics.hip (float32 CUDA, at most {FUSED_MAX_POINTS} points per part)")
+        out = _assembly_metrics_composed(pts, pred_trans, gt_trans, pred_rot, gt_rot, valids)
+        return (out, None) if ret_per_part else out
+    B, P, N = pts.shape[:3]
+    dev, f32 = pts.device, torch.float32
+    rmat = pred_rot.rot_type == "rmat"
+    args = [t.detach().to(f32).contiguous() for t in (pts, pred_trans, gt_trans, pred_rot.rot, gt_rot.rot, valids)]
+    L = _lib.lib()
+    nbytes = ctypes.c_int64()
+    _lib.check(L.mpa_assembly_metrics_workspace(B, P, ctypes.byref(nbytes)), "mpa_assembly_metrics_workspace")
+    ws = torch.empty(max(1, nbytes.value // 8), dtype=torch.float64, device=dev)
+    out = torch.empty((len(METRIC_KEYS), B), dtype=f32, device=dev)
+    per_part = torch.empty((B, P), dtype=f32, device=dev) if ret_per_part else None
+    fn = L.mpa_assembly_metrics_rmat if rmat else L.mpa_assembly_metrics
+    with torch.cuda.device(dev):
+        tok = _lib.KernelTimer.start(f"assembly_metrics[{B}x{P}x{N}]")
+        st = fn(*[_lib.ptr(a) for a in args], B, P, N, _lib.ptr(ws), _lib.ptr(out), _lib.ptr(per_part),
+                _lib.current_stream(dev))
+        _lib.KernelTimer.stop(tok)
+    _lib.check(st, "mpa_assembly_metrics")
+    res = {k: out[i] for i, k in enumerate(METRIC_KEYS)}
+    return (res, per_part) if ret_per_part else res

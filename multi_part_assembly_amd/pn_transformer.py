@@ -163,13 +163,16 @@ class PNTransformerRefine(PNTransformer):
 
 
 def build_model(cfg):
-    """Registry of reference models/__init__.py:10-26 (the identity baseline is out of scope)."""
+    """Registry of reference models/__init__.py:10-26."""
     model = _build_model(cfg)
     TransformerEncoder.assign_dropout_salts(model)  # sibling encoders draw different masks, reproducibly
     return model
 
 
 def _build_model(cfg):
+    if cfg.model.name == "identity":
+        from .identity import IdentityModel
+        return IdentityModel(cfg)
     if cfg.model.name == "pn_transformer":
         return PNTransformer(cfg)
     if cfg.model.name == "pn_transformer_refine":

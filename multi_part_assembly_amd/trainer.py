@@ -92,14 +92,71 @@ class Trainer:
         behind them, are undefined.  Without `synchronize` the answer covers every launch whose status copy has already
         arrived (a plain read of pinned memory: this runs after every step and replay); with it — in front of
         checkpoints and evaluation reports — every launch issued so far."""
-        _gru.raise_if_failed(self.flat.flat_param.device, synchronize=synchronize)
+        try:
+            _gru.raise_if_failed(self.flat.flat_param.device, synchronize=synchronize)
+        except RuntimeError:
+            # sticky: raise_if_failed clears the status word as it reports, so a caller that catches this error and goes
+            # on would otherwise get a clean bill of health — and a checkpoint — for parameters behind a failed launch
+            self._failed = True
+            raise
 
     def state_dict(self):
         """Model + optimiser state for a checkpoint; refuses (RuntimeError) if a launch behind the current parameters
-        gave up."""
+        gave up — now, or at any `check_health` since the parameters were last loaded.  Besides "model", "optimizer" and
+        "epoch" the dictionary carries "dropout_calls": the position of every dropout-seed stream, which
+        `load_state_dict` needs to continue a run with the masks the uninterrupted run draws (optional on loading)."""
+        if getattr(self, "_failed", False):
+            raise RuntimeError("Trainer.state_dict: an earlier check_health reported a launch that gave up; the parameters "
+                               "behind it are undefined — restore a checkpoint with load_state_dict first")
         self.check_health(synchronize=True)
         return {"model": self.model.state_dict(), "optimizer": self.optimizer.state_dict()
-                if hasattr(self.optimizer, "state_dict") else None, "epoch": self.epoch}
+                if hasattr(self.optimizer, "state_dict") else None, "epoch": self.epoch,
+                # position of every dropout-seed stream (transformer.TransformerEncoder._next_seed), in module order: a
+                # resumed run then draws the masks the uninterrupted one would have drawn
+                "dropout_calls": [m._calls for m in self.model.modules() if hasattr(m, "advance_seed")]}
+
+    def load_state_dict(self, state):
+        """Inverse of `state_dict()`: model weights and buffers (copied in place: the parameters stay views of the flat
+        buffer), the optimiser's moments and step count (host and device copy) and the epoch with its learning rate.
+        A Lightning-style checkpoint `{"state_dict": ...}` — what the reference's training writes — loads the weights
+        only.  A restored trainer is healthy again.
+
+        The dropout-seed positions are host counters; the device word a captured step reads its seed from is not
+        restored here because `train_step` rewrites it from the counter (`advance_seed`) in front of every replay, and a
+        freshly built `use_graph=True` trainer starts with its eager warm-up steps, whose seeds travel by value."""
+        if "state_dict" in state and "model" not in state:
+            self.model.load_state_dict(state["state_dict"])
+            self._failed = False
+            return
+        self.model.load_state_dict(state["model"])
+        if state.get("optimizer") is not None:
+            self.optimizer.load_state_dict(state["optimizer"])
+        if self.schedule is not None:
+            self.set_epoch(state["epoch"])  # (the schedule owns the rate)
+        else:
+            self.epoch = state["epoch"]
+        seeded = [m for m in self.model.modules() if hasattr(m, "advance_seed")]
+        calls = state.get("dropout_calls")
+        if calls is not None:
+            if len(calls) != len(seeded):
+                raise RuntimeError(f"Trainer.load_state_dict: the checkpoint holds {len(calls)} dropout-seed positions, "
+                                   f"the model has {len(seeded)} seeded modules")
+            for m, c in zip(seeded, calls):
+                m._calls = int(c)
+        self._failed = False
+
+    def evaluate(self, batches, prefix="val"):
+        """One evaluation pass over `batches` (evaluate.Evaluator on this trainer's model and process group): the
+        batch-size-weighted averages as floats.  Touches neither the optimiser nor the dropout seeds of training."""
+        from .evaluate import Evaluator
+        ev = getattr(self, "_evaluator", None)
+        if ev is None:
+            group = self.group  # (None in a multi-rank job means the default group, as everywhere in this class)
+            if group is None and self.world > 1:
+                group = dist.group.WORLD
+            ev = self._evaluator = Evaluator(self.model, process_group=group,
+                                             health=lambda: self.check_health(synchronize=True))
+        return ev.run(batches, prefix=prefix)
 
     def set_epoch(self, epoch):
         self.epoch = epoch

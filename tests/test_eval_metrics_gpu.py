@@ -1,0 +1,239 @@
+"""csrc/eval_metrics.hip on the GPU against tests/golden/eval_metrics_v2.npz (reference outputs for quaternion poses and
+for rot_type='rmat', at B = 4, P = 20, N = 1000 and at a small ragged shape; tests/golden/make_golden_eval.py asserts
+that no per-part Chamfer value and no contact distance lies within 1 % of the 0.01 threshold and that no rotation sits
+at the asin pole, so exact comparisons of the thresholded metrics are fair)."""
+import os
+import sys
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+import param_fill  # noqa: E402
+
+from multi_part_assembly_amd import config, eval_utils, rotation  # noqa: E402
+from multi_part_assembly_amd.chamfer import chamfer_distance  # noqa: E402
+from multi_part_assembly_amd.pn_transformer import build_model  # noqa: E402
+from multi_part_assembly_amd.rotation import Rotation3D  # noqa: E402
+from multi_part_assembly_amd.transforms import transform_pc  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+CASES = [(shape, kind) for shape in ("big", "small") for kind in ("quat", "rmat")]
+
+
+def _load(golden, dev, shape, kind):
+    z = golden("eval_metrics_v2")
+    t = lambda k: torch.from_numpy(z[k].copy()).to(dev)
+    pre = f"{shape}.{kind}."
+    d = dict(pcs=t(f"{shape}.pcs"), valids=t(f"{shape}.valids"), gt_t=t(f"{shape}.gt_t"), pr_t=t(f"{shape}.pr_t"),
+             contact=t(f"{shape}.contact_points"), pr_r=Rotation3D(t(pre + "pr_rot"), kind), gt_r=Rotation3D(t(pre + "gt_rot"), kind))
+    return z, pre, d
+
+
+def _fused(d, per_part=False):
+    return eval_utils.assembly_metrics(d["pcs"], d["pr_t"], d["gt_t"], d["pr_r"], d["gt_r"], d["valids"], ret_per_part=per_part)
+
+
+@pytest.mark.parametrize("shape,kind", CASES)
+def test_part_acc_and_trans_metrics_match_reference(golden, cuda_device, shape, kind):
+    z, pre, d = _load(golden, cuda_device, shape, kind)
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")  # inside the envelope: the fused path, silently
+        got = _fused(d)
+    assert list(got) == list(eval_utils.METRIC_KEYS)
+    np.testing.assert_array_equal(got["part_acc"].cpu().numpy(), z[pre + "part_acc"])  # exactly, no case excluded
+    for m in ("mse", "rmse", "mae"):
+        np.testing.assert_allclose(got[f"trans_{m}"].cpu().numpy(), z[pre + f"trans_{m}"], rtol=1e-5, err_msg=m)
+        np.testing.assert_allclose(got[f"rot_{m}"].cpu().numpy(), z[pre + f"rot_{m}"], rtol=2e-4, err_msg=m)
+
+
+@pytest.mark.parametrize("shape,kind", CASES)
+def test_per_part_chamfer_against_the_operators_own_distances(cuda_device, golden, shape, kind):
+    """The kernel's minima are the Chamfer operator's fp32 distances; only the two means differ.  Its summation shape —
+    at most 8 terms per thread, the six levels of the wave sum, three additions across the waves, a division and the
+    final addition — is at most 20 fp32 roundings of positive terms: 20 * 2^-24 = 1.2e-6 relative, below the 1e-5 asked."""
+    _, _, d = _load(golden, cuda_device, shape, kind)
+    _, per_part = _fused(d, per_part=True)
+    B, P = d["valids"].shape
+    a = transform_pc(d["pr_t"], d["pr_r"], d["pcs"]).flatten(0, 1)
+    b = transform_pc(d["gt_t"], d["gt_r"], d["pcs"]).flatten(0, 1)
+    d1, d2 = chamfer_distance(a, b)
+    want = (d1.double().mean(1) + d2.double().mean(1)).view(B, P)
+    valid = d["valids"] == 1
+    rel = ((per_part.double() - want).abs() / want.clamp_min(1e-30))[valid & (want > 0)]
+    print(f"{shape}/{kind}: per-part Chamfer, max relative error {float(rel.max()):.3e} (bound 1.2e-6)")
+    assert float(rel.max()) <= 20 * 2.0 ** -24
+    assert torch.equal(per_part[valid & (want == 0)], torch.zeros_like(per_part[valid & (want == 0)]))  # exact parts
+    assert not per_part[~valid].any()
+
+
+def _rot_reference64(d):
+    """eval_utils.rot_metrics' formula in float64 on the float32 inputs."""
+    def euler(r):
+        x = r.rot.double().cpu()
+        q = x if r.rot_type == "quat" else rotation.matrix_to_quaternion(x)
+        return eval_utils.quat_to_euler_zyx_deg(q)
+    diff = (euler(d["pr_r"]) - euler(d["gt_r"])).abs()
+    diff = torch.minimum(diff, 360.0 - diff)
+    v = d["valids"].double().cpu()
+    mean = lambda per_part: ((per_part * v).sum(1) / v.sum(1)).numpy()
+    mse = diff.pow(2).mean(-1)
+    return {"mse": mean(mse), "rmse": mean(mse ** 0.5), "mae": mean(diff.mean(-1))}
+
+
+@pytest.mark.parametrize("shape,kind", CASES)
+def test_rot_metrics_error_against_float64(cuda_device, golden, shape, kind):
+    """Kernel error <= max(2 x the error of the unchanged eval_utils.rot_metrics, 4 fp32 ulp of the value), both measured
+    against the reference formula in float64.
+    Measured on an MI355X (max over B of the error in fp32 ulp of the value, composition / kernel): big quat mse 25.2 / 0.20,
+    rmse 11.5 / 0.46, mae 14.6 / 0.49; big rmat 144.6 / 0.40, 89.4 / 0.48, 134.5 / 0.48; small quat 128.5 / 0.48, 50.0 / 0.05,
+    218.1 / 0.13; small rmat 279.5 / 0.48, 131.0 / 0.21, 231.7 / 0.27 — the kernel evaluates the formula in float64 and
+    rounds once, the composition carries the error of fp32 atan2 / asin through the degree conversion and the squares."""
+    _, _, d = _load(golden, cuda_device, shape, kind)
+    ref = _rot_reference64(d)
+    got = _fused(d)
+    for m in ("mse", "rmse", "mae"):
+        comp = eval_utils.rot_metrics(d["pr_r"], d["gt_r"], d["valids"], m).double().cpu().numpy()
+        mine = got[f"rot_{m}"].double().cpu().numpy()
+        ulp = np.spacing(np.abs(ref[m]).astype(np.float32)).astype(np.float64)
+        e_comp, e_mine = np.abs(comp - ref[m]), np.abs(mine - ref[m])
+        print(f"{shape}/{kind} rot_{m}: error vs float64 in ulp, composition {np.max(e_comp / ulp):.2f}, kernel "
+              f"{np.max(e_mine / ulp):.2f}")
+        assert (e_mine <= np.maximum(2 * e_comp, 4 * ulp)).all(), (m, e_mine / ulp, e_comp / ulp)
+
+
+@pytest.mark.parametrize("shape,kind", CASES)
+def test_connectivity_matches_reference_exactly(cuda_device, golden, shape, kind):
+    z, pre, d = _load(golden, cuda_device, shape, kind)
+    got = eval_utils.calc_connectivity_acc(d["pr_t"], d["pr_r"], d["contact"], fused=True)
+    np.testing.assert_array_equal(got.cpu().numpy(), z[pre + "connectivity_acc_pred"])
+    B, P = d["valids"].shape
+    ident = Rotation3D(torch.tensor([1.0, 0, 0, 0], device=cuda_device).repeat(B, P, 1))
+    ident = ident if kind == "quat" else ident.convert("rmat")
+    got = eval_utils.calc_connectivity_acc(torch.zeros_like(d["pr_t"]), ident, d["contact"], fused=True)
+    np.testing.assert_array_equal(got.cpu().numpy(), z[pre + "connectivity_acc_zero"])
+    assert 0.0 < float(z[pre + "connectivity_acc_pred"][0]) < 1.0  # the case decides something
+    none = eval_utils.calc_connectivity_acc(d["pr_t"], d["pr_r"], torch.zeros_like(d["contact"]), fused=True)
+    assert none.shape == (B,) and torch.isnan(none).all()  # no contacts: 0 / 0, as the composition gives
+
+
+@pytest.mark.parametrize("shape,kind", CASES)
+def test_two_runs_are_bit_identical_and_padded_slots_are_never_read(cuda_device, golden, shape, kind):
+    _, _, d = _load(golden, cuda_device, shape, kind)
+    first, pp1 = _fused(d, per_part=True)
+    second, pp2 = _fused(d, per_part=True)
+    for k in first:
+        assert torch.equal(first[k], second[k]) or (torch.isnan(first[k]) == torch.isnan(second[k])).all(), k
+        assert torch.equal(first[k].view(torch.int32), second[k].view(torch.int32)), k
+    assert torch.equal(pp1, pp2)
+    # arbitrary finite garbage in the points and poses of the padded slots
+    g = torch.Generator().manual_seed(77)
+    pad = (d["valids"] == 0)
+    assert pad.any()
+    junk = lambda t: (torch.randn(t.shape, generator=g) * 1e3).to(t.device)
+    e = dict(d)
+    e["pcs"] = torch.where(pad[..., None, None], junk(d["pcs"]), d["pcs"])
+    e["pr_t"] = torch.where(pad[..., None], junk(d["pr_t"]), d["pr_t"])
+    e["gt_t"] = torch.where(pad[..., None], junk(d["gt_t"]), d["gt_t"])
+    sel = pad[..., None] if kind == "quat" else pad[..., None, None]
+    e["pr_r"] = Rotation3D(torch.where(sel, junk(d["pr_r"].rot), d["pr_r"].rot), kind)
+    e["gt_r"] = Rotation3D(torch.where(sel, junk(d["gt_r"].rot), d["gt_r"].rot), kind)
+    third, pp3 = _fused(e, per_part=True)
+    for k in first:
+        assert torch.equal(first[k].view(torch.int32), third[k].view(torch.int32)), k
+    assert torch.equal(pp1, pp3)
+    c1 = eval_utils.calc_connectivity_acc(d["pr_t"], d["pr_r"], d["contact"], fused=True)
+    c2 = eval_utils.calc_connectivity_acc(e["pr_t"], e["pr_r"], d["contact"], fused=True)  # (no contact touches a padded slot)
+    assert torch.equal(c1, c2)
+
+
+def test_validation_step_with_fused_metrics_holds_the_fixture(golden, cuda_device):
+    """tests/test_eval_gpu.py's evaluation fixture at its tolerances with `fused_metrics = True`; the loss keys do not
+    depend on the switch at all."""
+    z = golden("pn_transformer_eval")
+    d, heads, ffn, layers = (int(v) for v in z["cfg"])
+    cfg = config.pn_transformer_everyday()
+    cfg.model.pc_feat_dim, cfg.model.transformer_heads = d, heads
+    cfg.model.transformer_feat_dim, cfg.model.transformer_layers = ffn, layers
+    cfg.data.max_num_part = 5
+    seed = int(z["seed"][0])
+    torch.manual_seed(seed)
+    model = build_model(cfg)
+    param_fill.fill_parameters(model, seed)
+    model.to(cuda_device).eval()
+    assert model.fused_metrics is False
+    data = {k[5:]: torch.from_numpy(z[k].copy()).to(cuda_device) for k in z if k.startswith("data.")}
+    with torch.no_grad():
+        plain = model.validation_step(data, 0)
+        model.fused_metrics = True
+        fused = model.validation_step(data, 0)
+    assert list(fused) == list(plain)
+    for k in z:
+        if k.startswith("res."):
+            np.testing.assert_allclose(float(fused[k[4:]]), float(z[k]), rtol=3e-4, atol=1e-6, err_msg=k)
+    for k in plain:
+        if k == "loss" or k.endswith("_loss"):
+            assert torch.equal(plain[k], fused[k]), k
+
+
+def test_out_of_envelope_takes_the_composition_with_one_warning(cuda_device, monkeypatch):
+    monkeypatch.setattr(eval_utils, "_warned", set())
+    g = torch.Generator().manual_seed(3)
+    B, P, N = 2, 3, eval_utils.FUSED_MAX_POINTS + 1
+    valids = torch.tensor([[1.0, 1, 0], [1, 1, 1]], device=cuda_device)
+    pts = (torch.randn(B, P, N, 3, generator=g) * 0.1).to(cuda_device) * valids[..., None, None]
+    gt_t = (torch.randn(B, P, 3, generator=g) * 0.3).to(cuda_device)
+    pr_t = gt_t + 0.05
+    q = torch.nn.functional.normalize(torch.randn(B, P, 4, generator=g), dim=-1).to(cuda_device)
+    r = Rotation3D(q)
+    with pytest.warns(UserWarning, match="assembly_metrics") as rec:
+        got = eval_utils.assembly_metrics(pts, pr_t, gt_t, r, r, valids)
+        eval_utils.assembly_metrics(pts, pr_t, gt_t, r, r, valids)
+    assert len([w for w in rec if "assembly_metrics" in str(w.message)]) == 1
+    assert torch.equal(got["part_acc"], eval_utils.calc_part_acc(pts, pr_t, gt_t, r, r, valids))
+    for m in ("mse", "rmse", "mae"):
+        assert torch.equal(got[f"trans_{m}"], eval_utils.trans_metrics(pr_t, gt_t, valids, m))
+        assert torch.equal(got[f"rot_{m}"], eval_utils.rot_metrics(r, r, valids, m))
+
+
+def _metric_launches():
+    import importlib.util
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "eval_rate.py")
+    spec = importlib.util.spec_from_file_location("tools_eval_rate", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod.metric_launches
+
+
+def test_fused_calc_metrics_is_at_most_three_launches_plus_one_for_connectivity(cuda_device):
+    """Device kernels of one `_calc_metrics` call, counted by the profiler (tools/eval_rate.py): the fused path is the two
+    kernels of mpa_assembly_metrics, plus mpa_connectivity_acc on semantic data with contacts — and no memcpy / memset."""
+    from multi_part_assembly_amd import synthetic
+    count = _metric_launches()
+    cfg = config.pn_transformer_everyday()
+    cfg.model.transformer_layers, cfg.data.max_num_part = 2, 6
+    torch.manual_seed(0)
+    model = build_model(cfg).to(cuda_device).eval()
+    batch = synthetic.make_batch(4, max_parts=6, num_points=256, seed=3, device=cuda_device)
+    on, names, copies = count(model, batch, True)
+    off, _, _ = count(model, batch, False)
+    print(f"c2 _calc_metrics launches: composed {off}, fused {on} {names}, memcpy / memset events {copies}")
+    assert 1 <= on <= 3 and off > on and copies == 0
+    assert set(names) == {"slot_metrics_kernel", "batch_metrics_kernel"}
+
+    cfg = config.global_partnet_chair()
+    cfg.data.max_num_part = 4
+    model = build_model(cfg).to(cuda_device).eval()
+    batch = synthetic.make_semantic_batch(3, max_parts=4, num_points=200, seed=41, device=cuda_device)
+    contact = torch.zeros(3, 4, 4, 4)
+    contact[..., 0] = (torch.rand(3, 4, 4) < 0.5).float()
+    contact[..., 1:] = torch.randn(3, 4, 4, 3) * 0.05
+    batch["contact_points"] = contact.to(cuda_device)
+    on, names, copies = count(model, batch, True)
+    off, _, _ = count(model, batch, False)
+    print(f"B-Global _calc_metrics launches: composed {off}, fused {on} {names}, memcpy / memset events {copies}")
+    assert 1 <= on <= 4 and off > on and copies == 0
+    assert set(names) == {"slot_metrics_kernel", "batch_metrics_kernel", "connectivity_kernel"}
