@@ -1111,8 +1111,7 @@ int loss_forward(const float* part_pcs, const float* valids, const float* quat_p
   const dim3 grid(parts * w.tiles, 2, 1);
   // Steering a sample's blocks to one XCD (L2 affinity) loses more to the static load imbalance between
   // XCDs than it gains (measured 2.56 vs 2.21 ms at B=32, P=20, N=1000): off unless MPA_XCD_REMAP=1.
-  const char* re = getenv("MPA_XCD_REMAP");
-  const int remap = re ? (re[0] != '0') : 0;
+  const int remap = mpa::env_flag("MPA_XCD_REMAP", false);
   // per-part Chamfer: the matrix-core gated search (gate_nn.hip) unless MPA_PART_SEARCH=scan asks for the exhaustive scan
   // of rounds 1-4 (identical results; the knob exists for A/B timing and the cross-check tests)
   const bool part_gate = part_search_gate(N);

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/mpa_hip.h"
 
@@ -15,6 +16,13 @@ int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 int check_launch(const char* what);
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// An on/off run-time knob: `dflt` when the variable is unset, otherwise off exactly when its value starts with '0'.
+// Callers keep the result in a function-local `static const`, so a knob is read once per process.
+inline bool env_flag(const char* name, bool dflt) {
+  const char* e = getenv(name);
+  return e == nullptr ? dflt : e[0] != '0';
+}
 
 // Zero-fills `words` 32-bit words with a KERNEL.  hipMemsetAsync is deliberately not used anywhere in the library:
 // as a node of a captured HIP graph it misbehaved on replay (ROCm 7.0/7.2: faults on large fills, stale data on

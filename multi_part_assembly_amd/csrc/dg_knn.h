@@ -155,20 +155,12 @@ __device__ __forceinline__ void queue_flush(Queue& q, Best& b) {
 // Block -> (cloud, query block).  Workgroups go to the 8 XCDs round-robin and every XCD has its own L2; the query blocks
 // of one cloud all stream the same candidate rows, so they are given to ONE XCD: linear block id L runs on XCD L % 8 and
 // takes cloud (L / 8 / Q) * 8 + L % 8, query block (L / 8) % Q.  grid.y must be a multiple of 8 (DG_KNN_GRID_Y).
-#ifndef DG_KNN_XCD
-#define DG_KNN_XCD 1
-#endif
 #define DG_KNN_GRID_Y(n) ((unsigned)(((n) + 7) / 8 * 8))
 __device__ __forceinline__ void knn_block(int& v, int& qb) {
-#if DG_KNN_XCD
   const int Q = (int)gridDim.x, L = (int)blockIdx.y * Q + (int)blockIdx.x;
   const int xcd = L & 7, k = L >> 3;
   v = (k / Q) * 8 + xcd;
   qb = k % Q;
-#else
-  v = (int)blockIdx.y;
-  qb = (int)blockIdx.x;
-#endif
 }
 
 // ---- C = 3 -------------------------------------------------------------------------------------------------------------

@@ -4,7 +4,7 @@
 // 20 per lane: 0.87 / 1.46 ms per stage at 353 x 1000 points.  Here the exact arithmetic is spent only on a SHORTLIST:
 //
 //   split   (round 5, default) y = x - mu of the cloud, hi = bf16(y); row norms n_j in the pinned chain order, centred norms m_j
-//           (rounds 3-4, MPA_KNN_PRODUCTS=3: x = hi + lo + r on the raw features, three products per tile)
+//           (rounds 3-4 split x = hi + lo + r on the raw features and took three products per tile: retired)
 //   BOUND   (knn_bound = knn_gram_kernel<.., false>)   Gram tiles  a^ = hi.hi  on v_mfma_f32_32x32x16_bf16 (ONE product: 16x
 //           the fp32-MFMA rate).  lower(i,j) = 2 a^ - NL_j - NL_i <= score(i,j) <= upper(i,j) = 2 a^ - NU_j - NU_i with the
 //           per-row scaled norms NL / NU derived next to KnnFast below.
@@ -22,7 +22,8 @@
 // Result: bit-identical indices to dg_knn.h on every input (tests/test_dgcnn_gpu.py: index-exact against oracle/knn_ref.c
 // and against the reference's own graphs).
 //
-// kappa.  With |x - hi| <= 2^-8 |x| (bf16 keeps 8 significant bits, round to nearest even), |lo| <= 2^-8 (1 + 2^-8) |x|,
+// kappa of the retired three-product form (kept: the one-product derivation below charges the matrix core's accumulation
+// and the pinned chain the same way).  With |x - hi| <= 2^-8 |x| (bf16 keeps 8 significant bits, round to nearest even), |lo| <= 2^-8 (1 + 2^-8) |x|,
 // |r| <= 2^-16 |x|:  x.y - (hi.hi + hi.lo + lo.hi) = lo.lo + (hi + lo).r_y + r_x.y, at most 3.02 * 2^-16 sum_k |x_k y_k|.
 // The bf16 products are exact in fp32; their 3C-term accumulation inside the matrix core is charged 2^-23 per term (twice
 // round-to-nearest, the internal order is not documented): 3C * 2^-23 * 1.01 sum_k |x_k y_k|.  The pinned fp32 chain is
@@ -41,19 +42,13 @@ namespace dg {
 typedef __bf16 kf_bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 kf_bf16x4 __attribute__((ext_vector_type(4)));
 
-#ifndef MPA_KNN_PRODUCTS  // 1 (round 5): centred one-product Gram tiles; 3: the hi.hi + hi.lo + lo.hi tiles of rounds 3-4
-#define MPA_KNN_PRODUCTS 1
-#endif
-constexpr int kKfProducts = MPA_KNN_PRODUCTS;
-static_assert(kKfProducts == 1 || kKfProducts == 3, "MPA_KNN_PRODUCTS is 1 or 3");
-
 // ONE product (round 5).  The score is a distance: -|x_i - x_j|^2 does not move when every row of a cloud is shifted by
 // the same vector mu, and the bound's slack is proportional to the rows' squared norms — so the tiles are built on
 // y = x - mu (mu = the mean of the cloud's first 16 rows: any vector is valid, this one takes the features' common
 // offset out and the norms down ~2.3x) and a single bf16 product hi_i . hi_j suffices:
 //   y^ = fl(x - mu) = y (1 + t), |t| <= 2^-24;  hi = bf16(y^): |y - hi| <= u |y|, u = 2^-8 (1 + 2^-15)
 //   |y_i.y_j - hi_i.hi_j| <= u (2 + u) sum_k |y_ik y_jk| <= u (2 + u) (M_i + M_j) / 2          (M = |y|^2)
-//   accumulation inside the matrix core: <= C 2^-23 1.03 (M_i + M_j) / 2  (as charged for three products below)
+//   accumulation inside the matrix core: <= C 2^-23 1.03 (M_i + M_j) / 2  (2^-23 per term, as charged above)
 //   => |2 a^ - 2 y_i.y_j| <= kg (M_i + M_j),  kg = 7.845e-3 (C = 128), 7.836e-3 (C = 64)
 //   m = fp32 sum of y^_k^2 (fixed order) is within (C + 3) 2^-24 of M; evaluating lower / upper in fp32 adds 4 * 2^-24.
 //   kappa_g = 7.9e-3 covers kg and those with 0.6 % to spare.
@@ -62,7 +57,7 @@ static_assert(kKfProducts == 1 || kKfProducts == 3, "MPA_KNN_PRODUCTS is 1 or 3"
 //   => (2C + 5) 2^-24 1.02 = 1.59e-5 (C = 128), 8.1e-6 (C = 64); kappa_raw = 1.75e-5 / 9e-6.
 // So, with NL = (1 + kappa_g) m + kappa_raw n (rounded up) and NU = (1 - kappa_g) m - kappa_raw n (rounded down):
 //   lower(i,j) = 2 a^ - NL_j - NL_i <= score(i,j) <= upper(i,j) = 2 a^ - NU_j - NU_i
-// — the same two per-row arrays the three-product form hands the Gram kernels.  Looser bounds, more survivors (the
+// — the same two per-row arrays the three-product form handed the Gram kernels.  Looser bounds, more survivors (the
 // benchmark's features: ~21 per lane half instead of ~16), a third of the matrix-core work and half of the operand bytes.
 //
 // Round 5b: the bf16 truncation term per ROW instead of the worst case.  With e = y^ - hi (exact in fp32),
@@ -77,14 +72,9 @@ static_assert(kKfProducts == 1 || kKfProducts == 3, "MPA_KNN_PRODUCTS is 1 or 3"
 // E^2 is an fp32 sum of C squares (relative error < (C + 1) 2^-24): inflated by 2e-5.  Survivors per query: ~22 (was 27-30).
 template <int C>
 struct KnnFast {
-  static constexpr float kappa = C > 64 ? 1.15e-4f : 8.5e-5f;      // three products, raw features
-  static constexpr float kappa_g = 7.9e-3f;                         // one product, centred features: worst-case truncation (rounds 5a)
   static constexpr float kappa_acc = C > 64 ? 2.7e-5f : 1.4e-5f;    // one product: everything but the truncation
   static constexpr float kappa_raw = C > 64 ? 1.75e-5f : 9.0e-6f;   // pinned chain vs exact, raw features
 };
-#ifndef MPA_KNN_ROWSLACK  // 1: per-row truncation slack (round 5b); 0: kappa_g (M_i + M_j)
-#define MPA_KNN_ROWSLACK 1
-#endif
 
 #ifndef MPA_KNN_CAP
 #define MPA_KNN_CAP 32
@@ -101,48 +91,12 @@ __device__ __forceinline__ float next_float(float x) { return -prev_float(-x); }
 template <int C>
 __device__ __forceinline__ void kf_scaled_norms(float m, float e2, float n, float& nl, float& nu) {
   const float kr = KnnFast<C>::kappa_raw;
-#if MPA_KNN_ROWSLACK
   constexpr float kLam = 0.0009765625f;  // lambda = 2^-10 (the division below is an exact scaling)
   // 2P = e2 / lambda (1 + 2e-5) + 1.01 lambda m, every step rounded up
   const float p2 = next_float(next_float(e2 * 1024.0f * 1.00002f) + next_float(m * (1.01f * kLam)));
   const float slack = next_float(next_float(p2 + next_float(m * KnnFast<C>::kappa_acc)) + next_float(kr * n));
   nl = next_float(m + slack);
   nu = prev_float(m - slack);
-#else
-  const float kg = KnnFast<C>::kappa_g;
-  nl = next_float(next_float(__builtin_fmaf(m, kg, m)) + next_float(kr * n));
-  nu = prev_float(prev_float(__builtin_fmaf(m, -kg, m)) - next_float(kr * n));
-#endif
-}
-
-// ---- split: x -> (hi | lo) bf16 rows, scaled norms ----------------------------------------------------------------------
-// x [R][ld] (first C columns), norm [R] (rownorm_kernel), xs [R][2C] bf16 = hi(0..C-1) | lo(0..C-1), nl / nu [R].
-// One thread per 4 elements.  grid = ceil(Rmax * C / 4 / 256).
-template <int C>
-__global__ __launch_bounds__(256) void knn_split_kernel(const float* __restrict__ x, int ld, const float* __restrict__ norm,
-                                                        unsigned short* __restrict__ xs, float* __restrict__ nl,
-                                                        float* __restrict__ nu, const int* __restrict__ hdr) {
-  const long long R = hdr[1];
-  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long r = t / (C / 4);
-  if (r >= R) return;
-  const int c4 = (int)(t % (C / 4));
-  const float4 v = *reinterpret_cast<const float4*>(x + r * ld + 4 * c4);
-  const float f[4] = {v.x, v.y, v.z, v.w};
-  kf_bf16x4 hi, lo;
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    hi[u] = (__bf16)f[u];
-    lo[u] = (__bf16)(f[u] - (float)hi[u]);
-  }
-  unsigned short* row = xs + r * (2 * C);
-  *reinterpret_cast<kf_bf16x4*>(row + 4 * c4) = hi;
-  *reinterpret_cast<kf_bf16x4*>(row + C + 4 * c4) = lo;
-  if (c4 == 0) {
-    const float n = norm[r], k = KnnFast<C>::kappa;
-    nl[r] = next_float(__builtin_fmaf(n, k, n));
-    nu[r] = prev_float(__builtin_fmaf(n, -k, n));
-  }
 }
 
 // ---- one product: the cloud's centre, then hi(x - mu) rows and the two scaled norms -------------------------------------------
@@ -190,13 +144,13 @@ __global__ __launch_bounds__(256) void knn_split1_kernel(const float* __restrict
 }
 
 // ---- shared Gram-tile machinery of the bound / collect kernels ------------------------------------------------------------
-// Block = WAVES waves handling 256 queries; a wave owns SETS sets of 32 queries (B operands hi / lo, register-resident:
-// SETS * C / 2 VGPRs); candidate tiles of 32 rows (hi | lo, 4C bytes per row) go through a double-buffered LDS panel
+// Block = WAVES waves handling 256 queries; a wave owns SETS sets of 32 queries (B operands hi, register-resident);
+// candidate tiles of 32 rows (hi, 2C bytes per row) go through a double-buffered LDS panel
 // shared by the waves.  Accumulator layout as in dg_knn.h: lane (j, h) holds, for query j of a set, the candidates
 // acc_row(r, h).  (C = 128 with two sets per wave needs more than 256 registers: it runs 8 waves x 1 set.)
 template <int C>
 struct KfTile {
-  static constexpr int XW = kKfProducts == 1 ? C : 2 * C;  // bf16 words per row of xs: hi, or hi | lo
+  static constexpr int XW = C;                     // bf16 words per row of xs
   static constexpr int ROWB = 2 * XW + 16;         // LDS row stride in bytes (odd multiple of 16: conflict-free b128 reads)
   static constexpr int KS = C / 16;                // MFMA k-steps
 };
@@ -248,18 +202,15 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void knn_gram_kerne
   const unsigned short* xp = xs + (long long)v * N * XW;
   const float* np_ = nsc + (long long)v * N;   // the scaled candidate norms this pass uses (nl: bound, nu: collect)
   const int q0 = qb * kKfQB + wave * (32 * SETS);
-  // query operands: hi / lo fragments of the k-steps
-  kf_bf16x8 bh[SETS][KS], bl[SETS][kKfProducts == 3 ? KS : 1];
+  // query operands: hi fragments of the k-steps
+  kf_bf16x8 bh[SETS][KS];
   float thr[SETS];
 #pragma unroll
   for (int s = 0; s < SETS; ++s) {
     const int qrow = q0 + 32 * s + j < N ? q0 + 32 * s + j : N - 1;
     const unsigned short* src = xp + (long long)qrow * XW + 8 * h;
 #pragma unroll
-    for (int kk = 0; kk < KS; ++kk) {
-      bh[s][kk] = *reinterpret_cast<const kf_bf16x8*>(src + 16 * kk);
-      if constexpr (kKfProducts == 3) bl[s][kk] = *reinterpret_cast<const kf_bf16x8*>(src + C + 16 * kk);
-    }
+    for (int kk = 0; kk < KS; ++kk) bh[s][kk] = *reinterpret_cast<const kf_bf16x8*>(src + 16 * kk);
     // (a threshold of -inf would let the -inf scores of the rows past N through: clamp)
     thr[s] = COLLECT ? __builtin_fmaxf(theta[(long long)v * N + qrow], -3.0e38f) : 0.0f;
   }
@@ -325,13 +276,6 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void knn_gram_kerne
       const kf_bf16x8 ah = *reinterpret_cast<const kf_bf16x8*>(arow + 32 * kk);
 #pragma unroll
       for (int s = 0; s < SETS; ++s) acc[s] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[s][kk], acc[s], 0, 0, 0);
-      if constexpr (kKfProducts == 3) {
-        const kf_bf16x8 al = *reinterpret_cast<const kf_bf16x8*>(arow + 2 * C + 32 * kk);
-#pragma unroll
-        for (int s = 0; s < SETS; ++s) acc[s] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[s][kk], acc[s], 0, 0, 0);
-#pragma unroll
-        for (int s = 0; s < SETS; ++s) acc[s] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[s][kk], acc[s], 0, 0, 0);
-      }
     }
     if constexpr ((MODE & 1) != 0) {
 #pragma unroll

@@ -46,10 +46,7 @@ using namespace dg;
 // exhaustive knn3_kernel of rounds 2-5 (identical indices; the knob exists for A/B timing and the cross-check test)
 // the kernel that writes a stage's output also leaves the next stage's kNN operands (MPA_KNN_PRODUCER=0: the separate
 // rownorm / centre / split kernels of rounds 3-5a; identical operands either way)
-bool knn_producer() {
-  const char* e = getenv("MPA_KNN_PRODUCER");
-  return !(e != nullptr && e[0] == '0');
-}
+bool knn_producer() { return mpa::env_flag("MPA_KNN_PRODUCER", true); }  // (read at every call: the cross-check test flips it)
 bool knn3_gate() {
   const char* e = getenv("MPA_KNN3");
   return !(e != nullptr && e[0] == 's');
@@ -1347,24 +1344,16 @@ void knn_wide(const float* x, int ld, float* norm, const KnnWs& k, int64_t M, in
   const int64_t R = M * N;
   constexpr int SETS = 1, WAVES = 8;
   const dim3 ggram((unsigned)((N + kKfQB - 1) / kKfQB), DG_KNN_GRID_Y(M));
-  if (!(prepared && kKfProducts == 1)) {  // prepared: the producer of x left norm, xs, nl, nu (dg_apply_knn_kernel)
+  if (!prepared) {  // prepared: the producer of x left norm, xs, nl, nu (dg_apply_knn_kernel)
   // (round 5: one fused pass — norm chain + split from the same staged float4 — was built and measured 0.03-0.05 ms SLOWER
   // per C = 128 search on one box, three alternations: its hi / lo stores are 32-byte segments per row and slab, where the
   // split kernels write full lines; LABBOOK 5.2)
   hipLaunchKernelGGL(rownorm_kernel<C>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, x, ld, norm, hdr);
-  if constexpr (kKfProducts == 1) {
-    hipLaunchKernelGGL(knn_centre_kernel<C>, dim3((unsigned)M), dim3(C), 0, s, x, ld, (int)N, k.mu, hdr);
-    hipLaunchKernelGGL(knn_split1_kernel<C>, dim3((unsigned)((R * (C / 4) + 255) / 256)), dim3(256), 0, s, x, ld,
-                       (const float*)norm, (const float*)k.mu, (int)N, k.xs, k.nl, k.nu, hdr);
-  } else {
-    hipLaunchKernelGGL(knn_split_kernel<C>, dim3((unsigned)((R * (C / 4) + 255) / 256)), dim3(256), 0, s, x, ld,
-                       (const float*)norm, k.xs, k.nl, k.nu, hdr);
+  hipLaunchKernelGGL(knn_centre_kernel<C>, dim3((unsigned)M), dim3(C), 0, s, x, ld, (int)N, k.mu, hdr);
+  hipLaunchKernelGGL(knn_split1_kernel<C>, dim3((unsigned)((R * (C / 4) + 255) / 256)), dim3(256), 0, s, x, ld,
+                     (const float*)norm, (const float*)k.mu, (int)N, k.xs, k.nl, k.nu, hdr);
   }
-  }
-#ifndef KF_BOUND_MODE  // timing probes only (tools/build_variant.sh): see knn_gram_kernel's MODE
-#define KF_BOUND_MODE 0
-#endif
-  hipLaunchKernelGGL((knn_gram_kernel<C, false, SETS, WAVES, KF_BOUND_MODE>), ggram, dim3(64 * WAVES), 0, s, (const unsigned short*)k.xs,
+  hipLaunchKernelGGL((knn_gram_kernel<C, false, SETS, WAVES, 0>), ggram, dim3(64 * WAVES), 0, s, (const unsigned short*)k.xs,
                      (const float*)k.nl, (const float*)k.nl, (const float*)k.nu, (int)N, k.theta, k.surv, k.scnt, hdr);
   hipLaunchKernelGGL((knn_gram_kernel<C, true, SETS, WAVES>), ggram, dim3(64 * WAVES), 0, s, (const unsigned short*)k.xs,
                      (const float*)k.nu, (const float*)k.nl, (const float*)k.nu, (int)N, k.theta, k.surv, k.scnt, hdr);
@@ -1610,7 +1599,7 @@ int dgcnn_forward_impl(const float* points, const float* valids, const float* co
              (const float*)running_mean[l], (const float*)running_var[l], eps, w.bn[l]);
     }
     // BatchNorm + LeakyReLU into the concatenation; stages 1-3 also leave the next stage's kNN operands
-    const bool feeds_knn = l < 3 && kKfProducts == 1 && knn_producer() && !(graphs != nullptr && graphs[l + 1] != nullptr);
+    const bool feeds_knn = l < 3 && knn_producer() && !(graphs != nullptr && graphs[l + 1] != nullptr);
     if (feeds_knn && CO == 64) {
       launch(dg_apply_centre_kernel<64>, dim3((unsigned)M), dim3(64), s, (const float*)w.esel[l], (const float*)w.bn[l],
              (int)N, w.knn.mu, (const int*)w.hdr);

@@ -43,9 +43,6 @@ constexpr int kStartStride = kMaxCells + 8;   // ints per (sample, shape, role) 
 #ifndef MPA_GRID_KS
 #define MPA_GRID_KS 2
 #endif
-#ifndef MPA_GRID_XCD  // 1: XCD-aware, work-proportional wave table (grid_assign_plan); 0: waves x of pair y
-#define MPA_GRID_XCD 1
-#endif
 #ifndef MPA_GRID_WAVES
 #define MPA_GRID_WAVES 768
 #endif
@@ -774,12 +771,6 @@ struct LaneState {
 // Magnitudes whose squares may overflow take the pinned path unconditionally (tn' = -inf / qnlo = -inf); a NaN gate value
 // (inf - inf, 0 * inf) belongs to a pair whose pinned distance is inf or NaN, which never wins; 1e-30 of absolute slack covers
 // underflowing products.  The sentinel records (inf, inf, inf, +inf) give f = +inf or NaN.
-#ifndef MPA_GRID_EXP  // 3: every scan runs twice (same results) — the time difference is what the scans cost (LABBOOK 6.3)
-#define MPA_GRID_EXP 0
-#endif
-#ifndef MPA_GRID_FMA_GATE
-#define MPA_GRID_FMA_GATE 1  // 0: the pinned distance for every pair (the scan of rounds 2-5; A/B builds)
-#endif
 constexpr float kGateC = 4e-6f;
 __device__ __forceinline__ float gate_norm_lo(float x, float y, float z) {
   const float n = (x * x + y * y) + z * z;
@@ -788,11 +779,7 @@ __device__ __forceinline__ float gate_norm_lo(float x, float y, float z) {
 // the LDS form of a target record: coordinates and tn'; the original point index goes to a list of its own (read only by the
 // few pairs that pass the gate)
 __device__ __forceinline__ float4 gate_record(const float4 t) {
-#if MPA_GRID_FMA_GATE
   return make_float4(-2.0f * t.x, -2.0f * t.y, -2.0f * t.z, gate_norm_lo(t.x, t.y, t.z));
-#else
-  return t;
-#endif
 }
 
 __device__ __forceinline__ float dist_exact_s(float dx, float dy, float dz) { return (dx * dx + dy * dy) + dz * dz; }
@@ -926,7 +913,6 @@ __device__ unsigned long long g_grid_stats[24];  // 0-7: items, active lanes, sc
 #endif
 
 // every lane scans the wn candidate records staged in LDS (padded to a multiple of 8 with sentinels)
-#if MPA_GRID_FMA_GATE
 // STEP = s.split as a constant: the T reads of a chunk are one address register plus immediate offsets
 template <int T, int STEP>
 __device__ __forceinline__ void scan_cand_step(LaneState& s, const float4* __restrict__ cand, const int* __restrict__ cidx,
@@ -972,45 +958,10 @@ __device__ __forceinline__ void scan_cand_step(LaneState& s, const float4* __res
 }
 template <int T>
 __device__ __forceinline__ void scan_cand(LaneState& s, const float4* __restrict__ cand, const int* __restrict__ cidx, int wn) {
-#if MPA_GRID_EXP == 3  // (timing experiment: every scan twice)
-  if (s.split == 1) scan_cand_step<T, 1>(s, cand, cidx, wn);
-  else if (s.split == 2) scan_cand_step<T, 2>(s, cand, cidx, wn);
-  else scan_cand_step<T, 4>(s, cand, cidx, wn);
-  asm volatile("" : "+v"(s.best), "+v"(s.bidx));
-#endif
   if (s.split == 1) scan_cand_step<T, 1>(s, cand, cidx, wn);  // (wave-uniform)
   else if (s.split == 2) scan_cand_step<T, 2>(s, cand, cidx, wn);
   else scan_cand_step<T, 4>(s, cand, cidx, wn);
 }
-#else
-template <int T>
-__device__ __forceinline__ void scan_cand(LaneState& s, const float4* __restrict__ cand, const int* __restrict__ cidx, int wn) {
-  // split > 1: this group of lanes takes candidates sub, sub + split, ... (split LDS addresses per read, not one)
-  const int step = s.split, sub = (int)threadIdx.x / (64 / s.split);
-  for (int rep = 0; rep < (MPA_GRID_EXP == 3 ? 2 : 1); ++rep)
-  for (int j0 = 0; j0 < wn; j0 += T * step) {
-    float4 cur[T];
-#pragma unroll
-    for (int t = 0; t < T; ++t) cur[t] = cand[j0 + t * step + sub];
-    float d[T];
-#pragma unroll
-    for (int t = 0; t < T; ++t) d[t] = dist_exact_s(s.X - cur[t].x, s.Y - cur[t].y, s.Z - cur[t].z);
-    float cmin = d[0];
-#pragma unroll
-    for (int t = 1; t < T; ++t) cmin = __builtin_fminf(cmin, d[t]);
-    if (cmin <= s.best) {  // rare: an improvement, or a tie that may carry a lower index
-#pragma unroll
-      for (int t = 0; t < T; ++t) {
-        const int ti = __float_as_int(cur[t].w);
-        if (d[t] < s.best || (d[t] == s.best && ti < s.bidx)) {
-          s.best = d[t];
-          s.bidx = ti;
-        }
-      }
-    }
-  }
-}
-#endif
 
 // split mode: every group ends up with the best (distance, index) of all groups
 __device__ __forceinline__ void merge_halves(LaneState& s) {
@@ -1046,13 +997,13 @@ __device__ __forceinline__ void scan_range_coop(LaneState& s, const float4* __re
       for (int u = 0; u < U; ++u)
         if (j0 + 64 * u < wn) {
           cand[j0 + 64 * u] = gate_record(t[u]);
-          if (MPA_GRID_FMA_GATE) cidx[j0 + 64 * u] = __float_as_int(t[u].w);
+          cidx[j0 + 64 * u] = __float_as_int(t[u].w);
         }
     }
     if (lane < T) {
       const float inf = __builtin_inff();
-      cand[wn + lane] = make_float4(inf, inf, inf, MPA_GRID_FMA_GATE ? inf : __int_as_float(0x7fffffff));
-      if (MPA_GRID_FMA_GATE) cidx[wn + lane] = 0x7fffffff;
+      cand[wn + lane] = make_float4(inf, inf, inf, inf);
+      cidx[wn + lane] = 0x7fffffff;
     }
     __syncthreads();
     scan_cand<TC>(s, cand, cidx, wn);
@@ -1108,13 +1059,13 @@ __device__ __forceinline__ void scan_batch(LaneState& s, const float4* __restric
       for (int u = 0; u < U; ++u)
         if (j0 + 64 * u < wn) {
           cand[j0 + 64 * u] = gate_record(t[u]);
-          if (MPA_GRID_FMA_GATE) cidx[j0 + 64 * u] = __float_as_int(t[u].w);
+          cidx[j0 + 64 * u] = __float_as_int(t[u].w);
         }
     }
     if (lane < T) {  // pad the last chunk of 8 with records that can never win
       const float inf = __builtin_inff();
-      cand[wn + lane] = make_float4(inf, inf, inf, MPA_GRID_FMA_GATE ? inf : __int_as_float(0x7fffffff));
-      if (MPA_GRID_FMA_GATE) cidx[wn + lane] = 0x7fffffff;
+      cand[wn + lane] = make_float4(inf, inf, inf, inf);
+      cidx[wn + lane] = 0x7fffffff;
     }
     __syncthreads();
     scan_cand<TC>(s, cand, cidx, wn);
@@ -1139,7 +1090,7 @@ __global__ __launch_bounds__(64) void grid_search_kernel(
     IdxT* __restrict__ idx2, const XcdPlan* __restrict__ plan) {
   __shared__ float4 cand[kCand];
   __shared__ int sidx[kCand];  // record index of every position of the current window
-  __shared__ int cidx[MPA_GRID_FMA_GATE ? kCand : 1];  // original point index of every candidate of the window
+  __shared__ int cidx[kCand];  // original point index of every candidate of the window
   // candidates per step of the LDS scan: the operator's instantiation carries a few more registers (relative geometry, border
   // cells) and reaches six waves per SIMD with 3 (77 registers; 4: 81)
   constexpr int TC = GENERIC ? MPA_GRID_CAND_CHUNK_GENERIC : MPA_GRID_CAND_CHUNK;
@@ -1430,7 +1381,7 @@ int launch_grid_shape_search(const float* valids, const float* S1, const float* 
   int* worklist = batches + 4 * B * (int64_t)kStartStride;
   // persistent waves (768 per (sample, direction) on average) walk a pair's work list of (super-cell, 64-query batch) items
   XcdPlan* plan = reinterpret_cast<XcdPlan*>(worklist + 4 * B * (int64_t)kWorkStride);
-  const bool xcd_table = MPA_GRID_XCD && 2 * B >= 8 && 2 * B <= kMaxPairs;
+  const bool xcd_table = 2 * B >= 8 && 2 * B <= kMaxPairs;
   const int nwaves = (int)(MPA_GRID_WAVES * 2 * B);
   if (phases & 1)
     hipLaunchKernelGGL(grid_sort_kernel, dim3((unsigned)(4 * B)), dim3(1024), 0, s, valids, S1, S2, (int)P, (int)N,
@@ -1504,7 +1455,7 @@ int launch_cloud_grid_search(const float* xyz1, const float* xyz2, int64_t B, in
                              int64_t* idx1, float* dist2, int64_t* idx2, void* workspace, const int** fallback,
                              hipStream_t s) {
   const CloudWs w = cloud_ws(workspace, B, n1, n2);
-  const bool xcd_table = MPA_GRID_XCD && 2 * B >= 8 && 2 * B <= kMaxPairs;
+  const bool xcd_table = 2 * B >= 8 && 2 * B <= kMaxPairs;
   const int nwaves = (int)(MPA_GRID_WAVES * 2 * B);
   zero_words_async(w.ticket, 16, s);
   hipLaunchKernelGGL(cloud_stats_kernel, dim3(2, (unsigned)B), dim3(1024), 0, s, xyz1, xyz2, (int)n1, (int)n2,

@@ -31,9 +31,6 @@
 namespace mpa {
 namespace {
 
-#ifndef MPA_LEAF_GATE  // 1: leaves are screened on the matrix cores (default); 0: every visited leaf is scanned exactly
-#define MPA_LEAF_GATE 1
-#endif
 constexpr int kLeaf = 32;                 // points per leaf
 constexpr int kLeafMaxPad = 2048;         // padded points per part (<= 64 leaves: one lane per leaf)
 constexpr int kNoIdx = 0x7fffffff;
@@ -409,10 +406,8 @@ __device__ __forceinline__ bool leaf_search_wave(const LeafArgs& g, int m, int k
   int scans = 0;
   bool done = true;
   [[maybe_unused]] int st_tests = 0, st_parts = 0, st_exact = 0;
-#if MPA_LEAF_GATE
   GateWave gw;
   gate_setup(gw, qlo, qhi, X, Y, Z, has);
-#endif
   // The leaves of target part tp, nearest first.  Lane l holds leaf l's box and its distance to the query box; the
   // records of the leaf to come are requested while the current one is scanned.
   auto search_part = [&](int tp) {
@@ -433,32 +428,16 @@ __device__ __forceinline__ bool leaf_search_wave(const LeafArgs& g, int m, int k
     };
     unsigned clm, nlm;
     int cur = pick(clm);
-#if MPA_LEAF_GATE
     float4 tG;  // lane l: record l % 32 of the leaf
     if (cur >= 0) tG = rec[cur * kLeaf + (lane & 31)];
-#else
-    float4 tA, tB;
-    if (cur >= 0) {
-      tA = rec[cur * kLeaf + (lane & 15)];
-      tB = rec[cur * kLeaf + 16 + (lane & 15)];
-    }
-#endif
     while (cur >= 0) {
       if (scans >= cap) {  // deferred to the second pass (which visits every leaf again, with this wave's best as bound)
         done = false;
         return;
       }
       const int nxt = pick(nlm);
-#if MPA_LEAF_GATE
       float4 nG = tG;
       if (nxt >= 0) nG = rec[nxt * kLeaf + (lane & 31)];
-#else
-      float4 nA = tA, nB = tB;
-      if (nxt >= 0) {
-        nA = rec[nxt * kLeaf + (lane & 15)];
-        nB = rec[nxt * kLeaf + 16 + (lane & 15)];
-      }
-#endif
       if (clm <= bound) {  // (the bound may have shrunk since this leaf was picked)
         const float bx[8] = {readlane_f(blo.x, cur), readlane_f(blo.y, cur), readlane_f(blo.z, cur), 0.0f,
                              readlane_f(bhi.x, cur), readlane_f(bhi.y, cur), readlane_f(bhi.z, cur), 0.0f};
@@ -466,11 +445,6 @@ __device__ __forceinline__ bool leaf_search_wave(const LeafArgs& g, int m, int k
         MPA_LSTAT(st_tests);
         if (__ballot(mine <= key_dist(best))) {
           ++scans;
-#ifdef MPA_LEAF_EXP  // timing experiments: the scan of a visited leaf 0 (wrong results) or 2 times
-          for (int rep_ = 0; rep_ < MPA_LEAF_EXP; ++rep_) {
-            asm volatile("" : "+v"(X));
-#endif
-#if MPA_LEAF_GATE
           // the gate: 4 matrix instructions, ~12 VALU instructions per 16 values
           const bool lo = lane < 32;
           const bool padrec = __float_as_int(tG.w) == kNoIdx;
@@ -524,24 +498,12 @@ __device__ __forceinline__ bool leaf_search_wave(const LeafArgs& g, int m, int k
             const u64 k = make_key(dist3(X - wx, Y - wy, Z - wz), wi);
             best = (cand && k < best) ? k : best;
           }
-#else
-          scan16(tA, X, Y, Z, best);
-          scan16(tB, X, Y, Z, best);
-#endif
-#ifdef MPA_LEAF_EXP
-          }
-#endif
           bound = wave_max_u((unsigned)(best >> 32));
         }
       }
       cur = nxt;
       clm = nlm;
-#if MPA_LEAF_GATE
       tG = nG;
-#else
-      tA = nA;
-      tB = nB;
-#endif
     }
   };
   if constexpr (SHAPE) {

@@ -97,9 +97,10 @@ struct GemmArgs {
   // partial tile in sk_buf and takes the tile's ticket; the second block to arrive adds the two halves (lower half first,
   // whichever arrived first) and runs the epilogue.  The half tiles cross XCDs as agent-scope atomic stores / loads ordered
   // by the ticket (coop_reduce.h's hand-over: a release FENCE per block is a write-back of the XCD's L2 and made this
-  // kernel 3 x slower, LABBOOK 5.3 xvii; -DMPA_TF_SK_FENCE=1 builds that textbook form: the fallback should a part or a
-  // compiler ever stop acknowledging sc1 stores at agent scope — tests/test_model_gpu.py holds the hand-over to bit-equal
-  // results over hundreds of launches).  Tickets are zero between launches (reset after use).
+  // kernel 3 x slower, LABBOOK 5.3 xvii.  That textbook form — plain stores, then an agent-scope release fence before the
+  // ticket and an acquire fence after it — is the fallback should a part or a compiler ever stop acknowledging sc1 stores
+  // at agent scope; tests/test_model_gpu.py holds the hand-over to bit-equal results over hundreds of launches).  Tickets
+  // are zero between launches (reset after use).
   float* sk_buf;        // [tiles][2][1024]
   unsigned* sk_ticket;  // [tiles]
   int zero_n;           // words of `zero` to clear (0: 64)
@@ -116,9 +117,6 @@ struct GemmArgs {
 // partial tiles meet in LDS (fixed order) and the epilogue writes 128-byte row segments.
 // Requires N % 32 == 0 and K % 64 == 0.
 // WT: the weight is given as W^T, i.e. [K, N] row-major (input gradients reuse the forward weights untransposed).
-#ifndef MPA_TF_SK_FENCE
-#define MPA_TF_SK_FENCE 0
-#endif
 constexpr int kGW = 8, kGT = kGW * 64, kKP = 128, kLD = kKP + 4;
 
 __host__ __device__ inline int gemm_phase(int K) {
@@ -136,15 +134,6 @@ template <int EPI, bool WT, int NPH, int LNM = 0, bool SK = false>
 __global__ __launch_bounds__(kGT) void gemm_kernel(const GemmArgs g) {
   static_assert(!SK || (NPH > 0 && LNM == 0 && EPI != EPI_STATS), "split-K: whole phases, plain operands");
   const Drop drop = (EPI == EPI_RELU_DROP || EPI == EPI_DROP_RESID || LNM == 2) ? resolve_seed(g.drop) : g.drop;
-#ifdef MPA_GEMM_STAMPS  // s_memtime stamps of one block of the FFN-up GEMM (EPI_RELU_DROP with the fused LayerNorm), printed
-  constexpr bool kStamp = EPI == EPI_RELU_DROP && LNM == 1;
-  unsigned long long ts[8];
-  int nts = 0;
-#define GEMM_STAMP() do { if (kStamp) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); ts[nts++] = __builtin_amdgcn_s_memtime(); } } while (0)
-#else
-#define GEMM_STAMP() do { } while (0)
-#endif
-  GEMM_STAMP();
   const int kz = SK ? (int)blockIdx.z * NPH : 0;  // first K phase of this block
   constexpr bool LNF = LNM == 1;
   static_assert(LNM == 0 || NPH == 2, "the fused LayerNorm needs the whole K = 2 x 128 row in registers");
@@ -212,7 +201,6 @@ __global__ __launch_bounds__(kGT) void gemm_kernel(const GemmArgs g) {
     Stage st[NPH];
 #pragma unroll
     for (int ph = 0; ph < NPH; ++ph) fetch(ph, st[ph]);
-    GEMM_STAMP();
     if constexpr (LNF) {
       // thread t holds, per phase, columns 4 (t % 32) .. + 3 of rows t / 32 and 16 + t / 32: a row lives in one half-wave
       const int c4 = threadIdx.x & 31;
@@ -358,7 +346,6 @@ __global__ __launch_bounds__(kGT) void gemm_kernel(const GemmArgs g) {
         __syncthreads();
       }
     }
-    GEMM_STAMP();
 #pragma unroll
     for (int ph = 0; ph < NPH; ++ph) {
       stash(ph, st[ph], ph % kBuf);
@@ -378,7 +365,6 @@ __global__ __launch_bounds__(kGT) void gemm_kernel(const GemmArgs g) {
       __syncthreads();
     }
   }
-  GEMM_STAMP();
   float(*red)[16][64] = reinterpret_cast<float(*)[16][64]>(lds);  // 32 KB, the panels are dead
 #pragma unroll
   for (int r = 0; r < 16; ++r) red[wave][r][lane] = acc[r];
@@ -401,15 +387,9 @@ __global__ __launch_bounds__(kGT) void gemm_kernel(const GemmArgs g) {
     __shared__ int sk_last;
     const long long tile = (long long)blockIdx.x * gridDim.y + blockIdx.y;
     float* mine = g.sk_buf + (tile * 2 + blockIdx.z) * 1024;
-#if MPA_TF_SK_FENCE  // the textbook form (A/B and fallback builds): plain stores, agent-scope release / acquire fences
-    mine[threadIdx.x] = tot[0];
-    mine[kGT + threadIdx.x] = tot[1];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-#else
     __hip_atomic_store(mine + threadIdx.x, tot[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(mine + kGT + threadIdx.x, tot[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // written through and acknowledged before the ticket is taken
-#endif
     __syncthreads();
     if (threadIdx.x == 0) {
       const unsigned old = atomicAdd(g.sk_ticket + tile, 1u);
@@ -419,13 +399,8 @@ __global__ __launch_bounds__(kGT) void gemm_kernel(const GemmArgs g) {
     __syncthreads();
     if (!sk_last) return;
     const float* other = g.sk_buf + (tile * 2 + (1 - blockIdx.z)) * 1024;
-#if MPA_TF_SK_FENCE
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    const float o0 = other[threadIdx.x], o1 = other[kGT + threadIdx.x];
-#else
     const float o0 = __hip_atomic_load(other + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const float o1 = __hip_atomic_load(other + kGT + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
     tot[0] = blockIdx.z == 0 ? tot[0] + o0 : o0 + tot[0];  // lower half of K first, whoever finishes
     tot[1] = blockIdx.z == 0 ? tot[1] + o1 : o1 + tot[1];
   }
@@ -453,12 +428,6 @@ __global__ __launch_bounds__(kGT) void gemm_kernel(const GemmArgs g) {
     }
     g.C[o] = v;
   }
-#ifdef MPA_GEMM_STAMPS
-  GEMM_STAMP();
-  if (kStamp && ((blockIdx.x == 5 && blockIdx.y == 7) || (blockIdx.x + blockIdx.y * gridDim.x) % 97 == 0) && threadIdx.x == 0)
-    printf("gemm stamps block (%d, %d) start %llu (s_memtime ticks): loads %llu, prologue %llu, stash + chains %llu, reduce + epilogue %llu\n",
-           (int)blockIdx.x, (int)blockIdx.y, ts[0] % 10000000ull, ts[1] - ts[0], ts[2] - ts[1], ts[3] - ts[2], ts[4] - ts[3]);
-#endif
   if constexpr (EPI == EPI_STATS) {  // column sums of the 32 x 32 tile, rows in ascending order
     __syncthreads();                 // every partial tile has been read
     float(*tile)[33] = reinterpret_cast<float(*)[33]>(lds);

@@ -392,11 +392,8 @@ __global__ __launch_bounds__(64) void attn_fwd_mfma_kernel(const float* __restri
 //             and write it to qkv (for backward); waves 3..6 hash the dropout keep-scales of the probabilities meanwhile;
 //   attention wave 0, as attn_fwd_mfma_kernel, on registers.
 // The normalised rows and their statistics are written by head 0's block as the standalone kernels wrote them.
-// 13.7 us against 9.5 + 9.0 us and a launch boundary (s_memtime stamps of a block, -DMPA_QKV_EXP=9: loads 2.4 us, LayerNorm +
+// 13.7 us against 9.5 + 9.0 us and a launch boundary (s_memtime stamps of a block: loads 2.4 us, LayerNorm +
 // panel 2.0, chains 1.9, reduction 2.9, attention 2.9).
-#ifndef MPA_QKV_EXP  // timing experiments: 1 stop after the staging, 2 after the chains, 3 after the reduction (wrong results)
-#define MPA_QKV_EXP 0
-#endif
 constexpr int kQT = 512, kQLD = 256 + 4;  // (padded rows: the lane-per-row fragment reads are conflict-free)
 __global__ __launch_bounds__(kQT, 2) void attn_qkv_fwd_kernel(const float* __restrict__ x, const float* __restrict__ wqkv,
                                                            const float* __restrict__ bqkv, const float* __restrict__ gamma,
@@ -417,14 +414,6 @@ __global__ __launch_bounds__(kQT, 2) void attn_qkv_fwd_kernel(const float* __res
   const int b = blockIdx.x / H, hd = blockIdx.x % H;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
   if (zero != nullptr && blockIdx.x == 0 && (int)threadIdx.x < zero_n) zero[threadIdx.x] = 0u;
-#if MPA_QKV_EXP == 9
-  unsigned long long ts[8];
-  int nts = 0;
-#define QKV_STAMP() do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); ts[nts++] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define QKV_STAMP() do { } while (0)
-#endif
-  QKV_STAMP();
   // ---- loads, all in flight at once and fully coalesced: a wave reads one 1 KB row per instruction
   float4 xr[4];
 #pragma unroll
@@ -458,7 +447,6 @@ __global__ __launch_bounds__(kQT, 2) void attn_qkv_fwd_kernel(const float* __res
   const float bv = bqkv[2 * D + hd * DH + c];
 #pragma unroll
   for (int r = 0; r < 16; ++r) kv[r] = (acc_row(r, h) < P && kv[r] == 1.0f) ? 1.0f : 0.0f;
-  QKV_STAMP();
   // ---- LayerNorm: a wave holds a whole row (two passes, as ln_fwd_kernel: mean, then the variance of the deviations)
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -479,10 +467,6 @@ __global__ __launch_bounds__(kQT, 2) void attn_qkv_fwd_kernel(const float* __res
     }
   }
   __syncthreads();
-  QKV_STAMP();
-#if MPA_QKV_EXP == 1
-  return;
-#endif
   // ---- three chains per wave over its eighth of K: k = 32 wave + 8 v + 4 h + e
   f32x16 aq = {0}, ak = {0}, av = {0};
   {
@@ -507,10 +491,6 @@ __global__ __launch_bounds__(kQT, 2) void attn_qkv_fwd_kernel(const float* __res
       av = __builtin_amdgcn_mfma_f32_32x32x2f32(hv.w, v4.w, av, 0, 0, 0);
     }
   }
-  QKV_STAMP();
-#if MPA_QKV_EXP == 2
-  if (aq[0] + ak[1] + av[2] != 12345.0f) return;
-#endif
   __syncthreads();  // every wave is done with the panels: their memory takes the partial tiles
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
@@ -571,10 +551,6 @@ __global__ __launch_bounds__(kQT, 2) void attn_qkv_fwd_kernel(const float* __res
     }
   }
   if (wave != 0) return;
-  QKV_STAMP();
-#if MPA_QKV_EXP == 3
-  if (tl[0] != 12345.0f) return;
-#endif
   float ka[16], qb[16], vb[16];
   const float scale = 1.0f / __builtin_sqrtf((float)DH);
   const float onf = on ? 1.0f : 0.0f;
@@ -626,12 +602,6 @@ __global__ __launch_bounds__(kQT, 2) void attn_qkv_fwd_kernel(const float* __res
     const int i = acc_row(r, h);
     if (i < P) out[((long long)b * P + i) * D + hd * DH + c] = o[r];
   }
-#if MPA_QKV_EXP == 9
-  QKV_STAMP();
-  if (blockIdx.x == 100 && lane == 0)
-    printf("attn_qkv stamps (s_memtime ticks): loads %llu, LN+stage %llu, chains %llu, reduce %llu, attention %llu\n", ts[1] - ts[0],
-           ts[2] - ts[1], ts[3] - ts[2], ts[4] - ts[3], ts[5] - ts[4]);
-#endif
 }
 
 // Backward of the same.  dP = dO V^T is taken in BOTH orientations (two chains over the head dimension): lane = query i
@@ -757,7 +727,7 @@ __global__ __launch_bounds__(64) void attn_bwd_mfma_kernel(const float* __restri
 // enumerated in that order on both operands).  Partial tiles meet in LDS; wave 0 runs attn_bwd_mfma_kernel's arithmetic.
 // Head 0's block writes what the standalone LayerNorm backward would have written: d x_mid, its masked copy, and the
 // sample's dgamma / dbeta partial row (ln_part[sample]: the reduction kernel is told B rows for this site).
-// 14.6 us against 9.0 + 7.8 us and a launch boundary (-DMPA_QKV_EXP=9 stamps of a block, in us: requests 3.7 — the saved
+// 14.6 us against 9.0 + 7.8 us and a launch boundary (s_memtime stamps of a block, in us: requests 3.7 — the saved
 // probabilities come from HBM —, LayerNorm backward + masks + panels 2.6, chains 0.6, reduction 2.2, attention 3.9).
 // CHAIN: the kernel goes on with what follows the attention's gradient on the way down — rows of a sample again:
 //   d(LN1 output)[tokens][256] = dqkv[tokens][768] . Wqkv[768][256] is a sum over the heads, so every (sample, head) block adds
@@ -812,11 +782,6 @@ __global__ __launch_bounds__(kBT, 2) void attn_do_bwd_kernel(
   float4(*part)[4][8][64] = reinterpret_cast<float4(*)[4][8][64]>(panel);
   static_assert(sizeof(float4) * 2 * 4 * 8 * 64 <= sizeof(float) * 64 * kQLD, "the partial tiles fit the panels");
   const Drop drop = resolve_seed(drop_in);
-#if MPA_QKV_EXP == 9
-  unsigned long long ts[8];
-  int nts = 0;
-#endif
-  QKV_STAMP();
   const int b = blockIdx.x / H, hd = blockIdx.x % H;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
   const long long row0 = (long long)b * P;
@@ -881,7 +846,6 @@ __global__ __launch_bounds__(kBT, 2) void attn_do_bwd_kernel(
       kb0[r] = qkv[tk * 3 * D + D + hd * DH + c] * o2;
     }
   }
-  QKV_STAMP();
   // ---- LayerNorm backward of the rows, dropout mask, panel
   float4 pxh = make_float4(0.f, 0.f, 0.f, 0.f), pg = make_float4(0.f, 0.f, 0.f, 0.f);
   float4 vrow[4];  // d x_mid of the block's rows (CHAIN: the residual of LN1's backward)
@@ -937,7 +901,6 @@ __global__ __launch_bounds__(kBT, 2) void attn_do_bwd_kernel(
     for (int w = 0; w < 8; ++w) sm += colp[w][k >> 8][k & 255];
     ln_part[(long long)b * 2 * D + k] = sm;
   }
-  QKV_STAMP();
   // ---- two chains per wave over its eighth of K: k = 32 wave + 8 v + 4 h + e
   f32x16 as = {0}, at = {0};
   {
@@ -956,7 +919,6 @@ __global__ __launch_bounds__(kBT, 2) void attn_do_bwd_kernel(
       at = __builtin_amdgcn_mfma_f32_32x32x2f32(w4.w, m4.w, at, 0, 0, 0);
     }
   }
-  QKV_STAMP();
   __syncthreads();  // every wave is done with the panels: their memory takes the partial tiles
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
@@ -995,7 +957,6 @@ __global__ __launch_bounds__(kBT, 2) void attn_do_bwd_kernel(
     }
   }
   if (wave == 0) {
-  QKV_STAMP();
   float gb0[16];
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
@@ -1057,12 +1018,6 @@ __global__ __launch_bounds__(kBT, 2) void attn_do_bwd_kernel(
     }
   }
   }  // wave 0
-#if MPA_QKV_EXP == 9
-  if (wave == 0) QKV_STAMP();
-  if (blockIdx.x == 100 && lane == 0 && wave == 0)
-    printf("attn_do_bwd stamps (s_memtime ticks): loads %llu, LN backward + panels %llu, chains %llu, reduce %llu, attention %llu\n",
-           ts[1] - ts[0], ts[2] - ts[1], ts[3] - ts[2], ts[4] - ts[3], ts[5] - ts[4]);
-#endif
   if constexpr (CHAIN) {
     __syncthreads();  // the head's d q | d k | d v tiles are in LDS
     // what the sample's last block needs for LN1's backward (requested by every block: one of eight uses it, none waits —
@@ -1082,10 +1037,6 @@ __global__ __launch_bounds__(kBT, 2) void attn_do_bwd_kernel(
 #pragma unroll
       for (int k = 0; k < 48; ++k) wq[k] = wq0[k][lane];
     }
-#if MPA_QKV_EXP == 9
-    unsigned long long tc[6];
-    tc[0] = __builtin_amdgcn_s_memtime();
-#endif
     f32x16 acc = {0};
 #pragma unroll
     for (int t = 0; t < 3; ++t)
@@ -1103,13 +1054,7 @@ __global__ __launch_bounds__(kBT, 2) void attn_do_bwd_kernel(
       const int xr = acc_row(r, h);
       if (xr < P) __hip_atomic_store(mine + (long long)xr * D, acc[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-#if MPA_QKV_EXP == 9
-    tc[1] = __builtin_amdgcn_s_memtime();
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // written through and acknowledged before the ticket is taken
-#if MPA_QKV_EXP == 9
-    tc[2] = __builtin_amdgcn_s_memtime();
-#endif
     __syncthreads();
     if (threadIdx.x == 0) {
       const unsigned old = atomicAdd(ch.ticket + b, 1u);
@@ -1117,9 +1062,6 @@ __global__ __launch_bounds__(kBT, 2) void attn_do_bwd_kernel(
       if (old == (unsigned)(H - 1)) ch.ticket[b] = 0u;  // ready for the next launch
     }
     __syncthreads();
-#if MPA_QKV_EXP == 9
-    tc[3] = __builtin_amdgcn_s_memtime();
-#endif
     if (!last_s) return;
     // ---- the sample's last block: the eight heads' partial tiles in head order, then LN1's backward on the rows
     float4 dl[4];
@@ -1144,9 +1086,6 @@ __global__ __launch_bounds__(kBT, 2) void attn_do_bwd_kernel(
         dl[i] = make_float4(a.x, a.y, a.z, a.w);
       }
     }
-#if MPA_QKV_EXP == 9
-    tc[4] = __builtin_amdgcn_s_memtime();
-#endif
     float4 qxh = make_float4(0.f, 0.f, 0.f, 0.f), qg = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -1186,11 +1125,6 @@ __global__ __launch_bounds__(kBT, 2) void attn_do_bwd_kernel(
       for (int w = 0; w < 8; ++w) sm += colp[w][k >> 8][k & 255];
       ch.ln1_part[(long long)b * 2 * D + k] = sm;
     }
-#if MPA_QKV_EXP == 9
-    if (b == 12 && threadIdx.x == 0)
-      printf("attn chain stamps (ticks): product + stores %llu, store acknowledge %llu, ticket %llu, partial tiles %llu, LN1 backward %llu\n",
-             tc[1] - tc[0], tc[2] - tc[1], tc[3] - tc[2], tc[4] - tc[3], __builtin_amdgcn_s_memtime() - tc[4]);
-#endif
   }
 }
 
@@ -1551,46 +1485,31 @@ void launch_gemm_lnb(const GemmArgs& g, hipStream_t s) {
 
 // MPA_TF_LNB=0: every LayerNorm backward as its own launch (the A/B switch of the fusion above)
 bool lnb_fused() {
-  static const bool on = [] {
-    const char* e = getenv("MPA_TF_LNB");
-    return !(e != nullptr && e[0] == '0');
-  }();
+  static const bool on = mpa::env_flag("MPA_TF_LNB", true);
   return on;
 }
 
 // MPA_TF_QKVATTN=0: the qkv GEMM and the attention as two launches (the A/B switch of attn_qkv_fwd_kernel)
 bool qkv_attn_fused() {
-  static const bool on = [] {
-    const char* e = getenv("MPA_TF_QKVATTN");
-    return e == nullptr || e[0] != '0';
-  }();
+  static const bool on = mpa::env_flag("MPA_TF_QKVATTN", true);
   return on;
 }
 
 // MPA_TF_CHAIN=0: the d(LN1 output) GEMM and LN1's backward as launches of their own (attn_do_bwd_kernel<true>'s switch)
 bool chain_fused() {
-  static const bool on = [] {
-    const char* e = getenv("MPA_TF_CHAIN");
-    return e == nullptr || e[0] != '0';
-  }();
+  static const bool on = mpa::env_flag("MPA_TF_CHAIN", true);
   return on;
 }
 
 // MPA_TF_DOATTN=0: the d o GEMM (with LN2's backward) and the attention backward as two launches (attn_do_bwd_kernel's switch)
 bool do_attn_fused() {
-  static const bool on = [] {
-    const char* e = getenv("MPA_TF_DOATTN");
-    return e == nullptr || e[0] != '0';
-  }();
+  static const bool on = mpa::env_flag("MPA_TF_DOATTN", true);
   return on;
 }
 
 // MPA_TF_SPLITK=0: the K >= 768 GEMMs as one block per tile (the A/B switch of tf_gemm.h's split-K)
 bool splitk_on() {
-  static const bool on = [] {
-    const char* e = getenv("MPA_TF_SPLITK");
-    return !(e != nullptr && e[0] == '0');
-  }();
+  static const bool on = mpa::env_flag("MPA_TF_SPLITK", true);
   return on;
 }
 

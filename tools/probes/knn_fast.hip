@@ -40,10 +40,10 @@ void run(int n, int N, int mode) {
       if (r % N >= 8)
         for (int c = 0; c < C; ++c) h[r * C + c] = h[centre * C + c] * 3.0f + 0.02f * h[r * C + c];
     }
-  float *x, *norm, *nl, *nu, *theta; unsigned short *xs, *surv, *idx_ref, *idx_new; unsigned char* scnt; int *hdr, *flags;
+  float *x, *norm, *nl, *nu, *theta, *mu; unsigned short *xs, *surv, *idx_ref, *idx_new; unsigned char* scnt; int *hdr, *flags;
   const int Q128 = (N + 127) / 128;
-  hipMalloc(&x, R * C * 4); hipMalloc(&norm, R * 4); hipMalloc(&nl, R * 4); hipMalloc(&nu, R * 4); hipMalloc(&theta, R * 4);
-  hipMalloc(&xs, R * 2 * C * 2); hipMalloc(&surv, R * 2 * dg::kKfCap * 2); hipMalloc(&scnt, R * 2);
+  hipMalloc(&x, R * C * 4); hipMalloc(&norm, R * 4); hipMalloc(&nl, R * 4); hipMalloc(&nu, R * 4); hipMalloc(&theta, R * 4); hipMalloc(&mu, (size_t)n * C * 4);
+  hipMalloc(&xs, R * C * 2); hipMalloc(&surv, R * 2 * dg::kKfCap * 2); hipMalloc(&scnt, R * 2);
   hipMalloc(&idx_ref, R * 20 * 2); hipMalloc(&idx_new, R * 20 * 2); hipMalloc(&hdr, 64); hipMalloc(&flags, (size_t)(n + 8) * Q128 * 4);
   hipMemcpy(x, h.data(), R * C * 4, hipMemcpyHostToDevice);
   int hh[2] = {n, (int)R}; hipMemcpy(hdr, hh, 8, hipMemcpyHostToDevice);
@@ -53,7 +53,8 @@ void run(int n, int N, int mode) {
   printf("C=%d n=%d N=%d mode=%d\n", C, n, N, mode);
   TIME("rownorm", 5, hipLaunchKernelGGL((dg::rownorm_kernel<C>), dim3((R + 255) / 256), dim3(256), 0, 0, x, C, norm, hdr));
   TIME("exhaustive exact (old)", 3, hipLaunchKernelGGL((dg::knn_mfma_kernel<C, unsigned short>), gold, dim3(256), 0, 0, x, C, norm, N, idx_ref, hdr));
-  TIME("split", 5, hipLaunchKernelGGL((dg::knn_split_kernel<C>), dim3((R * (C / 4) + 255) / 256), dim3(256), 0, 0, x, C, norm, xs, nl, nu, hdr));
+  TIME("centre", 5, hipLaunchKernelGGL((dg::knn_centre_kernel<C>), dim3(n), dim3(C), 0, 0, x, C, N, mu, hdr));
+  TIME("split", 5, hipLaunchKernelGGL((dg::knn_split1_kernel<C>), dim3((R * (C / 4) + 255) / 256), dim3(256), 0, 0, x, C, norm, mu, N, xs, nl, nu, hdr));
   TIME("bound", 5, hipLaunchKernelGGL((dg::knn_gram_kernel<C, false, S, W>), gnew, dim3(64 * W), 0, 0, xs, nl, nl, nu, N, theta, surv, scnt, hdr));
   if (mode == 0 && n > 100) {
     TIME("bound, no epilogue", 5, hipLaunchKernelGGL((dg::knn_gram_kernel<C, false, S, W, 1>), gnew, dim3(64 * W), 0, 0, xs, nl, nl, nu, N, theta, surv, scnt, hdr));
@@ -62,7 +63,7 @@ void run(int n, int N, int mode) {
     TIME("bound", 5, hipLaunchKernelGGL((dg::knn_gram_kernel<C, false, S, W>), gnew, dim3(64 * W), 0, 0, xs, nl, nl, nu, N, theta, surv, scnt, hdr));
   }
   TIME("collect", 5, hipLaunchKernelGGL((dg::knn_gram_kernel<C, true, S, W>), gnew, dim3(64 * W), 0, 0, xs, nu, nl, nu, N, theta, surv, scnt, hdr));
-  TIME("rerank", 5, hipLaunchKernelGGL((dg::knn_rerank_kernel<C, unsigned short>), grr, dim3(256), 0, 0, x, C, norm, N, surv, scnt, idx_new, hdr));
+  TIME("rerank", 5, hipLaunchKernelGGL((dg::knn_rerank_kernel<C, unsigned short>), grr, dim3(256), 0, 0, x, C, norm, N, surv, scnt, idx_new, hdr, theta, nu));
   std::vector<unsigned short> a(R * 20), b(R * 20);
   std::vector<unsigned char> cnt(R * 2);
   std::vector<int> fl((size_t)n * Q128);
@@ -78,7 +79,7 @@ void run(int n, int N, int mode) {
   }
   printf("  survivors per query: mean %.2f max %d | queries scanned exhaustively (list overflow): %zu | MISMATCHED rows: %zu of %zu\n",
          (double)total / (R - over ? R - over : 1), mx, over, bad_rows, R);
-  hipFree(x); hipFree(norm); hipFree(nl); hipFree(nu); hipFree(theta); hipFree(xs); hipFree(surv); hipFree(scnt);
+  hipFree(x); hipFree(norm); hipFree(nl); hipFree(nu); hipFree(theta); hipFree(mu); hipFree(xs); hipFree(surv); hipFree(scnt);
   hipFree(idx_ref); hipFree(idx_new); hipFree(hdr); hipFree(flags);
 }
 
