@@ -406,6 +406,21 @@ int mpa_relation_mean_forward(const float* edge, const float* rel, int64_t G, in
                               void* stream);
 int mpa_relation_mean_backward(const float* grad_out, const float* edge, const float* rel, const float* out, int64_t G,
                                int64_t P, int64_t C, float* grad_edge, float* grad_rel, void* stream);
+/* Merging of equivalent parts (DGLModel._merge_nodes, multi_part_assembly/models/dgl/network.py:75-88,101-119; no host
+ * copy of the ids, no Python loop).  Slots p and q of a sample are equivalent when valids [B,P] is 1 at both and
+ * part_ids [B,P] (int32) agree.  Forward, both tensors in one launch: part_out [B,P,C1] / pose_out [B,P,C2] = channel-wise
+ * max of part_feats / pose_feats over the slots equivalent to p (padded slots and single-member classes pass through:
+ * a pure max, bit-equal to the host loop); arg_part / arg_pose (uint8, same shapes; P <= 64) = the slot the value came
+ * from, the LOWEST one on ties (torch's max(dim) on the host picks the same).  Backward: grad_part [B,P,C1] / grad_pose
+ * [B,P,C2] at slot q = the sum, in ascending p, of the output gradients of the slots p whose recorded arg is q.  No
+ * atomics: deterministic.  Valid parts are expected first in every sample, as the datasets lay them out (the reference
+ * indexes the compacted valid list). */
+int mpa_merge_equal_parts(const float* part_feats, const float* pose_feats, const float* valids, const int32_t* part_ids,
+                          int64_t B, int64_t P, int64_t C1, int64_t C2, float* part_out, float* pose_out,
+                          uint8_t* arg_part, uint8_t* arg_pose, void* stream);
+int mpa_merge_equal_parts_backward(const float* grad_part_out, const float* grad_pose_out, const uint8_t* arg_part,
+                                   const uint8_t* arg_pose, const float* valids, const int32_t* part_ids, int64_t B,
+                                   int64_t P, int64_t C1, int64_t C2, float* grad_part, float* grad_pose, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Recurrent half of a single-layer (bi)directional GRU — replaces the per-step library launches behind
@@ -557,7 +572,9 @@ int mpa_grad_clip_coef(const float* grad, int64_t numel, float max_norm, const f
  *   considered, groups with id > G are left unmatched), sample_idx [B,G,n] int32 point indices (the reference
  *   draws torch.randperm(N)[:n] per group), poses as [B,P,3] / [B,P,4] (w,x,y,z).  Writes new_trans / new_quat
  *   (the GT poses after rearrangement), perm [B,P] (source slot of every slot), and leaves the cost matrices
- *   [B,G,P,P] and assignments [B,G,P] in the two workspaces. */
+ *   [B,G,P,P] and assignments [B,G,P] in the two workspaces.  A caller that cannot read the ids on the host (a captured
+ *   step) passes the static bound G = max(1, P / 2): groups have at least two members and the datasets number them
+ *   consecutively from 1, so no id exceeds it; slots of groups a sample does not have cost an empty block each. */
 int mpa_linear_sum_assignment(const float* cost, const int32_t* sizes, int64_t problems, int64_t ld,
                               int32_t* col4row, void* stream);
 int mpa_match_parts(const float* part_pcs, const float* pred_trans, const float* pred_quat, const float* gt_trans,
@@ -570,6 +587,23 @@ int mpa_match_parts_rmat(const float* part_pcs, const float* pred_trans, const f
                          const float* gt_rmat, const int32_t* match_ids, const int32_t* sample_idx, int64_t B, int64_t P,
                          int64_t N, int64_t G, int64_t n, float* cost_ws, int32_t* col4row_ws, float* new_trans,
                          float* new_rmat, int32_t* perm, void* stream);
+/* mpa_match_sample_indices (csrc/match_sample.hip): the sample_idx [B,G,n] int32 of mpa_match_parts drawn on the device.
+ *   Row (b, g) holds the first n entries of a uniformly random permutation of 0..N-1 — what the reference's
+ *   `torch.randperm(N)[:n]` means — for every group slot, whether the sample has that group or not (the matching
+ *   kernels skip empty slots).  1 <= n <= min(N, 128), N <= 16384 (the permutation lives in LDS as 16-bit words; it is
+ *   never written to global memory), B * G <= 2^24; anything else: MPA_EINVAL.
+ *   Partial Fisher-Yates shuffle: perm = iota(N); for k = 0 .. n-1: j = k + mulhi32(w_k, N - k) (the high 32 bits of the
+ *   32 x 32-bit product), swap perm[k] and perm[j], emit perm[k].  mulhi32 picks j uniformly up to a relative bias below
+ *   N / 2^32 (< 4e-6 at the cap) per step.
+ *   Randomness: Philox4x32-10, stateless.  key = (seed low word, seed high word); w_k = word (k & 3) of the block with
+ *   counter = (slot, 0x6D610000 | (k >> 2), c low word, c high word), slot = b * G + g, c = (counter_dev != NULL ?
+ *   *counter_dev : counter) + salt (mod 2^64).  Word 1 of the counter is never below 4, the mesh sampler's (see
+ *   mpa_mesh_sample_batch) always is: equal seeds give unrelated streams.  `counter` numbers the caller's steps; `salt`
+ *   tells the calls of one step apart (the caller passes k * an odd constant for its k-th call).  A captured HIP graph
+ *   passes counter_dev, a DEVICE word the host rewrites between replays, so that every replay draws afresh; an eager call
+ *   passes the same number by value and draws the same rows. */
+int mpa_match_sample_indices(int64_t B, int64_t G, int64_t N, int64_t n, uint64_t seed, uint64_t counter,
+                             const uint64_t* counter_dev, uint64_t salt, int32_t* sample_idx, void* stream);
 
 /* ---- batch producer (device side) -------------------------------------------------------------------------
  * Replaces the per-part numpy work of GeometryPartDataset.__getitem__ (multi_part_assembly/datasets/

@@ -41,6 +41,7 @@ SIGNATURES: dict[str, tuple] = {
     "mpa_linear_sum_assignment": (_INT, [_P, _P, _I64, _I64, _P, _P]),
     "mpa_match_parts": (_INT, [_P] * 7 + [_I64] * 5 + [_P] * 6),
     "mpa_match_parts_rmat": (_INT, [_P] * 7 + [_I64] * 5 + [_P] * 6),
+    "mpa_match_sample_indices": (_INT, [_I64, _I64, _I64, _I64, _U64, _U64, _P, _U64, _P, _P]),
     "mpa_quat_sanitize": (_INT, [_P, _I64, _P, _P, _P]),
     "mpa_loss_reduce_forward": (_INT, [_P, _P, _I64, _I64, _P, _P, _P]),
     "mpa_loss_reduce_backward": (_INT, [_P, _P, _P, _I64, _I64, _P, _P]),
@@ -81,6 +82,8 @@ SIGNATURES: dict[str, tuple] = {
     "mpa_relation_head_backward": (_INT, [_P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P, _P]),
     "mpa_relation_mean_forward": (_INT, [_P, _P, _I64, _I64, _I64, _P, _P]),
     "mpa_relation_mean_backward": (_INT, [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P]),
+    "mpa_merge_equal_parts": (_INT, [_P] * 4 + [_I64] * 4 + [_P] * 5),
+    "mpa_merge_equal_parts_backward": (_INT, [_P] * 6 + [_I64] * 4 + [_P] * 3),
     "mpa_gru_workspace": (_INT, [_I64, _I64, _I64, _I64, _P]),
     "mpa_gru_resident": (_INT, [_I64, _I64, _I64, _P]),
     "mpa_gru_forward": (_INT, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),

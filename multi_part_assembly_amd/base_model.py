@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from .chamfer import chamfer_distance
 from .eval_utils import assembly_metrics, calc_connectivity_acc, calc_part_acc, rot_metrics, trans_metrics
-from .matching import SUBSAMPLE, match_parts
+from .matching import SUBSAMPLE, MatchSampler, match_parts
 from .loss import (LossTerms, geometric_assembly_loss, part_order, search_mode, rot_cosine_loss, rot_points_cd_loss,
                    rot_points_l2_loss, shape_cd_loss, trans_l2_loss)
 from .rotation import Rotation3D
@@ -50,6 +50,14 @@ class BaseModel(nn.Module):
         self.pc_feat_dim = cfg.model.pc_feat_dim
         self.use_part_label = "part_label" in cfg.data.data_keys
         self.sample_iter = cfg.loss.get("sample_iter", 1)
+        # where the matching's point sub-samples are drawn: "host" = torch.randperm on the CPU generator, as the reference
+        # (a device sync and a pinned copy per evaluation); "device" = csrc/match_sample.hip, nothing leaves the device and
+        # the step can be captured.  The sampler module holds no parameter or buffer: the state_dict keys do not change.
+        self.match_sample = cfg.loss.get("match_sample", "host")
+        if self.match_sample not in ("host", "device"):
+            raise ValueError(f"cfg.loss.match_sample must be 'host' or 'device', got {self.match_sample!r}")
+        if self.match_sample == "device" and self.semantic:
+            self.match_sampler = MatchSampler()
         # fused HIP loss path for geometric data (csrc/assembly_loss.hip); the per-function path is
         # kept for the semantic datasets and as a cross-check.  keep_pts: also return the transformed
         # clouds (only visualisation needs them).  Quaternions and rotation matrices alike.
@@ -107,6 +115,11 @@ class BaseModel(nn.Module):
         reference's order, so a seeded run consumes the CPU generator exactly as the reference does.  `ids_host`
         (numpy [B,P]) spares the one device-to-host copy of `match_ids` when the loader still has it."""
         B, P, N, _ = part_pcs.shape
+        if self.match_sample == "device":
+            # drawn by csrc/match_sample.hip for the static P // 2 group slots: no host copy either way
+            new_trans, new_rot = match_parts(part_pcs, pred_trans, pred_rot.rot, gt_trans, gt_rot.rot, match_ids,
+                                             **self.match_sampler.draw_args(part_pcs.device))
+            return new_trans, Rotation3D(new_rot, rot_type=self.rot_type)
         if ids_host is None:
             ids_host = match_ids.long().cpu().numpy()
         n = min(SUBSAMPLE, N)
@@ -126,7 +139,10 @@ class BaseModel(nn.Module):
         pred_trans, pred_rot = out_dict["trans"], out_dict["rot"]
         part_pcs, valids = data_dict["part_pcs"], data_dict["part_valids"]
         gt_trans, gt_rot = data_dict["part_trans"], data_dict["part_rot"]
-        if self.semantic:
+        if self.semantic and self.match_sample == "device":
+            new_trans, new_rot = self._match_parts(part_pcs, pred_trans, pred_rot, gt_trans, gt_rot,
+                                                   data_dict["match_ids"])
+        elif self.semantic:
             if "_match_ids_host" not in data_dict:  # one copy per batch, shared by the min-of-N samples
                 data_dict["_match_ids_host"] = data_dict["match_ids"].long().cpu().numpy()
             new_trans, new_rot = self._match_parts(part_pcs, pred_trans, pred_rot, gt_trans, gt_rot,
@@ -262,6 +278,8 @@ class BaseModel(nn.Module):
     def loss_function(self, data_dict, optimizer_idx=-1):
         """Min-of-N over `sample_iter` stochastic predictions, per sample (base_model.py:348-387)."""
         data_dict = self._start_part_order(data_dict)
+        if self.semantic and self.match_sample == "device":
+            self.match_sampler.begin_step(self.training)
         try:
             return self._loss_function_impl(data_dict, optimizer_idx)
         finally:

@@ -137,6 +137,35 @@ def global_partnet_chair():
                   loss=semantic_loss())
 
 
+def _partnet_chair_graph_data():
+    """The data block of configs/{dgl,rgl_net}/*-partnet_chair.py: the graph networks also read the valid matrix."""
+    data = partnet_chair()
+    data.data_keys = ("part_ids", "match_ids", "contact_points", "valid_matrix")
+    return data
+
+
+def dgl_partnet_chair():
+    """configs/dgl/dgl-32x1-cosine_300e-partnet_chair.py (semantic data: matching + min-of-N, equivalent parts merged at
+    odd GNN iterations; 300 epochs)."""
+    return Config(exp=_exp(300), data=_partnet_chair_graph_data(), optimizer=adam_cosine(), model=dgl_model(),
+                  loss=semantic_loss())
+
+
+def rgl_net_partnet_chair():
+    """configs/rgl_net/rgl_net-32x1-cosine_300e-partnet_chair.py (as DGL's; the parts are shuffled to avoid part-label
+    leakage from their order)."""
+    data = _partnet_chair_graph_data()
+    data.shuffle_parts = True
+    return Config(exp=_exp(300), data=data, optimizer=adam_cosine(), model=rgl_net_model(), loss=semantic_loss())
+
+
+def pn_transformer_partnet_chair():
+    """configs/pn_transformer/pn_transformer/pn_transformer-32x1-cosine_400e-partnet_chair.py."""
+    opt = adam_cosine()
+    opt.warmup_ratio = 0.05
+    return Config(exp=_exp(400), data=partnet_chair(), optimizer=opt, model=pn_transformer_model(), loss=semantic_loss())
+
+
 def pn_transformer_refine_model():
     """configs/_base_/models/pn_transformer/pn_transformer_refine.py:5-19."""
     return Config(name="pn_transformer_refine", rot_type="quat", pc_feat_dim=128, encoder="pointnet",

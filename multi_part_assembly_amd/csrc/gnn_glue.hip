@@ -5,6 +5,7 @@
 //                                                                    dgl/modules.py:61-73, dgl/network.py:121-133
 //   relation-weighted mean    sum_j edge_ij * rel_ij / (sum_j rel_ij + 1e-6)      dgl/network.py:135-152
 //   pair rows                 [a_i ; b_j] for every part pair (i, j) of a sample  dgl/network.py:121-125, 135-141
+//   merge of equal parts      channel-wise max over each class of equivalent parts dgl/network.py:75-88, 101-119
 //
 // Each is a few hundred kilobytes to tens of megabytes of traffic per GNN iteration; as library ops they were ~35
 // launches per iteration, forward and backward (element-wise products, reductions, 1-column GEMMs, their transposes).
@@ -322,6 +323,93 @@ __global__ __launch_bounds__(128) void pr_bwd_kernel(const float* __restrict__ g
   }
 }
 
+// ---- merging of equivalent parts ---------------------------------------------------------------------------------------
+// Slots p and q of a sample are equivalent when both are valid (valids == 1) and part_ids[b][p] == part_ids[b][q]; every
+// slot of a class receives the channel-wise max over the class (dgl/network.py:101-119), padded slots and single-member
+// classes pass through.  Both feature tensors in one launch: channel c < C1 belongs to the part features, c >= C1 to the
+// pose features.  grid = B * P (one block per slot), block = 128 (channels c, c + 128, ...).  arg records the slot the
+// value came from — the LOWEST one on ties (strict `>` scan in slot order, what torch's max(dim) returns on the host).
+constexpr int kMergeMaxP = 64;
+
+__device__ __forceinline__ int merge_class(const float* __restrict__ valids, const int* __restrict__ ids, int P, int p,
+                                           int* __restrict__ mem) {
+  int c = 0;
+  if (valids[p] == 1.0f) {
+    const int id = ids[p];
+    for (int q = 0; q < P; ++q)
+      if (valids[q] == 1.0f && ids[q] == id) mem[c++] = q;
+  }
+  return c;  // 0: a padded slot
+}
+
+__global__ __launch_bounds__(128) void merge_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                        const float* __restrict__ valids, const int* __restrict__ ids,
+                                                        int P, int C1, int C2, float* __restrict__ out_a,
+                                                        float* __restrict__ out_b, uint8_t* __restrict__ arg_a,
+                                                        uint8_t* __restrict__ arg_b) {
+  __shared__ int mem[kMergeMaxP];
+  __shared__ int count;
+  const long long row = blockIdx.x, s0 = row / P;
+  const int p = (int)(row - s0 * P);
+  if (threadIdx.x == 0) count = merge_class(valids + s0 * P, ids + s0 * P, P, p, mem);
+  __syncthreads();
+  const int cnt = count;
+  for (int c = threadIdx.x; c < C1 + C2; c += 128) {
+    const bool first = c < C1;
+    const float* src = first ? a : b;
+    const int C = first ? C1 : C2, cc = first ? c : c - C1;
+    float best = src[row * C + cc];
+    int at = p;
+    if (cnt > 1) {
+      at = mem[0];
+      best = src[(s0 * P + at) * C + cc];
+      for (int k = 1; k < cnt; ++k) {
+        const float v = src[(s0 * P + mem[k]) * C + cc];
+        if (v > best) {
+          best = v;
+          at = mem[k];
+        }
+      }
+    }
+    (first ? out_a : out_b)[row * C + cc] = best;
+    (first ? arg_a : arg_b)[row * C + cc] = (uint8_t)at;
+  }
+}
+
+// grad_in[b][q][c] = sum, over the slots p of q's class in ascending order, of grad_out[b][p][c] where arg[b][p][c] == q
+// (a padded or single slot: its own gradient).  One block per slot q, no atomics.
+__global__ __launch_bounds__(128) void merge_bwd_kernel(const float* __restrict__ ga, const float* __restrict__ gb,
+                                                        const uint8_t* __restrict__ arg_a,
+                                                        const uint8_t* __restrict__ arg_b,
+                                                        const float* __restrict__ valids, const int* __restrict__ ids,
+                                                        int P, int C1, int C2, float* __restrict__ grad_a,
+                                                        float* __restrict__ grad_b) {
+  __shared__ int mem[kMergeMaxP];
+  __shared__ int count;
+  const long long row = blockIdx.x, s0 = row / P;
+  const int q = (int)(row - s0 * P);
+  if (threadIdx.x == 0) count = merge_class(valids + s0 * P, ids + s0 * P, P, q, mem);
+  __syncthreads();
+  const int cnt = count;
+  for (int c = threadIdx.x; c < C1 + C2; c += 128) {
+    const bool first = c < C1;
+    const float* g = first ? ga : gb;
+    const uint8_t* arg = first ? arg_a : arg_b;
+    const int C = first ? C1 : C2, cc = first ? c : c - C1;
+    float acc;
+    if (cnt > 1) {
+      acc = 0.0f;
+      for (int k = 0; k < cnt; ++k) {
+        const long long o = (s0 * P + mem[k]) * C + cc;
+        if (arg[o] == q) acc += g[o];
+      }
+    } else {
+      acc = g[row * C + cc];
+    }
+    (first ? grad_a : grad_b)[row * C + cc] = acc;
+  }
+}
+
 }  // namespace
 
 extern "C" int mpa_narrow_linear_relu_forward(const float* x, const float* w, const float* bias, int64_t R, int64_t K,
@@ -435,4 +523,35 @@ extern "C" int mpa_pair_rows_backward(const float* grad_out, int64_t S, int64_t 
   launch(pr_bwd_kernel, dim3((unsigned)(2 * S * P)), dim3(128), mpa::as_stream(stream), grad_out, (int)(S * P), (int)P, (int)F,
          swap, grad_a, grad_b);
   return mpa::check_launch("pair_rows_backward");
+}
+
+static int merge_check(int64_t B, int64_t P, int64_t C1, int64_t C2, const char* who) {
+  MPA_REQUIRE(B >= 1 && P >= 1 && P <= kMergeMaxP && B * P <= (1 << 24) && C1 >= 1 && C2 >= 1 && C1 <= (1 << 16) &&
+                  C2 <= (1 << 16), "%s: B=%lld P=%lld (<= 64) C1=%lld C2=%lld out of range", who, (long long)B, (long long)P,
+              (long long)C1, (long long)C2);
+  return MPA_OK;
+}
+
+extern "C" int mpa_merge_equal_parts(const float* part_feats, const float* pose_feats, const float* valids,
+                                     const int32_t* part_ids, int64_t B, int64_t P, int64_t C1, int64_t C2,
+                                     float* part_out, float* pose_out, uint8_t* arg_part, uint8_t* arg_pose,
+                                     void* stream) {
+  if (int st = merge_check(B, P, C1, C2, "merge_equal_parts")) return st;
+  MPA_REQUIRE(part_feats && pose_feats && valids && part_ids && part_out && pose_out && arg_part && arg_pose,
+              "merge_equal_parts: null pointer");
+  launch(merge_fwd_kernel, dim3((unsigned)(B * P)), dim3(128), mpa::as_stream(stream), part_feats, pose_feats, valids,
+         (const int*)part_ids, (int)P, (int)C1, (int)C2, part_out, pose_out, arg_part, arg_pose);
+  return mpa::check_launch("merge_equal_parts");
+}
+
+extern "C" int mpa_merge_equal_parts_backward(const float* grad_part_out, const float* grad_pose_out,
+                                              const uint8_t* arg_part, const uint8_t* arg_pose, const float* valids,
+                                              const int32_t* part_ids, int64_t B, int64_t P, int64_t C1, int64_t C2,
+                                              float* grad_part, float* grad_pose, void* stream) {
+  if (int st = merge_check(B, P, C1, C2, "merge_equal_parts_backward")) return st;
+  MPA_REQUIRE(grad_part_out && grad_pose_out && arg_part && arg_pose && valids && part_ids && grad_part && grad_pose,
+              "merge_equal_parts_backward: null pointer");
+  launch(merge_bwd_kernel, dim3((unsigned)(B * P)), dim3(128), mpa::as_stream(stream), grad_part_out, grad_pose_out,
+         arg_part, arg_pose, valids, (const int*)part_ids, (int)P, (int)C1, (int)C2, grad_part, grad_pose);
+  return mpa::check_launch("merge_equal_parts_backward");
 }

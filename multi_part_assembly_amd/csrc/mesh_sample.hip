@@ -15,27 +15,15 @@
 
 #include "common.h"
 #include "part_transform.h"
+#include "philox.h"
 
 namespace {
 
 constexpr int kThreads = mpa::kPartThreads;
 constexpr int64_t kMaxPoints = 2048;  // 48 KiB of LDS for the cloud; loss.part_order has the same limit
 
-struct U4 {
-  uint32_t x, y, z, w;
-};
-
-// Philox4x32-10 (Salmon et al., SC'11; the Random123 constants).
-__device__ __forceinline__ U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int round = 0; round < 10; ++round) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c.x, p1 = (uint64_t)0xCD9E8D57u * c.z;
-    c = U4{(uint32_t)(p1 >> 32) ^ c.y ^ k0, (uint32_t)p1, (uint32_t)(p0 >> 32) ^ c.w ^ k1, (uint32_t)p0};
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c;
-}
+using mpa::U4;
+using mpa::philox4x32_10;  // philox.h
 
 // numpy's random_sample construction: 53 bits from two words, the first one the high part; exact in float64.
 __device__ __forceinline__ double uniform53(uint32_t hi, uint32_t lo) {

@@ -523,13 +523,17 @@ def instance_labels(geo_part_ids: np.ndarray, max_num_part: int) -> np.ndarray:
 
 def match_ids(geo_part_ids: np.ndarray, max_num_part: int) -> np.ndarray:
     """Groups of >= 2 equivalent parts numbered 1, 2, ... in increasing id order; everything else (unique ids,
-    id 0, padding) is 0 (partnet_data.py:194-208)."""
+    id 0, padding) is 0 (partnet_data.py:194-208).  The device-side matching draw (`cfg.loss.match_sample = "device"`,
+    `matching.static_groups`) runs a static max_num_part // 2 group slots and would leave a larger id unmatched: every
+    group has two members or more, so none can occur — checked here, on the host, not inside the step."""
     ids = np.zeros(max_num_part, dtype=np.float32)
     ids[: len(geo_part_ids)] = geo_part_ids
     out = np.zeros_like(ids)
     values, counts = np.unique(ids[ids >= 1], return_counts=True)  # ascending, like the reference's range(1, max+1)
     for label, v in enumerate(values[counts >= 2], start=1):
         out[ids == v] = label
+    if out.max() > max(1, max_num_part // 2):
+        raise ValueError(f"match_ids: group id {int(out.max())} exceeds max_num_part // 2 = {max_num_part // 2}")
     return out
 
 

@@ -10,7 +10,8 @@ bulk of the graph network — the P x P edge MLPs, the node MLPs and the wide la
 Linear + BatchNorm1d + ReLU layers: csrc/mlp.hip, exact-fp32 MFMA), the recurrence of RGL-NET's bidirectional GRU
 (csrc/gru.hip: all steps of both directions in one launch) and the pose heads — are the HIP hot path, as are the small pieces between them (the 7-wide
 first layer of the pose encoder, the 512 -> 1 relation head with its sigmoid and mask, the relation-weighted mean:
-csrc/gnn_glue.hip); the GRU's input projection and the concatenations stay on PyTorch-ROCm library ops.
+csrc/gnn_glue.hip), and on semantic data the merging of equivalent parts (one launch of csrc/gnn_glue.hip, no host copy
+of the ids; `merge_on_device = False` keeps the reference's host loop as the cross-check); the GRU's input projection and the concatenations stay on PyTorch-ROCm library ops.
 
 Differences from the reference, none of them numerical beyond fp32 re-association:
   * part features are extracted with the mask-in / zeros-out PointNet entry (no boolean-mask sync);
@@ -27,8 +28,8 @@ import torch.nn as nn
 
 from .base_model import BaseModel
 from .encoder import build_encoder
-from .gnn_ops import (NARROW_MAX_IN, RELATION_MEAN_MAX_PARTS, narrow_linear_relu, pair_rows, pair_rows_supported,
-                      relation_head, relation_head_supported, relation_mean)
+from .gnn_ops import (MERGE_MAX_PARTS, NARROW_MAX_IN, RELATION_MEAN_MAX_PARTS, merge_equal_parts, narrow_linear_relu,
+                      pair_rows, pair_rows_supported, relation_head, relation_head_supported, relation_mean)
 from .gru import gru_recurrent, supported as gru_supported
 from .loss import LossTerms
 from .mlp import bn_counter_batch, mlp_layer, pair_layer, pair_layer_supported, supported as mlp_supported
@@ -155,6 +156,9 @@ class DGLModel(BaseModel):
         super().__init__(cfg)
         self.iter = cfg.model.gnn_iter
         self.merge_node = cfg.model.merge_node
+        # equivalent parts merged by csrc/gnn_glue.hip (no host copy of part_valids / part_ids, no Python loop); False: the
+        # host loop of the reference (`_gather_same_class` + `_merge_nodes`), kept as the cross-check
+        self.merge_on_device = True
         self.encoder = build_encoder(cfg.model.encoder, feat_dim=self.pc_feat_dim, global_feat=True)
         self.edge_mlps = _clones(_PairMLP(2 * self.pc_feat_dim, self.pc_feat_dim), self.iter)
         self.node_mlps = self._init_node_mlps()
@@ -242,7 +246,10 @@ class DGLModel(BaseModel):
         instance_label = data_dict["instance_label"].type_as(part_feats)
         B, P = instance_label.shape[:2]
         pred_pose = self.zero_pose.to(part_feats).expand(B, P, -1)
-        class_list = self._gather_same_class(data_dict)
+        merging = self.merge_node and self.semantic
+        on_device = (merging and self.merge_on_device and part_feats.is_cuda and data_dict.get("class_list") is None
+                     and P <= MERGE_MAX_PARTS)
+        class_list = data_dict.get("class_list") if on_device else self._gather_same_class(data_dict)
         rots, transs = [], []
         for it in range(self.iter):
             if it == 0:
@@ -250,8 +257,12 @@ class DGLModel(BaseModel):
             else:
                 pose_feats = self.pose_extractor(pred_pose)
                 feats_in = part_feats
-                if self.merge_node and self.semantic and it % 2 == 1:
-                    feats_in, pose_feats = self._merge_nodes(part_feats, pose_feats, class_list)
+                if merging and it % 2 == 1:
+                    if on_device:
+                        feats_in, pose_feats = merge_equal_parts(part_feats, pose_feats, data_dict["part_valids"],
+                                                                 data_dict["part_ids"])
+                    else:
+                        feats_in, pose_feats = self._merge_nodes(part_feats, pose_feats, class_list)
                 relation = self._update_relation(pose_feats, it, valid_matrix)
             messages = self._message_passing(feats_in, relation, it)
             part_feats = self._node_update(part_feats, messages.type_as(part_feats), data_dict, it)

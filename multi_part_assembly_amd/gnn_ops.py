@@ -1,6 +1,7 @@
 """The small per-iteration pieces of the graph networks on the HIP library (csrc/gnn_glue.hip): the 7-wide first layer
 of the pose encoder, the 512 -> 1 relation head with its sigmoid and valid-pair mask, the relation-weighted mean of the
-edge features and the [part i ; part j] pair rows the edge MLP and the relation net read (reference models/dgl/modules.py:61-86, models/dgl/network.py:121-152).  The torch modules keep
+edge features, the [part i ; part j] pair rows the edge MLP and the relation net read and the merging of equivalent
+parts (reference models/dgl/modules.py:61-86, models/dgl/network.py:75-152).  The torch modules keep
 holding the parameters (same state_dict keys); this only replaces what they compute."""
 from __future__ import annotations
 
@@ -212,3 +213,58 @@ def pair_rows(a, b, swap=False):
     if not a.is_cuda:
         raise RuntimeError("pair_rows: only CUDA (HIP) tensors are supported — no CPU fallback")
     return _PairRows.apply(_f32c(a), _f32c(b), bool(swap))
+
+
+class _MergeEqualParts(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, part_feats, pose_feats, valids, ids):
+        B, P, C1 = part_feats.shape
+        C2 = pose_feats.shape[-1]
+        dev = part_feats.device
+        part_out, pose_out = torch.empty_like(part_feats), torch.empty_like(pose_feats)
+        arg_part = torch.empty((B, P, C1), dtype=torch.uint8, device=dev)
+        arg_pose = torch.empty((B, P, C2), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            tok = _lib.KernelTimer.start(f"merge_equal_parts[{B}x{P}x{C1}+{C2}]")
+            st = _lib.lib().mpa_merge_equal_parts(_lib.ptr(part_feats), _lib.ptr(pose_feats), _lib.ptr(valids), _lib.ptr(ids),
+                                                  B, P, C1, C2, _lib.ptr(part_out), _lib.ptr(pose_out), _lib.ptr(arg_part),
+                                                  _lib.ptr(arg_pose), _lib.current_stream(dev))
+            _lib.KernelTimer.stop(tok)
+        _lib.check(st, "mpa_merge_equal_parts")
+        ctx.save_for_backward(arg_part, arg_pose, valids, ids)
+        ctx.mark_non_differentiable(arg_part, arg_pose)
+        return part_out, pose_out, arg_part, arg_pose
+
+    @staticmethod
+    def backward(ctx, g_part, g_pose, _ga, _gb):
+        arg_part, arg_pose, valids, ids = ctx.saved_tensors
+        B, P, C1 = arg_part.shape
+        C2 = arg_pose.shape[-1]
+        dev = arg_part.device
+        g_part = torch.zeros((B, P, C1), dtype=torch.float32, device=dev) if g_part is None else _f32c(g_part)
+        g_pose = torch.zeros((B, P, C2), dtype=torch.float32, device=dev) if g_pose is None else _f32c(g_pose)
+        grad_part, grad_pose = torch.empty_like(g_part), torch.empty_like(g_pose)
+        with torch.cuda.device(dev):
+            tok = _lib.KernelTimer.start(f"merge_equal_parts_backward[{B}x{P}x{C1}+{C2}]")
+            st = _lib.lib().mpa_merge_equal_parts_backward(
+                _lib.ptr(g_part), _lib.ptr(g_pose), _lib.ptr(arg_part), _lib.ptr(arg_pose), _lib.ptr(valids), _lib.ptr(ids),
+                B, P, C1, C2, _lib.ptr(grad_part), _lib.ptr(grad_pose), _lib.current_stream(dev))
+            _lib.KernelTimer.stop(tok)
+        _lib.check(st, "mpa_merge_equal_parts_backward")
+        return grad_part, grad_pose, None, None
+
+
+MERGE_MAX_PARTS = 64
+
+
+def merge_equal_parts(part_feats, pose_feats, part_valids, part_ids, ret_arg=False):
+    """Every class of equivalent parts (valid slots of a sample with equal `part_ids`) shares the channel-wise max of its
+    members' features: part_feats [B, P, C1], pose_feats [B, P, C2] -> the two merged tensors, in one launch, with no
+    host copy of the ids (`DGLModel._merge_nodes` is the host loop it replaces; bit-equal).  Valid parts come first in
+    every sample.  ret_arg: also the uint8 slot every value came from (the lowest on ties)."""
+    if not part_feats.is_cuda:
+        raise RuntimeError("merge_equal_parts: only CUDA (HIP) tensors are supported — no CPU fallback")
+    valids = _f32c(part_valids.detach())
+    ids = part_ids.detach().to(torch.int32).contiguous()
+    out = _MergeEqualParts.apply(_f32c(part_feats), _f32c(pose_feats), valids, ids)
+    return out if ret_arg else out[:2]

@@ -76,6 +76,66 @@ def make_semantic_batch(batch_size, max_parts=2, num_points=1000, seed=1234, dev
     return batch
 
 
+def make_partnet_like_batch(batch_size, max_parts=20, num_points=1000, seed=1234, device="cuda"):
+    """Semantic-dataset stand-in at PartNet's shape statistics, with everything the `*_partnet_chair` presets' `data_keys`
+    ask for.  Per shape (P = `max_parts` slots, P >= 2), valid parts first:
+      * 1 .. min(3, P // 4) groups (at least one) of 2-4 geometrically identical parts — one cloud per group, different
+        poses — with `match_ids` 1, 2, ... in slot order and one shared `part_ids` value per group;
+      * 0-3 unique parts (`match_ids` 0, a `part_ids` value of their own), as far as the slots allow;
+      * padding behind them (all-zero, `part_ids` / `match_ids` 0).
+    `instance_label` [B, P, P] is the one-hot rank of a part inside its class (partnet_data.py:163-173), `part_label`
+    zero-width, `valid_matrix` the outer product of the validity vector, `contact_points` [B, P, P, 4] a symmetric
+    contact flag between consecutive valid parts with the midpoint of their centroids.  A function of the arguments only
+    (a private CPU generator)."""
+    B, P, N = batch_size, max_parts, num_points
+    if P < 2:
+        raise ValueError("make_partnet_like_batch: needs at least two part slots")
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    draw = lambda lo, hi: int(torch.randint(lo, hi + 1, (1,), generator=g))
+    part_ids = np.zeros((B, P), dtype=np.int64)
+    match = np.zeros((B, P), dtype=np.int64)
+    source = np.tile(np.arange(P), (B, 1))   # slot whose cloud a slot shares
+    num_parts = []
+    for b in range(B):
+        slot, label = 0, 0
+        for group in range(draw(1, max(1, min(3, P // 4)))):
+            size = min(draw(2, 4), P - slot)
+            if size < 2:
+                break
+            label += 1
+            part_ids[b, slot:slot + size], match[b, slot:slot + size] = label, group + 1
+            source[b, slot:slot + size] = slot
+            slot += size
+        for _ in range(min(draw(0, 3), P - slot)):
+            label += 1
+            part_ids[b, slot] = label
+            slot += 1
+        num_parts.append(slot)
+    batch = make_batch(B, P, N, preset="everyday", seed=seed, device=device, num_parts=num_parts)
+    dev = batch["part_pcs"].device
+    src = torch.from_numpy(source).to(dev)
+    batch["part_pcs"] = torch.gather(batch["part_pcs"], 1, src[:, :, None, None].expand(B, P, N, 3)).contiguous()
+    v = batch["part_valids"]
+    batch["part_ids"] = torch.from_numpy(part_ids).to(dev)
+    batch["match_ids"] = torch.from_numpy(match).to(dev)
+    inst = np.zeros((B, P, P), dtype=np.float32)
+    contact = np.zeros((B, P, P, 4), dtype=np.float32)
+    centre = batch["part_trans"].cpu().numpy()
+    for b in range(B):
+        seen = {}
+        for p in range(num_parts[b]):
+            k = seen.get(part_ids[b, p], 0)
+            inst[b, p, k] = 1.0
+            seen[part_ids[b, p]] = k + 1
+            if p + 1 < num_parts[b]:
+                mid = 0.5 * (centre[b, p] + centre[b, p + 1])
+                contact[b, p, p + 1] = contact[b, p + 1, p] = (1.0, *mid)
+    batch["instance_label"] = torch.from_numpy(inst).to(dev)
+    batch["contact_points"] = torch.from_numpy(contact).to(dev)
+    batch["valid_matrix"] = v[:, :, None] * v[:, None, :]
+    return batch
+
+
 def _uv_sphere(segments, rings):
     """Closed latitude / longitude triangulation of the unit sphere: `segments * (rings - 1) + 2` vertices,
     `2 * segments * (rings - 1)` triangles, outward orientation."""
