@@ -640,6 +640,53 @@ int mpa_mesh_sample_batch(const double* tri, const double* cum_area, const int64
                           const int32_t* perm, uint64_t seed, const int64_t* stream_id, double rot_range,
                           float* part_pcs, float* part_trans, float* part_quat, double* raw_out, void* stream);
 
+/* PartNet batches gathered from a device-resident store (csrc/partnet_gather.hip): one launch writes the whole data_dict
+ * of PartNetPartDataset.__getitem__ + default collate (multi_part_assembly/datasets/partnet_data.py:127-243) for B shapes.
+ *   The store (datasets.PartNetStore validates it when it is built; the kernel trusts it): pcs [parts_total,N,3], poses
+ * [parts_total,7] (translation, then scalar-first quaternion), sym [parts_total,3] float32; geo_ids, sem_ids
+ * [parts_total] int32 (geo_part_ids >= 0; the files' 1-based part_ids); shape_part_off [S+1] int64 (shape s owns the parts
+ * shape_part_off[s] .. shape_part_off[s+1]-1, their number p_s <= P); shape_ids [S] int64; optional contacts
+ * [sum_s p_s^2, 4] float32 with contact_off [S+1] int64 in rows of 4 (shape s: its p_s x p_s x 4 block, row-major).
+ *   shape_index [B] int64 in DEVICE memory selects the shapes.  P = max_num_part in [1, 64], N points per part, C =
+ * num_part_category (0: part_label is zero-width and not written).
+ *   Part order of sample b, a permutation `order` of 0..p-1 (slot j holds stored part start + order[j]):
+ *     - perm == NULL and random_order == 0: the identity;
+ *     - replay, perm [B,P] int32 != NULL: order[j] = perm[b,j] for j < p (the rest of the row is ignored);
+ *     - device-random, random_order != 0: a full Fisher-Yates shuffle of iota(p): for k = 0 .. p-2: j = k + mulhi32(w_k,
+ *       p - k) (the high 32 bits of the 32 x 32-bit product), swap order[k] and order[j].  Philox4x32-10, stateless: key =
+ *       (seed low word, seed high word); w_k = word (k & 3) of the block with counter = (b, 0x706E0000 | (k >> 2), c low
+ *       word, c high word), c = (counter_dev != NULL ? *counter_dev : counter).  Word 1 of the counter is one neither
+ *       other user of the generator produces (mpa_mesh_sample_batch: below 4; mpa_match_sample_indices: 0x6D61xxxx).  A
+ *       captured HIP graph passes counter_dev, a DEVICE word the host rewrites between replays.
+ *   Outputs, one pointer per key, NULL = not produced; every byte of every other one is written on every call (nothing
+ * relies on an earlier fill).  For slot (b, j) with j < p and part = start + order[j]: part_pcs [B,P,N,3] = the cloud,
+ * part_trans [B,P,3] / part_quat [B,P,4] = the pose split, sym_out [B,P,3]; slots j >= p are zeros.  From the ordered ids
+ * g_j = geo_ids[part]: part_valids [B,P] (1 for j < p); part_ids [B,P] = g_j as float32; instance_label [B,P,P] = one-hot
+ * at the number of i < j with g_i == g_j; match_ids [B,P] float32: ids >= 1 that occur at least twice are numbered 1, 2, ..
+ * in ascending id value, every other slot is 0; part_label [B,P,C] = one-hot at sem_ids[part] - 1 (an id above C gives a
+ * zero row); valid_matrix [B,P,P] = valids outer valids; shape_id [B] int64 = shape_ids[shape_index[b]].
+ * contact_points [B,P,P,4] is the stored p x p x 4 block zero-padded and stays in STORED part order even when the parts
+ * are shuffled or replayed: the reference reads the contact file after its shuffle and does not permute it.
+ * order_out [B,P] int32 (debugging, tests): the order used, -1 in padded slots.
+ *   Checked at run time, because they come from device memory: a shape_index outside [0, S) reads nothing from the store,
+ * is written as an all-padding sample (valids 0, shape_id -1) and stores 1 into the device word `status`; a replay row
+ * whose first p entries are not a permutation of 0..p-1 is treated the same way with status 2.  The kernel never clears
+ * `status` (the caller does, after reading it).  No input makes the kernel read outside the store.
+ *   The cloud moves with 16-byte accesses when N % 4 == 0 and pcs / part_pcs are 16-byte aligned, with dword accesses
+ * otherwise.  One launch, no atomics, no memset / memcpy nodes: capturable.
+ *   MPA_EINVAL (before any launch): P outside [1, 64]; negative or oversized B, S, N, C; perm together with random_order;
+ * contact_points requested from a store without contacts (contacts or contact_off NULL); NULL shape_part_off /
+ * shape_index / status; a requested output whose store array is NULL.  B == 0 with valid sizes is MPA_OK. */
+int mpa_partnet_gather_batch(const float* pcs, const float* poses, const float* sym, const int32_t* geo_ids,
+                             const int32_t* sem_ids, const int64_t* shape_part_off, const int64_t* shape_ids,
+                             const float* contacts, const int64_t* contact_off, int64_t S, const int64_t* shape_index,
+                             int64_t B, int64_t P, int64_t N, int64_t C, const int32_t* perm, int32_t random_order,
+                             uint64_t seed, uint64_t counter, const uint64_t* counter_dev, float* part_pcs,
+                             float* part_trans, float* part_quat, float* part_valids, float* part_ids,
+                             float* instance_label, float* match_ids, float* part_label, float* contact_points,
+                             float* sym_out, float* valid_matrix, int64_t* shape_id, int32_t* order_out, int32_t* status,
+                             void* stream);
+
 /* ---- rotation matrices (rot_type='rmat'; csrc/rmat.hip, the 6D pose head in csrc/transformer.hip) -------------------------
  * Replaces the rmat half of multi_part_assembly/utils/rotation.py:134-167 and utils/transforms.py:126-244, and the 6D
  * branch of models/modules/regressor.py:6-27,33-69.  Matrices are [.., 3, 3] row-major fp32.

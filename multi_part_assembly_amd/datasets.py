@@ -22,6 +22,9 @@ the same keys, shapes and dtypes, batched `[B, ...]` and already on the device.
 * PartNet-style semantic data: the on-disk format is plain numpy (`{category}.{split}.npy` id lists,
   `shape_data/{id}_level3.npy` pickled dicts, `contact_points/pairs_with_contact_points_{id}_level3.npy`);
   the label derivations (`instance_label`, `match_ids`, one-hot `part_label`) are host integer logic.
+* Device-resident PartNet data: `PartNetStore` reads a split once and packs it into flat arrays; `DevicePartNetProducer.batch`
+  gathers a batch from them and derives every label in ONE launch (`mpa_partnet_gather_batch`, csrc/partnet_gather.hip).
+  Same `data_dict` as `PartNetBatchProducer`, which stays the yardstick.
 """
 from __future__ import annotations
 
@@ -360,9 +363,10 @@ class MeshStore:
         return self._device[device]
 
 
-def _check_store_bytes(nbytes, max_bytes):
+def _check_store_bytes(nbytes, max_bytes, what="MeshStore"):
     if max_bytes is not None and nbytes > max_bytes:
-        raise ValueError(f"MeshStore: {nbytes} bytes of mesh data exceed max_bytes={max_bytes}")
+        raise ValueError(f"{what}: {nbytes} bytes of {'mesh' if what == 'MeshStore' else 'part'} data exceed "
+                         f"max_bytes={max_bytes}")
 
 
 MAX_DEVICE_SAMPLE_POINTS = 2048  # the sampled float64 cloud of a part lives in LDS (csrc/mesh_sample.hip)
@@ -629,3 +633,361 @@ class PartNetBatchProducer:
             else:
                 out[k] = torch.as_tensor(vals, dtype=torch.int64)
         return out
+
+
+# ---- device-resident PartNet data ---------------------------------------------------------------------------------
+PARTNET_KEYS = ("part_label", "part_ids", "match_ids", "contact_points", "sym", "valid_matrix")
+MAX_DEVICE_PARTS = 64        # one lane per part in csrc/partnet_gather.hip
+_MAX_EXACT_ID = 1 << 24      # `part_ids` travels as float32: every id below 2^24 survives the cast
+
+
+class PartNetStore:
+    """Every shape of a PartNet split, read once and packed into flat arrays the gather kernel reads
+    (csrc/partnet_gather.hip) — the `MeshStore` of the semantic data:
+
+    * `pcs` float32 [parts_total, N, 3], `poses` float32 [parts_total, 7], `sym` float32 [parts_total, 3]: the float32
+      cast `PartNetBatchProducer._pad` applies per batch, done once;
+    * `geo_ids` int32 [parts_total] (`geo_part_ids`), `sem_ids` int32 [parts_total] (the files' 1-based `part_ids`);
+    * `shape_part_off` int64 [S + 1]: shape s owns the parts `shape_part_off[s]:shape_part_off[s + 1]`;
+    * `shape_ids` int64 [S];
+    * optional `contacts` float32 [sum_s p_s^2, 4] with `contact_off` int64 [S + 1]: per shape its p x p x 4 block.
+
+    Everything the kernel relies on is checked here, once: consistent offsets, `min_num_part <= p <= max_num_part`,
+    `sem_ids >= 1`, `0 <= geo_ids < 2^24`, and the group-count check of `match_ids`.  `nbytes` / `max_bytes` as
+    `MeshStore`.  The arrays live on the host; `device_arrays(device)` uploads them once per device."""
+
+    ARRAYS = ("pcs", "poses", "sym", "geo_ids", "sem_ids", "shape_part_off", "shape_ids")
+
+    def __init__(self, pcs, poses, sym, geo_ids, sem_ids, shape_part_off, shape_ids, contacts=None, contact_off=None,
+                 min_num_part=2, max_num_part=20, max_bytes=None):
+        pcs = np.asarray(pcs)
+        if pcs.ndim != 3 or pcs.shape[2] != 3:
+            raise ValueError(f"PartNetStore: pcs must be [parts_total, N, 3], got {pcs.shape}")
+        self.pcs = np.ascontiguousarray(pcs, dtype=np.float32)
+        self.poses = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 7)
+        self.sym = np.ascontiguousarray(sym, dtype=np.float32).reshape(-1, 3)
+        geo, sem = np.asarray(geo_ids).reshape(-1), np.asarray(sem_ids).reshape(-1)
+        self.shape_part_off = np.ascontiguousarray(shape_part_off, dtype=np.int64).reshape(-1)
+        self.shape_ids = np.ascontiguousarray(shape_ids, dtype=np.int64).reshape(-1)
+        self.min_num_part, self.max_num_part = int(min_num_part), int(max_num_part)
+        off, total = self.shape_part_off, len(self.pcs)
+        if (len(off) < 2 or off[0] != 0 or off[-1] != total or len(self.shape_ids) != len(off) - 1
+                or any(len(a) != total for a in (self.poses, self.sym, geo, sem))):
+            raise ValueError("PartNetStore: inconsistent offsets (shape_part_off must run from 0 to the number of parts, "
+                             "with one entry per shape and one more, and every per-part array must have that many rows)")
+        count = np.diff(off)
+        if (count < self.min_num_part).any() or (count > self.max_num_part).any():
+            raise ValueError(f"PartNetStore: a shape has a part count outside [{self.min_num_part}, {self.max_num_part}]")
+        if (sem < 1).any() or (sem >= _MAX_EXACT_ID).any():
+            raise ValueError("PartNetStore: sem_ids (the files' part_ids) start from 1")
+        if (geo < 0).any() or (geo >= _MAX_EXACT_ID).any():
+            raise ValueError(f"PartNetStore: geo_ids must lie in [0, {_MAX_EXACT_ID})")
+        self.geo_ids = np.ascontiguousarray(geo, dtype=np.int32)
+        self.sem_ids = np.ascontiguousarray(sem, dtype=np.int32)
+        for s in range(len(count)):  # the static group slots of the device-side matching draw (see `match_ids`)
+            try:
+                match_ids(self.geo_ids[off[s]:off[s + 1]], self.max_num_part)
+            except ValueError as e:
+                raise ValueError(f"PartNetStore: shape {s} (id {self.shape_ids[s]}): {e}") from None
+        if (contacts is None) != (contact_off is None):
+            raise ValueError("PartNetStore: contacts and contact_off come together")
+        self.contacts = self.contact_off = None
+        if contacts is not None:
+            self.contacts = np.ascontiguousarray(contacts, dtype=np.float32).reshape(-1, 4)
+            self.contact_off = np.ascontiguousarray(contact_off, dtype=np.int64).reshape(-1)
+            want = np.concatenate([[0], np.cumsum(count * count)])
+            if len(self.contact_off) != len(want) or (self.contact_off != want).any() or len(self.contacts) != want[-1]:
+                raise ValueError("PartNetStore: inconsistent offsets (contact_off must be the running sum of p * p)")
+        _check_store_bytes(self.nbytes, max_bytes, "PartNetStore")
+        self._device = {}
+
+    @property
+    def nbytes(self):
+        arrays = [getattr(self, n) for n in self.ARRAYS]
+        if self.contacts is not None:
+            arrays += [self.contacts, self.contact_off]
+        return sum(a.nbytes for a in arrays)
+
+    @property
+    def num_shapes(self):
+        return len(self.shape_ids)
+
+    @property
+    def num_parts(self):
+        return len(self.pcs)
+
+    @property
+    def num_points(self):
+        return self.pcs.shape[1]
+
+    @property
+    def has_contacts(self):
+        return self.contacts is not None
+
+    def __len__(self):
+        return self.num_shapes
+
+    @classmethod
+    def from_arrays(cls, shapes, shape_ids=None, contacts=None, min_num_part=2, max_num_part=20, max_bytes=None):
+        """shapes: per shape a dict with the entries of a `shape_data` file (`part_pcs` [p, N, 3], `part_poses` [p, 7],
+        `sym` [p, 3], `geo_part_ids` [p], `part_ids` [p]); `shape_ids` defaults to 0, 1, ...; `contacts`: per shape a
+        [p, p, 4] array, or None for a store without contact points."""
+        shapes = list(shapes)
+        if not shapes:
+            raise ValueError("PartNetStore: no shapes")
+        pcs = [np.asarray(d["part_pcs"]) for d in shapes]
+        if any(a.ndim != 3 or a.shape[2] != 3 for a in pcs) or len({a.shape[1] for a in pcs}) != 1:
+            raise ValueError(f"PartNetStore: every shape must hold [p, N, 3] clouds of one N, got "
+                             f"{sorted({a.shape[1:] for a in pcs})}")
+        count = np.array([len(a) for a in pcs], dtype=np.int64)
+        if (count < min_num_part).any() or (count > max_num_part).any():
+            raise ValueError(f"PartNetStore: a shape has a part count outside [{min_num_part}, {max_num_part}]")
+        _check_store_bytes(int(count.sum()) * (12 * pcs[0].shape[1] + 48), max_bytes, "PartNetStore")
+        cat = lambda key, width: np.concatenate(
+            [np.asarray(d[key]).reshape((len(a),) + width) for d, a in zip(shapes, pcs)])
+        c = co = None
+        if contacts is not None:
+            contacts = [np.asarray(x) for x in contacts]
+            if len(contacts) != len(shapes) or any(x.shape != (p, p, 4) for x, p in zip(contacts, count)):
+                raise ValueError("PartNetStore: contacts must hold one [p, p, 4] array per shape")
+            c = np.concatenate([x.reshape(-1, 4) for x in contacts])
+            co = np.concatenate([[0], np.cumsum(count * count)])
+        return cls(np.concatenate(pcs), cat("part_poses", (7,)), cat("sym", (3,)), cat("geo_part_ids", ()),
+                   cat("part_ids", ()), np.concatenate([[0], np.cumsum(count)]),
+                   np.arange(len(shapes)) if shape_ids is None else shape_ids, c, co,
+                   min_num_part=min_num_part, max_num_part=max_num_part, max_bytes=max_bytes)
+
+    @classmethod
+    def from_folder(cls, data_dir, data_fn, min_num_part=2, max_num_part=20, overfit=-1, with_contacts=None,
+                    max_bytes=None):
+        """The split `data_dir/data_fn` in the reference's on-disk format, with the shape filter, the order and the
+        `overfit` cut of `PartNetBatchProducer.__init__`; every file is read once.  `with_contacts`: None reads the
+        contact files when the `contact_points` folder exists, True requires them, False leaves them out."""
+        level = PartNetBatchProducer.LEVEL
+        ids, shapes = [], []
+        for s in np.load(os.path.join(data_dir, data_fn)):
+            cur = np.load(os.path.join(data_dir, "shape_data", f"{s}_level{level}.npy"), allow_pickle=True).item()
+            if min_num_part <= np.asarray(cur["part_pcs"]).shape[0] <= max_num_part:
+                ids.append(int(s))
+                shapes.append(cur)
+        if overfit > 0:
+            ids, shapes = ids[:overfit], shapes[:overfit]
+        if with_contacts is None:
+            with_contacts = os.path.isdir(os.path.join(data_dir, "contact_points"))
+        contacts = None
+        if with_contacts:
+            contacts = [np.load(os.path.join(data_dir, "contact_points", f"pairs_with_contact_points_{s}_level{level}.npy"),
+                                allow_pickle=True) for s in ids]
+        return cls.from_arrays(shapes, ids, contacts, min_num_part, max_num_part, max_bytes)
+
+    def save(self, path):
+        """One .npz of plain arrays (no pickle): the per-file parse is paid once per split."""
+        arrays = {n: getattr(self, n) for n in self.ARRAYS}
+        arrays["part_limits"] = np.array([self.min_num_part, self.max_num_part], dtype=np.int64)
+        if self.contacts is not None:
+            arrays.update(contacts=self.contacts, contact_off=self.contact_off)
+        with open(path, "wb") as fh:
+            np.savez(fh, **arrays)
+
+    @classmethod
+    def load(cls, path, max_bytes=None):
+        with np.load(path, allow_pickle=False) as z:
+            lo, hi = (int(x) for x in z["part_limits"])
+            extra = (z["contacts"], z["contact_off"]) if "contacts" in z.files else (None, None)
+            return cls(*(z[n] for n in cls.ARRAYS), *extra, min_num_part=lo, max_num_part=hi, max_bytes=max_bytes)
+
+    def device_arrays(self, device):
+        """name -> tensor on `device` for every array of the store (`contacts` / `contact_off`: None without contact
+        points), uploaded at the first call."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("PartNetStore: the gather runs on the HIP device only (there is no CPU fallback)")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device not in self._device:
+            names = self.ARRAYS + (("contacts", "contact_off") if self.contacts is not None else ())
+            arrays = {n: torch.from_numpy(getattr(self, n)).to(device) for n in names}
+            arrays.setdefault("contacts", None)
+            arrays.setdefault("contact_off", None)
+            self._device[device] = arrays
+        return self._device[device]
+
+
+class DevicePartNetProducer:
+    """`PartNetBatchProducer.batch` with the data resident on the device: the split sits in a `PartNetStore`, and ONE HIP
+    launch per batch (`mpa_partnet_gather_batch`, csrc/partnet_gather.hip) gathers the clouds, poses and symmetries of
+    the chosen shapes and derives every label (`part_valids`, `part_ids`, `instance_label`, `match_ids`, `part_label`,
+    `valid_matrix`, `shape_id`) on the device.  `.batch()` returns the `data_dict` of the host producer — same keys,
+    shapes, dtypes and values; the tensors of the kernel's outputs (`shape_id` among them) are on the device.
+
+    `shuffle_parts` permutes the parts of every shape on the device: a Fisher-Yates shuffle on Philox4x32-10 keyed by
+    `seed`, with the batch counter and the sample's position in the batch as the stream (include/mpa_hip.h fixes the
+    layout) — the reference's DISTRIBUTION (`np.random.permutation`), not numpy's stream.  `contact_points` stays in
+    stored part order under a shuffle, as in the reference, which reads the contact file after its shuffle.
+    `.replay` feeds host-drawn orders through the same kernel, for parity tests.
+
+    A shape index the kernel finds outside the store (it can only come from a device tensor: host sequences are checked
+    before the launch) reads nothing, yields an all-padding sample and sets a device status word; `.check()` turns it
+    into a RuntimeError.  Call `.batch()` once outside a graph capture first: it allocates that word."""
+
+    def __init__(self, store: PartNetStore, data_keys, num_part_category=20, min_num_part=2, max_num_part=20,
+                 shuffle_parts=False, seed=0, device="cuda"):
+        self.store = store
+        self.data_keys = tuple(data_keys)
+        for key in self.data_keys:  # partnet_data.py:210-241
+            if key not in PARTNET_KEYS:
+                raise ValueError(f"ERROR: unknown data {key}")
+        self.num_part_category = int(num_part_category)
+        self.min_num_part, self.max_num_part = int(min_num_part), int(max_num_part)
+        if not 1 <= self.max_num_part <= MAX_DEVICE_PARTS:
+            raise ValueError(f"DevicePartNetProducer: max_num_part={max_num_part} outside [1, {MAX_DEVICE_PARTS}]")
+        count = np.diff(store.shape_part_off)
+        if (count < self.min_num_part).any() or (count > self.max_num_part).any():
+            raise ValueError(f"DevicePartNetProducer: the store holds a shape with a part count outside "
+                             f"[{self.min_num_part}, {self.max_num_part}]")
+        if "part_label" in self.data_keys and (self.num_part_category < 1
+                                               or int(store.sem_ids.max()) > self.num_part_category):
+            raise ValueError(f"DevicePartNetProducer: the store holds part label {int(store.sem_ids.max())}, "
+                             f"num_part_category is {self.num_part_category}")
+        if "contact_points" in self.data_keys and not store.has_contacts:
+            raise ValueError("DevicePartNetProducer: contact_points requested from a store without contacts")
+        self.shuffle_parts = bool(shuffle_parts)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.device = torch.device(device)
+        self.batch_counter = 0  # the default `batch_counter` of the next batch() call
+        self._status = None
+
+    def __len__(self):
+        return self.store.num_shapes
+
+    def _spec(self, B):
+        """key -> (shape, dtype) of every tensor the kernel writes, in the host producer's key order."""
+        P, N = self.max_num_part, self.store.num_points
+        C = self.num_part_category if "part_label" in self.data_keys else 0
+        f32 = torch.float32
+        spec = {"part_pcs": ((B, P, N, 3), f32), "part_trans": ((B, P, 3), f32), "part_quat": ((B, P, 4), f32),
+                "part_valids": ((B, P), f32), "shape_id": ((B,), torch.int64), "instance_label": ((B, P, P), f32),
+                "part_label": ((B, P, C), f32)}
+        extra = {"part_ids": (B, P), "match_ids": (B, P), "contact_points": (B, P, P, 4), "sym": (B, P, 3),
+                 "valid_matrix": (B, P, P)}
+        for key in self.data_keys:
+            if key != "part_label":
+                spec[key] = (extra[key], f32)
+        return spec
+
+    def _run(self, indices, perm=None, counter=None, out=None, return_order=False):
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError("DevicePartNetProducer: the gather runs on the HIP device only (there is no CPU fallback)")
+        S, P, N = self.store.num_shapes, self.max_num_part, self.store.num_points
+        with torch.cuda.device(dev):
+            arrays = self.store.device_arrays(dev)
+            host_idx = None
+            if isinstance(indices, torch.Tensor) and indices.device.type == "cuda":
+                if indices.dtype != torch.int64 or indices.dim() != 1 or not indices.is_contiguous():
+                    raise ValueError("DevicePartNetProducer: device indices must be a contiguous int64 vector")
+                d_idx = data_id = indices
+            else:
+                host_idx = np.asarray(indices.numpy() if isinstance(indices, torch.Tensor) else list(indices),
+                                      dtype=np.int64).reshape(-1)
+                if ((host_idx < 0) | (host_idx >= S)).any():
+                    raise IndexError(f"DevicePartNetProducer: shape index outside [0, {S})")
+                pinned = torch.empty(len(host_idx), dtype=torch.int64, pin_memory=True)
+                pinned.numpy()[:] = host_idx
+                d_idx = pinned.to(dev, non_blocking=True)
+                data_id = torch.as_tensor(host_idx, dtype=torch.int64)
+            B = d_idx.numel()
+            if self._status is None:
+                self._status = torch.zeros(1, dtype=torch.int32, device=dev)
+            d_perm = None
+            if perm is not None:
+                if isinstance(perm, torch.Tensor) and perm.device.type == "cuda":
+                    d_perm = perm
+                    if d_perm.dtype != torch.int32 or tuple(d_perm.shape) != (B, P) or not d_perm.is_contiguous():
+                        raise ValueError(f"replay: a device perm must be contiguous int32 [{B}, {P}]")
+                else:
+                    h_perm = np.ascontiguousarray(perm, dtype=np.int32)
+                    if h_perm.shape != (B, P):
+                        raise ValueError(f"replay: perm must be ({B}, {P}), got {h_perm.shape}")
+                    if host_idx is not None:  # what the wrapper can see: every row permutes 0..p-1
+                        count = np.diff(self.store.shape_part_off)[host_idx]
+                        for b, p in enumerate(count):
+                            if not np.array_equal(np.sort(h_perm[b, :p]), np.arange(p)):
+                                raise ValueError(f"replay: perm[{b}, :{p}] is not a permutation of 0..{p - 1}")
+                    d_perm = _to_device(h_perm, dev)
+            counter_val, counter_dev = 0, None
+            if isinstance(counter, torch.Tensor):
+                if counter.dtype != torch.int64 or counter.numel() != 1 or counter.device.type != "cuda":
+                    raise ValueError("DevicePartNetProducer: a device batch_counter must be one int64 word on the device")
+                counter_dev = counter
+            elif counter is not None:
+                counter_val = int(counter) & 0xFFFFFFFFFFFFFFFF
+            random_order = 1 if (self.shuffle_parts and perm is None) else 0
+            result, ptrs = {}, {}
+            for key, (shape, dtype) in self._spec(B).items():
+                t = None if out is None else out.get(key)
+                if t is not None and t.device.type != "cuda":
+                    t = None  # (a host tensor of a host-built batch, `shape_id`: the kernel cannot write it)
+                if t is None:
+                    t = torch.empty(shape, dtype=dtype, device=dev)
+                elif tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != d_idx.device:
+                    raise ValueError(f"DevicePartNetProducer: out[{key!r}] must be a contiguous {dtype} tensor of shape "
+                                     f"{shape} on {d_idx.device}")
+                result[key] = t
+                ptrs[key] = _lib.ptr(t) if t.numel() else None
+            order = torch.empty((B, P), dtype=torch.int32, device=dev) if return_order else None
+            st = _lib.lib().mpa_partnet_gather_batch(
+                *(_lib.ptr(arrays[n]) for n in PartNetStore.ARRAYS), _lib.ptr(arrays["contacts"]),
+                _lib.ptr(arrays["contact_off"]), S, _lib.ptr(d_idx), B, P, N, result["part_label"].shape[2],
+                _lib.ptr(d_perm), random_order, self.seed, counter_val, _lib.ptr(counter_dev),
+                ptrs["part_pcs"], ptrs["part_trans"], ptrs["part_quat"], ptrs["part_valids"], ptrs.get("part_ids"),
+                ptrs["instance_label"], ptrs.get("match_ids"), ptrs["part_label"], ptrs.get("contact_points"),
+                ptrs.get("sym"), ptrs.get("valid_matrix"), ptrs["shape_id"], _lib.ptr(order), _lib.ptr(self._status),
+                _lib.current_stream(dev))
+        _lib.check(st, "mpa_partnet_gather_batch")
+        if out is not None and host_idx is not None:  # the host-side entries of a host-built batch, filled in place
+            for key, val in (("data_id", data_id), ("shape_id", self.store.shape_ids[host_idx])):
+                t = out.get(key)
+                if t is not None and t.device.type == "cpu" and t.dtype == torch.int64 and tuple(t.shape) == (B,):
+                    t.copy_(torch.as_tensor(val))
+                    if key == "data_id":
+                        data_id = t
+                    else:
+                        result[key] = t
+        batch = {}
+        for key in ("part_pcs", "part_trans", "part_quat", "part_valids"):
+            batch[key] = result.pop(key)
+        batch["data_id"] = data_id
+        batch.update(result)
+        return (batch, order) if return_order else batch
+
+    def batch(self, indices, batch_counter=None, out=None, return_order=False):
+        """The `data_dict` of the shapes `indices`, gathered and labelled on the device.
+
+        `indices`: a host sequence (one pinned asynchronous copy; `data_id` is a host tensor, as the host producer's) or a
+        device int64 tensor (no host work at all; `data_id` is that tensor).  `batch_counter` selects the random streams
+        of `shuffle_parts` (default: the number of batches drawn so far); an int64 device word instead of a number is
+        read by the kernel at run time, so that a captured launch draws afresh after the host rewrites it.  `out`: a dict
+        of preallocated tensors (for instance `Trainer.static_batch`) — the kernel writes into those of its keys that
+        are device tensors, so their data pointers stay, and `Trainer._graph_step` has nothing to copy.  With
+        `return_order` also the part order used, int32 [B, P] (-1 in padded slots), as a second result."""
+        if batch_counter is None and self.shuffle_parts:
+            batch_counter = self.batch_counter
+            self.batch_counter += 1
+        return self._run(indices, counter=batch_counter, out=out, return_order=return_order)
+
+    def replay(self, indices, perm, out=None):
+        """Replay mode: `perm` int32 [B, P], row b holding in its first p entries the order `np.random.permutation(p)`
+        gave the caller.  Bit-equal to `PartNetBatchProducer(shuffle_parts=True).batch` under the same draws."""
+        return self._run(indices, perm=perm, out=out)
+
+    def check(self):
+        """RuntimeError if a launch since the last check met a shape index outside the store (or a replayed order that
+        is no permutation); synchronises.  The word is cleared as it is reported."""
+        if self._status is None:
+            return
+        code = int(self._status.item())
+        if code:
+            self._status.zero_()
+            what = "a shape index outside the store" if code == 1 else "a replayed part order that is no permutation"
+            raise RuntimeError(f"DevicePartNetProducer: a gather launch met {what}; that sample was written as padding")

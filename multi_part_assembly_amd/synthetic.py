@@ -136,6 +136,78 @@ def make_partnet_like_batch(batch_size, max_parts=20, num_points=1000, seed=1234
     return batch
 
 
+def make_partnet_like_store(num_shapes, max_parts=20, num_points=1000, seed=1234, num_part_category=20,
+                            with_contacts=True, min_parts=2):
+    """A `datasets.PartNetStore` of `num_shapes` shapes at the statistics of `make_partnet_like_batch`, on the host and
+    without a dataset: per shape 1 .. min(3, P // 4) groups of 2-4 geometrically identical parts (one centred cloud per
+    group, different poses, one shared `geo_part_ids` value >= 1) and 0-3 unique parts, the first of them with
+    `geo_part_ids` 0 as in the PartNet files; `part_ids` (semantic labels) uniform in 1 .. `num_part_category`; `sym`
+    a 0/1 flag per axis; with `with_contacts` a symmetric contact flag between consecutive parts with the midpoint of
+    their translations.  The parts of a shape are NOT sorted by group: their order is shuffled, so equal ids are
+    scattered as in the files.  A function of the arguments only (a private generator)."""
+    from .datasets import PartNetStore
+    P, N = max_parts, num_points
+    if P < 2:
+        raise ValueError("make_partnet_like_store: needs at least two part slots")
+    rng = np.random.RandomState(seed)
+    lo, hi = PRESETS["everyday"]["half_extent"]
+    shapes, contacts = [], []
+    for _ in range(num_shapes):
+        geo, label = [], 0
+        for _ in range(rng.randint(1, max(1, min(3, P // 4)) + 1)):
+            size = min(rng.randint(2, 5), P - len(geo))
+            if size < 2:
+                break
+            label += 1
+            geo += [label] * size
+        for k in range(min(rng.randint(0, 4), P - len(geo))):
+            label += 1
+            geo.append(0 if k == 0 else label)
+        geo = np.array(geo, dtype=np.int64)
+        while len(geo) < min_parts:
+            label += 1
+            geo = np.append(geo, label)
+        geo = geo[rng.permutation(len(geo))]
+        p = len(geo)
+        clouds = {}
+        for g in np.unique(geo):
+            pts = (2.0 * rng.random_sample((N, 3)) - 1.0) * (lo + (hi - lo) * rng.random_sample(3))
+            clouds[g] = (pts - pts.mean(0)).astype(np.float32)
+        quat = rng.standard_normal((p, 4))
+        quat /= np.linalg.norm(quat, axis=1, keepdims=True)
+        trans = 0.8 * rng.random_sample((p, 3)) - 0.4
+        shapes.append({"part_pcs": np.stack([clouds[g] for g in geo]),
+                       "part_poses": np.concatenate([trans, quat], axis=1).astype(np.float32),
+                       "part_ids": rng.randint(1, num_part_category + 1, size=p).astype(np.int64),
+                       "geo_part_ids": geo,
+                       "sym": rng.randint(0, 2, size=(p, 3)).astype(np.float32)})
+        c = np.zeros((p, p, 4), dtype=np.float32)
+        for i in range(p - 1):
+            c[i, i + 1] = c[i + 1, i] = (1.0, *(0.5 * (trans[i] + trans[i + 1])))
+        contacts.append(c)
+    return PartNetStore.from_arrays(shapes, shape_ids=1000 + np.arange(num_shapes),
+                                    contacts=contacts if with_contacts else None, min_num_part=min_parts, max_num_part=P)
+
+
+def write_partnet_folder(store, data_dir, data_fn="Chair.train.npy", level=3):
+    """Write a `PartNetStore` as a split in the reference's on-disk format (`data_fn` id list, `shape_data/{id}_level3.npy`
+    pickled dicts, `contact_points/pairs_with_contact_points_{id}_level3.npy`), so that `datasets.PartNetBatchProducer`
+    really loads files of the same data."""
+    import os
+    os.makedirs(os.path.join(data_dir, "shape_data"), exist_ok=True)
+    np.save(os.path.join(data_dir, data_fn), store.shape_ids)
+    if store.has_contacts:
+        os.makedirs(os.path.join(data_dir, "contact_points"), exist_ok=True)
+    for s, sid in enumerate(store.shape_ids):
+        a, b = store.shape_part_off[s], store.shape_part_off[s + 1]
+        np.save(os.path.join(data_dir, "shape_data", f"{sid}_level{level}.npy"),
+                {"part_pcs": store.pcs[a:b], "part_poses": store.poses[a:b], "part_ids": store.sem_ids[a:b].astype(np.int64),
+                 "geo_part_ids": store.geo_ids[a:b].astype(np.int64), "sym": store.sym[a:b]}, allow_pickle=True)
+        if store.has_contacts:
+            c = store.contacts[store.contact_off[s]:store.contact_off[s + 1]].reshape(b - a, b - a, 4)
+            np.save(os.path.join(data_dir, "contact_points", f"pairs_with_contact_points_{sid}_level{level}.npy"), c)
+
+
 def _uv_sphere(segments, rings):
     """Closed latitude / longitude triangulation of the unit sphere: `segments * (rings - 1) + 2` vertices,
     `2 * segments * (rings - 1)` triangles, outward orientation."""

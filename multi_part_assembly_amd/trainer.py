@@ -165,6 +165,13 @@ class Trainer:
             self.optimizer.lr = self.schedule(epoch)
 
     # ---- graph mode -----------------------------------------------------------------------------------
+    @property
+    def static_batch(self):
+        """The static input tensors of the captured step (None before the capture).  A producer that writes a batch
+        straight into them (`DevicePartNetProducer.batch(..., out=trainer.static_batch)`) leaves `_graph_step` nothing
+        to copy: it skips every tensor whose data pointer already is the static one."""
+        return self._static_batch
+
     def _tensor_items(self, data_dict):
         return {k: v for k, v in data_dict.items() if isinstance(v, torch.Tensor)}
 
