@@ -6,6 +6,7 @@ from pathlib import Path
 import pytest
 import torch
 
+import anchored as A
 from multi_part_assembly_amd import config
 from multi_part_assembly_amd.encoder import build_encoder
 from multi_part_assembly_amd.optim import FusedAdam
@@ -36,8 +37,20 @@ def _rel(a, b):
     return np.abs(a - b).max() / (np.abs(b).max() + 1e-12)
 
 
+def _sd(z, prefix, keep_prefix=False):
+    """The float32 state dict recorded in a fixture under `prefix`."""
+    return {(k if keep_prefix else k[len(prefix):]): T(v.copy()) for k, v in z.items() if k.startswith(prefix)}
+
+
+def _grads(named_parameters, prefix="grad."):
+    return {prefix + k: p.grad.detach().cpu() for k, p in named_parameters}
+
+
 @pytest.mark.parametrize("name,feat", [("pointnet", 256), ("dgcnn", 128)])
-def test_encoder_matches_reference(golden, cuda_device, name, feat):
+def test_encoder_matches_reference(golden, cuda_device, capsys, name, feat):
+    """PointNet: features and every parameter gradient are anchored at the float64 evaluation of oracle.nets.pointnet on
+    the fixture's weights and points (tests/test_oracle_golden.py pins that oracle to this fixture), with the fixture's
+    float32 reference gradients as the `ref32` of the bar (tests/anchored.py)."""
     z = golden(name)
     enc = build_encoder(name, feat)
     _load(enc, z, "sd0.")
@@ -54,7 +67,7 @@ def test_encoder_matches_reference(golden, cuda_device, name, feat):
     ref_dev = {"grad_x": 3e-2, "conv1.0.weight": 3e-3}
 
     def close(a, b, who):
-        tol = 1e-3 if name == "pointnet" else ref_dev.get(who, 2e-4)
+        tol = ref_dev.get(who, 2e-4)
         assert _rel(a, b) < tol, (who, _rel(a, b))
         if name == "dgcnn" and who in ref_dev:  # ... and the deviation is isolated: the bulk of the entries agree
             bad = (np.abs(a - b) > 2e-4 * np.abs(b).max()).mean()
@@ -62,8 +75,14 @@ def test_encoder_matches_reference(golden, cuda_device, name, feat):
 
     if name == "dgcnn":  # the HIP PointNet does not differentiate w.r.t. its input points (data)
         close(x.grad.cpu().numpy(), z["grad_x"], "grad_x")
-    for k, p in enc.named_parameters():
-        close(p.grad.cpu().numpy(), z["grad." + k], k)
+    if name == "pointnet":
+        r64 = A.oracle_run(A.pointnet_fn(True), _sd(z, "sd0."), {"pts": T(z["x"]), "w": T(z["w"])})
+        r32 = {"out.feat": T(z["feat_train"]), **{"grad." + k: T(z["grad." + k]) for k, _ in enc.named_parameters()}}
+        A.assert_anchored({"out.feat": out.detach().cpu(), **_grads(enc.named_parameters())}, r32, r64,
+                          "PointNet vs the reference fixture", capsys)
+    else:
+        for k, p in enc.named_parameters():
+            close(p.grad.cpu().numpy(), z["grad." + k], k)
     for k, v in enc.state_dict().items():  # running statistics after the training-mode forward
         np.testing.assert_allclose(v.cpu().numpy(), z["sd1." + k], rtol=1e-4, atol=1e-5, err_msg=k)
     enc.eval()
@@ -173,11 +192,13 @@ def test_pointnet_masked_parts_equal_compacted(cuda_device):
 
 
 @pytest.mark.parametrize("mixed_gamma", [False, True])
-def test_pointnet_matches_torch_ops_at_full_width(cuda_device, mixed_gamma):
+def test_pointnet_matches_torch_ops_at_full_width(cuda_device, capsys, mixed_gamma):
     """N=1000 (4 row tiles per part, ragged tail), F=256: against the same network written with stock
     torch ops on the GPU (Conv1d/BatchNorm1d), forward and all parameter gradients.  mixed_gamma: the last
     BatchNorm has negative and zero weights too (its max over points then is a min / a constant of the
-    pre-BatchNorm values, which the HIP path never stores)."""
+    pre-BatchNorm values, which the HIP path never stores).  The library comparison is the self-family check (two float32
+    evaluations on the same device); beside it, features and gradients are held to the float64-anchored bar of
+    tests/anchored.py against oracle.nets.pointnet on the CPU."""
     import torch.nn.functional as Fn
 
     torch.manual_seed(4)
@@ -190,6 +211,7 @@ def test_pointnet_matches_torch_ops_at_full_width(cuda_device, mixed_gamma):
             enc.bn4.weight[::5] *= -0.5
     x = (torch.randn(9, 1000, 3) * 0.2).to(cuda_device)
     w = torch.randn(9, 256, device=cuda_device)
+    sd0 = {k: v.detach().cpu().clone() for k, v in enc.state_dict().items()}
     ref_params = {k: v.detach().clone().requires_grad_() for k, v in enc.named_parameters()}
     h = x.transpose(2, 1)
     for i in range(1, 6):
@@ -202,11 +224,33 @@ def test_pointnet_matches_torch_ops_at_full_width(cuda_device, mixed_gamma):
     out = enc(x)
     (out * w).sum().backward()
     assert _rel(out.detach().cpu().numpy(), ref.detach().cpu().numpy()) < 1e-4
-    for k, p in enc.named_parameters():
+    for k, p in enc.named_parameters():  # (self-family: HIP against the library's float32 on the same device)
         assert _rel(p.grad.cpu().numpy(), ref_params[k].grad.cpu().numpy()) < 1e-3, k
+    r32, r64 = A.oracle_pair(A.pointnet_fn(True), sd0, {"pts": x.cpu(), "w": w.cpu()})
+    got = {"out.feat": out.detach().cpu(), **_grads(enc.named_parameters())}
+    A.assert_anchored(got, {k: r32[k] for k in got}, {k: r64[k] for k in got},
+                      f"PointNet N=1000 F=256 mixed_gamma={mixed_gamma}", capsys)
 
 
-def test_transformer_and_pose_head_match_reference(golden, cuda_device):
+def _encoder_and_head_fn(layers, heads, feat_weight=0.0):
+    """oracle.nets: transformer_encoder (parameters under `enc.`) + pose_head (`head.`); the loss of the tests below."""
+    from oracle import nets as on
+
+    def fn(sd, inp):
+        feats = on.transformer_encoder(inp["tok"], inp["valid"], sd, "enc.", layers, heads)
+        rot, trans = on.pose_head(feats, sd, "head.")
+        vm = inp["valid"][..., None].to(feats.dtype)
+        loss = (rot * inp["w_rot"] * vm).sum() + (trans * inp["w_trans"] * vm).sum()
+        if feat_weight:
+            loss = loss + feat_weight * (feats * vm).sum()
+        v = inp["valid"]
+        return {"feats": feats[v], "rot": rot[v], "trans": trans[v]}, loss
+    return fn
+
+
+def test_transformer_and_pose_head_match_reference(golden, cuda_device, capsys):
+    """Outputs against the fixture at the parity bar; every parameter gradient anchored at the float64 evaluation of
+    oracle.nets on the fixture's weights and inputs, the fixture's float32 reference gradients being the `ref32` of the bar."""
     z = golden("transformer")
     d, heads, ffn, layers = (int(v) for v in z["cfg"])
     enc = TransformerEncoder(d, heads, ffn, layers, norm_first=True, dropout=0.0)
@@ -225,16 +269,22 @@ def test_transformer_and_pose_head_match_reference(golden, cuda_device):
     assert _rel(feats.detach().cpu().numpy()[v], z["feats"][v]) < 1e-4
     assert _rel(rot.detach().cpu().numpy()[v], z["rot"][v]) < 1e-4
     assert _rel(trans.detach().cpu().numpy()[v], z["trans"][v]) < 1e-4
-    for k, p in enc.named_parameters():
-        assert _rel(p.grad.cpu().numpy(), z["genc." + k]) < 1e-3, k
-    for k, p in head.named_parameters():
-        assert _rel(p.grad.cpu().numpy(), z["ghead." + k]) < 1e-3, k
+    inputs = {"tok": T(z["tokens"]), "valid": T(z["valid"]), "w_rot": T(z["w_rot"]), "w_trans": T(z["w_trans"])}
+    r64 = A.oracle_run(_encoder_and_head_fn(layers, heads), {**_sd(z, "enc.", True), **_sd(z, "head.", True)}, inputs)
+    r32 = {"out.feats": T(z["feats"][v]), "out.rot": T(z["rot"][v]), "out.trans": T(z["trans"][v])}
+    r32.update({"grad.enc." + k: T(z["genc." + k]) for k, _ in enc.named_parameters()})
+    r32.update({"grad.head." + k: T(z["ghead." + k]) for k, _ in head.named_parameters()})
+    got = {"out.feats": A.valid_rows(feats, valid), "out.rot": A.valid_rows(rot, valid), "out.trans": A.valid_rows(trans, valid)}
+    got.update(_grads(enc.named_parameters(), "grad.enc."))
+    got.update(_grads(head.named_parameters(), "grad.head."))
+    A.assert_anchored(got, r32, r64, "transformer + pose head vs the reference fixture", capsys)
 
 
-def test_transformer_dropout_matches_oracle_with_same_masks(golden, cuda_device):
+def test_transformer_dropout_matches_oracle_with_same_masks(golden, cuda_device, capsys):
     """Training-mode dropout (p = 0.1 upstream, transformer.py:10): the oracle regenerates the HIP kernels'
     counter-based masks (oracle.nets.dropout_keep_scale), so outputs and every gradient are compared value by
-    value — forward masks, the masks regenerated in backward and the ReLU/dropout gradient gates included."""
+    value — forward masks, the masks regenerated in backward and the ReLU/dropout gradient gates included — against
+    the float64 evaluation of that oracle, under the bar of tests/anchored.py."""
     from multi_part_assembly_amd.transformer import _TransformerFn
     from oracle import nets as on
     z = golden("transformer")
@@ -254,9 +304,15 @@ def test_transformer_dropout_matches_oracle_with_same_masks(golden, cuda_device)
     out = _TransformerFn.apply(tok, valid.reshape(-1).float().to(cuda_device), heads, p_drop, seed, None, *enc._params())
     (out * w.to(cuda_device)).sum().backward()
     assert _rel(out.detach().cpu().numpy(), ref.detach().numpy()) < 1e-4
-    assert _rel(tok.grad.cpu().numpy(), tok_ref.grad.numpy()) < 1e-3
-    for k, p in enc.named_parameters():
-        assert _rel(p.grad.cpu().numpy(), sd[k].grad.numpy()) < 1e-3, k
+
+    def fn(sd_, inp):
+        o = on.transformer_encoder(inp["tok"], inp["valid"], sd_, "", layers, heads, dropout_p=p_drop, seed=seed)
+        return {"out": o}, (o * inp["w"]).sum()
+
+    r32, r64 = A.oracle_pair(fn, {k: v.detach() for k, v in sd.items()}, {"tok": T(z["tokens"]), "valid": valid, "w": w}, ("tok",))
+    assert torch.equal(r32["gin.tok"], tok_ref.grad.double())  # (the float32 oracle of the bar is the one above)
+    got = {"out.out": out.detach().cpu(), "gin.tok": tok.grad.cpu(), **_grads(enc.named_parameters())}
+    A.assert_anchored(got, r32, r64, "transformer fixture, dropout 0.1", capsys)
     # module-level behaviour: a fresh mask per call in train mode, none in eval mode
     with torch.no_grad():
         a, b = enc(tok, valid.to(cuda_device)), enc(tok, valid.to(cuda_device))
@@ -269,7 +325,7 @@ def test_transformer_dropout_matches_oracle_with_same_masks(golden, cuda_device)
 
 
 @pytest.mark.parametrize("B,P", [(3, 7), (5, 14)])
-def test_transformer_width_256_dropout_matches_oracle_with_same_masks(cuda_device, B, P):
+def test_transformer_width_256_dropout_matches_oracle_with_same_masks(cuda_device, capsys, B, P):
     """D = 256 is the width at which both LayerNorm passes ride in GEMM operand loads (tf_gemm.h LNM = 1 / 2): forward,
     the d x / masked d x / dgamma / dbeta of every fused LayerNorm backward and the ragged last 32-row tile (M = 21, 70)
     against the oracle regenerating the same counter-based masks."""
@@ -297,14 +353,20 @@ def test_transformer_width_256_dropout_matches_oracle_with_same_masks(cuda_devic
     out = _TransformerFn.apply(tok, valid.reshape(-1).float().to(cuda_device), H, p_drop, seed, None, *enc._params())
     (out * w.to(cuda_device)).sum().backward()
     assert _rel(out.detach().cpu().numpy(), ref.detach().numpy()) < 1e-4
-    assert _rel(tok.grad.cpu().numpy(), tok_ref.grad.numpy()) < 1e-3
-    for k, p in enc.named_parameters():
-        assert _rel(p.grad.cpu().numpy(), sd[k].grad.numpy()) < 1e-3, k
+
+    def fn(sd_, inp):
+        o = on.transformer_encoder(inp["tok"], inp["valid"], sd_, "", L, H, dropout_p=p_drop, seed=seed)
+        return {"out": o}, (o * inp["w"]).sum()
+
+    r32, r64 = A.oracle_pair(fn, {k: v.detach() for k, v in sd.items()}, {"tok": tok0, "valid": valid, "w": w}, ("tok",))
+    got = {"out.out": out.detach().cpu(), "gin.tok": tok.grad.cpu(), **_grads(enc.named_parameters())}
+    A.assert_anchored(got, r32, r64, f"transformer D=256 B={B} P={P}, dropout 0.1", capsys)
 
 
-def test_transformer_and_pose_head_full_size_match_library_ops(cuda_device):
+def test_transformer_and_pose_head_full_size_match_library_ops(cuda_device, capsys):
     """BASELINE.json configs[1] shapes (B=32, P=20, D=256, 8 heads, FF=1024, 4 layers; head F=256): the HIP
-    kernels against PyTorch-ROCm's nn.TransformerEncoder / Linear stack on the same device, dropout off."""
+    kernels against PyTorch-ROCm's nn.TransformerEncoder / Linear stack on the same device, dropout off (the self-family
+    check), and beside it against the float64 evaluation of oracle.nets under the bar of tests/anchored.py."""
     torch.manual_seed(3)
     B, P, D, H, FF, L = 32, 20, 256, 8, 1024, 4
     enc = TransformerEncoder(D, H, FF, L, norm_first=True, dropout=0.0).to(cuda_device).train()
@@ -318,6 +380,8 @@ def test_transformer_and_pose_head_full_size_match_library_ops(cuda_device):
     valid = (torch.arange(P)[None] < num[:, None]).to(cuda_device)
     tok = (torch.randn(B, P, D, generator=g) * valid.cpu()[..., None]).to(cuda_device)
     w_r, w_t = torch.randn(B, P, 4, generator=g).to(cuda_device), torch.randn(B, P, 3, generator=g).to(cuda_device)
+    sd0 = {**{"enc." + k: t.detach().cpu().clone() for k, t in enc.state_dict().items()},
+           **{"head." + k: t.detach().cpu().clone() for k, t in head.state_dict().items()}}
 
     def run(native):
         enc.native = head.native = native
@@ -336,12 +400,22 @@ def test_transformer_and_pose_head_full_size_match_library_ops(cuda_device):
     v = valid.cpu().numpy()
     for a, b in ((f1, f0), (r1, r0), (t1, t0)):
         assert _rel(a.cpu().numpy()[v], b.cpu().numpy()[v]) < 1e-4
-    assert _rel(gx1.cpu().numpy(), gx0.cpu().numpy()) < 1e-3
+    assert _rel(gx1.cpu().numpy(), gx0.cpu().numpy()) < 1e-3  # (self-family: against the library's float32, as for g below)
     for k in g0:
         assert _rel(g1[k].cpu().numpy(), g0[k].cpu().numpy()) < 1e-3, k
+    vc = valid.cpu()
+    r32, r64 = A.oracle_pair(_encoder_and_head_fn(L, H, 0.01), sd0,
+                             {"tok": tok.cpu(), "valid": vc, "w_rot": w_r.cpu(), "w_trans": w_t.cpu()}, ("tok",))
+    for r in (r32, r64):
+        r["gin.tok"] = r["gin.tok"][vc]
+    got = {"out.feats": A.valid_rows(f1, vc), "out.rot": A.valid_rows(r1, vc), "out.trans": A.valid_rows(t1, vc),
+           "gin.tok": A.valid_rows(gx1, vc)}
+    got.update({"grad.enc." + k: g1[k].cpu() for k, _ in enc.named_parameters()})
+    got.update({"grad.head." + k: g1[k].cpu() for k, _ in head.named_parameters()})
     # bit-reproducible: the same call twice gives identical gradients (fixed-order reductions)
     f2, _, _, gx2, g2 = run(True)
     assert torch.equal(f1, f2) and torch.equal(gx1, gx2) and all(torch.equal(g1[k], g2[k]) for k in g1)
+    A.assert_anchored(got, r32, r64, f"transformer + pose head at full size {(B, P, D, H, FF, L)}", capsys)
 
 
 def test_transformer_cross_block_hand_overs_are_stable_over_many_launches(cuda_device):
@@ -376,10 +450,11 @@ def test_transformer_cross_block_hand_overs_are_stable_over_many_launches(cuda_d
 
 
 @pytest.mark.parametrize("B,P", [(1, 1), (3, 2), (5, 31), (2, 32), (33, 7), (40, 20)])
-def test_transformer_fused_kernels_at_the_edges_of_their_envelope(cuda_device, B, P):
+def test_transformer_fused_kernels_at_the_edges_of_their_envelope(cuda_device, capsys, B, P):
     """attn_qkv_fwd_kernel / attn_do_bwd_kernel hold a sample's tokens in one 32-row tile and hand tiles between blocks per
     sample: one token, a full tile, more samples than row tiles, a batch that is not a multiple of anything — against
-    PyTorch-ROCm's own TransformerEncoder on the same device (dropout off), every gradient."""
+    PyTorch-ROCm's own TransformerEncoder on the same device (dropout off), every gradient (the self-family check), and
+    beside it against the float64 evaluation of oracle.nets.transformer_encoder under the bar of tests/anchored.py."""
     torch.manual_seed(100 * B + P)
     D, H, FF, L = 256, 8, 1024, 2
     enc = TransformerEncoder(D, H, FF, L, norm_first=True, dropout=0.0).to(cuda_device).train()
@@ -402,9 +477,17 @@ def test_transformer_fused_kernels_at_the_edges_of_their_envelope(cuda_device, B
     o0, gx0, g0 = run(False)
     v = valid.cpu().numpy()
     assert _rel(o1.cpu().numpy()[v], o0.cpu().numpy()[v]) < 1e-4
-    assert _rel(gx1.cpu().numpy()[v], gx0.cpu().numpy()[v]) < 1e-3
+    assert _rel(gx1.cpu().numpy()[v], gx0.cpu().numpy()[v]) < 1e-3  # (self-family: against the library's float32)
     for k in g0:
         assert _rel(g1[k].cpu().numpy(), g0[k].cpu().numpy()) < 1e-3, k
+    vc = valid.cpu()
+    sd0 = {k: t.detach().cpu().clone() for k, t in enc.state_dict().items()}
+    r32, r64 = A.oracle_pair(A.transformer_fn((B, P, D, H, FF, L)), sd0,
+                             {"tok": tok.cpu(), "valid": vc, "w": (w * valid[..., None].float()).cpu()}, ("tok",))
+    for r in (r32, r64):
+        r["out.out"], r["gin.tok"] = r["out.out"][vc], r["gin.tok"][vc]
+    got = {"out.out": A.valid_rows(o1, vc), "gin.tok": A.valid_rows(gx1, vc), **{"grad." + k: t.cpu() for k, t in g1.items()}}
+    A.assert_anchored(got, r32, r64, f"transformer envelope edge B={B} P={P}", capsys)
 
 
 _TF_KNOB_SCRIPT = r"""
@@ -478,9 +561,12 @@ def test_encoders_without_any_valid_part_give_zeros(cuda_device, arch, N):
     assert float(mixed[0].abs().max()) == 0.0 and float(mixed[1].abs().max()) > 0.0
 
 
-def test_pose_head_odd_input_width_matches_library_ops(cuda_device):
+def test_pose_head_odd_input_width_matches_library_ops(cuda_device, capsys):
     """Input widths that are not multiples of 64 (semantic models append P labels and 32 noise channels; the
-    refinement model appends the 7-d pose) run on the HIP head, which zero-pads its panels inside the workspace."""
+    refinement model appends the 7-d pose) run on the HIP head, which zero-pads its panels inside the workspace: against
+    the library path on the same device (the self-family check) and, where the head draws no noise, against the float64
+    evaluation of oracle.nets.pose_head under the bar of tests/anchored.py (the noisy width stays a library comparison:
+    the channels are drawn inside the module)."""
     torch.manual_seed(5)
     for width, noise in ((180, 0), (128 + 20, 32), (263, 0)):
         head = StocasticPoseRegressor(feat_dim=width, noise_dim=noise).to(cuda_device).train()
@@ -502,8 +588,13 @@ def test_pose_head_odd_input_width_matches_library_ops(cuda_device):
         assert (width + noise) % 64 != 0
         assert _rel(r1.cpu().numpy(), r0.cpu().numpy()) < 1e-4 and _rel(t1.cpu().numpy(), t0.cpu().numpy()) < 1e-4
         assert gx1.shape == x.shape and _rel(gx1.cpu().numpy(), gx0.cpu().numpy()) < 1e-3
-        for k in g0:
+        for k in g0:  # (self-family: against the library's float32, as for gx above)
             assert g1[k].shape == g0[k].shape and _rel(g1[k].cpu().numpy(), g0[k].cpu().numpy()) < 1e-3, k
+        if noise == 0:
+            sd0 = {k: t.detach().cpu().clone() for k, t in head.state_dict().items()}
+            r32, r64 = A.oracle_pair(A.pose_head_fn, sd0, {"x": x.cpu(), "w_rot": w_r.cpu(), "w_trans": w_t.cpu()}, ("x",))
+            got = {"out.rot": r1.cpu(), "out.trans": t1.cpu(), "gin.x": gx1.cpu(), **{"grad." + k: t.cpu() for k, t in g1.items()}}
+            A.assert_anchored(got, r32, r64, f"pose head, input width {width}", capsys)
 
 
 def test_grad_sink_direct_writes_equal_autograd_accumulation(cuda_device):
@@ -570,8 +661,24 @@ def _small_cfg(z):
     return cfg
 
 
+def _step_anchor(z, cfg, dtype):
+    """The PNTransformer step of the fixture (forward_pass + loss + backward, dropout off) on oracle.nets /
+    oracle.geometry in `dtype`: loss and every parameter gradient."""
+    from oracle import nets as on
+
+    def fn(sd, batch):
+        losses, _ = on.pn_transformer_loss(sd, batch, cfg.model.transformer_layers, cfg.model.transformer_heads)
+        return {"loss": losses["loss"]}, losses["loss"]
+
+    batch = {k[5:]: T(v.copy()) for k, v in z.items() if k.startswith("data.")}
+    return A.oracle_run(fn, _sd(z, "sd0."), batch, (), dtype)
+
+
 @pytest.mark.parametrize("fused", [True, False])
-def test_pn_transformer_step_matches_reference(golden, cuda_device, fused):
+def test_pn_transformer_step_matches_reference(golden, cuda_device, capsys, fused):
+    """Loss terms, running statistics and features against the fixture at the parity bar; every parameter gradient
+    anchored at the float64 evaluation of the oracle's step on the fixture's weights and batch, the fixture's float32
+    reference gradients being the `ref32` of the bar (tests/anchored.py)."""
     z = golden("pn_transformer_step")
     model = build_model(_small_cfg(z))
     model.fused_loss = fused  # fused assembly-loss kernels vs per-function composition
@@ -584,8 +691,10 @@ def test_pn_transformer_step_matches_reference(golden, cuda_device, fused):
     for k in ("trans_loss", "rot_pt_cd_loss", "transform_pt_cd_loss", "rot_loss", "rot_pt_l2_loss", "loss"):
         np.testing.assert_allclose(float(losses[k]), float(z["loss." + k]), rtol=1e-4, err_msg=k)
     assert "part_quat" in batch  # forward_pass must not mutate the caller's dict
-    for k, p in model.named_parameters():
-        assert _rel(p.grad.cpu().numpy(), z["grad." + k]) < 2e-3, k
+    r64 = _step_anchor(z, _small_cfg(z), torch.float64)
+    r32 = {"out.loss": T(z["loss.loss"]).reshape(()), **{"grad." + k: T(z["grad." + k]) for k, _ in model.named_parameters()}}
+    got = {"out.loss": losses["loss"].detach().cpu().reshape(()), **_grads(model.named_parameters())}
+    A.assert_anchored(got, r32, r64, f"PNTransformer step vs the reference fixture, fused loss {fused}", capsys)
     for k, v in model.state_dict().items():
         if "running" in k:
             np.testing.assert_allclose(v.cpu().numpy(), z["sd1." + k], rtol=1e-4, atol=1e-5, err_msg=k)
@@ -648,10 +757,9 @@ def test_fused_adamw_param_groups_and_clipping_match_torch(cuda_device):
         np.testing.assert_allclose(a.detach().cpu().numpy(), b.detach().cpu().numpy(), rtol=1e-4, atol=1e-5)
 
 
-def test_trainer_step_matches_oracle_step(golden, cuda_device):
-    """Full optimiser step: loss and gradients equal the oracle's (CPU autograd), and the parameter
-    update is exactly Adam's first step on those gradients."""
-    from oracle import nets as on
+def test_trainer_step_matches_oracle_step(golden, cuda_device, capsys):
+    """Full optimiser step: loss and gradients equal the oracle's (CPU autograd, anchored at its float64 evaluation
+    under the bar of tests/anchored.py), and the parameter update is exactly Adam's first step on those gradients."""
 
     z = golden("pn_transformer_step")
     cfg = _small_cfg(z)
@@ -666,13 +774,9 @@ def test_trainer_step_matches_oracle_step(golden, cuda_device):
     loss = trainer.train_step(batch)
     np.testing.assert_allclose(float(loss), float(z["loss.loss"]), rtol=1e-4)
 
-    sd = {k[4:]: T(v.copy()) for k, v in z.items() if k.startswith("sd0.")}
-    params = {k: sd[k].requires_grad_() for k, _ in model.named_parameters()}
-    cpu_batch = {k[5:]: T(v) for k, v in z.items() if k.startswith("data.")}
-    losses, _ = on.pn_transformer_loss(sd, cpu_batch, cfg.model.transformer_layers, cfg.model.transformer_heads)
-    losses["loss"].backward()
-    for k, p in model.named_parameters():
-        assert _rel(p.grad.cpu().numpy(), params[k].grad.numpy()) < 2e-3, k
+    r32, r64 = _step_anchor(z, cfg, torch.float32), _step_anchor(z, cfg, torch.float64)
+    got = {"out.loss": loss.detach().cpu().reshape(()), **_grads(model.named_parameters())}
+    A.assert_anchored(got, r32, r64, "Trainer step vs the oracle step", capsys)
     # first Adam step: m_hat = g, v_hat = g^2  ->  p -= lr * g / (|g| + eps)
     g = trainer.flat.flat_grad
     want = before - cfg.optimizer.lr * g / (g.abs() + 1e-8)

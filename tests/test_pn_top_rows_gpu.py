@@ -9,23 +9,18 @@ a part whose rows 1 .. N-2 copy row 0 has them on row 0 or on row N-1; a part wh
 on the 32 rows of its first tile.  Copies have equal activations, so the parameter gradients do not depend on which of
 them a tie goes to: the oracle needs no tie rule.  Ordinary random parts share every batch (healthy BatchNorm statistics).
 
-Tolerances are those of tests/test_model_gpu.py for the same quantities (test_pointnet_matches_torch_ops_at_full_width,
-test_encoder_matches_reference): features 1e-4, parameter gradients 1e-3, both relative to the largest reference entry."""
+Features and every parameter gradient are held to the float64-anchored bar of tests/anchored.py: per tensor, 8 x the float32
+CPU oracle's own deviation from float64 on the same inputs (or 8 x the median of those deviations), never above 1e-4."""
 import ctypes
 
-import numpy as np
 import pytest
 import torch
 
+import anchored as A
 from multi_part_assembly_amd import _lib
 from multi_part_assembly_amd.encoder import build_encoder
-from oracle import nets as on
 
 gpu = pytest.mark.gpu
-
-
-def _rel(a, b):
-    return np.abs(a - b).max() / (np.abs(b).max() + 1e-12)
 
 
 def _one_row(n, g):
@@ -63,12 +58,12 @@ def _run(enc, pts, valids, w):
     return out.detach().clone(), {k: p.grad.detach().clone() for k, p in enc.named_parameters()}
 
 
-def _check(cuda_device, feat, pts, valids, seed=0):
+def _check(cuda_device, capsys, feat, pts, valids, seed=0):
     torch.manual_seed(seed)
     enc = build_encoder("pointnet", feat).to(cuda_device).train()
     with torch.no_grad():  # both signs of the last BatchNorm's weight: maxima and minima of the never-stored Y5
         enc.bn5.weight[::3] *= -1.0
-    sd = {k: v.detach().double().cpu() for k, v in enc.state_dict().items()}
+    sd = {k: v.detach().cpu().clone() for k, v in enc.state_dict().items()}
     M = pts.shape[0]
     w = torch.randn(M, feat, generator=torch.Generator().manual_seed(seed + 1))
     out, grads = _run(enc, pts.to(cuda_device), valids.to(cuda_device), w.to(cuda_device))
@@ -82,57 +77,49 @@ def _check(cuda_device, feat, pts, valids, seed=0):
         for k, gk in grads.items():
             assert bool(torch.isfinite(gk).all()) and float(gk.abs().max()) == 0.0, k
         return
-    ref_p = {k: sd[k].clone().requires_grad_() for k, _ in enc.named_parameters()}
-    ref = on.pointnet(pts[keep].double(), {**sd, **ref_p}, training=True)
-    (ref * w[keep].double()).sum().backward()
-    r_out = _rel(out[keep.to(cuda_device)].cpu().numpy(), ref.detach().numpy())
-    print(f"features: {r_out:.3e}")
-    worst = {}
-    for k, gk in grads.items():
-        worst[k] = _rel(gk.cpu().numpy().astype(np.float64), ref_p[k].grad.numpy())
-        print(f"grad {k}: {worst[k]:.3e}")
-    assert r_out < 1e-4, r_out
-    for k, v in worst.items():
-        assert v < 1e-3, (k, v)
+    r32, r64 = A.oracle_pair(A.pointnet_fn(True), sd, {"pts": pts[keep], "w": w[keep]})
+    got = {"out.feat": out.cpu()[keep], **{"grad." + k: gk.cpu() for k, gk in grads.items()}}
+    A.assert_anchored(got, {k: r32[k] for k in got}, {k: r64[k] for k in got},
+                      f"PointNet arg-max rows, F={feat}, {tuple(pts.shape)}, {int(keep.sum())} valid", capsys)
 
 
 @gpu
 @pytest.mark.parametrize("feat", [256, 128, 64])
 @pytest.mark.parametrize("N", [1000, 37])
-def test_all_arg_maxima_on_one_row(cuda_device, feat, N):
+def test_all_arg_maxima_on_one_row(cuda_device, capsys, feat, N):
     kinds = [_one_row, _random, _one_row, _random, _random, _one_row]
-    _check(cuda_device, feat, _batch(kinds, N, 11), torch.ones(len(kinds)))
+    _check(cuda_device, capsys, feat, _batch(kinds, N, 11), torch.ones(len(kinds)))
 
 
 @gpu
 @pytest.mark.parametrize("feat", [256, 128, 64])
 @pytest.mark.parametrize("N", [1000, 37])
-def test_arg_maxima_on_first_and_last_valid_row(cuda_device, feat, N):
+def test_arg_maxima_on_first_and_last_valid_row(cuda_device, capsys, feat, N):
     kinds = [_first_and_last, _random, _first_and_last, _random, _first_and_last]
-    _check(cuda_device, feat, _batch(kinds, N, 12), torch.ones(len(kinds)))
+    _check(cuda_device, capsys, feat, _batch(kinds, N, 12), torch.ones(len(kinds)))
 
 
 @gpu
 @pytest.mark.parametrize("feat", [256, 128, 64])
 @pytest.mark.parametrize("N", [1000, 37])
-def test_arg_maxima_on_the_32_rows_of_one_tile(cuda_device, feat, N):
+def test_arg_maxima_on_the_32_rows_of_one_tile(cuda_device, capsys, feat, N):
     kinds = [_full_tile, _random, _full_tile, _full_tile, _random]
-    _check(cuda_device, feat, _batch(kinds, N, 13), torch.ones(len(kinds)))
+    _check(cuda_device, capsys, feat, _batch(kinds, N, 13), torch.ones(len(kinds)))
 
 
 @gpu
 @pytest.mark.parametrize("feat", [256, 64])
-def test_padded_parts_between_valid_ones(cuda_device, feat):
+def test_padded_parts_between_valid_ones(cuda_device, capsys, feat):
     kinds = [_random, _one_row, _random, _full_tile, _first_and_last, _random, _random, _one_row]
     valids = torch.tensor([0.0, 1.0, 0.0, 1.0, 1.0, 0.0, 1.0, 0.0])
-    _check(cuda_device, feat, _batch(kinds, 1000, 14), valids)
+    _check(cuda_device, capsys, feat, _batch(kinds, 1000, 14), valids)
 
 
 @gpu
 @pytest.mark.parametrize("N", [1000, 37])
-def test_batch_without_a_valid_part(cuda_device, N):
+def test_batch_without_a_valid_part(cuda_device, capsys, N):
     kinds = [_random, _one_row, _full_tile]
-    _check(cuda_device, 256, _batch(kinds, N, 15), torch.zeros(len(kinds)))
+    _check(cuda_device, capsys, 256, _batch(kinds, N, 15), torch.zeros(len(kinds)))
 
 
 # sizes of the workspace before the row table existed (float elements, int elements), recorded from that build
