@@ -298,6 +298,17 @@ int mpa_dgcnn_forward_graphs(const float* points, const float* valids, const flo
                              const int32_t* const* graphs, void* stream);
 int mpa_dgcnn_export_graph(const void* ws, int64_t M, int64_t N, int64_t F, int64_t stage, int32_t* idx,
                            void* stream);
+/* The selections a forward stored for its backward, for parity tests that hold the maxima fixed (read-only on the
+ * workspace, rows in the order of mpa_dgcnn_export_graph).  stage 0..3: out [M*N, CO] int32 (CO = 64, 64, 128, 256), the
+ * selected neighbour SLOT (0..19) of every point and channel of that EdgeConv stage; stage 4: out [M, F] int32, the point
+ * (0..N-1) the max-pooling of the tail took per part and channel.  Rows past the valid parts = -1. */
+int mpa_dgcnn_export_selection(const void* ws, int64_t M, int64_t N, int64_t F, int64_t stage, int32_t* out,
+                               void* stream);
+/* LeakyReLU is the encoder's third discrete choice: the slope the backward takes at every activation it differentiates.
+ * stage 0..3: out [M*N, CO] int32, 1 where the stage's stored output is positive (unit slope), 0 where the backward
+ * takes the slope 0.2; stage 4: out [M*N, F], the same for the tail's rows.  To be read BEFORE the backward (it
+ * overwrites the tail's rows).  Rows past the valid parts = -1. */
+int mpa_dgcnn_export_branch(const void* ws, int64_t M, int64_t N, int64_t F, int64_t stage, int32_t* out, void* stream);
 int mpa_dgcnn_backward(const float* grad_feat, const float* const* conv_w, const float* const* bn_w,
                        const float* fc_w, int64_t M, int64_t N, int64_t F, void* ws, float* const* grad_conv_w,
                        float* const* grad_bn_w, float* const* grad_bn_b, float* grad_fc_w, float* grad_fc_b,

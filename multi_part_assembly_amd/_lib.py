@@ -64,6 +64,8 @@ SIGNATURES: dict[str, tuple] = {
     "mpa_dgcnn_forward": (_INT, [_P] * 9 + [_INT, _F32, _F32, _I64, _I64, _I64, _P, _P, _P, _P]),
     "mpa_dgcnn_forward_graphs": (_INT, [_P] * 9 + [_INT, _F32, _F32, _I64, _I64, _I64, _P, _P, _P, _P]),
     "mpa_dgcnn_export_graph": (_INT, [_P, _I64, _I64, _I64, _I64, _P, _P]),
+    "mpa_dgcnn_export_selection": (_INT, [_P, _I64, _I64, _I64, _I64, _P, _P]),
+    "mpa_dgcnn_export_branch": (_INT, [_P, _I64, _I64, _I64, _I64, _P, _P]),
     "mpa_dgcnn_backward": (_INT, [_P] * 4 + [_I64, _I64, _I64] + [_P] * 8),
     "mpa_knn_exact_workspace": (_INT, [_I64, _I64, _P]),
     "mpa_knn_exact": (_INT, [_P, _I64, _I64, _I64, _I64, _P, _P, _P]),

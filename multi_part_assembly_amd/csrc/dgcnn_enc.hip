@@ -1669,6 +1669,73 @@ extern "C" int mpa_dgcnn_export_graph(const void* ws, int64_t M, int64_t N, int6
   return mpa::check_launch("dgcnn_export_graph");
 }
 
+namespace {
+// the forward's stored selections, widened: `valid` leading elements are read, the rest of `total` is -1
+template <typename T>
+__global__ void dg_export_selection_kernel(const T* __restrict__ src, int32_t* __restrict__ dst,
+                                           const int* __restrict__ hdr, int per_row, int per_part, long long total) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long valid = per_row != 0 ? (long long)hdr[1] * per_row : (long long)hdr[0] * per_part;
+  if (i < total) dst[i] = i < valid ? (int32_t)src[i] : -1;
+}
+}  // namespace
+
+extern "C" int mpa_dgcnn_export_selection(const void* ws, int64_t M, int64_t N, int64_t F, int64_t stage, int32_t* out,
+                                          void* stream) {
+  if (int st = dg_check(M, N, F, "dgcnn_export_selection")) return st;
+  MPA_REQUIRE(stage >= 0 && stage <= 4, "dgcnn_export_selection: stage must be 0..4");
+  if (M == 0) return MPA_OK;
+  MPA_REQUIRE(ws && out, "dgcnn_export_selection: null pointer");
+  const Ws w = dg_carve(static_cast<char*>(const_cast<void*>(ws)), M, N, F);
+  if (stage < 4) {
+    const long long total = (long long)M * N * kCO[stage];
+    launch(dg_export_selection_kernel<unsigned char>, dim3((unsigned)((total + 255) / 256)), dim3(256),
+           mpa::as_stream(stream), (const unsigned char*)w.ssel[stage], out, (const int*)w.hdr, kCO[stage], 0, total);
+  } else {
+    const long long total = (long long)M * F;
+    launch(dg_export_selection_kernel<int>, dim3((unsigned)((total + 255) / 256)), dim3(256), mpa::as_stream(stream),
+           (const int*)w.arg5, out, (const int*)w.hdr, 0, (int)F, total);
+  }
+  return mpa::check_launch("dgcnn_export_selection");
+}
+
+namespace {
+// 1 where the backward takes LeakyReLU's unit slope, 0 where it takes kSlope: the sign tests of dg_bwd_head_kernel /
+// dg_agg_bwd_sums_kernel (on the stored activation) and of dg_tail_dz (on bn(y5)), row for row
+__global__ void dg_export_branch_kernel(const float* __restrict__ src, int ld, int off, int C, const float* __restrict__ bn,
+                                        int32_t* __restrict__ dst, const int* __restrict__ hdr, long long total) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const long long r = i / C;
+  const int c = (int)(i % C);
+  if (r >= hdr[1]) {
+    dst[i] = -1;
+    return;
+  }
+  float z = src[r * ld + off + c];
+  if (bn != nullptr) z = __builtin_fmaf(z, bn[c], bn[C + c]);
+  dst[i] = z > 0.0f ? 1 : 0;
+}
+}  // namespace
+
+extern "C" int mpa_dgcnn_export_branch(const void* ws, int64_t M, int64_t N, int64_t F, int64_t stage, int32_t* out,
+                                       void* stream) {
+  if (int st = dg_check(M, N, F, "dgcnn_export_branch")) return st;
+  MPA_REQUIRE(stage >= 0 && stage <= 4, "dgcnn_export_branch: stage must be 0..4");
+  if (M == 0) return MPA_OK;
+  MPA_REQUIRE(ws && out, "dgcnn_export_branch: null pointer");
+  const Ws w = dg_carve(static_cast<char*>(const_cast<void*>(ws)), M, N, F);
+  const int C = stage < 4 ? kCO[stage] : (int)F;
+  const long long total = (long long)M * N * C;
+  if (stage < 4)
+    launch(dg_export_branch_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), mpa::as_stream(stream),
+           (const float*)w.hcat, kCat, kOff[stage], C, (const float*)nullptr, out, (const int*)w.hdr, total);
+  else
+    launch(dg_export_branch_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), mpa::as_stream(stream),
+           (const float*)w.y5, C, 0, C, (const float*)w.bn[4], out, (const int*)w.hdr, total);
+  return mpa::check_launch("dgcnn_export_branch");
+}
+
 extern "C" int mpa_dgcnn_backward(const float* grad_feat, const float* const* conv_w, const float* const* bn_w,
                                   const float* fc_w, int64_t M, int64_t N, int64_t F, void* ws,
                                   float* const* grad_conv_w, float* const* grad_bn_w, float* const* grad_bn_b,

@@ -308,6 +308,21 @@ class _DGCNNFn(torch.autograd.Function):
                                                         _lib.current_stream(dev)), "mpa_dgcnn_export_graph")
                     out.append(g)
                 hooks["exported"] = out
+            if hooks is not None and hooks.get("export_selection"):
+                out = []
+                for l, width in enumerate((64, 64, 128, 256, F_)):
+                    t = torch.empty((M * N, width) if l < 4 else (M, F_), dtype=torch.int32, device=dev)
+                    _lib.check(L.mpa_dgcnn_export_selection(_lib.ptr(ws), M, N, F_, l, _lib.ptr(t),
+                                                            _lib.current_stream(dev)), "mpa_dgcnn_export_selection")
+                    out.append(t)
+                hooks["selection"] = out
+                out = []
+                for l, width in enumerate((64, 64, 128, 256, F_)):
+                    t = torch.empty((M * N, width), dtype=torch.int32, device=dev)
+                    _lib.check(L.mpa_dgcnn_export_branch(_lib.ptr(ws), M, N, F_, l, _lib.ptr(t),
+                                                         _lib.current_stream(dev)), "mpa_dgcnn_export_branch")
+                    out.append(t)
+                hooks["branch"] = out
             for n, p in zip(knn_names, pairs):
                 _lib.KernelTimer.add_phases([n], p)
         _lib.check(st, "mpa_dgcnn_forward")
@@ -393,7 +408,10 @@ class DGCNN(nn.Module):
         if global_feat:
             self.out_fc = nn.Linear(feat_dim * 2, feat_dim)
         # parity-test hooks (None in production): {"graphs": [4 x (None | int32 [nv*N, 20])]} holds stages' kNN graphs
-        # fixed; {"export": True} leaves the graphs the forward built under "exported" ([M*N, 20] int32 per stage)
+        # fixed; {"export": True} leaves the graphs the forward built under "exported" ([M*N, 20] int32 per stage);
+        # {"export_selection": True} leaves the maxima it took under "selection" (the neighbour slot, [M*N, CO] int32 per
+        # stage, and the pooled point, [M, F]) and the LeakyReLU slopes its backward will take under "branch"
+        # ([M*N, CO] per stage and [M*N, F] for the tail, 1 = unit slope); rows past the valid parts are -1
         self.graph_hooks = None
 
     def _fused_ok(self, N):
