@@ -182,6 +182,33 @@ def current_stream(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def launch(name: str, dev, *args, timer: str | None = None) -> None:
+    """Call the entry point `name`, whose last parameter is the stream, on torch's current stream of `dev`.
+
+    A tensor goes as its device pointer, a list or tuple of tensors as the host pointer array `ptr_array` builds, and
+    everything else as it is: ctypes' own conversion through `argtypes` takes None as NULL, a bool as an int, and numbers
+    and ready-made ctypes arrays (the event handles of `KernelTimer.handles`) unchanged.  The stream is read at call
+    time, inside the device guard; `timer` names the KernelTimer bracket around the call.  Raises MpaError under `name`."""
+    fn = getattr(lib(), name)
+    conv = [a.data_ptr() if isinstance(a, torch.Tensor) else ptr_array(a) if isinstance(a, (list, tuple)) else a
+            for a in args]  # `args` and `conv` keep tensors and pointer arrays alive until the call has returned
+    with torch.cuda.device(dev):
+        tok = KernelTimer.start(timer) if timer is not None else None
+        st = fn(*conv, torch.cuda.current_stream(dev).cuda_stream)
+        KernelTimer.stop(tok)
+    if st != 0:
+        check(st, name)
+
+
+def query(name: str, *sizes, slot=ctypes.c_int64):
+    """Call the pure host query `name` (workspace sizes and their like): `sizes` in, every remaining parameter an out-slot
+    of type `slot` (the `*_resident` queries write an int).  Returns the value, or a tuple where there are several."""
+    fn = getattr(lib(), name)
+    outs = [slot() for _ in range(len(fn.argtypes) - len(sizes))]
+    check(fn(*sizes, *[ctypes.byref(o) for o in outs]), name)
+    return outs[0].value if len(outs) == 1 else tuple(o.value for o in outs)
+
+
 class KernelTimer:
     """Optional per-launch HIP-event timing of named kernels, on the stream they are launched on.
 

@@ -39,13 +39,10 @@ def _workspace(B: int, n1: int, n2: int, dev, variant: int = -1) -> tuple[torch.
     """Scratch for the grid-pruned search, sized by the library (the library itself never allocates) for the search the
     call will actually take — nothing for the sizes the exhaustive scan answers; torch's caching allocator makes the
     per-call request free after the first."""
-    import ctypes
-    nbytes = ctypes.c_int64(0)
-    _lib.check(_lib.lib().mpa_chamfer_workspace_variant(B, n1, n2, int(variant), ctypes.byref(nbytes)),
-               "mpa_chamfer_workspace_variant")
-    if nbytes.value == 0:
+    nbytes = _lib.query("mpa_chamfer_workspace_variant", B, n1, n2, int(variant))
+    if nbytes == 0:
         return None, 0
-    return torch.empty(nbytes.value, dtype=torch.uint8, device=dev), nbytes.value
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
 
 
 def chamfer_forward(xyz1: torch.Tensor, xyz2: torch.Tensor, variant: int | None = None):
@@ -70,24 +67,16 @@ def chamfer_forward(xyz1: torch.Tensor, xyz2: torch.Tensor, variant: int | None 
     dist2 = torch.empty((B, n2), dtype=xyz1.dtype, device=dev)
     idx1 = torch.empty((B, n1), dtype=torch.int64, device=dev)
     idx2 = torch.empty((B, n2), dtype=torch.int64, device=dev)
-    L = _lib.lib()
-    with torch.cuda.device(dev):
-        s = _lib.current_stream(dev)
-        args = (_lib.ptr(xyz1), _lib.ptr(xyz2), B, n1, n2, _lib.ptr(dist1), _lib.ptr(idx1),
-                _lib.ptr(dist2), _lib.ptr(idx2))
-        if xyz1.dtype == torch.float64:
-            tok = _lib.KernelTimer.start(f"chamfer_forward[{B}x{n1}x{n2}]")
-            st = L.mpa_chamfer_forward_f64(*args, s)
-        else:
-            ws, nbytes = _workspace(B, n1, n2, dev, -1 if variant is None else variant) if variant in (None, 3, -1) else (None, 0)
-            tok = _lib.KernelTimer.start(f"chamfer_forward[{B}x{n1}x{n2}]")
-            if variant is None:
-                st = L.mpa_chamfer_forward(*args, _lib.ptr(ws) if ws is not None else None, nbytes, s)
-            else:
-                st = L.mpa_chamfer_forward_variant(*args, int(variant), _lib.ptr(ws) if ws is not None else None,
-                                                   nbytes, s)
-        _lib.KernelTimer.stop(tok)
-    _lib.check(st, "mpa_chamfer_forward")
+    args = (xyz1, xyz2, B, n1, n2, dist1, idx1, dist2, idx2)
+    timer = f"chamfer_forward[{B}x{n1}x{n2}]"
+    if xyz1.dtype == torch.float64:
+        _lib.launch("mpa_chamfer_forward_f64", dev, *args, timer=timer)
+        return [dist1, idx1, dist2, idx2]
+    ws, nbytes = _workspace(B, n1, n2, dev, -1 if variant is None else variant) if variant in (None, 3, -1) else (None, 0)
+    if variant is None:
+        _lib.launch("mpa_chamfer_forward", dev, *args, ws, nbytes, timer=timer)
+    else:
+        _lib.launch("mpa_chamfer_forward_variant", dev, *args, int(variant), ws, nbytes, timer=timer)
     return [dist1, idx1, dist2, idx2]
 
 
@@ -111,13 +100,8 @@ def chamfer_backward(grad_dist1, grad_dist2, xyz1, xyz2, idx1, idx2):
     dev = xyz1.device
     grad_xyz1 = torch.empty((B, n1, 3), dtype=xyz1.dtype, device=dev)
     grad_xyz2 = torch.empty((B, n2, 3), dtype=xyz1.dtype, device=dev)
-    L = _lib.lib()
-    fn = L.mpa_chamfer_backward_f64 if xyz1.dtype == torch.float64 else L.mpa_chamfer_backward
-    with torch.cuda.device(dev):
-        st = fn(_lib.ptr(grad_dist1), _lib.ptr(grad_dist2), _lib.ptr(xyz1), _lib.ptr(xyz2),
-                _lib.ptr(idx1), _lib.ptr(idx2), B, n1, n2, _lib.ptr(grad_xyz1),
-                _lib.ptr(grad_xyz2), _lib.current_stream(dev))
-    _lib.check(st, "mpa_chamfer_backward")
+    _lib.launch("mpa_chamfer_backward_f64" if xyz1.dtype == torch.float64 else "mpa_chamfer_backward", dev,
+                grad_dist1, grad_dist2, xyz1, xyz2, idx1, idx2, B, n1, n2, grad_xyz1, grad_xyz2)
     return [grad_xyz1, grad_xyz2]
 
 

@@ -222,10 +222,7 @@ class GeometryBatchProducer:
             d_raw, d_rot, d_perm, d_val = (_to_device(a, dev) for a in (raw, rot, perm, valids))
             part_pcs = torch.empty((B, P, N, 3), dtype=torch.float32, device=dev)
             part_trans = torch.empty((B, P, 3), dtype=torch.float32, device=dev)
-            st = _lib.lib().mpa_part_batch_transform(_lib.ptr(d_raw), _lib.ptr(d_rot), _lib.ptr(d_perm),
-                                                     _lib.ptr(d_val), B * P, N, _lib.ptr(part_pcs),
-                                                     _lib.ptr(part_trans), _lib.current_stream(dev))
-        _lib.check(st, "mpa_part_batch_transform")
+            _lib.launch("mpa_part_batch_transform", dev, d_raw, d_rot, d_perm, d_val, B * P, N, part_pcs, part_trans)
         out = {
             "part_pcs": part_pcs,
             "part_quat": _to_device(quat, dev),
@@ -456,16 +453,11 @@ class DeviceGeometryProducer:
             if replay:
                 d_uni, d_rot, d_perm = (_to_device(a, dev) for a in (uniforms, rot, perm))
                 part_quat = _to_device(quat, dev)
-                args = (_lib.ptr(d_uni), _lib.ptr(d_rot), _lib.ptr(d_perm), 0, None, 0.0, _lib.ptr(part_pcs),
-                        _lib.ptr(part_trans), None)
+                args = (d_uni, d_rot, d_perm, 0, None, 0.0, part_pcs, part_trans, None)
             else:
                 part_quat = torch.empty((B, P, 4), dtype=torch.float32, device=dev)
-                args = (None, None, None, self.seed, _lib.ptr(d64[1]), self.rot_range, _lib.ptr(part_pcs),
-                        _lib.ptr(part_trans), _lib.ptr(part_quat))
-            st = _lib.lib().mpa_mesh_sample_batch(_lib.ptr(tri), _lib.ptr(cum), _lib.ptr(pf), self.store.num_parts,
-                                                  _lib.ptr(d64[0]), M, N, *args, _lib.ptr(raw),
-                                                  _lib.current_stream(dev))
-        _lib.check(st, "mpa_mesh_sample_batch")
+                args = (None, None, None, self.seed, d64[1], self.rot_range, part_pcs, part_trans, part_quat)
+            _lib.launch("mpa_mesh_sample_batch", dev, tri, cum, pf, self.store.num_parts, d64[0], M, N, *args, raw)
         d_val = d32[0]
         out = {
             "part_pcs": part_pcs,
@@ -923,7 +915,7 @@ class DevicePartNetProducer:
             elif counter is not None:
                 counter_val = int(counter) & 0xFFFFFFFFFFFFFFFF
             random_order = 1 if (self.shuffle_parts and perm is None) else 0
-            result, ptrs = {}, {}
+            result, slots = {}, {}  # slots: what the kernel writes (None: an empty entry, passed as NULL)
             for key, (shape, dtype) in self._spec(B).items():
                 t = None if out is None else out.get(key)
                 if t is not None and t.device.type != "cuda":
@@ -934,17 +926,15 @@ class DevicePartNetProducer:
                     raise ValueError(f"DevicePartNetProducer: out[{key!r}] must be a contiguous {dtype} tensor of shape "
                                      f"{shape} on {d_idx.device}")
                 result[key] = t
-                ptrs[key] = _lib.ptr(t) if t.numel() else None
+                slots[key] = t if t.numel() else None
             order = torch.empty((B, P), dtype=torch.int32, device=dev) if return_order else None
-            st = _lib.lib().mpa_partnet_gather_batch(
-                *(_lib.ptr(arrays[n]) for n in PartNetStore.ARRAYS), _lib.ptr(arrays["contacts"]),
-                _lib.ptr(arrays["contact_off"]), S, _lib.ptr(d_idx), B, P, N, result["part_label"].shape[2],
-                _lib.ptr(d_perm), random_order, self.seed, counter_val, _lib.ptr(counter_dev),
-                ptrs["part_pcs"], ptrs["part_trans"], ptrs["part_quat"], ptrs["part_valids"], ptrs.get("part_ids"),
-                ptrs["instance_label"], ptrs.get("match_ids"), ptrs["part_label"], ptrs.get("contact_points"),
-                ptrs.get("sym"), ptrs.get("valid_matrix"), ptrs["shape_id"], _lib.ptr(order), _lib.ptr(self._status),
-                _lib.current_stream(dev))
-        _lib.check(st, "mpa_partnet_gather_batch")
+            _lib.launch(
+                "mpa_partnet_gather_batch", dev, *(arrays[n] for n in PartNetStore.ARRAYS), arrays["contacts"],
+                arrays["contact_off"], S, d_idx, B, P, N, result["part_label"].shape[2], d_perm, random_order, self.seed,
+                counter_val, counter_dev, slots["part_pcs"], slots["part_trans"], slots["part_quat"],
+                slots["part_valids"], slots.get("part_ids"), slots["instance_label"], slots.get("match_ids"),
+                slots["part_label"], slots.get("contact_points"), slots.get("sym"), slots.get("valid_matrix"),
+                slots["shape_id"], order, self._status)
         if out is not None and host_idx is not None:  # the host-side entries of a host-built batch, filled in place
             for key, val in (("data_id", data_id), ("shape_id", self.store.shape_ids[host_idx])):
                 t = out.get(key)

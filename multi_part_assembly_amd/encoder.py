@@ -28,134 +28,67 @@ def _deliver(params, returned, skip):
 
 
 class _PointNetFn(torch.autograd.Function):
-    """PointNet forward/backward on the HIP library (csrc/pointnet.hip)."""
+    """PointNet forward/backward on the HIP library (csrc/pointnet.hip).  The bf16 performance variant
+    (csrc/pointnet_bf16.hip, `_PointNetBF16Fn`) differs in the entry points' suffix and in its workspace only."""
+
+    SUFFIX, LABEL = "", "PointNet"
 
     @staticmethod
-    def forward(ctx, points, valids, training, momentum, eps, running, *params):
+    def _workspace(M, N, F_, dev):
+        nf, ni = _lib.query("mpa_pointnet_workspace", M, N, F_)
+        return (torch.empty(nf, dtype=torch.float32, device=dev), torch.empty(ni, dtype=torch.int32, device=dev))
+
+    @classmethod
+    def forward(cls, ctx, points, valids, training, momentum, eps, running, *params):
         conv_w, bn_w, bn_b = params[0:5], params[5:10], params[10:15]
         run_mean, run_var = running
         M, N, _ = points.shape
         F_ = conv_w[4].shape[0]
         dev = points.device
-        L = _lib.lib()
-        nf, ni = ctypes.c_int64(), ctypes.c_int64()
-        _lib.check(L.mpa_pointnet_workspace(M, N, F_, ctypes.byref(nf), ctypes.byref(ni)),
-                   "mpa_pointnet_workspace")
-        fws = torch.empty(nf.value, dtype=torch.float32, device=dev)
-        iws = torch.empty(ni.value, dtype=torch.int32, device=dev)
+        ws = cls._workspace(M, N, F_, dev)
         feat = torch.empty((M, F_), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"pointnet_forward[{M}x{N}x{F_}]")
-            st = L.mpa_pointnet_forward(
-                _lib.ptr(points), _lib.ptr(valids), _lib.ptr_array(conv_w), _lib.ptr_array(bn_w),
-                _lib.ptr_array(bn_b), _lib.ptr_array(run_mean), _lib.ptr_array(run_var), int(training),
-                float(momentum), float(eps), M, N, F_, _lib.ptr(fws), _lib.ptr(iws), _lib.ptr(feat),
-                _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_pointnet_forward")
+        _lib.launch("mpa_pointnet_forward" + cls.SUFFIX, dev, points, valids, conv_w, bn_w, bn_b, run_mean, run_var,
+                    training, float(momentum), float(eps), M, N, F_, *ws, feat,
+                    timer=f"pointnet_forward{cls.SUFFIX}[{M}x{N}x{F_}]")
         ctx.training = bool(training)
         ctx.params = params
         GradSink.note_use(params)
-        ctx.save_for_backward(points, valids, fws, iws)
+        ctx.save_for_backward(points, valids, *ws)
         return feat
 
-    @staticmethod
-    def backward(ctx, grad_feat):
+    @classmethod
+    def backward(cls, ctx, grad_feat):
         if not ctx.training:
-            raise RuntimeError("PointNet: backward is implemented for training-mode BatchNorm only")
+            raise RuntimeError(f"{cls.LABEL}: backward is implemented for training-mode BatchNorm only")
         if DeferredBackward.active is not None:  # graph-mode data parallelism: run later, behind the first all-reduce
             saved = ctx.saved_tensors  # (autograd releases them when its own pass is over)
-            DeferredBackward.park(lambda g: _deliver(ctx.params, _PointNetFn._run_backward(ctx, g, saved), 6), grad_feat, ctx.params)
+            DeferredBackward.park(lambda g: _deliver(ctx.params, cls._run_backward(ctx, g, saved), 6), grad_feat, ctx.params)
             return (None,) * (6 + len(ctx.params))
-        return _PointNetFn._run_backward(ctx, grad_feat, ctx.saved_tensors)
+        return cls._run_backward(ctx, grad_feat, ctx.saved_tensors)
 
-    @staticmethod
-    def _run_backward(ctx, grad_feat, saved):
-        points, valids, fws, iws = saved
+    @classmethod
+    def _run_backward(cls, ctx, grad_feat, saved):
+        points, valids, *ws = saved
         params = ctx.params
         conv_w, bn_w = params[0:5], params[5:10]
         M, N, _ = points.shape
         F_ = conv_w[4].shape[0]
-        dev = points.device
         grads, direct = GradSink.outputs(params)
         g_conv, g_bnw, g_bnb = grads[0:5], grads[5:10], grads[10:15]
-        grad_feat = grad_feat.contiguous()
-        with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"pointnet_backward[{M}x{N}x{F_}]")
-            st = _lib.lib().mpa_pointnet_backward(
-                _lib.ptr(grad_feat), _lib.ptr(points), _lib.ptr(valids), _lib.ptr_array(conv_w),
-                _lib.ptr_array(bn_w), M, N, F_, _lib.ptr(fws), _lib.ptr(iws), _lib.ptr_array(g_conv),
-                _lib.ptr_array(g_bnw), _lib.ptr_array(g_bnb), _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_pointnet_backward")
+        _lib.launch("mpa_pointnet_backward" + cls.SUFFIX, points.device, grad_feat.contiguous(), points, valids, conv_w,
+                    bn_w, M, N, F_, *ws, g_conv, g_bnw, g_bnb, timer=f"pointnet_backward{cls.SUFFIX}[{M}x{N}x{F_}]")
         if direct:
             GradSink.delivered(params)
             return (None,) * (6 + len(params))
         return (None, None, None, None, None, None, *grads)
 
 
-class _PointNetBF16Fn(torch.autograd.Function):
-    """The bf16 performance variant of the PointNet encoder (csrc/pointnet_bf16.hip): same interface as _PointNetFn."""
+class _PointNetBF16Fn(_PointNetFn):
+    SUFFIX, LABEL = "_bf16", "PointNet (bf16)"
 
     @staticmethod
-    def forward(ctx, points, valids, training, momentum, eps, running, *params):
-        conv_w, bn_w, bn_b = params[0:5], params[5:10], params[10:15]
-        run_mean, run_var = running
-        M, N, _ = points.shape
-        F_ = conv_w[4].shape[0]
-        dev = points.device
-        L = _lib.lib()
-        nb = ctypes.c_int64()
-        _lib.check(L.mpa_pointnet_workspace_bf16(M, N, F_, ctypes.byref(nb)), "mpa_pointnet_workspace_bf16")
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
-        feat = torch.empty((M, F_), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"pointnet_forward_bf16[{M}x{N}x{F_}]")
-            st = L.mpa_pointnet_forward_bf16(
-                _lib.ptr(points), _lib.ptr(valids), _lib.ptr_array(conv_w), _lib.ptr_array(bn_w),
-                _lib.ptr_array(bn_b), _lib.ptr_array(run_mean), _lib.ptr_array(run_var), int(training),
-                float(momentum), float(eps), M, N, F_, _lib.ptr(ws), _lib.ptr(feat), _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_pointnet_forward_bf16")
-        ctx.training = bool(training)
-        ctx.params = params
-        GradSink.note_use(params)
-        ctx.save_for_backward(points, valids, ws)
-        return feat
-
-    @staticmethod
-    def backward(ctx, grad_feat):
-        if not ctx.training:
-            raise RuntimeError("PointNet (bf16): backward is implemented for training-mode BatchNorm only")
-        if DeferredBackward.active is not None:
-            saved = ctx.saved_tensors
-            DeferredBackward.park(lambda g: _deliver(ctx.params, _PointNetBF16Fn._run_backward(ctx, g, saved), 6), grad_feat, ctx.params)
-            return (None,) * (6 + len(ctx.params))
-        return _PointNetBF16Fn._run_backward(ctx, grad_feat, ctx.saved_tensors)
-
-    @staticmethod
-    def _run_backward(ctx, grad_feat, saved):
-        points, valids, ws = saved
-        params = ctx.params
-        conv_w, bn_w = params[0:5], params[5:10]
-        M, N, _ = points.shape
-        F_ = conv_w[4].shape[0]
-        dev = points.device
-        grads, direct = GradSink.outputs(params)
-        g_conv, g_bnw, g_bnb = grads[0:5], grads[5:10], grads[10:15]
-        grad_feat = grad_feat.contiguous()
-        with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"pointnet_backward_bf16[{M}x{N}x{F_}]")
-            st = _lib.lib().mpa_pointnet_backward_bf16(
-                _lib.ptr(grad_feat), _lib.ptr(points), _lib.ptr(valids), _lib.ptr_array(conv_w),
-                _lib.ptr_array(bn_w), M, N, F_, _lib.ptr(ws), _lib.ptr_array(g_conv), _lib.ptr_array(g_bnw),
-                _lib.ptr_array(g_bnb), _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_pointnet_backward_bf16")
-        if direct:
-            GradSink.delivered(params)
-            return (None,) * (6 + len(params))
-        return (None, None, None, None, None, None, *grads)
+    def _workspace(M, N, F_, dev):
+        return (torch.empty(_lib.query("mpa_pointnet_workspace_bf16", M, N, F_), dtype=torch.uint8, device=dev),)
 
 
 # ---- configurations outside the HIP kernels' instantiation ------------------------------------------------------------------
@@ -251,12 +184,8 @@ def knn_exact(x, n, N, C=None):
     R, ld = x.shape
     C = (3 if ld == 4 else ld) if C is None else C
     idx = torch.empty((R, 20), dtype=torch.int32, device=x.device)
-    nbytes = ctypes.c_int64()
-    _lib.check(_lib.lib().mpa_knn_exact_workspace(n, N, ctypes.byref(nbytes)), "mpa_knn_exact_workspace")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=x.device)
-    with torch.cuda.device(x.device):
-        st = _lib.lib().mpa_knn_exact(_lib.ptr(x), ld, n, N, C, _lib.ptr(ws), _lib.ptr(idx), _lib.current_stream(x.device))
-    _lib.check(st, "mpa_knn_exact")
+    ws = torch.empty(_lib.query("mpa_knn_exact_workspace", n, N), dtype=torch.uint8, device=x.device)
+    _lib.launch("mpa_knn_exact", x.device, x, ld, n, N, C, ws, idx)
     return idx
 
 
@@ -270,14 +199,10 @@ class _DGCNNFn(torch.autograd.Function):
         M, N, _ = points.shape
         F_ = fc_w.shape[0]
         dev = points.device
-        L = _lib.lib()
-        nbytes = ctypes.c_int64()
-        _lib.check(L.mpa_dgcnn_workspace(M, N, F_, ctypes.byref(nbytes)), "mpa_dgcnn_workspace")
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        ws = torch.empty(_lib.query("mpa_dgcnn_workspace", M, N, F_), dtype=torch.uint8, device=dev)
         feat = torch.empty((M, F_), dtype=torch.float32, device=dev)
         pts = points.detach()
         with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"dgcnn_forward[{M}x{N}x{F_}]")
             # library-recorded events [2l] / [2l + 1] right around the kNN kernels of stage l
             knn_names = [f"dgcnn_knn[{M}x{N} stage {l + 1} C={C}]" for l, C in enumerate((3, 64, 64, 128))]
             pairs = [_lib.KernelTimer.phase_events([n]) for n in knn_names]
@@ -287,45 +212,35 @@ class _DGCNNFn(torch.autograd.Function):
             graphs = hooks.get("graphs") if hooks else None
             if graphs is not None:  # parity tests: hold some stages' kNN graphs fixed (mpa_dgcnn_forward_graphs)
                 graphs = [None if g is None else g.to(device=dev, dtype=torch.int32).contiguous() for g in graphs]
+                # a hole (None) is a stage whose graph the forward builds itself, so the array is made here
                 gp = (ctypes.c_void_p * 4)(*[None if g is None else g.data_ptr() for g in graphs])
-                st = L.mpa_dgcnn_forward_graphs(
-                    _lib.ptr(pts), _lib.ptr(valids), _lib.ptr_array(conv_w), _lib.ptr_array(bn_w),
-                    _lib.ptr_array(bn_b), _lib.ptr_array(run_mean), _lib.ptr_array(run_var), _lib.ptr(fc_w),
-                    _lib.ptr(fc_b), int(training), float(momentum), float(eps), M, N, F_, _lib.ptr(ws), _lib.ptr(feat),
-                    gp, _lib.current_stream(dev))
+                name, last = "mpa_dgcnn_forward_graphs", gp
             else:
-                st = L.mpa_dgcnn_forward(
-                    _lib.ptr(pts), _lib.ptr(valids), _lib.ptr_array(conv_w), _lib.ptr_array(bn_w),
-                    _lib.ptr_array(bn_b), _lib.ptr_array(run_mean), _lib.ptr_array(run_var), _lib.ptr(fc_w),
-                    _lib.ptr(fc_b), int(training), float(momentum), float(eps), M, N, F_, _lib.ptr(ws), _lib.ptr(feat),
-                    _lib.KernelTimer.handles(flat), _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
+                name, last = "mpa_dgcnn_forward", _lib.KernelTimer.handles(flat)
+            _lib.launch(name, dev, pts, valids, conv_w, bn_w, bn_b, run_mean, run_var, fc_w, fc_b, training,
+                        float(momentum), float(eps), M, N, F_, ws, feat, last, timer=f"dgcnn_forward[{M}x{N}x{F_}]")
             if hooks is not None and hooks.get("export"):
                 out = []
                 for l in range(4):
                     g = torch.empty((M * N, 20), dtype=torch.int32, device=dev)
-                    _lib.check(L.mpa_dgcnn_export_graph(_lib.ptr(ws), M, N, F_, l, _lib.ptr(g),
-                                                        _lib.current_stream(dev)), "mpa_dgcnn_export_graph")
+                    _lib.launch("mpa_dgcnn_export_graph", dev, ws, M, N, F_, l, g)
                     out.append(g)
                 hooks["exported"] = out
             if hooks is not None and hooks.get("export_selection"):
                 out = []
                 for l, width in enumerate((64, 64, 128, 256, F_)):
                     t = torch.empty((M * N, width) if l < 4 else (M, F_), dtype=torch.int32, device=dev)
-                    _lib.check(L.mpa_dgcnn_export_selection(_lib.ptr(ws), M, N, F_, l, _lib.ptr(t),
-                                                            _lib.current_stream(dev)), "mpa_dgcnn_export_selection")
+                    _lib.launch("mpa_dgcnn_export_selection", dev, ws, M, N, F_, l, t)
                     out.append(t)
                 hooks["selection"] = out
                 out = []
                 for l, width in enumerate((64, 64, 128, 256, F_)):
                     t = torch.empty((M * N, width), dtype=torch.int32, device=dev)
-                    _lib.check(L.mpa_dgcnn_export_branch(_lib.ptr(ws), M, N, F_, l, _lib.ptr(t),
-                                                         _lib.current_stream(dev)), "mpa_dgcnn_export_branch")
+                    _lib.launch("mpa_dgcnn_export_branch", dev, ws, M, N, F_, l, t)
                     out.append(t)
                 hooks["branch"] = out
             for n, p in zip(knn_names, pairs):
                 _lib.KernelTimer.add_phases([n], p)
-        _lib.check(st, "mpa_dgcnn_forward")
         ctx.training = bool(training)
         ctx.want_point_grad = bool(want_point_grad)
         ctx.params = params
@@ -360,15 +275,8 @@ class _DGCNNFn(torch.autograd.Function):
         # is overwritten in full) instead of 17 AccumulateGrad `add_` launches
         grads, direct = GradSink.outputs(params)
         gpts = torch.empty_like(pts) if ctx.want_point_grad else None
-        grad_feat = grad_feat.contiguous()
-        with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"dgcnn_backward[{M}x{N}x{F_}]")
-            st = _lib.lib().mpa_dgcnn_backward(
-                _lib.ptr(grad_feat), _lib.ptr_array(conv_w), _lib.ptr_array(bn_w), _lib.ptr(fc_w), M, N, F_,
-                _lib.ptr(ws), _lib.ptr_array(grads[0:5]), _lib.ptr_array(grads[5:10]), _lib.ptr_array(grads[10:15]),
-                _lib.ptr(grads[15]), _lib.ptr(grads[16]), _lib.ptr(gpts), _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_dgcnn_backward")
+        _lib.launch("mpa_dgcnn_backward", dev, grad_feat.contiguous(), conv_w, bn_w, fc_w, M, N, F_, ws, grads[0:5],
+                    grads[5:10], grads[10:15], grads[15], grads[16], gpts, timer=f"dgcnn_backward[{M}x{N}x{F_}]")
         if direct:
             GradSink.delivered(params)
             return (gpts,) + (None,) * (7 + len(params))

@@ -6,7 +6,6 @@ outputs.  Part accuracy runs the per-part Chamfer search on the HIP operator; th
 (eval_utils.py:84-96); the pair order — (b, i, j) ascending — is the same, and the result does not depend on it."""
 from __future__ import annotations
 
-import ctypes
 import math
 import warnings
 
@@ -119,10 +118,7 @@ def _connectivity_fused(trans, rot, rot_type, contact_points):
     out = torch.empty(B, dtype=torch.float32, device=dev)
     contact = contact_points.to(torch.float32).contiguous()
     trans, rot = trans.contiguous(), rot.to(torch.float32).contiguous()
-    with torch.cuda.device(dev):
-        st = _lib.lib().mpa_connectivity_acc(_lib.ptr(contact), _lib.ptr(trans), _lib.ptr(rot), int(rot_type == "rmat"),
-                                             B, P, _lib.ptr(out), _lib.current_stream(dev))
-    _lib.check(st, "mpa_connectivity_acc")
+    _lib.launch("mpa_connectivity_acc", dev, contact, trans, rot, int(rot_type == "rmat"), B, P, out)
     return out
 
 
@@ -163,18 +159,10 @@ def assembly_metrics(pts, pred_trans, gt_trans, pred_rot, gt_rot, valids, ret_pe
     dev, f32 = pts.device, torch.float32
     rmat = pred_rot.rot_type == "rmat"
     args = [t.detach().to(f32).contiguous() for t in (pts, pred_trans, gt_trans, pred_rot.rot, gt_rot.rot, valids)]
-    L = _lib.lib()
-    nbytes = ctypes.c_int64()
-    _lib.check(L.mpa_assembly_metrics_workspace(B, P, ctypes.byref(nbytes)), "mpa_assembly_metrics_workspace")
-    ws = torch.empty(max(1, nbytes.value // 8), dtype=torch.float64, device=dev)
+    ws = torch.empty(max(1, _lib.query("mpa_assembly_metrics_workspace", B, P) // 8), dtype=torch.float64, device=dev)
     out = torch.empty((len(METRIC_KEYS), B), dtype=f32, device=dev)
     per_part = torch.empty((B, P), dtype=f32, device=dev) if ret_per_part else None
-    fn = L.mpa_assembly_metrics_rmat if rmat else L.mpa_assembly_metrics
-    with torch.cuda.device(dev):
-        tok = _lib.KernelTimer.start(f"assembly_metrics[{B}x{P}x{N}]")
-        st = fn(*[_lib.ptr(a) for a in args], B, P, N, _lib.ptr(ws), _lib.ptr(out), _lib.ptr(per_part),
-                _lib.current_stream(dev))
-        _lib.KernelTimer.stop(tok)
-    _lib.check(st, "mpa_assembly_metrics")
+    _lib.launch("mpa_assembly_metrics_rmat" if rmat else "mpa_assembly_metrics", dev, *args, B, P, N, ws, out, per_part,
+                timer=f"assembly_metrics[{B}x{P}x{N}]")
     res = {k: out[i] for i, k in enumerate(METRIC_KEYS)}
     return (res, per_part) if ret_per_part else res

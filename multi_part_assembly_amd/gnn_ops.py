@@ -5,8 +5,6 @@ parts (reference models/dgl/modules.py:61-86, models/dgl/network.py:75-152).  Th
 holding the parameters (same state_dict keys); this only replaces what they compute."""
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _lib
@@ -23,12 +21,8 @@ class _NarrowLinearReLU(torch.autograd.Function):
         R, K = x.shape
         N = weight.shape[0]
         out = torch.empty((R, N), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            tok = _lib.KernelTimer.start(f"narrow_linear_relu_forward[{R}x{K}x{N}]")
-            st = _lib.lib().mpa_narrow_linear_relu_forward(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), R, K, N,
-                                                           _lib.ptr(out), _lib.current_stream(x.device))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_narrow_linear_relu_forward")
+        _lib.launch("mpa_narrow_linear_relu_forward", x.device, x, weight, bias, R, K, N, out,
+                    timer=f"narrow_linear_relu_forward[{R}x{K}x{N}]")
         ctx.params = [p for p in (weight, bias) if p is not None]
         ctx.has_bias = bias is not None
         GradSink.note_use(ctx.params)
@@ -45,16 +39,9 @@ class _NarrowLinearReLU(torch.autograd.Function):
         gw = bufs[0]
         gb = bufs[1] if ctx.has_bias else None
         grad_out = grad_out.contiguous()
-        n = ctypes.c_int64()
-        _lib.check(_lib.lib().mpa_narrow_linear_relu_workspace(R, K, N, ctypes.byref(n)), "mpa_narrow_linear_relu_workspace")
-        ws = torch.empty(n.value, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            tok = _lib.KernelTimer.start(f"narrow_linear_relu_backward[{R}x{K}x{N}]")
-            st = _lib.lib().mpa_narrow_linear_relu_backward(
-                _lib.ptr(grad_out), _lib.ptr(out), _lib.ptr(x), _lib.ptr(weight), R, K, N, _lib.ptr(ws), _lib.ptr(gx),
-                _lib.ptr(gw), _lib.ptr(gb), _lib.current_stream(x.device))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_narrow_linear_relu_backward")
+        ws = torch.empty(_lib.query("mpa_narrow_linear_relu_workspace", R, K, N), dtype=torch.float32, device=x.device)
+        _lib.launch("mpa_narrow_linear_relu_backward", x.device, grad_out, out, x, weight, R, K, N, ws, gx, gw, gb,
+                    timer=f"narrow_linear_relu_backward[{R}x{K}x{N}]")
         if direct:
             GradSink.delivered(ctx.params)
             return gx, None, None
@@ -78,17 +65,11 @@ class _RelationHead(torch.autograd.Function):
     def forward(ctx, h, weight, bias, mask):
         R, K = h.shape
         dev = h.device
-        n = ctypes.c_int64()
-        _lib.check(_lib.lib().mpa_relation_head_workspace(R, K, ctypes.byref(n)), "mpa_relation_head_workspace")
-        ws = torch.empty(n.value, dtype=torch.float32, device=dev)
+        ws = torch.empty(_lib.query("mpa_relation_head_workspace", R, K), dtype=torch.float32, device=dev)
         out = torch.empty(R, dtype=torch.float32, device=dev)
         w = weight.reshape(-1)  # the Linear weight [1, K]: the same bytes
-        with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"relation_head_forward[{R}x{K}]")
-            st = _lib.lib().mpa_relation_head_forward(_lib.ptr(h), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(mask), R, K,
-                                                      _lib.ptr(ws), _lib.ptr(out), _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_relation_head_forward")
+        _lib.launch("mpa_relation_head_forward", dev, h, w, bias, mask, R, K, ws, out,
+                    timer=f"relation_head_forward[{R}x{K}]")
         ctx.params = [p for p in (weight, bias) if p is not None]
         ctx.has_bias = bias is not None
         GradSink.note_use(ctx.params)
@@ -105,13 +86,8 @@ class _RelationHead(torch.autograd.Function):
         gw = bufs[0]
         gb = bufs[1] if ctx.has_bias else None
         grad_out = grad_out.contiguous()
-        with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"relation_head_backward[{R}x{K}]")
-            st = _lib.lib().mpa_relation_head_backward(
-                _lib.ptr(grad_out), _lib.ptr(h), _lib.ptr(w), _lib.ptr(mask), R, K, _lib.ptr(ws), _lib.ptr(gh),
-                _lib.ptr(gw), _lib.ptr(gb), _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_relation_head_backward")
+        _lib.launch("mpa_relation_head_backward", dev, grad_out, h, w, mask, R, K, ws, gh, gw, gb,
+                    timer=f"relation_head_backward[{R}x{K}]")
         if direct:
             GradSink.delivered(ctx.params)
             return gh, None, None, None
@@ -136,12 +112,8 @@ class _RelationMean(torch.autograd.Function):
     def forward(ctx, edge, rel):
         G, P, C = edge.shape
         out = torch.empty((G, C), dtype=torch.float32, device=edge.device)
-        with torch.cuda.device(edge.device):
-            tok = _lib.KernelTimer.start(f"relation_mean_forward[{G}x{P}x{C}]")
-            st = _lib.lib().mpa_relation_mean_forward(_lib.ptr(edge), _lib.ptr(rel), G, P, C, _lib.ptr(out),
-                                                      _lib.current_stream(edge.device))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_relation_mean_forward")
+        _lib.launch("mpa_relation_mean_forward", edge.device, edge, rel, G, P, C, out,
+                    timer=f"relation_mean_forward[{G}x{P}x{C}]")
         ctx.save_for_backward(edge, rel, out)
         return out
 
@@ -152,13 +124,8 @@ class _RelationMean(torch.autograd.Function):
         ge = torch.empty_like(edge) if ctx.needs_input_grad[0] else None
         gr = torch.empty_like(rel) if ctx.needs_input_grad[1] else None
         grad_out = grad_out.contiguous()
-        with torch.cuda.device(edge.device):
-            tok = _lib.KernelTimer.start(f"relation_mean_backward[{G}x{P}x{C}]")
-            st = _lib.lib().mpa_relation_mean_backward(_lib.ptr(grad_out), _lib.ptr(edge), _lib.ptr(rel), _lib.ptr(out), G,
-                                                       P, C, _lib.ptr(ge), _lib.ptr(gr),
-                                                       _lib.current_stream(edge.device))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_relation_mean_backward")
+        _lib.launch("mpa_relation_mean_backward", edge.device, grad_out, edge, rel, out, G, P, C, ge, gr,
+                    timer=f"relation_mean_backward[{G}x{P}x{C}]")
         return ge, gr
 
 
@@ -179,12 +146,8 @@ class _PairRows(torch.autograd.Function):
     def forward(ctx, a, b, swap):
         S, P, F = a.shape
         out = torch.empty((S, P, P, 2 * F), dtype=torch.float32, device=a.device)
-        with torch.cuda.device(a.device):
-            tok = _lib.KernelTimer.start(f"pair_rows_forward[{S}x{P}x{F}]")
-            st = _lib.lib().mpa_pair_rows_forward(_lib.ptr(a), _lib.ptr(b), S, P, F, int(swap), _lib.ptr(out),
-                                                  _lib.current_stream(a.device))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_pair_rows_forward")
+        _lib.launch("mpa_pair_rows_forward", a.device, a, b, S, P, F, int(swap), out,
+                    timer=f"pair_rows_forward[{S}x{P}x{F}]")
         ctx.dims = (S, P, F, int(swap))
         return out
 
@@ -195,12 +158,8 @@ class _PairRows(torch.autograd.Function):
         ga = torch.empty((S, P, F), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
         gb = torch.empty((S, P, F), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
         grad_out = grad_out.contiguous()
-        with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"pair_rows_backward[{S}x{P}x{F}]")
-            st = _lib.lib().mpa_pair_rows_backward(_lib.ptr(grad_out), S, P, F, swap, _lib.ptr(ga), _lib.ptr(gb),
-                                                   _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_pair_rows_backward")
+        _lib.launch("mpa_pair_rows_backward", dev, grad_out, S, P, F, swap, ga, gb,
+                    timer=f"pair_rows_backward[{S}x{P}x{F}]")
         return ga, gb, None
 
 
@@ -224,13 +183,8 @@ class _MergeEqualParts(torch.autograd.Function):
         part_out, pose_out = torch.empty_like(part_feats), torch.empty_like(pose_feats)
         arg_part = torch.empty((B, P, C1), dtype=torch.uint8, device=dev)
         arg_pose = torch.empty((B, P, C2), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"merge_equal_parts[{B}x{P}x{C1}+{C2}]")
-            st = _lib.lib().mpa_merge_equal_parts(_lib.ptr(part_feats), _lib.ptr(pose_feats), _lib.ptr(valids), _lib.ptr(ids),
-                                                  B, P, C1, C2, _lib.ptr(part_out), _lib.ptr(pose_out), _lib.ptr(arg_part),
-                                                  _lib.ptr(arg_pose), _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_merge_equal_parts")
+        _lib.launch("mpa_merge_equal_parts", dev, part_feats, pose_feats, valids, ids, B, P, C1, C2, part_out, pose_out,
+                    arg_part, arg_pose, timer=f"merge_equal_parts[{B}x{P}x{C1}+{C2}]")
         ctx.save_for_backward(arg_part, arg_pose, valids, ids)
         ctx.mark_non_differentiable(arg_part, arg_pose)
         return part_out, pose_out, arg_part, arg_pose
@@ -244,13 +198,8 @@ class _MergeEqualParts(torch.autograd.Function):
         g_part = torch.zeros((B, P, C1), dtype=torch.float32, device=dev) if g_part is None else _f32c(g_part)
         g_pose = torch.zeros((B, P, C2), dtype=torch.float32, device=dev) if g_pose is None else _f32c(g_pose)
         grad_part, grad_pose = torch.empty_like(g_part), torch.empty_like(g_pose)
-        with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"merge_equal_parts_backward[{B}x{P}x{C1}+{C2}]")
-            st = _lib.lib().mpa_merge_equal_parts_backward(
-                _lib.ptr(g_part), _lib.ptr(g_pose), _lib.ptr(arg_part), _lib.ptr(arg_pose), _lib.ptr(valids), _lib.ptr(ids),
-                B, P, C1, C2, _lib.ptr(grad_part), _lib.ptr(grad_pose), _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_merge_equal_parts_backward")
+        _lib.launch("mpa_merge_equal_parts_backward", dev, g_part, g_pose, arg_part, arg_pose, valids, ids, B, P, C1,
+                    C2, grad_part, grad_pose, timer=f"merge_equal_parts_backward[{B}x{P}x{C1}+{C2}]")
         return grad_part, grad_pose, None, None
 
 

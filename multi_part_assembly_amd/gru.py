@@ -64,20 +64,13 @@ class _GRURecurrentFn(torch.autograd.Function):
         D, B, T, H3 = gi.shape
         H = H3 // 3
         dev = gi.device
-        L = _lib.lib()
-        n = ctypes.c_int64()
-        _lib.check(L.mpa_gru_workspace(D, B, T, H, ctypes.byref(n)), "mpa_gru_workspace")
-        ws = torch.empty(n.value, dtype=torch.float32, device=dev)
+        ws = torch.empty(_lib.query("mpa_gru_workspace", D, B, T, H), dtype=torch.float32, device=dev)
         out = torch.empty((D, B, T, H), dtype=torch.float32, device=dev)
         raise_if_failed(dev)
         word, host = _status(dev)
-        with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"gru_forward[{D}x{B}x{T}x{H}]")
-            st = L.mpa_gru_forward(_lib.ptr(gi), _lib.ptr(h0), _lib.ptr(whh), _lib.ptr(bhh), D, B, T, H, _lib.ptr(ws),
-                                   _lib.ptr(out), _lib.ptr(word), _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
-            host.copy_(word, non_blocking=True)
-        _lib.check(st, "mpa_gru_forward")
+        _lib.launch("mpa_gru_forward", dev, gi, h0, whh, bhh, D, B, T, H, ws, out, word,
+                    timer=f"gru_forward[{D}x{B}x{T}x{H}]")
+        host.copy_(word, non_blocking=True)
         ctx.save_for_backward(h0, whh, out, ws)
         return out
 
@@ -92,14 +85,9 @@ class _GRURecurrentFn(torch.autograd.Function):
         grad_out = grad_out.contiguous()
         raise_if_failed(dev)
         word, host = _status(dev)
-        with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"gru_backward[{D}x{B}x{T}x{H}]")
-            st = _lib.lib().mpa_gru_backward(_lib.ptr(grad_out), _lib.ptr(h0), _lib.ptr(whh), _lib.ptr(out), D, B, T, H,
-                                             _lib.ptr(ws), _lib.ptr(ggi), _lib.ptr(gw), _lib.ptr(gb), _lib.ptr(word),
-                                             _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
-            host.copy_(word, non_blocking=True)
-        _lib.check(st, "mpa_gru_backward")
+        _lib.launch("mpa_gru_backward", dev, grad_out, h0, whh, out, D, B, T, H, ws, ggi, gw, gb, word,
+                    timer=f"gru_backward[{D}x{B}x{T}x{H}]")
+        host.copy_(word, non_blocking=True)
         return ggi, None, gw, gb
 
 
@@ -116,9 +104,7 @@ def supported(hidden, batch, directions=2):
         return False
     key = (hidden, batch, directions, torch.cuda.current_device())
     if key not in _RESIDENT:
-        ok = ctypes.c_int(0)
-        _lib.check(_lib.lib().mpa_gru_resident(directions, batch, hidden, ctypes.byref(ok)), "mpa_gru_resident")
-        _RESIDENT[key] = bool(ok.value)
+        _RESIDENT[key] = bool(_lib.query("mpa_gru_resident", directions, batch, hidden, slot=ctypes.c_int))
     return _RESIDENT[key]
 
 

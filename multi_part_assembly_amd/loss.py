@@ -9,8 +9,6 @@ from __future__ import annotations
 
 import torch
 
-import ctypes
-
 from . import _lib
 from .chamfer import chamfer_distance
 from .transforms import pose_apply, pose_apply_rmat, rot_pc
@@ -136,17 +134,13 @@ def part_order(part_pcs, valids):
     if not part_pcs.is_cuda:
         raise RuntimeError("part_order: only CUDA (HIP) tensors are supported")
     B, P, N, _ = part_pcs.shape
-    L = _lib.lib()
-    ne = ctypes.c_int64()
-    _lib.check(L.mpa_assembly_order_elems(B, P, N, ctypes.byref(ne)), "mpa_assembly_order_elems")
-    if ne.value == 0:
+    ne = _lib.query("mpa_assembly_order_elems", B, P, N)
+    if ne == 0:
         return None
     pcs = part_pcs.detach().to(torch.float32).contiguous()
     v = valids.detach().to(torch.float32).contiguous()
-    order = torch.empty(ne.value, dtype=torch.float32, device=pcs.device)
-    with torch.cuda.device(pcs.device):
-        st = L.mpa_assembly_order(_lib.ptr(pcs), _lib.ptr(v), B, P, N, _lib.ptr(order), _lib.current_stream(pcs.device))
-    _lib.check(st, "mpa_assembly_order")
+    order = torch.empty(ne, dtype=torch.float32, device=pcs.device)
+    _lib.launch("mpa_assembly_order", pcs.device, pcs, v, B, P, N, order)
     return order
 
 
@@ -159,12 +153,9 @@ class _AssemblyLoss(torch.autograd.Function):
                 search=-1):
         B, P, N, _ = part_pcs.shape
         dev = part_pcs.device
-        L = _lib.lib()
-        nf, ni = ctypes.c_int64(), ctypes.c_int64()
-        _lib.check(L.mpa_assembly_loss_workspace(B, P, N, ctypes.byref(nf), ctypes.byref(ni)),
-                   "mpa_assembly_loss_workspace")
-        fws = torch.empty(nf.value, dtype=torch.float32, device=dev)
-        iws = torch.empty(ni.value, dtype=torch.int32, device=dev)
+        nf, ni = _lib.query("mpa_assembly_loss_workspace", B, P, N)
+        fws = torch.empty(nf, dtype=torch.float32, device=dev)
+        iws = torch.empty(ni, dtype=torch.int32, device=dev)
         losses = torch.empty((5, B), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             # library-recorded events: [0..4] bound the four phases, [5] / [6] sit right around the grid search kernel
@@ -176,16 +167,12 @@ class _AssemblyLoss(torch.autograd.Function):
             both = None
             if evs is not None or gs is not None:
                 both = (evs if evs is not None else [None] * 5) + (gs if gs is not None else [None] * 2)
-            fwd = L.mpa_assembly_loss_forward_rmat_ordered if quat_pred.dim() == 4 else L.mpa_assembly_loss_forward_ordered
-            st = fwd(
-                _lib.ptr(part_pcs), _lib.ptr(valids), _lib.ptr(quat_pred), _lib.ptr(trans_pred),
-                _lib.ptr(quat_gt), _lib.ptr(trans_gt), B, P, N, int(training), int(fill_pads),
-                _lib.ptr(order) if order is not None else None, int(search),
-                _lib.ptr(fws), _lib.ptr(iws), _lib.ptr(losses), _lib.KernelTimer.handles(both),
-                _lib.current_stream(dev))
+            _lib.launch(
+                "mpa_assembly_loss_forward_rmat_ordered" if quat_pred.dim() == 4 else "mpa_assembly_loss_forward_ordered",
+                dev, part_pcs, valids, quat_pred, trans_pred, quat_gt, trans_gt, B, P, N, training, fill_pads,
+                order, int(search), fws, iws, losses, _lib.KernelTimer.handles(both))
             _lib.KernelTimer.add_phases(names, evs)
             _lib.KernelTimer.add_phases(["shape_search_kernel" + tag], gs)
-        _lib.check(st, "mpa_assembly_loss_forward")
         ctx.save_for_backward(part_pcs, valids, quat_pred, trans_pred, quat_gt, trans_gt, fws, iws)
         ctx.training = int(training)
         cloud = B * P * N * 3
@@ -208,14 +195,9 @@ class _AssemblyLoss(torch.autograd.Function):
         gq = torch.empty_like(quat_pred)
         gt = torch.empty_like(trans_pred)
         grad_losses = grad_losses.contiguous()
-        with torch.cuda.device(dev):
-            L = _lib.lib()
-            bwd = L.mpa_assembly_loss_backward_rmat if quat_pred.dim() == 4 else L.mpa_assembly_loss_backward
-            st = bwd(
-                _lib.ptr(grad_losses), _lib.ptr(part_pcs), _lib.ptr(valids), _lib.ptr(quat_pred),
-                _lib.ptr(trans_pred), _lib.ptr(quat_gt), _lib.ptr(trans_gt), B, P, N, ctx.training,
-                _lib.ptr(fws), _lib.ptr(iws), _lib.ptr(gq), _lib.ptr(gt), _lib.current_stream(dev))
-        _lib.check(st, "mpa_assembly_loss_backward")
+        _lib.launch("mpa_assembly_loss_backward_rmat" if quat_pred.dim() == 4 else "mpa_assembly_loss_backward", dev,
+                    grad_losses, part_pcs, valids, quat_pred, trans_pred, quat_gt, trans_gt, B, P, N, ctx.training,
+                    fws, iws, gq, gt)
         return None, None, gq, gt, None, None, None, None, None, None
 
 
@@ -232,10 +214,7 @@ class _LossReduce(torch.autograd.Function):
         K, B = terms.shape
         means = torch.empty(K, dtype=torch.float32, device=terms.device)
         loss = torch.empty((), dtype=torch.float32, device=terms.device)
-        with torch.cuda.device(terms.device):
-            st = _lib.lib().mpa_loss_reduce_forward(_lib.ptr(terms), _lib.ptr(weights), K, B, _lib.ptr(means),
-                                                    _lib.ptr(loss), _lib.current_stream(terms.device))
-        _lib.check(st, "mpa_loss_reduce_forward")
+        _lib.launch("mpa_loss_reduce_forward", terms.device, terms, weights, K, B, means, loss)
         ctx.save_for_backward(weights)
         ctx.shape = (K, B)
         ctx.set_materialize_grads(False)
@@ -250,11 +229,7 @@ class _LossReduce(torch.autograd.Function):
         g_terms = torch.empty((K, B), dtype=torch.float32, device=weights.device)
         gm = g_means.contiguous() if g_means is not None else None
         gl = g_loss.contiguous() if g_loss is not None else None
-        with torch.cuda.device(weights.device):
-            st = _lib.lib().mpa_loss_reduce_backward(_lib.ptr(gl) if gl is not None else None,
-                                                     _lib.ptr(gm) if gm is not None else None, _lib.ptr(weights), K, B,
-                                                     _lib.ptr(g_terms), _lib.current_stream(weights.device))
-        _lib.check(st, "mpa_loss_reduce_backward")
+        _lib.launch("mpa_loss_reduce_backward", weights.device, gl, gm, weights, K, B, g_terms)
         return g_terms, None
 
 

@@ -41,9 +41,7 @@ _DEC_RESIDENT: dict = {}
 def _decoder_resident(batch):
     key = (batch, torch.cuda.current_device())
     if key not in _DEC_RESIDENT:
-        ok = ctypes.c_int(0)
-        _lib.check(_lib.lib().mpa_seq2seq_decoder_resident(batch, ctypes.byref(ok)), "mpa_seq2seq_decoder_resident")
-        _DEC_RESIDENT[key] = bool(ok.value)
+        _DEC_RESIDENT[key] = bool(_lib.query("mpa_seq2seq_decoder_resident", batch, slot=ctypes.c_int))
     return _DEC_RESIDENT[key]
 
 
@@ -56,7 +54,6 @@ class _DecoderFn(torch.autograd.Function):
     def forward(ctx, h0, target, mask, P, w_ih, b_ih, w_hh, b_hh, w1, b1, w2, b2):
         B = h0.shape[0]
         dev = h0.device
-        L = _lib.lib()
         h0 = h0.detach().float().contiguous()
         gi = None
         if target is not None:  # teacher forcing: the step inputs are known, their projections are one GEMM
@@ -64,24 +61,16 @@ class _DecoderFn(torch.autograd.Function):
             if mask is not None:
                 x = x * mask
             gi = F.linear(x, w_ih, b_ih).contiguous()
-        n = ctypes.c_int64()
-        _lib.check(L.mpa_seq2seq_decoder_workspace(B, P, ctypes.byref(n)), "mpa_seq2seq_decoder_workspace")
-        ws = torch.empty(n.value, dtype=torch.float32, device=dev)
+        ws = torch.empty(_lib.query("mpa_seq2seq_decoder_workspace", B, P), dtype=torch.float32, device=dev)
         hs = torch.empty((P, B, _H), dtype=torch.float32, device=dev)
         z1 = torch.empty((P, B, _Z), dtype=torch.float32, device=dev)
         y = torch.empty((P, B, _C), dtype=torch.float32, device=dev)
         mask_c = mask.contiguous() if (mask is not None and target is None) else None
         _gru.raise_if_failed(dev)
         word, host = _gru._status(dev)
-        with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"seq2seq_decoder_forward[{B}x{P}]")
-            st = L.mpa_seq2seq_decoder_forward(_lib.ptr(gi), _lib.ptr(mask_c), _lib.ptr(h0), _lib.ptr(w_ih),
-                                               _lib.ptr(b_ih), _lib.ptr(w_hh), _lib.ptr(b_hh), _lib.ptr(w1), _lib.ptr(b1),
-                                               _lib.ptr(w2), _lib.ptr(b2), B, P, _lib.ptr(ws), _lib.ptr(hs), _lib.ptr(z1),
-                                               _lib.ptr(y), _lib.ptr(word), _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
-            host.copy_(word, non_blocking=True)
-        _lib.check(st, "mpa_seq2seq_decoder_forward")
+        _lib.launch("mpa_seq2seq_decoder_forward", dev, gi, mask_c, h0, w_ih, b_ih, w_hh, b_hh, w1, b1, w2, b2, B, P, ws,
+                    hs, z1, y, word, timer=f"seq2seq_decoder_forward[{B}x{P}]")
+        host.copy_(word, non_blocking=True)
         if target is None:  # free running: the inputs were the launch's own outputs (the same values)
             x = torch.cat([torch.zeros_like(y[:1]), y[:-1]], dim=0)
             if mask is not None:
@@ -108,14 +97,9 @@ class _DecoderFn(torch.autograd.Function):
         dh0 = torch.empty((B, _H), dtype=torch.float32, device=dev)
         _gru.raise_if_failed(dev)
         word, host = _gru._status(dev)
-        with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"seq2seq_decoder_backward[{B}x{P}]")
-            st = _lib.lib().mpa_seq2seq_decoder_backward(_lib.ptr(dh), _lib.ptr(h0), _lib.ptr(w_hh), _lib.ptr(hs), B, P,
-                                                         _lib.ptr(ws), _lib.ptr(dgi), _lib.ptr(dwhh), _lib.ptr(dbhh),
-                                                         _lib.ptr(dh0), _lib.ptr(word), _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
-            host.copy_(word, non_blocking=True)
-        _lib.check(st, "mpa_seq2seq_decoder_backward")
+        _lib.launch("mpa_seq2seq_decoder_backward", dev, dh, h0, w_hh, hs, B, P, ws, dgi, dwhh, dbhh, dh0, word,
+                    timer=f"seq2seq_decoder_backward[{B}x{P}]")
+        host.copy_(word, non_blocking=True)
         dgi2 = dgi.reshape(P * B, 3 * _H)
         dwih = dgi2.t() @ x.reshape(P * B, _C)
         dbih = dgi2.sum(0)

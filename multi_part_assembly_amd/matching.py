@@ -33,10 +33,8 @@ def sample_indices(B, G, N, n, seed, counter=0, counter_dev=None, salt=0, device
     if counter_dev is not None:
         assert counter_dev.dtype == torch.int64 and counter_dev.device == dev and counter_dev.numel() == 1
     out = torch.empty((B, G, n), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        st = _lib.lib().mpa_match_sample_indices(B, G, N, n, int(seed) & _U64, int(counter) & _U64, _lib.ptr(counter_dev),
-                                                 int(salt) & _U64, _lib.ptr(out), _lib.current_stream(dev))
-    _lib.check(st, "mpa_match_sample_indices")
+    _lib.launch("mpa_match_sample_indices", dev, B, G, N, n, int(seed) & _U64, int(counter) & _U64, counter_dev,
+                int(salt) & _U64, out)
     return out
 
 
@@ -108,10 +106,7 @@ def linear_sum_assignment(cost: torch.Tensor, sizes: torch.Tensor | None = None)
         sizes = torch.full((problems,), ld, dtype=torch.int32, device=dev)
     sizes = sizes.to(device=dev, dtype=torch.int32).contiguous()
     out = torch.empty((problems, ld), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        st = _lib.lib().mpa_linear_sum_assignment(_lib.ptr(cost), _lib.ptr(sizes), problems, ld, _lib.ptr(out),
-                                                  _lib.current_stream(dev))
-    _lib.check(st, "mpa_linear_sum_assignment")
+    _lib.launch("mpa_linear_sum_assignment", dev, cost, sizes, problems, ld, out)
     return out
 
 
@@ -144,9 +139,6 @@ def match_parts(part_pcs, pred_trans, pred_quat, gt_trans, gt_quat, match_ids, s
     new_q = torch.empty((B, P) + tuple(pred_quat.shape[2:]), dtype=torch.float32, device=dev)
     perm = torch.empty((B, P), dtype=torch.int32, device=dev)
     args = [f(part_pcs), f(pred_trans), f(pred_quat), f(gt_trans), f(gt_quat), i32(match_ids), sample_idx]
-    with torch.cuda.device(dev):
-        fn = _lib.lib().mpa_match_parts_rmat if rmat else _lib.lib().mpa_match_parts
-        st = fn(*[_lib.ptr(a) for a in args], B, P, N, G, n, _lib.ptr(cost), _lib.ptr(col4row), _lib.ptr(new_t),
-                _lib.ptr(new_q), _lib.ptr(perm), _lib.current_stream(dev))
-    _lib.check(st, "mpa_match_parts_rmat" if rmat else "mpa_match_parts")
+    _lib.launch("mpa_match_parts_rmat" if rmat else "mpa_match_parts", dev, *args, B, P, N, G, n, cost, col4row, new_t,
+                new_q, perm)
     return (new_t, new_q, perm, cost, col4row) if ret_aux else (new_t, new_q)

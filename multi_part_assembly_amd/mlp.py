@@ -4,8 +4,6 @@ models/rgl_net/modules.py:5-30).  The torch modules keep holding the parameters 
 replaces what `conv(x)`, `bn(.)`, `relu(.)` compute."""
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _lib
@@ -19,20 +17,11 @@ class _MLPLayerFn(torch.autograd.Function):
         N = weight.shape[0]
         w = weight.reshape(N, -1)  # a Conv1d weight [N, K, 1] or a Linear weight [N, K]: the same bytes
         dev = x.device
-        L = _lib.lib()
-        nbytes = ctypes.c_int64()
-        _lib.check(L.mpa_mlp_layer_workspace(R, K, N, ctypes.byref(nbytes)), "mpa_mlp_layer_workspace")
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        ws = torch.empty(_lib.query("mpa_mlp_layer_workspace", R, K, N), dtype=torch.uint8, device=dev)
         out = torch.empty((R, N), dtype=torch.float32, device=dev)
         rm, rv = running if running is not None else (None, None)
-        with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"mlp_layer_forward[{R}x{K}x{N}]")
-            st = L.mpa_mlp_layer_forward(_lib.ptr(x), x.stride(0), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(gamma),
-                                         _lib.ptr(beta), _lib.ptr(rm), _lib.ptr(rv), int(training), float(momentum),
-                                         float(eps), int(relu), R, K, N, _lib.ptr(ws), _lib.ptr(out),
-                                         _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_mlp_layer_forward")
+        _lib.launch("mpa_mlp_layer_forward", dev, x, x.stride(0), w, bias, gamma, beta, rm, rv, int(training),
+                    float(momentum), float(eps), int(relu), R, K, N, ws, out, timer=f"mlp_layer_forward[{R}x{K}x{N}]")
         ctx.meta = (bool(relu), bool(training), bias is not None, gamma is not None)
         # the parameters themselves (not views of them): with a GradSink active their gradients are written straight
         # into the flat gradient buffer instead of going through one AccumulateGrad `add` launch per parameter
@@ -62,14 +51,8 @@ class _MLPLayerFn(torch.autograd.Function):
         gg = next(it) if has_bn else None
         gbe = next(it) if has_bn else None
         grad_out = grad_out.contiguous()
-        with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"mlp_layer_backward[{R}x{K}x{N}]")
-            st = _lib.lib().mpa_mlp_layer_backward(
-                _lib.ptr(grad_out), _lib.ptr(x), x.stride(0), _lib.ptr(w), _lib.ptr(gamma), _lib.ptr(out), int(relu), R, K,
-                N, _lib.ptr(ws), _lib.ptr(gx), _lib.ptr(gw), _lib.ptr(gb), _lib.ptr(gg), _lib.ptr(gbe),
-                _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_mlp_layer_backward")
+        _lib.launch("mpa_mlp_layer_backward", dev, grad_out, x, x.stride(0), w, gamma, out, int(relu), R, K, N, ws, gx,
+                    gw, gb, gg, gbe, timer=f"mlp_layer_backward[{R}x{K}x{N}]")
         if direct:
             GradSink.delivered(ctx.params)
             return gx, None, None, None, None, None, None, None, None, None
@@ -85,20 +68,11 @@ class _PairLayerFn(torch.autograd.Function):
         N = weight.shape[0]
         w = weight.reshape(N, -1)  # Conv1d weight [N, 2F, 1]: the same bytes
         dev = a.device
-        L = _lib.lib()
-        nbytes = ctypes.c_int64()
-        _lib.check(L.mpa_pair_layer_workspace(B, P, F, N, ctypes.byref(nbytes)), "mpa_pair_layer_workspace")
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        ws = torch.empty(_lib.query("mpa_pair_layer_workspace", B, P, F, N), dtype=torch.uint8, device=dev)
         out = torch.empty((B * P * P, N), dtype=torch.float32, device=dev)
         rm, rv = running
-        with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"pair_layer_forward[{B}x{P}x{P}x{2 * F}x{N}]")
-            st = L.mpa_pair_layer_forward(_lib.ptr(a), _lib.ptr(b), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(gamma),
-                                          _lib.ptr(beta), _lib.ptr(rm), _lib.ptr(rv), int(training), float(momentum),
-                                          float(eps), int(relu), B, P, F, N, _lib.ptr(ws), _lib.ptr(out),
-                                          _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_pair_layer_forward")
+        _lib.launch("mpa_pair_layer_forward", dev, a, b, w, bias, gamma, beta, rm, rv, int(training), float(momentum),
+                    float(eps), int(relu), B, P, F, N, ws, out, timer=f"pair_layer_forward[{B}x{P}x{P}x{2 * F}x{N}]")
         ctx.meta = (bool(relu), bool(training), bias is not None)
         ctx.same = a.data_ptr() == b.data_ptr() and a.shape == b.shape
         ctx.params = [p for p in (weight, bias, gamma, beta) if p is not None]
@@ -130,14 +104,8 @@ class _PairLayerFn(torch.autograd.Function):
         gbias = next(it) if has_bias else None
         gg, gbe = next(it), next(it)
         grad_out = grad_out.contiguous()
-        with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"pair_layer_backward[{B}x{P}x{P}x{2 * F}x{N}]")
-            st = _lib.lib().mpa_pair_layer_backward(
-                _lib.ptr(grad_out), _lib.ptr(a), _lib.ptr(b), _lib.ptr(w), _lib.ptr(gamma), _lib.ptr(out), int(relu), B, P, F,
-                N, _lib.ptr(ws), _lib.ptr(ga), _lib.ptr(gb), _lib.ptr(gw), _lib.ptr(gbias), _lib.ptr(gg), _lib.ptr(gbe),
-                _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_pair_layer_backward")
+        _lib.launch("mpa_pair_layer_backward", dev, grad_out, a, b, w, gamma, out, int(relu), B, P, F, N, ws, ga, gb,
+                    gw, gbias, gg, gbe, timer=f"pair_layer_backward[{B}x{P}x{P}x{2 * F}x{N}]")
         if same:
             gb = None  # (already inside ga)
         if direct:

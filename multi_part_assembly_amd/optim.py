@@ -129,10 +129,8 @@ class FusedAdam:
     def _ensure_clip_ws(self):
         """Allocated on first use, so `clip_grad` may be assigned after construction or after the first step."""
         if self._clip_ws is None:
-            import ctypes
-            nbytes = ctypes.c_int64()
-            _lib.check(_lib.lib().mpa_grad_clip_workspace(ctypes.byref(nbytes)), "mpa_grad_clip_workspace")
-            self._clip_ws = torch.empty(nbytes.value // 8, dtype=torch.float64, device=self.flat_param.device)
+            self._clip_ws = torch.empty(_lib.query("mpa_grad_clip_workspace") // 8, dtype=torch.float64,
+                                        device=self.flat_param.device)
 
     def _set_device_step(self, step):
         self._hyper_dev[4:5].view(torch.int32).fill_(int(step))
@@ -151,25 +149,17 @@ class FusedAdam:
         """[clip coefficient +] step-count advance + Adam update, all on the stream (safe to capture in a HIP
         graph: every launch argument is constant across replays)."""
         dev = self.flat_param.device
-        lib = _lib.lib()
-        with torch.cuda.device(dev):
-            stream = _lib.current_stream(dev)
-            if not self.clip_grad and self._clip_written:  # clipping was switched off: back to "no clipping"
-                self._hyper_dev[5:6].fill_(1.0)
-                self._clip_written = False
-            if self.clip_grad:
-                self._ensure_clip_ws()
-                self._clip_written = True
-                st = lib.mpa_grad_clip_coef(_lib.ptr(self.flat_grad), self.numel, float(self.clip_grad),
-                                            self._hyper_dev.data_ptr() + 12, 1.0, _lib.ptr(self._clip_ws),
-                                            self._hyper_dev.data_ptr() + 20, stream)
-                _lib.check(st, "mpa_grad_clip_coef")
-            st = lib.mpa_adam_step_dev(
-                _lib.ptr(self.flat_param), _lib.ptr(self.flat_grad), _lib.ptr(self.exp_avg),
-                _lib.ptr(self.exp_avg_sq), self.numel, _lib.ptr(self._hyper_dev), float(self.betas[0]),
-                float(self.betas[1]), float(self.eps), float(self.weight_decay), int(self.decoupled),
-                _lib.ptr(self.decay_mask), stream)
-        _lib.check(st, "mpa_adam_step_dev")
+        if not self.clip_grad and self._clip_written:  # clipping was switched off: back to "no clipping"
+            self._hyper_dev[5:6].fill_(1.0)
+            self._clip_written = False
+        if self.clip_grad:
+            self._ensure_clip_ws()
+            self._clip_written = True
+            _lib.launch("mpa_grad_clip_coef", dev, self.flat_grad, self.numel, float(self.clip_grad),
+                        self._hyper_dev.data_ptr() + 12, 1.0, self._clip_ws, self._hyper_dev.data_ptr() + 20)
+        _lib.launch("mpa_adam_step_dev", dev, self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.numel,
+                    self._hyper_dev, float(self.betas[0]), float(self.betas[1]), float(self.eps),
+                    float(self.weight_decay), int(self.decoupled), self.decay_mask)
 
     def step(self, lr=None):
         if lr is not None:

@@ -8,8 +8,6 @@ one kernel for both heads + the rotation's normalisation, deterministic backward
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -27,19 +25,11 @@ class _PoseHeadFn(torch.autograd.Function):
     def forward(ctx, x, rot_type, *params):
         M, Fdim = x.shape
         dev = x.device
-        lib = _lib.lib()
         width, name = _HEADS[rot_type]
-        n = ctypes.c_int64()
-        _lib.check(getattr(lib, name + "_workspace")(M, Fdim, ctypes.byref(n)), name + "_workspace")
-        ws = torch.empty(n.value, dtype=torch.float32, device=dev)
+        ws = torch.empty(_lib.query(name + "_workspace", M, Fdim), dtype=torch.float32, device=dev)
         rot = torch.empty((M, width), dtype=torch.float32, device=dev)
         trans = torch.empty((M, 3), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"pose_head_forward[{M}x{Fdim}]")
-            st = getattr(lib, name + "_forward")(_lib.ptr(x), _lib.ptr_array(params), M, Fdim, _lib.ptr(ws),
-                                                 _lib.ptr(rot), _lib.ptr(trans), _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, name + "_forward")
+        _lib.launch(name + "_forward", dev, x, params, M, Fdim, ws, rot, trans, timer=f"pose_head_forward[{M}x{Fdim}]")
         ctx.params, ctx.name = params, name
         GradSink.note_use(params)
         ctx.save_for_backward(x, ws)
@@ -53,14 +43,8 @@ class _PoseHeadFn(torch.autograd.Function):
         dev = x.device
         grad_x = torch.empty_like(x)
         grads, direct = GradSink.outputs(params)
-        with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"pose_head_backward[{M}x{Fdim}]")
-            st = getattr(_lib.lib(), ctx.name + "_backward")(
-                _lib.ptr(grad_rot.contiguous()), _lib.ptr(grad_trans.contiguous()), _lib.ptr(x),
-                _lib.ptr_array(params), M, Fdim, _lib.ptr(ws), _lib.ptr(grad_x), _lib.ptr_array(grads),
-                _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, ctx.name + "_backward")
+        _lib.launch(ctx.name + "_backward", dev, grad_rot.contiguous(), grad_trans.contiguous(), x, params, M, Fdim, ws,
+                    grad_x, grads, timer=f"pose_head_backward[{M}x{Fdim}]")
         if direct:
             GradSink.delivered(params)
             return (grad_x, None, *([None] * len(params)))

@@ -40,10 +40,7 @@ class _SanitizeFn(torch.autograd.Function):
         q = rot.contiguous()
         out = torch.empty_like(q)
         keep = torch.empty(q.shape[:-1] + (1,), dtype=torch.float32, device=q.device)
-        with torch.cuda.device(q.device):
-            st = _lib.lib().mpa_quat_sanitize(_lib.ptr(q), q.numel() // 4, _lib.ptr(out), _lib.ptr(keep),
-                                              _lib.current_stream(q.device))
-        _lib.check(st, "mpa_quat_sanitize")
+        _lib.launch("mpa_quat_sanitize", q.device, q, q.numel() // 4, out, keep)
         ctx.save_for_backward(keep)
         return out
 
@@ -76,9 +73,7 @@ class _Rot6dFn(torch.autograd.Function):
         from . import _lib
         M = d6.shape[0]
         out = torch.empty((M, 3, 3), dtype=torch.float32, device=d6.device)
-        with torch.cuda.device(d6.device):
-            st = _lib.lib().mpa_rot6d_to_rmat_forward(_lib.ptr(d6), M, _lib.ptr(out), _lib.current_stream(d6.device))
-        _lib.check(st, "mpa_rot6d_to_rmat_forward")
+        _lib.launch("mpa_rot6d_to_rmat_forward", d6.device, d6, M, out)
         ctx.save_for_backward(d6)
         return out
 
@@ -88,10 +83,7 @@ class _Rot6dFn(torch.autograd.Function):
         (d6,) = ctx.saved_tensors
         gd6 = torch.empty_like(d6)
         grad = grad.contiguous()
-        with torch.cuda.device(d6.device):
-            st = _lib.lib().mpa_rot6d_to_rmat_backward(_lib.ptr(d6), _lib.ptr(grad), d6.shape[0], _lib.ptr(gd6),
-                                                        _lib.current_stream(d6.device))
-        _lib.check(st, "mpa_rot6d_to_rmat_backward")
+        _lib.launch("mpa_rot6d_to_rmat_backward", d6.device, d6, grad, d6.shape[0], gd6)
         return gd6
 
 
@@ -117,9 +109,7 @@ def quat_to_matrix(quat):
             raise RuntimeError("quat_to_matrix: the device conversion has no backward (it converts ground-truth poses)")
         q = quat.reshape(-1, 4).contiguous()
         out = torch.empty((q.shape[0], 3, 3), dtype=torch.float32, device=q.device)
-        with torch.cuda.device(q.device):
-            st = _lib.lib().mpa_quat_to_rmat(_lib.ptr(q), q.shape[0], _lib.ptr(out), _lib.current_stream(q.device))
-        _lib.check(st, "mpa_quat_to_rmat")
+        _lib.launch("mpa_quat_to_rmat", q.device, q, q.shape[0], out)
         return out.reshape(*lead, 3, 3)
     r, i, j, k = quat.unbind(-1)
     two_s = 2.0 / (((r * r + i * i) + j * j) + k * k)

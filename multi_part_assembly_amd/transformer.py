@@ -8,8 +8,6 @@ attention over the part tokens, deterministic backward).
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 import torch.nn as nn
 
@@ -28,20 +26,11 @@ class _TransformerFn(torch.autograd.Function):
         L = (len(params) - 2) // len(_LAYER_PARAMS)
         FF = params[4].shape[0]
         dev = tokens.device
-        lib = _lib.lib()
-        n = ctypes.c_int64()
-        _lib.check(lib.mpa_transformer_workspace(B, P, D, heads, FF, L, ctypes.byref(n)),
-                   "mpa_transformer_workspace")
-        ws = torch.empty(n.value, dtype=torch.float32, device=dev)
+        ws = torch.empty(_lib.query("mpa_transformer_workspace", B, P, D, heads, FF, L), dtype=torch.float32, device=dev)
         out = torch.empty_like(tokens)
-        with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"transformer_forward[{B}x{P}x{D}]")
-            st = lib.mpa_transformer_forward(_lib.ptr(tokens), _lib.ptr(valid), _lib.ptr_array(params), B, P, D,
-                                             heads, FF, L, float(dropout_p), int(seed),
-                                             None if seed_dev is None else _lib.ptr(seed_dev), _lib.ptr(ws),
-                                             _lib.ptr(out), _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_transformer_forward")
+        _lib.launch("mpa_transformer_forward", dev, tokens, valid, params, B, P, D, heads, FF, L, float(dropout_p),
+                    int(seed), seed_dev, ws, out,
+                    timer=f"transformer_forward[{B}x{P}x{D}]")
         ctx.meta = (heads, FF, L, float(dropout_p), int(seed))
         ctx.params = params  # the Parameter objects themselves (GradSink writes into their .grad)
         GradSink.note_use(params)
@@ -59,14 +48,9 @@ class _TransformerFn(torch.autograd.Function):
         grad_out = grad_out.contiguous()
         grad_tokens = torch.empty_like(grad_out)
         grads, direct = GradSink.outputs(params)
-        with torch.cuda.device(dev):
-            tok = _lib.KernelTimer.start(f"transformer_backward[{B}x{P}x{D}]")
-            st = _lib.lib().mpa_transformer_backward(
-                _lib.ptr(grad_out), _lib.ptr(valid), _lib.ptr_array(params), B, P, D, heads, FF, L, dropout_p,
-                seed, None if ctx.seed_dev is None else _lib.ptr(ctx.seed_dev), _lib.ptr(ws), _lib.ptr(grad_tokens),
-                _lib.ptr_array(grads), _lib.current_stream(dev))
-            _lib.KernelTimer.stop(tok)
-        _lib.check(st, "mpa_transformer_backward")
+        _lib.launch("mpa_transformer_backward", dev, grad_out, valid, params, B, P, D, heads, FF, L, dropout_p, seed,
+                    ctx.seed_dev, ws, grad_tokens, grads,
+                    timer=f"transformer_backward[{B}x{P}x{D}]")
         if direct:
             GradSink.delivered(params)
             return (grad_tokens, None, None, None, None, None, *([None] * len(params)))

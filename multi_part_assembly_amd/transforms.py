@@ -22,11 +22,7 @@ class _PoseApply(torch.autograd.Function):
     def forward(ctx, pc, quat, trans, mask, fill):
         M, N = pc.shape[0], pc.shape[1]
         out = torch.empty_like(pc)
-        with torch.cuda.device(pc.device):
-            st = _lib.lib().mpa_pose_apply_forward(
-                _lib.ptr(pc), _lib.ptr(quat), _lib.ptr(trans), _lib.ptr(mask), float(fill), M, N,
-                _lib.ptr(out), _lib.current_stream(pc.device))
-        _lib.check(st, "mpa_pose_apply_forward")
+        _lib.launch("mpa_pose_apply_forward", pc.device, pc, quat, trans, mask, float(fill), M, N, out)
         ctx.save_for_backward(pc, quat, mask)
         ctx.fill = float(fill)
         ctx.has_trans = trans is not None
@@ -41,11 +37,7 @@ class _PoseApply(torch.autograd.Function):
         gq = torch.empty_like(quat)
         gt = torch.empty((M, 3), dtype=pc.dtype, device=pc.device) if (ctx.has_trans and need_t) else None
         gpc = torch.empty_like(pc) if need_pc else None
-        with torch.cuda.device(pc.device):
-            st = _lib.lib().mpa_pose_apply_backward(
-                _lib.ptr(gout), _lib.ptr(pc), _lib.ptr(quat), _lib.ptr(mask), ctx.fill, M, N,
-                _lib.ptr(gq), _lib.ptr(gt), _lib.ptr(gpc), _lib.current_stream(pc.device))
-        _lib.check(st, "mpa_pose_apply_backward")
+        _lib.launch("mpa_pose_apply_backward", pc.device, gout, pc, quat, mask, ctx.fill, M, N, gq, gt, gpc)
         return gpc, (gq if need_q else None), gt, None, None
 
 
@@ -77,11 +69,7 @@ class _PoseApplyRmat(torch.autograd.Function):
     def forward(ctx, pc, rmat, trans, mask, fill):
         M, N = pc.shape[0], pc.shape[1]
         out = torch.empty_like(pc)
-        with torch.cuda.device(pc.device):
-            st = _lib.lib().mpa_pose_apply_rmat_forward(
-                _lib.ptr(pc), _lib.ptr(rmat), _lib.ptr(trans), _lib.ptr(mask), float(fill), M, N,
-                _lib.ptr(out), _lib.current_stream(pc.device))
-        _lib.check(st, "mpa_pose_apply_rmat_forward")
+        _lib.launch("mpa_pose_apply_rmat_forward", pc.device, pc, rmat, trans, mask, float(fill), M, N, out)
         ctx.save_for_backward(pc, rmat, mask)
         ctx.fill = float(fill)
         ctx.has_trans = trans is not None
@@ -96,11 +84,7 @@ class _PoseApplyRmat(torch.autograd.Function):
         gr = torch.empty_like(rmat)
         gt = torch.empty((M, 3), dtype=pc.dtype, device=pc.device) if (ctx.has_trans and need_t) else None
         gpc = torch.empty_like(pc) if need_pc else None
-        with torch.cuda.device(pc.device):
-            st = _lib.lib().mpa_pose_apply_rmat_backward(
-                _lib.ptr(gout), _lib.ptr(pc), _lib.ptr(rmat), _lib.ptr(mask), ctx.fill, M, N,
-                _lib.ptr(gr), _lib.ptr(gt), _lib.ptr(gpc), _lib.current_stream(pc.device))
-        _lib.check(st, "mpa_pose_apply_rmat_backward")
+        _lib.launch("mpa_pose_apply_rmat_backward", pc.device, gout, pc, rmat, mask, ctx.fill, M, N, gr, gt, gpc)
         return gpc, (gr if need_r else None), gt, None, None
 
 

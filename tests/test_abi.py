@@ -1,6 +1,7 @@
 """CPU-side checks of the drop-in boundary: the C-ABI library loads and exports exactly what
 include/mpa_hip.h declares (no compute calls — those need a GPU)."""
 import ctypes
+import re
 import subprocess
 
 import pytest
@@ -15,6 +16,36 @@ def built():
 
 def test_header_and_signature_table_agree():
     assert sorted(_lib.SIGNATURES) == _lib.declared_functions()
+
+
+# (int32_t: one parameter, mpa_partnet_gather_batch's random_order; ctypes.c_int32 is c_int where int has 32 bits)
+_C_TYPES = {"int64_t": ctypes.c_int64, "int": ctypes.c_int, "int32_t": ctypes.c_int32, "float": ctypes.c_float,
+            "uint64_t": ctypes.c_uint64, "double": ctypes.c_double}
+
+
+def _ctype_of(decl):
+    """ctypes type of one C parameter or return declaration of the header; an unknown type is an error."""
+    if "*" in decl:
+        return ctypes.c_void_p
+    words = [w for w in decl.replace("const", " ").split()]
+    assert words and words[0] in _C_TYPES, f"type not known to the test: {decl!r}"
+    return _C_TYPES[words[0]]
+
+
+def test_header_and_signature_table_agree_on_every_type():
+    """Every prototype of include/mpa_hip.h against _lib.SIGNATURES: return type, and count and type of the parameters —
+    an `int` written where the header says `int64_t` passes every other CPU check and corrupts a call on the device."""
+    text = re.sub(r"/\*.*?\*/", "", _lib.HEADER_PATH.read_text(), flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    protos = re.findall(r"([A-Za-z_][\w \t]*?[\w*])\s+(mpa_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)
+    assert len(protos) == len(_lib.SIGNATURES) == len({name for _, name, _ in protos})
+    for ret, name, params in protos:
+        params = [] if params.strip() in ("", "void") else [p.strip() for p in params.split(",")]
+        want_ret = ctypes.c_char_p if name == "mpa_last_error" else _ctype_of(ret)
+        assert ret.replace(" ", "") == ("constchar*" if name == "mpa_last_error" else "int"), (name, ret)
+        restype, argtypes = _lib.SIGNATURES[name]
+        assert restype is want_ret, name
+        assert list(argtypes) == [_ctype_of(p) for p in params], name
 
 
 def test_library_exports_every_declared_symbol(built):
