@@ -793,6 +793,49 @@ int mpa_assembly_metrics_rmat(const float* part_pcs, const float* trans_pred, co
 int mpa_connectivity_acc(const float* contact_points, const float* trans, const float* rot, int is_rmat, int64_t B,
                          int64_t P, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Assembled shapes for export (csrc/assemble.hip) -- replace the tail of
+ *   BaseModel.sample_assembly : multi_part_assembly/models/modules/base_model.py:427-460 (+ utils/utils.py:49-64)
+ * and the mesh half of scripts/vis.py:75-96.
+ *
+ * mpa_assemble_clouds[_rmat]: part_pcs [B, P, N, 3], valids [B, P] (a part is real iff its entry == 1), S predicted
+ * poses rot [S, B, P, 4] (quaternions, real part first, not normalised) or [S, B, P, 9] (row-major matrices) with
+ * trans [S, B, P, 3], the ground truth gt_rot [B, P, 4 | 9], gt_trans [B, P, 3], colors [C, 3]; all contiguous fp32.
+ *   offsets int64 [B + 1]: shape b owns the rows offsets[b] : offsets[b + 1] of every slab, counted in points;
+ *     offsets[b + 1] - offsets[b] = (valid parts of b) * N.
+ *   clouds fp32 [S + 1, B * P * N, 6] is the capacity; only the first offsets[B] rows of a slab are written, no row
+ *     behind them is touched.  Slab s < S holds prediction s, slab S the ground truth.  A row is (x, y, z, r, g, b):
+ *     xyz exactly what mpa_pose_apply[_rmat]_forward writes for the point (same operations, same order, no FMA), the
+ *     colour colors[k] with k the part's rank among the valid parts of its shape.  Parts in slot order, points in
+ *     their order inside the part.
+ * Two launches (the prefix over valids, then the posing), no host synchronisation, no atomics: capturable and
+ * bit-identical from run to run.  Padded slots are never read: any values in their points and poses leave every
+ * output bit unchanged.  Envelope: C >= P (refused otherwise), B * P < 2^31, N <= 65535 * 256.  B == 0 is a no-op;
+ * with P == 0 or N == 0 only offsets (all zero) is written.  S == 0 writes the ground-truth slab alone.
+ *
+ * mpa_mesh_pose_parts: the triangles of M selected parts of a MeshStore (tri float64 [F, 9] = origin, e1, e2;
+ * part_face_off int64 [parts_total + 1]) posed in one launch.  slot_part int64 [M]: a store part id, or < 0 for a
+ * slot that owns no rows and touches nothing; out_face_off int64 [M + 1]: slot m writes the rows
+ * out_face_off[m] : out_face_off[m + 1] (its part's face count; fewer rows truncate, rows >= faces_out are never
+ * written); max_faces: the largest face count of a slot (sizes the grid).  gt_rmat / pred_rmat [M, 9] row-major and
+ * gt_trans / pred_trans [M, 3] fp32.  Three outputs fp32 [faces_out, 3, 3], vertex triples per face:
+ *   orig  v0 = origin, v1 = origin + e1, v2 = origin + e2
+ *   input R_gt^T (v - T_gt)            (the part as the network sees it)
+ *   pred  R_pred . input + T_pred
+ * all in float64 on the fp32 poses widened -- (a b + c d) + e f per row, left to right, no FMA -- and rounded to
+ * fp32 once at the store.
+ * ---------------------------------------------------------------------------------------------- */
+int mpa_assemble_clouds(const float* part_pcs, const float* valids, const float* quat, const float* trans,
+                        const float* gt_quat, const float* gt_trans, const float* colors, int64_t S, int64_t B,
+                        int64_t P, int64_t N, int64_t C, int64_t* offsets, float* clouds, void* stream);
+int mpa_assemble_clouds_rmat(const float* part_pcs, const float* valids, const float* rmat, const float* trans,
+                             const float* gt_rmat, const float* gt_trans, const float* colors, int64_t S, int64_t B,
+                             int64_t P, int64_t N, int64_t C, int64_t* offsets, float* clouds, void* stream);
+int mpa_mesh_pose_parts(const double* tri, const int64_t* part_face_off, int64_t parts_total, const int64_t* slot_part,
+                        const int64_t* out_face_off, int64_t M, int64_t faces_out, int64_t max_faces,
+                        const float* gt_rmat, const float* gt_trans, const float* pred_rmat, const float* pred_trans,
+                        float* orig, float* input, float* pred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

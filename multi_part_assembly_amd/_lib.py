@@ -122,6 +122,9 @@ SIGNATURES: dict[str, tuple] = {
     "mpa_assembly_metrics": (_INT, [_P] * 6 + [_I64, _I64, _I64, _P, _P, _P, _P]),
     "mpa_assembly_metrics_rmat": (_INT, [_P] * 6 + [_I64, _I64, _I64, _P, _P, _P, _P]),
     "mpa_connectivity_acc": (_INT, [_P, _P, _P, _INT, _I64, _I64, _P, _P]),
+    "mpa_assemble_clouds": (_INT, [_P] * 7 + [_I64] * 5 + [_P, _P, _P]),
+    "mpa_assemble_clouds_rmat": (_INT, [_P] * 7 + [_I64] * 5 + [_P, _P, _P]),
+    "mpa_mesh_pose_parts": (_INT, [_P, _P, _I64, _P, _P, _I64, _I64, _I64] + [_P] * 8),
 }
 
 ABI_VERSION = 10

@@ -60,7 +60,7 @@ class BaseModel(nn.Module):
             self.match_sampler = MatchSampler()
         # fused HIP loss path for geometric data (csrc/assembly_loss.hip); the per-function path is
         # kept for the semantic datasets and as a cross-check.  keep_pts: also return the transformed
-        # clouds (only visualisation needs them).  Quaternions and rotation matrices alike.
+        # clouds (`sample_assembly` poses its own: csrc/assemble.hip).  Quaternions and rotation matrices alike.
         self.fused_loss = True
         self.keep_pts = False
         # evaluation metrics by csrc/eval_metrics.hip (two launches + one for the connectivity accuracy) instead of the
@@ -359,6 +359,30 @@ class BaseModel(nn.Module):
             schedule = cosine_warmup_lr(total, int(total * opt_cfg.warmup_ratio), opt_cfg.lr,
                                         opt_cfg.lr / opt_cfg.lr_decay_factor)
         return optimizer, schedule
+
+    @torch.no_grad()
+    def sample_assembly(self, data_dict):
+        """Assembled shapes for visualisation (base_model.py:427-460 of the reference): `sample_iter` predictions of the
+        batch in the module's current mode, then `(gt_pcs_lst, pred_pcs_lst)` — per shape the coloured ground-truth cloud
+        [p N, 6] and one coloured cloud per prediction, numpy float64 rows (x, y, z, r, g, b), the parts coloured by
+        `cfg.data.colors` in their order.  The posing, masking and colouring of all samples is one `assemble_clouds`
+        call and the result reaches the host in one copy.  The caller's dict keeps its `part_quat`."""
+        from .assemble import assemble_clouds
+
+        data_dict = dict(data_dict)
+        if "part_rot" not in data_dict:
+            part_rot = Rotation3D(data_dict.pop("part_quat"), rot_type="quat")
+            data_dict["part_rot"] = part_rot if self.rot_type == "quat" else part_rot.convert(self.rot_type)
+        part_pcs = data_dict["part_pcs"]
+        rots, trans = [], []
+        for _ in range(self.sample_iter):
+            out_dict = self.forward(data_dict)
+            rots.append(out_dict["rot"].rot)
+            trans.append(out_dict["trans"])
+        colors = torch.tensor(self.cfg.data.colors, dtype=torch.float32, device=part_pcs.device).reshape(-1, 3)
+        clouds = assemble_clouds(part_pcs, data_dict["part_valids"], torch.stack(rots), torch.stack(trans),
+                                 data_dict["part_rot"].rot, data_dict["part_trans"], colors, rot_type=self.rot_type)
+        return clouds.to_lists()
 
     def _wrap_rotation(self, rot_tensor):
         return Rotation3D(rot_tensor, rot_type=self.rot_type)

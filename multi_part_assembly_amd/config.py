@@ -35,10 +35,26 @@ def semantic_loss():
                   transform_pt_cd_loss_w=10.0, use_rot_loss=False, use_rot_pt_l2_loss=False)
 
 
+def part_palette(count=24):
+    """RGB rows (0-255) that colour the parts of an exported assembly by their order (`cfg.data.colors`).  The project's
+    own table: hues step by the golden angle, so neighbouring parts never look alike, at three alternating
+    saturation / value levels; exact integers from integer arithmetic (HSV -> RGB in sixths of the hue circle)."""
+    rows = []
+    for k in range(count):
+        hue = (k * 137) % 360                      # degrees
+        sat, val = ((200, 230), (255, 180), (140, 255))[k % 3]
+        c = val * sat // 255
+        x = c * (60 - abs(hue % 120 - 60)) // 60
+        m = val - c
+        r, g, b = ((c, x, 0), (x, c, 0), (0, c, x), (0, x, c), (x, 0, c), (c, 0, x))[hue // 60]
+        rows.append((r + m, g + m, b + m))
+    return tuple(rows)
+
+
 def breaking_bad_everyday():
-    """configs/_base_/datasets/breaking_bad/everyday.py:5-16."""
+    """configs/_base_/datasets/breaking_bad/everyday.py:5-16 (+ the colour table of exported assemblies)."""
     return Config(dataset="geometry", data_keys=("part_ids",), num_pc_points=1000, min_num_part=2,
-                  max_num_part=20)
+                  max_num_part=20, colors=part_palette())
 
 
 def adam_cosine():
@@ -66,7 +82,7 @@ def pn_transformer_everyday():
 def partnet_chair():
     """configs/_base_/datasets/partnet/partnet_chair.py:5-16."""
     return Config(dataset="partnet", data_keys=("part_ids", "match_ids", "contact_points"), num_pc_points=1000,
-                  num_part_category=57, min_num_part=2, max_num_part=20)
+                  num_part_category=57, min_num_part=2, max_num_part=20, colors=part_palette())
 
 
 def dgl_model():

@@ -424,6 +424,15 @@ class DeviceGeometryProducer:
                 slot[b, :p] = slot[b, order]
         return slot, valid
 
+    def slot_parts(self, indices):
+        """The store part id behind every slot of the batch `indices`: numpy int64 [B, P], -1 in padded slots — what
+        `assemble.pose_meshes` needs to find the meshes of a batch's parts.  Refused with `shuffle_parts`: the order
+        of a batch already drawn is not kept (evaluation never shuffles)."""
+        if self.shuffle_parts:
+            raise RuntimeError("DeviceGeometryProducer.slot_parts: with shuffle_parts the slots of a batch are drawn anew "
+                               "in every call, so the table would not describe any batch")
+        return self._slots(indices)[0]
+
     def _run(self, indices, stream_ids=None, uniforms=None, rot=None, perm=None, quat=None, return_raw=False):
         dev = self.device
         if dev.type != "cuda":

@@ -1,0 +1,199 @@
+"""Cost of turning predictions into assembled shapes: the reference's op sequence on library operators against the fused
+path (csrc/assemble.hip), B = 32, P = 20, N = 1000, sample_iter = 5, part counts of `bench.representative_parts`.  The
+model's forwards are excluded from both arms: the poses are given.  One JSON line:
+
+  clouds_ms_ref      ms per `sample_assembly` tail the host-bound way of the reference (`host_bound_tail` below):
+                     `transform_pc` per sample, then per sample and per shape a boolean-mask gather, a blocking copy to
+                     the host and a Python loop over the parts for the colours
+  clouds_ms_fused    ms for `assemble_clouds` + `AssembledClouds.to_lists()`
+  clouds_ms_fused_device  ms for `assemble_clouds` alone (windows end in a device synchronise)
+  *_windows          both arms in ONE process, alternating windows after a warm-up; each figure is a host clock around a
+                     window that ends in a device synchronise, divided by its calls; the median of the windows is reported
+  *_launches / *_copies / *_host_syncs   device kernels, device-side memcpy events and blocking device-to-host
+                     transfers of ONE call (torch profiler; the transfers counted at `Tensor.cpu` / `Tensor.copy_`)
+  mesh_ms_fused / mesh_ms_numpy   `pose_meshes` (one launch + one copy to the host) on 32 shapes of 5000-face parts
+                     against the same float64 algebra in numpy on the host's copy of the store
+
+GPU only:  python tools/assembly_rate.py [--calls 10] [--windows 5] [--out profiles/r12_assembly_rate.json]"""
+import argparse
+import importlib.util
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from multi_part_assembly_amd import assemble, config, datasets, synthetic  # noqa: E402
+from multi_part_assembly_amd.rotation import Rotation3D  # noqa: E402
+from multi_part_assembly_amd.transforms import transform_pc  # noqa: E402
+
+
+def representative_parts(seed):
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench.representative_parts("everyday", seed)
+
+
+def window(fn, calls):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(calls):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / calls
+
+
+def coloured_rows_on_host(posed_shape, valid_row, palette):
+    """One shape of one slab the host-bound way: make the boolean mask, gather the valid parts with it on the device,
+    copy them to the host (a blocking transfer), and paint them part by part in a Python loop -> float64 [p N, 6]."""
+    parts = posed_shape[valid_row.bool()].cpu().numpy()
+    table = np.zeros(parts.shape[:2] + (6,))
+    table[..., :3] = parts
+    for k, rgb in enumerate(palette[:len(parts)]):
+        table[k, :, 3:] = rgb
+    return table.reshape(-1, 6)
+
+
+def host_bound_tail(part_pcs, valids, rots, trans, gt_rot, gt_trans, palette):
+    """The comparison arm: the operations the reference's `sample_assembly` issues behind its forwards, on this
+    library's operators -- one `transform_pc` per prediction and one for the ground truth, then for every prediction
+    and every shape `coloured_rows_on_host`, and once more per shape for the ground truth: (S + 1) B masks, gathers and
+    blocking copies, nothing hoisted or batched.  Returns the structure of `AssembledClouds.to_lists()`."""
+    slabs = [transform_pc(t, r, part_pcs) for r, t in zip(rots, trans)]
+    truth = transform_pc(gt_trans, gt_rot, part_pcs)
+    predicted = [[coloured_rows_on_host(slab[b], mask, palette) for slab in slabs] for b, mask in enumerate(valids)]
+    return [coloured_rows_on_host(truth[b], mask, palette) for b, mask in enumerate(valids)], predicted
+
+
+def census(fn):
+    """(device kernels, device-side memcpy events, blocking device-to-host transfers) of one call of `fn`."""
+    from torch.autograd import DeviceType
+    from torch.profiler import ProfilerActivity, profile
+    syncs = [0]
+    cpu, copy_ = torch.Tensor.cpu, torch.Tensor.copy_
+
+    def counted_cpu(t, *a, **k):
+        syncs[0] += bool(t.is_cuda)
+        return cpu(t, *a, **k)
+
+    def counted_copy(t, src, *a, **k):
+        syncs[0] += bool((not t.is_cuda) and torch.is_tensor(src) and src.is_cuda)
+        return copy_(t, src, *a, **k)
+
+    fn()
+    torch.cuda.synchronize()
+    torch.Tensor.cpu, torch.Tensor.copy_ = counted_cpu, counted_copy
+    try:
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+    finally:
+        torch.Tensor.cpu, torch.Tensor.copy_ = cpu, copy_
+    device = [e.name for e in prof.events() if e.device_type == DeviceType.CUDA]
+    copies = [n for n in device if "memcpy" in n.lower() or "memset" in n.lower() or "copyBuffer" in n or "fillBuffer" in n]
+    return len(device) - len(copies), len(copies), syncs[0]
+
+
+def mesh_algebra_numpy(store, slot_part, gt_rmat, gt_trans, pred_rmat, pred_trans):
+    """The arithmetic of mpa_mesh_pose_parts in numpy float64, float32 results."""
+    outs = ([], [], [])
+    for m, part in enumerate(slot_part):
+        if part < 0:
+            continue
+        rows = store.tri[store.part_face_off[part]:store.part_face_off[part + 1]]
+        Rg, Rp = gt_rmat[m].astype(np.float64), pred_rmat[m].astype(np.float64)
+        v = np.stack([rows[:, 0:3], rows[:, 0:3] + rows[:, 3:6], rows[:, 0:3] + rows[:, 6:9]], axis=1)
+        inp = (v - gt_trans[m].astype(np.float64)) @ Rg
+        pred = inp @ Rp.T + pred_trans[m].astype(np.float64)
+        for o, a in zip(outs, (v, inp, pred)):
+            o.append(a.astype(np.float32))
+    return tuple(np.concatenate(o) for o in outs)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=10)
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    B, P, N, S = 32, 20, 1000, 5
+    result = {"B": B, "P": P, "N": N, "sample_iter": S, "calls_per_window": args.calls, "windows": args.windows}
+    batch = synthetic.make_batch(B, P, N, seed=1234, device=dev, num_parts=representative_parts(1234))
+    result["valid_parts"] = int(sum(batch["num_parts"]))
+    g = torch.Generator().manual_seed(0)
+    quat = torch.nn.functional.normalize(torch.randn(S, B, P, 4, generator=g), dim=-1).to(dev)
+    trans = (torch.randn(S, B, P, 3, generator=g) * 0.3).to(dev)
+    part_pcs, valids = batch["part_pcs"], batch["part_valids"]
+    gt_rot, gt_trans = Rotation3D(batch["part_quat"], "quat"), batch["part_trans"]
+    rots = [Rotation3D(quat[s], "quat") for s in range(S)]
+    colors_host = np.array(config.pn_transformer_everyday().data.colors)
+    colors = torch.tensor(colors_host, dtype=torch.float32, device=dev)
+    out = assemble.AssembledClouds.empty(B, P, N, S, dev)
+
+    ref = lambda: host_bound_tail(part_pcs, valids, rots, trans, gt_rot, gt_trans, colors_host)
+    launch = lambda: assemble.assemble_clouds(part_pcs, valids, quat, trans, gt_rot.rot, gt_trans, colors,
+                                              rot_type="quat", out=out)
+    fused = lambda: launch().to_lists()
+    a, b = ref(), fused()
+    assert all(np.array_equal(x, y) for x, y in zip(a[0], b[0]))
+    assert all(np.array_equal(x, y) for xs, ys in zip(a[1], b[1]) for x, y in zip(xs, ys))
+    result["arms_agree_bitwise"] = True
+    arms = {"ref": ref, "fused": fused, "fused_device": launch}
+    for fn in arms.values():
+        window(fn, 2)
+    times = {k: [] for k in arms}
+    for _ in range(args.windows):
+        for k, fn in arms.items():
+            times[k].append(window(fn, args.calls))
+    for k, v in times.items():
+        result[f"clouds_ms_{k}"] = round(statistics.median(v), 4)
+        result[f"clouds_ms_{k}_windows"] = [round(t, 4) for t in v]
+    for k in ("ref", "fused"):
+        result[f"clouds_{k}_launches"], result[f"clouds_{k}_copies"], result[f"clouds_{k}_host_syncs"] = census(arms[k])
+    result["clouds_bytes_used"] = int(24 * (S + 1) * N * result["valid_parts"])
+    result["clouds_bytes_copied"] = int(out.packed.numel())
+
+    shapes = synthetic.make_fracture_meshes(77, B, representative_parts(1234), 5000)
+    store = datasets.MeshStore.from_arrays(shapes, max_num_part=P)
+    prod = datasets.DeviceGeometryProducer(store, num_points=N, max_num_part=P, device=dev)
+    slots = prod.slot_parts(list(range(B)))
+    result["mesh_parts"], result["mesh_faces"] = int((slots >= 0).sum()), int(len(store.tri))
+    posed = None
+
+    def mesh_fused():
+        nonlocal posed
+        posed = assemble.pose_meshes(store, slots, batch["part_quat"], gt_trans, quat[0], trans[0], rot_type="quat",
+                                     out=posed)
+        return posed.to_host()
+
+    g_rmat = gt_rot.to_rmat().reshape(-1, 3, 3).cpu().numpy()
+    p_rmat = rots[0].to_rmat().reshape(-1, 3, 3).cpu().numpy()
+    g_t, p_t = gt_trans.reshape(-1, 3).cpu().numpy(), trans[0].reshape(-1, 3).cpu().numpy()
+    mesh_numpy = lambda: mesh_algebra_numpy(store, slots.reshape(-1), g_rmat, g_t, p_rmat, p_t)
+    x, y = mesh_fused(), mesh_numpy()
+    result["mesh_max_abs_diff"] = float(max(np.abs(p - q).max() for p, q in zip(x, y)))
+    marms = {"fused": mesh_fused, "numpy": mesh_numpy}
+    mtimes = {k: [] for k in marms}
+    for _ in range(args.windows):
+        for k, fn in marms.items():
+            mtimes[k].append(window(fn, max(1, args.calls // 5)))
+    for k, v in mtimes.items():
+        result[f"mesh_ms_{k}"] = round(statistics.median(v), 4)
+        result[f"mesh_ms_{k}_windows"] = [round(t, 4) for t in v]
+    result["mesh_fused_launches"], result["mesh_fused_copies"], result["mesh_fused_host_syncs"] = census(mesh_fused)
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
