@@ -650,6 +650,42 @@ int mpa_mesh_sample_batch(const double* tri, const double* cum_area, const int64
                           const int64_t* slot_part, int64_t M, int64_t N, const double* uniforms, const double* rot,
                           const int32_t* perm, uint64_t seed, const int64_t* stream_id, double rot_range,
                           float* part_pcs, float* part_trans, float* part_quat, double* raw_out, void* stream);
+/* mpa_mesh_slot_table (csrc/mesh_sample.hip): the slot tables of mpa_mesh_sample_batch for B shapes whose indices
+ * shape_index [B] int64 live in DEVICE memory, from the store's shape_part_off [S+1] int64.  For slot m = b * P + j with
+ * p = the part count of shape shape_index[b]: slot_part [B*P] int64 = shape_part_off[s] + j for j < p, -1 otherwise;
+ * stream_id [B*P] int64 = stream_base + m (mod 2^64); valids [B*P] float32 = 1 for j < p, else 0; part_ids [B*P] float32 =
+ * j for j < p, else 0 — what datasets.DeviceGeometryProducer builds on the host from host indices.
+ *   Checked at run time, because they come from device memory: a shape index outside [0, S) reads nothing from
+ * shape_part_off and stores 1 into the device word `status`; a part count outside [min_part, max_part] stores 2.  Either
+ * way all P slots of that shape are padded (slot_part -1, valids 0).  The kernel never clears `status`.
+ *   MPA_EINVAL (before any launch): negative B / S, B > 2^24, P outside [1, 4096], limits that do not satisfy 0 <= min_part
+ * <= max_part <= P, a NULL pointer.  B == 0 with valid sizes is MPA_OK. */
+int mpa_mesh_slot_table(const int64_t* shape_part_off, int64_t S, const int64_t* shape_index, int64_t B, int64_t P,
+                        int64_t min_part, int64_t max_part, uint64_t stream_base, int64_t* slot_part,
+                        int64_t* stream_id, float* valids, float* part_ids, int32_t* status, void* stream);
+
+/* ---- the sample order of an epoch (csrc/epoch_order.hip) --------------------------------------------------------------
+ * Replaces torch.randperm + DistributedSampler behind the reference's loaders (multi_part_assembly/datasets/
+ * geometry_data.py:226-248, scripts/train.py:57-120) with two launches; multi_part_assembly_amd/sampler_ref.py restates
+ * the definition in numpy.
+ *   key_i, i = 0..S-1, is the 64-bit word x | (y << 32) of the Philox4x32-10 block with key = (seed low word, seed high
+ * word) and counter = (i, 0x65700000, e low word, e high word), e = (epoch_dev != NULL ? *epoch_dev : epoch) as an unsigned
+ * 64-bit number.  Word 1 of the counter is one no other user of the generator produces (mpa_mesh_sample_batch: below 4;
+ * mpa_match_sample_indices: 0x6D61xxxx; mpa_partnet_gather_batch: 0x706Exxxx), so equal seeds give unrelated streams.
+ *   perm = 0..S-1 sorted ascending by (key_i, i): a stable argsort, ties cannot make it ambiguous.
+ *   Sharding as torch.utils.data.DistributedSampler(shuffle=True, drop_last=False): total = ceil(S / world) * world;
+ * padded[q] = perm[q mod S] for q < total (perm followed by its first total - S entries, repeated where world > 2 S);
+ * out [total / world] int64 = padded[rank], padded[rank + world], padded[rank + 2 world], ...  Every rank computes the same
+ * permutation from (seed, e): no communication.  Exactly total / world entries of `out` are written.
+ *   A captured HIP graph passes epoch_dev, a DEVICE word the host rewrites between replays.  Deterministic: ranks are
+ * counted (rank_i = the number of j with (key_j, j) < (key_i, i), S^2 comparisons against LDS tiles), every entry is
+ * written once, no atomics; no memset / memcpy nodes: capturable.
+ *   workspace: mpa_epoch_order_workspace(S) bytes (8 S: the keys), 8-byte aligned, caller-owned.  S <= 2^18 = 262144.
+ *   MPA_EINVAL (before any launch, no device needed): S <= 0, world outside [1, 2^20], rank outside [0, world), S above
+ * the maximum, a NULL or misaligned workspace, NULL out. */
+int mpa_epoch_order_workspace(int64_t S, int64_t* bytes);
+int mpa_epoch_order(int64_t S, int64_t world, int64_t rank, uint64_t seed, int64_t epoch, const int64_t* epoch_dev,
+                    void* workspace, int64_t* out, void* stream);
 
 /* PartNet batches gathered from a device-resident store (csrc/partnet_gather.hip): one launch writes the whole data_dict
  * of PartNetPartDataset.__getitem__ + default collate (multi_part_assembly/datasets/partnet_data.py:127-243) for B shapes.

@@ -47,6 +47,9 @@ SIGNATURES: dict[str, tuple] = {
     "mpa_loss_reduce_backward": (_INT, [_P, _P, _P, _I64, _I64, _P, _P]),
     "mpa_part_batch_transform": (_INT, [_P] * 4 + [_I64, _I64, _P, _P, _P]),
     "mpa_mesh_sample_batch": (_INT, [_P, _P, _P, _I64, _P, _I64, _I64, _P, _P, _P, _U64, _P, _c.c_double, _P, _P, _P, _P, _P]),
+    "mpa_mesh_slot_table": (_INT, [_P, _I64, _P, _I64, _I64, _I64, _I64, _U64, _P, _P, _P, _P, _P, _P]),
+    "mpa_epoch_order_workspace": (_INT, [_I64, _P]),
+    "mpa_epoch_order": (_INT, [_I64, _I64, _I64, _U64, _I64, _P, _P, _P, _P]),
     "mpa_partnet_gather_batch": (_INT, [_P] * 9 + [_I64, _P] + [_I64] * 4 + [_P, _INT, _U64, _U64, _P] + [_P] * 15),
     "mpa_assembly_loss_forward": (_INT, [_P] * 6 + [_I64, _I64, _I64, _INT, _INT, _P, _P, _P, _P]),
     "mpa_assembly_loss_forward_timed": (_INT, [_P] * 6 + [_I64, _I64, _I64, _INT, _INT, _P, _P, _P, _P, _P]),

@@ -156,7 +156,58 @@ __global__ __launch_bounds__(kThreads) void mesh_sample_kernel(
     mpa::part_transform_block<false>(pts, rot_lds, nullptr, N, out, part_trans + 3 * m);
 }
 
+// The [B, P] slot table of a batch whose shape indices live in device memory: one thread per slot.  A shape index outside
+// [0, S) (status 1) or a part count outside [min_part, max_part] (status 2) marks every slot of that shape padded; for a
+// bad index nothing of shape_part_off is read.
+__global__ __launch_bounds__(kThreads) void mesh_slot_table_kernel(
+    const int64_t* __restrict__ shape_part_off, int64_t S, const int64_t* __restrict__ shape_index, int64_t M, int P,
+    int min_part, int max_part, uint64_t stream_base, int64_t* __restrict__ slot_part, int64_t* __restrict__ stream_id,
+    float* __restrict__ valids, float* __restrict__ part_ids, int32_t* __restrict__ status) {
+  const int64_t m = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (m >= M) return;
+  const int64_t b = m / P;
+  const int j = (int)(m % P);
+  const int64_t s = shape_index[b];
+  int64_t start = 0, count = 0;
+  int bad = 0;
+  if (s < 0 || s >= S) {
+    bad = 1;
+  } else {
+    start = shape_part_off[s];
+    count = shape_part_off[s + 1] - start;
+    if (count < min_part || count > max_part) {
+      bad = 2;
+      count = 0;
+    }
+  }
+  if (bad && j == 0) *status = bad;
+  const bool live = j < count;
+  slot_part[m] = live ? start + j : -1;
+  stream_id[m] = (int64_t)(stream_base + (uint64_t)m);
+  valids[m] = live ? 1.0f : 0.0f;
+  part_ids[m] = live ? (float)j : 0.0f;
+}
+
 }  // namespace
+
+extern "C" int mpa_mesh_slot_table(const int64_t* shape_part_off, int64_t S, const int64_t* shape_index, int64_t B,
+                                   int64_t P, int64_t min_part, int64_t max_part, uint64_t stream_base,
+                                   int64_t* slot_part, int64_t* stream_id, float* valids, float* part_ids,
+                                   int32_t* status, void* stream) {
+  MPA_REQUIRE(B >= 0 && S >= 0 && B <= (1LL << 24), "mesh_slot_table: negative or oversized B / S (B <= 2^24)");
+  MPA_REQUIRE(P >= 1 && P <= 4096, "mesh_slot_table: P=%lld outside [1, 4096]", (long long)P);
+  MPA_REQUIRE(min_part >= 0 && min_part <= max_part && max_part <= P,
+              "mesh_slot_table: part limits [%lld, %lld] do not fit the %lld slots of a shape", (long long)min_part,
+              (long long)max_part, (long long)P);
+  if (B == 0) return MPA_OK;
+  MPA_REQUIRE(shape_part_off && shape_index && slot_part && stream_id && valids && part_ids && status,
+              "mesh_slot_table: null pointer");
+  const int64_t M = B * P;
+  hipLaunchKernelGGL(mesh_slot_table_kernel, dim3((unsigned)((M + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                     mpa::as_stream(stream), shape_part_off, S, shape_index, M, (int)P, (int)min_part, (int)max_part,
+                     stream_base, slot_part, stream_id, valids, part_ids, status);
+  return mpa::check_launch("mesh_slot_table");
+}
 
 extern "C" int mpa_mesh_sample_batch(const double* tri, const double* cum_area, const int64_t* part_face_off,
                                      int64_t parts_total, const int64_t* slot_part, int64_t M, int64_t N,

@@ -278,6 +278,7 @@ class MeshStore:
             raise ValueError("MeshStore: a part with zero (or non-finite) total area cannot be sampled")
         _check_store_bytes(self.nbytes, max_bytes)
         self._device = {}
+        self._device_off = {}
 
     @property
     def nbytes(self):
@@ -359,6 +360,17 @@ class MeshStore:
                                          for a in (self.tri, self.cum_area, self.part_face_off))
         return self._device[device]
 
+    def device_shape_part_off(self, device):
+        """`shape_part_off` on `device`, uploaded at the first call: what builds a batch's slot table from device indices."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("MeshStore: the mesh sampler runs on the HIP device only (there is no CPU fallback)")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device not in self._device_off:
+            self._device_off[device] = torch.from_numpy(self.shape_part_off).to(device)
+        return self._device_off[device]
+
 
 def _check_store_bytes(nbytes, max_bytes, what="MeshStore"):
     if max_bytes is not None and nbytes > max_bytes:
@@ -400,6 +412,7 @@ class DeviceGeometryProducer:
         self.device = torch.device(device)
         self.shuffle_parts = shuffle_parts
         self.batch_counter = 0  # the default `batch_counter` of the next batch() call
+        self._status = None     # device word of the device-index path (csrc/mesh_sample.hip, mesh_slot_table)
 
     def __len__(self):
         return self.store.num_shapes
@@ -483,10 +496,78 @@ class DeviceGeometryProducer:
             out["valid_matrix"] = d_val[:, :, None] * d_val[:, None, :]
         return (out, raw) if return_raw else out
 
+    def _run_device(self, indices, batch_counter, return_raw=False):
+        """`batch` for a device index vector: the slot table is built by `mpa_mesh_slot_table` from the store's
+        `shape_part_off`, the sampler launch behind it is the host path's."""
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError("DeviceGeometryProducer: the mesh sampler runs on the HIP device only "
+                               "(there is no CPU fallback)")
+        if indices.dtype != torch.int64 or indices.dim() != 1 or not indices.is_contiguous():
+            raise ValueError("DeviceGeometryProducer: device indices must be a contiguous int64 vector")
+        if self.shuffle_parts:
+            raise ValueError("DeviceGeometryProducer: shuffle_parts draws its part orders on the host (random.shuffle) "
+                             "and is not available with device indices")
+        B, P, N = indices.numel(), self.max_num_part, self.num_points
+        M = B * P
+        with torch.cuda.device(dev):
+            tri, cum, pf = self.store.device_arrays(dev)
+            off = self.store.device_shape_part_off(dev)
+            if self._status is None:
+                self._status = torch.zeros(1, dtype=torch.int32, device=dev)
+            d64 = torch.empty((2, B, P), dtype=torch.int64, device=dev)
+            d32 = torch.empty((2, B, P), dtype=torch.float32, device=dev)
+            part_pcs = torch.empty((B, P, N, 3), dtype=torch.float32, device=dev)
+            part_trans = torch.empty((B, P, 3), dtype=torch.float32, device=dev)
+            part_quat = torch.empty((B, P, 4), dtype=torch.float32, device=dev)
+            raw = torch.empty((B, P, N, 3), dtype=torch.float64, device=dev) if return_raw else None
+            _lib.launch("mpa_mesh_slot_table", dev, off, self.store.num_shapes, indices, B, P, self.min_num_part,
+                        self.max_num_part, (int(batch_counter) * M) & 0xFFFFFFFFFFFFFFFF, d64[0], d64[1], d32[0], d32[1],
+                        self._status)
+            _lib.launch("mpa_mesh_sample_batch", dev, tri, cum, pf, self.store.num_parts, d64[0], M, N, None, None, None,
+                        self.seed, d64[1], self.rot_range, part_pcs, part_trans, part_quat, raw)
+        d_val = d32[0]
+        out = {
+            "part_pcs": part_pcs,
+            "part_quat": part_quat,
+            "part_trans": part_trans,
+            "part_valids": d_val,
+            "data_id": indices,
+            "instance_label": torch.zeros((B, P, 0), dtype=torch.float32, device=dev),
+            "part_label": torch.zeros((B, P, 0), dtype=torch.float32, device=dev),
+        }
+        if "part_ids" in self.data_keys:
+            out["part_ids"] = d32[1]
+        if "valid_matrix" in self.data_keys:
+            out["valid_matrix"] = d_val[:, :, None] * d_val[:, None, :]
+        return (out, raw) if return_raw else out
+
+    def check(self):
+        """RuntimeError if a device-index batch since the last check held a shape index outside the store or a shape whose
+        part count is outside [min_num_part, max_num_part]; synchronises.  The word is cleared as it is reported."""
+        if self._status is None:
+            return
+        code = int(self._status.item())
+        if code:
+            self._status.zero_()
+            what = "a shape index outside the store" if code == 1 else \
+                f"a shape with a part count outside [{self.min_num_part}, {self.max_num_part}]"
+            raise RuntimeError(f"DeviceGeometryProducer: a batch met {what}; that shape was written as padding")
+
     def batch(self, indices: Sequence[int], batch_counter: int | None = None, return_raw=False):
         """The `data_dict` of the shapes `indices`, sampled, rotated and cast on the device.  `batch_counter` selects the
         random streams (default: the number of batches drawn so far); with `return_raw` also the sampled float64 cloud
-        [B, P, N, 3] before the transform, as a second result."""
+        [B, P, N, 3] before the transform, as a second result.
+
+        `indices`: a host sequence, or a device int64 vector (for instance a batch of `sampler.EpochSampler`): then the
+        slot table is built on the device too, `data_id` is that vector, the bits are those of the host sequence with
+        the same values, and a bad index is reported by `check()` instead of an exception here (the host never sees
+        the values).  `shuffle_parts` is refused with device indices."""
+        if isinstance(indices, torch.Tensor) and indices.device.type == "cuda":
+            if batch_counter is None:
+                batch_counter = self.batch_counter
+                self.batch_counter += 1
+            return self._run_device(indices, batch_counter, return_raw=return_raw)
         indices = list(indices)
         if batch_counter is None:
             batch_counter = self.batch_counter

@@ -52,8 +52,10 @@ class Trainer:
                           "and decoder noise are drawn on the host every forward); running eager launches")
             use_graph = False
         self.use_graph, self.graph_warmup = use_graph, graph_warmup
+        self._fit_pending = None  # what `resume` read for the next `fit` (fit.py)
         self._graph, self._static_batch, self._static_loss, self._eager_steps = None, None, None, 0
         cfg = cfg if cfg is not None else model.cfg
+        self.cfg = cfg
         opt = cfg.optimizer
         self.flat = FlatBuffers(ordered_parameters(model))
         # weight decay > 0 -> AdamW with biases / normalisation weights exempt (base_model.py:394-404); clip_grad ->
@@ -163,6 +165,27 @@ class Trainer:
         self.epoch = epoch
         if self.schedule is not None:
             self.optimizer.lr = self.schedule(epoch)
+
+    @property
+    def rank(self):
+        return dist.get_rank(self.group) if dist.is_initialized() else 0
+
+    def fit(self, train_producer, sampler, val_batches=None, epochs=None, val_every=None, ckpt_dir=None, keep=5,
+            monitor="val/part_acc", log_every=50, on_log=None, max_steps=None):
+        """The epoch loop (fit.fit has the contract): order of the epoch from `sampler` (sampler.EpochSampler), batches
+        from `train_producer`, the schedule, validation every `val_every` epochs, the best `keep` checkpoints by
+        `monitor` plus `last.pt` in `ckpt_dir`.  Continues from the epoch a preceding `resume` returned.  Returns the
+        history, one dict per epoch."""
+        from . import fit as _fit
+        return _fit.fit(self, train_producer, sampler, val_batches=val_batches, epochs=epochs, val_every=val_every,
+                        ckpt_dir=ckpt_dir, keep=keep, monitor=monitor, log_every=log_every, on_log=on_log,
+                        max_steps=max_steps)
+
+    def resume(self, ckpt_dir):
+        """Load `ckpt_dir/last.pt` if it exists (model, optimiser, schedule, seed positions now; sampler position, producer
+        counters and generator states when the next `fit` starts).  Returns the epoch to continue from."""
+        from . import fit as _fit
+        return _fit.resume(self, ckpt_dir)
 
     # ---- graph mode -----------------------------------------------------------------------------------
     @property
