@@ -872,6 +872,41 @@ int mpa_mesh_pose_parts(const double* tri, const int64_t* part_face_off, int64_t
                         const float* gt_rmat, const float* gt_trans, const float* pred_rmat, const float* pred_trans,
                         float* orig, float* input, float* pred, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Contact points of a batch (csrc/contact_points.hip) -- the table `calc_connectivity_acc` consumes
+ * (multi_part_assembly/utils/eval_utils.py:56-99).  The reference only ever loads it from the PartNet release's
+ * `contact_points/pairs_with_contact_points_*.npy` files (datasets/partnet_data.py:210-222); here it is computed from
+ * what a batch carries, by an all-pairs closest-pair search between the posed parts.
+ *
+ * Inputs, contiguous fp32: part_pcs [B, P, N, 3] canonical; valids [B, P] (a part is real iff its entry == 1);
+ * trans [B, P, 3]; rotations as quaternions [B, P, 4] (real part first, not normalised; Rotation3D's zero-quaternion
+ * rule is applied: norm <= 0.5 -> identity, the test of mpa_quat_sanitize) or, for the _rmat twin, row-major matrices
+ * [B, P, 3, 3]; thre_sq, a bound on the SQUARED distance.  Inputs are finite.
+ * Arithmetic: posed_i[a] is the coordinate mpa_pose_apply[_rmat]_forward gives for point a of part i, bit for bit;
+ * d(a, c) = (dx*dx + dy*dy) + dz*dz with every operation rounded -- the Chamfer contract above.
+ * For every sample and every pair i < j of real parts, (a*, c*) is the lexicographically first minimiser of
+ * d(posed_i[a], posed_j[c]) (lowest a, then lowest c) and dmin that minimum.
+ *   contact_points [B, P, P, 4]: dmin < thre_sq: row [b, i, j] = (1, part_pcs[b, i, a*]) and row [b, j, i] =
+ *     (1, part_pcs[b, j, c*]) -- CANONICAL coordinates, copied bit for bit (the metric poses them itself); otherwise both
+ *     rows are zeros.  The diagonal and every row and column of a padded slot are zeros.
+ *   min_dist [B, P, P] (NULL: skipped): symmetric, dmin of every real pair whatever the flag, 1e32 on the diagonal and
+ *     in padded slots.
+ *   index [B, P, P] int32 (NULL: skipped): [b, i, j] = a*, [b, j, i] = c*, -1 on the diagonal and in padded slots.
+ * Every element of every output is written on every call.  Padded slots are never read: NaN in their points and poses
+ * changes no output bit.  One launch, no atomics, a fixed reduction order, no host synchronisation, a launch
+ * configuration that depends on the sizes only: capturable, bit-identical from run to run.  When neither min_dist nor
+ * index is requested, a pair whose posed bounding boxes are at least thre_sq apart (the gap evaluated with the same
+ * rounded formula, a lower bound of every computed d) is not searched; the outputs are those of the full search.
+ * Envelope: 1 <= N <= 2048 (both posed parts live in LDS, 24 N bytes), 1 <= P <= 64, B >= 0, 4 * B * P * P < 2^31;
+ * outside it the call is refused with MPA_EINVAL.  No workspace.
+ * ---------------------------------------------------------------------------------------------- */
+int mpa_contact_points(const float* part_pcs, const float* valids, const float* quat, const float* trans, float thre_sq,
+                       int64_t B, int64_t P, int64_t N, float* contact_points, float* min_dist, int32_t* index,
+                       void* stream);
+int mpa_contact_points_rmat(const float* part_pcs, const float* valids, const float* rmat, const float* trans,
+                            float thre_sq, int64_t B, int64_t P, int64_t N, float* contact_points, float* min_dist,
+                            int32_t* index, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -128,6 +128,8 @@ SIGNATURES: dict[str, tuple] = {
     "mpa_assemble_clouds": (_INT, [_P] * 7 + [_I64] * 5 + [_P, _P, _P]),
     "mpa_assemble_clouds_rmat": (_INT, [_P] * 7 + [_I64] * 5 + [_P, _P, _P]),
     "mpa_mesh_pose_parts": (_INT, [_P, _P, _I64, _P, _P, _I64, _I64, _I64] + [_P] * 8),
+    "mpa_contact_points": (_INT, [_P, _P, _P, _P, _F32, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "mpa_contact_points_rmat": (_INT, [_P, _P, _P, _P, _F32, _I64, _I64, _I64, _P, _P, _P, _P]),
 }
 
 ABI_VERSION = 10

@@ -188,14 +188,16 @@ class BaseModel(nn.Module):
 
     @torch.no_grad()
     def _calc_metrics(self, data_dict, out_dict, gt_trans, gt_rot):
-        """Evaluation-time metrics (base_model.py:316-339): part accuracy always; connectivity accuracy for the
-        semantic datasets that annotate contacts; translation / rotation MSE, RMSE, MAE for geometric data."""
+        """Evaluation-time metrics (base_model.py:316-339): part accuracy always; connectivity accuracy whenever the batch
+        carries `contact_points` (the reference: semantic data only, the one kind it has contact files for; here the
+        table can be computed for any batch, `contacts.contact_points`); translation / rotation MSE, RMSE, MAE for
+        geometric data."""
         part_pcs, valids = data_dict["part_pcs"], data_dict["part_valids"]
         pred_trans, pred_rot = out_dict["trans"], out_dict["rot"]
         if self.fused_metrics:
             fused = assembly_metrics(part_pcs, pred_trans, gt_trans, pred_rot, gt_rot, valids)
             metrics = {"part_acc": fused["part_acc"]}
-            if self.semantic and "contact_points" in data_dict:
+            if "contact_points" in data_dict:
                 metrics["connectivity_acc"] = calc_connectivity_acc(pred_trans, pred_rot, data_dict["contact_points"],
                                                                     fused=True)
             if not self.semantic:
@@ -204,7 +206,7 @@ class BaseModel(nn.Module):
                     metrics[f"rot_{m}"] = fused[f"rot_{m}"]
             return metrics
         metrics = {"part_acc": calc_part_acc(part_pcs, pred_trans, gt_trans, pred_rot, gt_rot, valids)}
-        if self.semantic and "contact_points" in data_dict:
+        if "contact_points" in data_dict:
             metrics["connectivity_acc"] = calc_connectivity_acc(pred_trans, pred_rot, data_dict["contact_points"])
         if not self.semantic:
             for m in ("mse", "rmse", "mae"):

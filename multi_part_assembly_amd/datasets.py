@@ -395,10 +395,15 @@ class DeviceGeometryProducer:
     uniformly random rotation; `> 0`: Euler angles uniform in [-rot_range, rot_range] degrees, as the reference.
     `shuffle_parts` permutes the parts of each shape with `random.shuffle`, like the reference.
 
-    `.replay` feeds host-drawn uniforms / rotations / point orders through the same kernel, for parity tests."""
+    `.replay` feeds host-drawn uniforms / rotations / point orders through the same kernel, for parity tests.
+
+    The data key `"contact_points"` (not one of the reference's geometry keys: its fracture data carries no contact
+    annotation) adds the table `contacts.contact_points` computes from the batch's own sampled clouds and ground-truth
+    poses, with `contact_thre` as its bound on the squared distance — one more launch (csrc/contact_points.hip); every
+    other entry of the batch is what it is without the key."""
 
     def __init__(self, store: MeshStore, num_points=1000, min_num_part=2, max_num_part=20, rot_range=-1,
-                 data_keys=("part_ids",), seed=0, device="cuda", shuffle_parts=False):
+                 data_keys=("part_ids",), seed=0, device="cuda", shuffle_parts=False, contact_thre=0.01):
         if not 1 <= num_points <= MAX_DEVICE_SAMPLE_POINTS:
             raise ValueError(f"DeviceGeometryProducer: num_points={num_points} outside [1, {MAX_DEVICE_SAMPLE_POINTS}]")
         self.store = store
@@ -406,13 +411,21 @@ class DeviceGeometryProducer:
         self.rot_range = float(rot_range)
         self.data_keys = tuple(data_keys)
         for key in self.data_keys:
-            if key not in ("part_ids", "valid_matrix"):
+            if key not in ("part_ids", "valid_matrix", "contact_points"):
                 raise ValueError(f"ERROR: unknown data {key}")
+        self.contact_thre = float(contact_thre)
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.device = torch.device(device)
         self.shuffle_parts = shuffle_parts
         self.batch_counter = 0  # the default `batch_counter` of the next batch() call
         self._status = None     # device word of the device-index path (csrc/mesh_sample.hip, mesh_slot_table)
+
+    def _add_contacts(self, out):
+        """The `contact_points` entry of a finished batch: the table of its own clouds and ground-truth poses."""
+        if "contact_points" in self.data_keys:
+            from .contacts import contact_points
+            out["contact_points"] = contact_points(out["part_pcs"], out["part_valids"], out["part_quat"], out["part_trans"],
+                                                   thre=self.contact_thre)
 
     def __len__(self):
         return self.store.num_shapes
@@ -494,6 +507,7 @@ class DeviceGeometryProducer:
             out["part_ids"] = d32[1]
         if "valid_matrix" in self.data_keys:
             out["valid_matrix"] = d_val[:, :, None] * d_val[:, None, :]
+        self._add_contacts(out)
         return (out, raw) if return_raw else out
 
     def _run_device(self, indices, batch_counter, return_raw=False):
@@ -540,6 +554,7 @@ class DeviceGeometryProducer:
             out["part_ids"] = d32[1]
         if "valid_matrix" in self.data_keys:
             out["valid_matrix"] = d_val[:, :, None] * d_val[:, None, :]
+        self._add_contacts(out)
         return (out, raw) if return_raw else out
 
     def check(self):
@@ -861,6 +876,38 @@ class PartNetStore:
             contacts = [np.load(os.path.join(data_dir, "contact_points", f"pairs_with_contact_points_{s}_level{level}.npy"),
                                 allow_pickle=True) for s in ids]
         return cls.from_arrays(shapes, ids, contacts, min_num_part, max_num_part, max_bytes)
+
+    def with_computed_contacts(self, device="cuda", thre=0.01, batch=64):
+        """A store of the same shapes whose `contacts` / `contact_off` are computed from its own clouds and poses instead of
+        read from the release's contact files: `batch` shapes at a time, padded to `max_num_part`, go through
+        `contacts.contact_points` (csrc/contact_points.hip) with `thre` as the bound on the squared distance, and the
+        p x p x 4 block of every shape is kept.  Contacts the store already holds are replaced.  `save`, `load` and
+        `DevicePartNetProducer` then work as they do for file-borne contacts."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("PartNetStore: the contact search runs on the HIP device only (there is no CPU fallback)")
+        if batch < 1:
+            raise ValueError(f"PartNetStore.with_computed_contacts: batch={batch} must be positive")
+        from .contacts import contact_points
+        off, P, N = self.shape_part_off, self.max_num_part, self.num_points
+        count = np.diff(off)
+        blocks = []
+        for s0 in range(0, self.num_shapes, int(batch)):
+            s1 = min(s0 + int(batch), self.num_shapes)
+            pcs = np.zeros((s1 - s0, P, N, 3), dtype=np.float32)
+            poses = np.zeros((s1 - s0, P, 7), dtype=np.float32)
+            valids = np.zeros((s1 - s0, P), dtype=np.float32)
+            for b, s in enumerate(range(s0, s1)):
+                pcs[b, :count[s]] = self.pcs[off[s]:off[s + 1]]
+                poses[b, :count[s]] = self.poses[off[s]:off[s + 1]]
+                valids[b, :count[s]] = 1.0
+            d_pcs, d_poses, d_val = (_to_device(a, device) for a in (pcs, poses, valids))
+            table = contact_points(d_pcs, d_val, d_poses[..., 3:].contiguous(), d_poses[..., :3].contiguous(),
+                                   thre=thre).cpu().numpy()
+            blocks += [table[b, :count[s], :count[s]].reshape(-1, 4) for b, s in enumerate(range(s0, s1))]
+        return PartNetStore(self.pcs, self.poses, self.sym, self.geo_ids, self.sem_ids, off, self.shape_ids,
+                            np.concatenate(blocks), np.concatenate([[0], np.cumsum(count * count)]),
+                            min_num_part=self.min_num_part, max_num_part=self.max_num_part)
 
     def save(self, path):
         """One .npz of plain arrays (no pickle): the per-file parse is paid once per split."""

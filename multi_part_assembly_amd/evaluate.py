@@ -30,6 +30,9 @@ PAPER_METRICS = {
     "transform_pt_cd_loss": 1000.0,  # x 1e-3
     "part_acc": 100.0,              # %
 }
+# the column `evaluate_categories(..., connectivity=True)` adds behind them when the runs report it (batches that carry a
+# contact table: `contacts.contact_points`, the data key "contact_points")
+CONNECTIVITY_METRIC = {"connectivity_acc": 100.0}  # %
 
 
 class Evaluator:
@@ -90,12 +93,15 @@ class Evaluator:
         return {f"{prefix}/{k}": float(host[i] / total) for i, k in enumerate(keys)}
 
 
-def evaluate_categories(evaluator, batches_for, categories, metrics=None, prefix="test"):
+def evaluate_categories(evaluator, batches_for, categories, metrics=None, prefix="test", connectivity=False):
     """The per-category loop of scripts/test.py:45-58: one `evaluator.run(batches_for(category))` per category, each paper
     metric scaled and rounded to one decimal, plus the mean over the categories (of the rounded values, rounded again —
     as the reference prints it).  Metrics a model does not report (rot_* / trans_* on semantic data) are left out.
+    `connectivity` adds the connectivity accuracy (%) behind the paper's metrics — a column only when the runs report it.
     Returns {"categories": [...], "metrics": {name: {"values": [per category], "mean": float}}}."""
     metrics = PAPER_METRICS if metrics is None else metrics
+    if connectivity:
+        metrics = {**metrics, **CONNECTIVITY_METRIC}
     categories = list(categories)
     rows = {m: [] for m in metrics}
     for cat in categories:

@@ -137,15 +137,19 @@ def make_partnet_like_batch(batch_size, max_parts=20, num_points=1000, seed=1234
 
 
 def make_partnet_like_store(num_shapes, max_parts=20, num_points=1000, seed=1234, num_part_category=20,
-                            with_contacts=True, min_parts=2):
+                            with_contacts=True, min_parts=2, device="cuda", thre=0.01):
     """A `datasets.PartNetStore` of `num_shapes` shapes at the statistics of `make_partnet_like_batch`, on the host and
     without a dataset: per shape 1 .. min(3, P // 4) groups of 2-4 geometrically identical parts (one centred cloud per
     group, different poses, one shared `geo_part_ids` value >= 1) and 0-3 unique parts, the first of them with
     `geo_part_ids` 0 as in the PartNet files; `part_ids` (semantic labels) uniform in 1 .. `num_part_category`; `sym`
     a 0/1 flag per axis; with `with_contacts` a symmetric contact flag between consecutive parts with the midpoint of
     their translations.  The parts of a shape are NOT sorted by group: their order is shuffled, so equal ids are
-    scattered as in the files.  A function of the arguments only (a private generator)."""
+    scattered as in the files.  `with_contacts="computed"`: the table `PartNetStore.with_computed_contacts(device, thre)`
+    derives from the clouds and poses instead (needs the HIP device).  A function of the arguments only (a private
+    generator)."""
     from .datasets import PartNetStore
+    if with_contacts not in (True, False, "computed"):
+        raise ValueError(f"make_partnet_like_store: with_contacts={with_contacts!r} is not True, False or 'computed'")
     P, N = max_parts, num_points
     if P < 2:
         raise ValueError("make_partnet_like_store: needs at least two part slots")
@@ -185,8 +189,10 @@ def make_partnet_like_store(num_shapes, max_parts=20, num_points=1000, seed=1234
         for i in range(p - 1):
             c[i, i + 1] = c[i + 1, i] = (1.0, *(0.5 * (trans[i] + trans[i + 1])))
         contacts.append(c)
-    return PartNetStore.from_arrays(shapes, shape_ids=1000 + np.arange(num_shapes),
-                                    contacts=contacts if with_contacts else None, min_num_part=min_parts, max_num_part=P)
+    store = PartNetStore.from_arrays(shapes, shape_ids=1000 + np.arange(num_shapes),
+                                     contacts=contacts if with_contacts is True else None, min_num_part=min_parts,
+                                     max_num_part=P)
+    return store.with_computed_contacts(device=device, thre=thre) if with_contacts == "computed" else store
 
 
 def write_partnet_folder(store, data_dir, data_fn="Chair.train.npy", level=3):

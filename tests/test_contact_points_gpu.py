@@ -1,0 +1,328 @@
+"""csrc/contact_points.hip against its numpy restatement, bit for bit on all three outputs, at the edges of its envelope,
+on both sides of its prune, eager and captured — and the table's way through the producers, the stores, the metrics and
+the evaluation tool."""
+import importlib.util
+import os
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+from multi_part_assembly_amd import assemble, config, contacts, contacts_ref, datasets, eval_utils, synthetic
+from multi_part_assembly_amd.evaluate import Evaluator
+from multi_part_assembly_amd.pn_transformer import build_model
+from multi_part_assembly_amd.rotation import Rotation3D, quat_to_matrix
+from test_contact_points import check_structure, duplicated_case, lattice_case, make_case
+
+pytestmark = [pytest.mark.gpu, pytest.mark.timeout(120)]
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F32 = np.float32
+
+
+def device_table(dev, pcs, valids, rot, trans, kind="quat", thre=0.01, full=True):
+    """The operator on sentinel-filled outputs -> numpy (table, min_dist, index) or the table alone.  A quaternion goes in
+    as a raw tensor, so that the kernel's own zero-quaternion rule is what is tested."""
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    r = t(rot) if kind == "quat" else Rotation3D(t(rot), "rmat")
+    B, P = valids.shape
+    out = [torch.full((B, P, P, 4), 7.0, device=dev)]
+    if full:
+        out += [torch.full((B, P, P), 7.0, device=dev), torch.full((B, P, P), 77, dtype=torch.int32, device=dev)]
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")  # inside the envelope nothing falls back
+        got = contacts.contact_points(t(pcs), t(valids), r, t(trans), thre=thre, return_dist=full, return_index=full,
+                                      out=tuple(out))
+    got = got if full else (got,)
+    assert all(g is o for g, o in zip(got, out))
+    res = tuple(g.cpu().numpy() for g in got)
+    return res if full else res[0]
+
+
+def assert_equal_bits(got, want):
+    for name, g, w in zip(("contact_points", "min_dist", "index"), got, want):
+        assert g.dtype == w.dtype and g.shape == w.shape, name
+        assert np.array_equal(g.view(np.uint32 if g.dtype == F32 else np.int32), w.view(np.uint32 if w.dtype == F32 else np.int32)), name
+
+
+def as_rmat(quat):
+    return quat_to_matrix(torch.from_numpy(contacts_ref.sanitize_quat(quat))).numpy()
+
+
+@pytest.mark.parametrize("kind", ["quat", "rmat"])
+@pytest.mark.parametrize("N", [1, 2, 63, 64, 65, 257])
+def test_kernel_equals_restatement(cuda_device, N, kind):
+    pcs, valids, quat, trans = make_case(50 + N, B=3, P=4, N=N, size=0.12 if N > 2 else 0.02, spread=0.35 if N > 2 else 0.2)
+    quat[1, 2] = 0  # a zero quaternion of a real part
+    rot = quat if kind == "quat" else as_rmat(quat)
+    want = contacts_ref.contact_points(pcs, valids, rot, trans)
+    got = device_table(cuda_device, pcs, valids, rot, trans, kind)
+    assert_equal_bits(got, want)
+    check_structure(*got, pcs, valids)
+    flags = got[0][..., 0]
+    assert N <= 2 or 0 < flags.sum() < 3 * 4 * 3  # the case decides something
+    assert_equal_bits((device_table(cuda_device, pcs, valids, rot, trans, kind, full=False),), want[:1])
+
+
+@pytest.mark.parametrize("kind", ["quat", "rmat"])
+def test_masks_and_nan_in_padded_slots(cuda_device, kind):
+    pcs, valids, quat, trans = make_case(7, B=4, P=5, N=65)
+    valids[0] = [1, 0, 1, 1, 0]   # no prefix
+    valids[1] = [0, 0, 1, 0, 0]   # one real part
+    valids[2] = 0                 # none
+    rot = quat if kind == "quat" else as_rmat(quat)
+    want = contacts_ref.contact_points(pcs, valids, rot, trans)
+    got = device_table(cuda_device, pcs, valids, rot, trans, kind)
+    assert_equal_bits(got, want)
+    check_structure(*got, pcs, valids)
+    dirty = [a.copy() for a in (pcs, rot, trans)]
+    for a in dirty:
+        a[valids != 1] = np.nan
+    assert_equal_bits(device_table(cuda_device, dirty[0], valids, dirty[1], dirty[2], kind), want)
+    assert_equal_bits((device_table(cuda_device, dirty[0], valids, dirty[1], dirty[2], kind, full=False),), want[:1])
+    assert_equal_bits(device_table(cuda_device, pcs, valids, rot, trans, kind), got)  # two runs, the same bits
+
+
+@pytest.mark.parametrize("P,N", [(64, 8), (2, 2048)])
+def test_edges_of_the_envelope(cuda_device, P, N):
+    pcs, valids, quat, trans = make_case(P + N, B=2, P=P, N=N, size=0.1, spread=0.3)
+    valids[1, P // 2:] = 0
+    want = contacts_ref.contact_points(pcs, valids, quat, trans)
+    assert_equal_bits(device_table(cuda_device, pcs, valids, quat, trans), want)
+    assert_equal_bits((device_table(cuda_device, pcs, valids, quat, trans, full=False),), want[:1])
+
+
+def test_empty_batch(cuda_device):
+    pcs, valids, quat, trans = make_case(1, B=0, P=4, N=16)
+    got = device_table(cuda_device, pcs, valids, quat, trans)
+    assert got[0].shape == (0, 4, 4, 4) and got[1].shape == (0, 4, 4) and got[2].shape == (0, 4, 4)
+
+
+@pytest.mark.parametrize("P,N", [(3, 2049), (65, 4)])
+def test_outside_the_envelope_the_wrapper_composes_with_one_warning(cuda_device, monkeypatch, P, N):
+    monkeypatch.setattr(eval_utils, "_warned", set())
+    pcs, valids, quat, trans = make_case(P * N, B=2, P=P, N=N, size=0.1, spread=0.3 if P == 3 else 1.0)
+    valids[1, 1] = 0
+    pcs[1, 1] = quat[1, 1] = trans[1, 1] = np.nan
+    quat[0, 0] = 0
+    t = lambda a: torch.from_numpy(a).to(cuda_device)
+    with pytest.warns(UserWarning, match="contact_points") as rec:
+        got = contacts.contact_points(t(pcs), t(valids), t(quat), t(trans), return_dist=True, return_index=True)
+        contacts.contact_points(t(pcs), t(valids), t(quat), t(trans))
+    assert len([w for w in rec if "contact_points" in str(w.message)]) == 1
+    want = contacts_ref.contact_points(pcs, valids, quat, trans, samples=None if P == 3 else [1])
+    if P == 3:
+        assert_equal_bits(tuple(g.cpu().numpy() for g in got), want)
+    else:  # 2080 pairs: one sample against the restatement, the structure of both
+        assert_equal_bits(tuple(g[1].cpu().numpy() for g in got), tuple(w[1] for w in want))
+        check_structure(*(g.cpu().numpy() for g in got), np.nan_to_num(pcs), valids)
+
+
+def test_tie_rule_on_the_device(cuda_device):
+    pcs, valids, quat, trans = duplicated_case()
+    got = device_table(cuda_device, pcs, valids, quat, trans)
+    assert_equal_bits(got, contacts_ref.contact_points(pcs, valids, quat, trans))
+    assert (got[2][0, 0, 1], got[2][0, 1, 0]) == (3, 2)
+    pcs, valids, quat, trans, perm = lattice_case()
+    got = device_table(cuda_device, pcs, valids, quat, trans)
+    assert_equal_bits(got, contacts_ref.contact_points(pcs, valids, quat, trans))
+    assert got[1][0, 0, 1] == 0 and got[2][0, 0, 1] == 0 and got[2][0, 1, 0] == int(np.argmax(perm == 0))
+    # every point of a 300-point part stored twice, and the nearest target of the other part stored in both chunks of four
+    rng = np.random.RandomState(12)
+    half = rng.uniform(-0.1, 0.1, (2, 150, 3)).astype(F32)
+    pcs = np.concatenate([half, half], axis=1)[None]
+    quat, trans = np.tile(F32([1, 0, 0, 0]), (1, 2, 1)), np.zeros((1, 2, 3), F32)
+    trans[0, 1, 0] = 0.05
+    got = device_table(cuda_device, pcs, np.ones((1, 2), F32), quat, trans)
+    want = contacts_ref.contact_points(pcs, np.ones((1, 2), F32), quat, trans)
+    assert_equal_bits(got, want)
+    assert got[2][0, 0, 1] < 150 and got[2][0, 1, 0] < 150
+
+
+def test_both_sides_of_the_prune_and_the_threshold(cuda_device):
+    pcs, valids, quat, trans = make_case(21, B=2, P=4, N=130, size=0.05)
+    trans[0] = (np.arange(4)[:, None] * F32([3.0, -2.0, 1.0])).astype(F32)  # sample 0: parts far apart
+    trans[1] = 0                                                             # sample 1: all overlapping
+    trans[0, 3] = trans[0, 2] + F32(0.1)                                     # boxes apart by less than the bound
+    want = contacts_ref.contact_points(pcs, valids, quat, trans)
+    assert want[0][0, :2, :, 0].sum() == 0 and want[0][1, ..., 0].sum() == 12
+    full = device_table(cuda_device, pcs, valids, quat, trans)
+    assert_equal_bits(full, want)
+    assert_equal_bits((device_table(cuda_device, pcs, valids, quat, trans, full=False),), want[:1])
+    # the bound itself: a contact needs dmin < thre, exactly
+    one = np.zeros((1, 2, 1, 3), F32)
+    one[0, 1, 0, 0] = 0.125
+    ident, zero, ok = np.tile(F32([1, 0, 0, 0]), (1, 2, 1)), np.zeros((1, 2, 3), F32), np.ones((1, 2), F32)
+    for flag_only in (False, True):
+        got = device_table(cuda_device, one, ok, ident, zero, thre=0.015625, full=not flag_only)
+        assert not (got if flag_only else got[0]).any()
+        below = one.copy()
+        below[0, 1, 0, 0] = np.nextafter(F32(0.125), F32(0))
+        got = device_table(cuda_device, below, ok, ident, zero, thre=0.015625, full=not flag_only)
+        assert (got if flag_only else got[0])[0, 0, 1, 0] == 1
+
+
+def test_captured_launch_equals_eager(cuda_device):
+    pcs, valids, quat, trans = make_case(31, B=3, P=4, N=100)
+    t = lambda a: torch.from_numpy(a).to(cuda_device)
+    d_pcs, d_val, d_trans = t(pcs), t(valids), t(trans)
+    static_quat = torch.zeros(3, 4, 4, device=cuda_device)
+    out = (torch.empty(3, 4, 4, 4, device=cuda_device), torch.empty(3, 4, 4, device=cuda_device),
+           torch.empty(3, 4, 4, dtype=torch.int32, device=cuda_device))
+    call = lambda: contacts.contact_points(d_pcs, d_val, static_quat, d_trans, return_dist=True, return_index=True, out=out)
+    side = torch.cuda.Stream(device=cuda_device)
+    side.wait_stream(torch.cuda.current_stream(cuda_device))
+    with torch.cuda.stream(side):
+        call()
+    torch.cuda.current_stream(cuda_device).wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        call()
+    static_quat.copy_(t(quat))
+    for o in out:
+        o.fill_(5)
+    graph.replay()
+    replayed = tuple(o.cpu().numpy() for o in out)
+    assert_equal_bits(replayed, device_table(cuda_device, pcs, valids, quat, trans))
+    assert_equal_bits(replayed, contacts_ref.contact_points(pcs, valids, quat, trans))
+
+
+def test_training_size_on_a_subset_and_the_fused_metric(cuda_device):
+    """B = 32, P = 20, N = 1000: eight fixed samples against the restatement, and the ground-truth poses score exactly 1
+    through the fused mpa_connectivity_acc on the kernel's own table."""
+    parts = [2 + (5 * b) % 19 for b in range(32)]
+    batch = synthetic.make_batch(32, 20, 1000, seed=99, device=cuda_device, num_parts=parts)
+    args = (batch["part_pcs"], batch["part_valids"], batch["part_quat"], batch["part_trans"])
+    table, dist, index = contacts.contact_points(*args, return_dist=True, return_index=True)
+    flag_only = contacts.contact_points(*args)
+    assert torch.equal(table, flag_only)
+    subset = [0, 4, 8, 12, 16, 19, 23, 27]  # 2, 3, 4, 5, 6, 2, 3, 4 parts
+    assert [parts[b] for b in subset] == [2, 3, 4, 5, 6, 2, 3, 4]
+    host = [a.cpu().numpy() for a in args]
+    want = contacts_ref.contact_points(*host, samples=subset)
+    for g, w in zip((table, dist, index), want):
+        assert np.array_equal(g[subset].cpu().numpy(), w[subset])
+    check_structure(table.cpu().numpy(), dist.cpu().numpy(), index.cpu().numpy(), host[0], host[1])
+    n = int(table[..., 0].sum().item())
+    print(f"contacts at B=32: {n // 2} of {sum(p * (p - 1) // 2 for p in parts)} real pairs")
+    assert n > 0
+    for kind in ("quat", "rmat"):
+        rot = Rotation3D(batch["part_quat"], "quat").convert(kind)
+        mine = contacts.contact_points(args[0], args[1], rot, args[3])
+        acc = eval_utils.calc_connectivity_acc(batch["part_trans"], rot, mine, fused=True)
+        assert acc.shape == (32,) and (acc == 1.0).all().item()
+    assert torch.equal(contacts.adjacency(table), (dist < torch.tensor(0.01, device=cuda_device)).float())
+
+
+# ---- producers and stores -------------------------------------------------------------------------------------------------------
+def touching_meshes(seed, shapes, parts):
+    """`make_fracture_meshes` with every part moved next to the origin, so that the parts of a shape touch."""
+    out = []
+    for shape in synthetic.make_fracture_meshes(seed, shapes, parts, 80):
+        out.append([(v - v.mean(0) + 0.04 * k, f) for k, (v, f) in enumerate(shape)])
+    return out
+
+
+def test_geometry_producer_carries_the_table(cuda_device):
+    store = datasets.MeshStore.from_arrays(touching_meshes(3, 5, [2, 4, 3, 4, 2]), max_num_part=4)
+    kw = dict(num_points=96, max_num_part=4, seed=9, device=cuda_device)
+    with_key = datasets.DeviceGeometryProducer(store, data_keys=("part_ids", "contact_points"), **kw)
+    without = datasets.DeviceGeometryProducer(store, data_keys=("part_ids",), **kw)
+    idx = [4, 1, 2]
+    a = with_key.batch(idx, batch_counter=3)
+    b = without.batch(idx, batch_counter=3)
+    c = with_key.batch(torch.tensor(idx, device=cuda_device), batch_counter=3)
+    with_key.check()
+    assert set(a) == set(b) | {"contact_points"} == set(c)
+    for k in b:
+        assert torch.equal(a[k].cpu(), b[k].cpu()) and torch.equal(a[k].cpu(), c[k].cpu()), k
+    assert torch.equal(a["contact_points"], c["contact_points"])
+    want = contacts_ref.contact_points(*(a[k].cpu().numpy() for k in ("part_pcs", "part_valids", "part_quat", "part_trans")))
+    assert np.array_equal(a["contact_points"].cpu().numpy(), want[0]) and want[0][..., 0].sum() > 0
+    # replay: the caller's draws through the same kernel
+    rng = np.random.RandomState(0)
+    B, P, N = 3, 4, 96
+    uni = rng.random_sample((B, P, N, 3))
+    rot = np.tile(np.eye(3).reshape(9), (B, P, 1))
+    perm = np.tile(np.arange(N, dtype=np.int32), (B, P, 1))
+    quat = np.tile(F32([1, 0, 0, 0]), (B, P, 1))
+    ra = with_key.replay(idx, uni, rot, perm, quat)
+    rb = without.replay(idx, uni, rot, perm, quat)
+    for k in rb:
+        assert torch.equal(ra[k].cpu(), rb[k].cpu()), k
+    want = contacts_ref.contact_points(*(ra[k].cpu().numpy() for k in ("part_pcs", "part_valids", "part_quat", "part_trans")))
+    assert np.array_equal(ra["contact_points"].cpu().numpy(), want[0])
+
+
+def test_store_with_computed_contacts_feeds_the_partnet_producer(cuda_device, tmp_path):
+    plain = synthetic.make_partnet_like_store(7, max_parts=5, num_points=64, seed=5, with_contacts=False)
+    plain.poses[:, :3] *= 0.3  # the parts of a shape closer together: some touch
+    store = plain.with_computed_contacts(device=cuda_device, batch=3)
+    assert store.has_contacts and not plain.has_contacts
+    assert np.array_equal(store.contact_off, np.concatenate([[0], np.cumsum(np.diff(store.shape_part_off) ** 2)]))
+    store.save(tmp_path / "s.npz")
+    again = datasets.PartNetStore.load(tmp_path / "s.npz")
+    assert np.array_equal(again.contacts, store.contacts)
+    prod = datasets.DevicePartNetProducer(again, ("part_ids", "contact_points"), max_num_part=5, device=cuda_device)
+    batch = prod.batch([6, 0, 3])
+    prod.check()
+    want = contacts.contact_points(batch["part_pcs"], batch["part_valids"], batch["part_quat"], batch["part_trans"])
+    assert torch.equal(batch["contact_points"], want)
+    ref = contacts_ref.contact_points(*(batch[k].cpu().numpy() for k in ("part_pcs", "part_valids", "part_quat", "part_trans")))
+    assert np.array_equal(want.cpu().numpy(), ref[0])
+    print(f"contacts in the computed store: {int(store.contacts[:, 0].sum()) // 2}")
+    other = synthetic.make_partnet_like_store(7, max_parts=5, num_points=64, seed=5, with_contacts="computed",
+                                              device=cuda_device)
+    assert other.has_contacts and len(other.contacts) == len(store.contacts)
+
+
+# ---- metrics and the tool --------------------------------------------------------------------------------------------------------
+def test_evaluator_reports_connectivity_on_a_geometry_store(cuda_device):
+    store = datasets.MeshStore.from_arrays(touching_meshes(8, 6, [2, 3, 4, 4, 3, 2]), max_num_part=4)
+    cfg = config.pn_transformer_everyday()
+    cfg.model.transformer_layers = 2
+    cfg.data.max_num_part = 4
+    torch.manual_seed(0)
+    model = build_model(cfg).to(cuda_device)
+    model.train()
+    state = {k: v.clone() for k, v in model.state_dict().items()}
+
+    def batches(keys):
+        prod = datasets.DeviceGeometryProducer(store, num_points=128, max_num_part=4, data_keys=keys, seed=2,
+                                               device=cuda_device)
+        return [prod.batch([0, 1, 2, 3]), prod.batch([4, 5])]
+
+    with_ca = Evaluator(model).run(batches(("part_ids", "contact_points")))
+    plain = Evaluator(model).run(batches(("part_ids",)))
+    assert model.training
+    for k, v in model.state_dict().items():
+        assert torch.equal(v, state[k]), k
+    assert set(with_ca) == set(plain) | {"val/connectivity_acc"} and "val/connectivity_acc" not in plain
+    assert {"val/loss", "val/part_acc", "val/trans_loss", "val/transform_pt_cd_loss", "val/trans_mae", "val/rot_rmse"} <= set(plain)
+    for k in plain:
+        np.testing.assert_allclose(with_ca[k], plain[k], rtol=1e-6, err_msg=k)
+    assert 0.0 <= with_ca["val/connectivity_acc"] <= 1.0
+
+
+def test_evaluate_tool_with_connectivity(cuda_device, tmp_path, capsys):
+    root = str(tmp_path)
+    shapes = touching_meshes(4, 2, [3, 2])
+    for s, shape in enumerate(shapes):
+        folder = os.path.join(root, "everyday", "Bottle", f"s{s}", "fractured_0")
+        os.makedirs(folder)
+        for k, (v, f) in enumerate(shape):
+            assemble.write_obj(os.path.join(folder, f"piece_{k}.obj"), v[f])
+    with open(os.path.join(root, "everyday.val.txt"), "w") as fh:
+        fh.write("everyday/Bottle/s0\neveryday/Bottle/s1\n")
+    spec = importlib.util.spec_from_file_location("tools_evaluate_ca", os.path.join(ROOT, "tools", "evaluate.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    base = ["--preset", "identity_everyday", "--data-dir", root, "--data-fn", "everyday.val.txt", "--max-num-part", "4"]
+    tool.main(base)
+    plain = dict(kv.split(": ") for kv in capsys.readouterr().out.strip().split("; "))
+    tool.main(base + ["--connectivity"])
+    with_ca = dict(kv.split(": ") for kv in capsys.readouterr().out.strip().split("; "))
+    assert set(with_ca) == set(plain) | {"test/connectivity_acc"} and "test/connectivity_acc" not in plain
+    assert 0.0 <= float(with_ca["test/connectivity_acc"]) <= 1.0
+    for k in plain:
+        assert plain[k] == with_ca[k], k

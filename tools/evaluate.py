@@ -3,12 +3,15 @@
 
   python tools/evaluate.py --preset pn_transformer_everyday --weight ckpt.pt --data-dir data/breaking_bad \\
       --data-fn everyday.val.txt [--category Bottle | --category all] [--min-num-part 2] [--max-num-part 20]
+      [--connectivity]
 
 `--preset` names a function of multi_part_assembly_amd.config; `--weight` a file written by `torch.save` holding either
 `Trainer.state_dict()`, a Lightning-style `{"state_dict": ...}` or a bare model state dict (not needed for the identity
 presets).  `--data-fn` lists shape folders (`everyday/Bottle/<id>`), one per line, as the Breaking-Bad split files do;
 every `fractured_*` / `mode_*` folder below them whose part count is in range is evaluated.  `--category all` evaluates
-every category of the everyday subset and prints the paper-table rows."""
+every category of the everyday subset and prints the paper-table rows.  `--connectivity` adds the data key
+`contact_points` — the contact table of every batch's own clouds and ground-truth poses, computed on the device — so
+that the connectivity accuracy is reported too (a `connectivity_acc` value, and a row of the table)."""
 import argparse
 import os
 import sys
@@ -53,7 +56,7 @@ def batches_for(cfg, args, category, device):
         yield producer.batch(list(range(start, min(start + size, len(producer)))))
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--preset", required=True)
     ap.add_argument("--weight", default="")
@@ -62,7 +65,13 @@ def main():
     ap.add_argument("--category", default="")
     ap.add_argument("--min-num-part", type=int, default=-1)
     ap.add_argument("--max-num-part", type=int, default=-1)
-    args = ap.parse_args()
+    ap.add_argument("--connectivity", action="store_true",
+                    help="compute every batch's contact table and report the connectivity accuracy")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(argv)
     cfg = getattr(config, args.preset)()
     if cfg.data.dataset != "geometry":
         raise SystemExit("tools/evaluate.py reads the Breaking-Bad folder layout; semantic presets need a PartNetBatchProducer")
@@ -70,6 +79,8 @@ def main():
         cfg.data.min_num_part = args.min_num_part
     if args.max_num_part > 0:
         cfg.data.max_num_part = args.max_num_part
+    if args.connectivity and "contact_points" not in cfg.data.data_keys:
+        cfg.data.data_keys = tuple(cfg.data.data_keys) + ("contact_points",)
     device = torch.device("cuda:0")
     model = build_model(cfg).to(device)
     if args.weight:
@@ -81,7 +92,8 @@ def main():
         res = evaluator.run(batches_for(cfg, args, args.category, device), prefix="test")
         print("; ".join(f"{k}: {v:.6f}" for k, v in res.items()))
         return
-    table = evaluate_categories(evaluator, lambda cat: batches_for(cfg, args, cat, device), config.EVERYDAY_CATEGORIES)
+    table = evaluate_categories(evaluator, lambda cat: batches_for(cfg, args, cat, device), config.EVERYDAY_CATEGORIES,
+                                connectivity=args.connectivity)
     print(format_table(table))
 
 
