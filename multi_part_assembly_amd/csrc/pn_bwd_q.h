@@ -51,6 +51,7 @@
 #define PN_LDS __attribute__((address_space(3)))
 typedef short pn_s16x4 __attribute__((ext_vector_type(4)));
 typedef short pn_s16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned int pn_u32x4 __attribute__((ext_vector_type(4)));
 
 // transposed MFMA fragment: this lane's address = row (8 * lane-half + (i >> 2)), column (16 * (group & 1) + 4 * (i & 3))
 // of the 16 k-rows x 32 columns the fragment covers (i = lane & 15, group = lane >> 4); the second read 4 rows further.
@@ -631,8 +632,9 @@ __global__ __launch_bounds__(64 * (NS + ND + NW), (NS + ND + NW + 3) / 4) void p
 // does the input gradient AND the Gram matrix in one pass over Y4 (two kernels that read it once each took 139 + 79 us:
 // LABBOOK 6.1) with the wave roles of pn_bwd_q_kernel: stagers convert Y4 rows into the A panel and stage the unit's
 // sparse rows (three-stage request pipeline: tile record, row sums, LDS); four input-gradient waves (one 32-column tile each,
-// Q register-resident) leave A Q + c0 raw in LDS; four weight-gradient waves accumulate the ten upper tiles of G; both kinds
-// then finish the previous unit: sparse rows added from the staged sums, ReLU mask, dZ4 stores, BatchNorm-backward sums.
+// Q register-resident) leave A Q + c0 raw in LDS; four Gram waves accumulate the ten upper tiles of G.  The stagers then
+// finish the previous unit from the Y4 rows they still hold: sparse rows added from the staged sums, ReLU mask, dZ4
+// stores, BatchNorm-backward sums (on the Gram waves until 2026-10-18: they re-read Y4 for it and were the critical role).
 struct PnGTile {
   signed char a, b;  // column tiles of A: row tile and column tile of G (a <= b)
 };
@@ -654,8 +656,7 @@ __global__ __launch_bounds__(64 * (NS + ND + NW), (NS + ND + NW + 3) / 4) void p
   constexpr int K = 0;  // (PN_T_REPORT prints them)
   constexpr bool FIRST = false;
   constexpr int RB = 32, SA = 6 * CIN + 16, CT = CIN / 32, KA = CIN / 16, KW = RB / 16;
-  constexpr int NTS = 64 * NS, QC = CIN / 4, RG = NTS / QC, NLY = RB * QC / NTS, EH = NLY;  // (the Gram waves run the whole epilogue: the
-  // input-gradient waves hold Q — 96 registers — and spilled with the epilogue's state on top)
+  constexpr int NTS = 64 * NS, QC = CIN / 4, RG = NTS / QC, NLY = RB * QC / NTS;
   constexpr int ELEMS = CIN * CIN + CIN;
   static_assert(CIN == 128 && ND == CT && NW == 4 && NS == 4 && NLY % 2 == 0, "shapes");
   __shared__ __attribute__((aligned(16))) unsigned char pa[2][RB * SA];  // A planes h | m | l
@@ -669,78 +670,26 @@ __global__ __launch_bounds__(64 * (NS + ND + NW), (NS + ND + NW + 3) / 4) void p
     return u < U && it >= 0 ? vlist[4 + u / TB] : 0;
   };
   auto n0_of = [&](int it) { return (((int)blockIdx.x + it * G) % TB) * RB; };
-  // ---- the input gradient's epilogue (see pn_bwd_q_kernel), run by the Gram waves ---------------------------------------------
-  const int te = threadIdx.x & (NTS - 1);
-  const int cy4 = te % QC, ry0 = te / QC;
-  const float4 sc = reinterpret_cast<const float4*>(bn_prev)[cy4];
-  const float4 sh = reinterpret_cast<const float4*>(bn_prev + CIN)[cy4];
-  const float4 mn = reinterpret_cast<const float4*>(bn_prev + 2 * CIN)[cy4];
-  float4 ye[EH];
-  float4 s1v = make_float4(0.0f, 0.0f, 0.0f, 0.0f), t2v = s1v;
-  auto load_y = [&](int it, int m, auto half_tag) {
-    constexpr int HALF = decltype(half_tag)::value;
-    const int n0 = n0_of(it);
-    const long long row0 = (long long)m * N + n0;
-#pragma unroll
-    for (int i = 0; i < EH; ++i) {
-      const int rl = ry0 + (HALF * EH + i) * RG;
-      const int rr = n0 + rl < N ? rl : N - 1 - n0;
-      ye[i] = reinterpret_cast<const float4*>(y_prev)[(row0 + rr) * QC + cy4];
-    }
-  };
-  auto epilogue = [&](int it, int m, auto half_tag) {
-    constexpr int HALF = decltype(half_tag)::value;
-    const int n0 = n0_of(it), slot = it % 3;
-    const long long row0 = (long long)m * N + n0;
-    const float* ob = &outp[it & 1][0];
-#pragma unroll
-    for (int i = 0; i < EH; ++i) {  // one row at a time: its dense part, + S W5 (summed per row by the stagers an iteration ago)
-      const int rl = ry0 + (HALF * EH + i) * RG;
-      const bool ok = n0 + rl < N;
-      float4 o = *reinterpret_cast<const float4*>(ob + rl * CIN + 4 * cy4);
-      const float4 sp = *reinterpret_cast<const float4*>(&rowsum[slot][rl * CIN + 4 * cy4]);
-      o.x += sp.x;
-      o.y += sp.y;
-      o.z += sp.z;
-      o.w += sp.w;
-      const float4 yv = ye[i];
-      float4 d;
-      d.x = (ok && __builtin_fmaf(yv.x, sc.x, sh.x) > 0.0f) ? o.x : 0.0f;
-      d.y = (ok && __builtin_fmaf(yv.y, sc.y, sh.y) > 0.0f) ? o.y : 0.0f;
-      d.z = (ok && __builtin_fmaf(yv.z, sc.z, sh.z) > 0.0f) ? o.z : 0.0f;
-      d.w = (ok && __builtin_fmaf(yv.w, sc.w, sh.w) > 0.0f) ? o.w : 0.0f;
-      if (ok) reinterpret_cast<float4*>(dz_prev)[(row0 + rl) * QC + cy4] = d;
-      s1v.x += d.x;
-      s1v.y += d.y;
-      s1v.z += d.z;
-      s1v.w += d.w;
-      t2v.x = __builtin_fmaf(d.x, yv.x - mn.x, t2v.x);
-      t2v.y = __builtin_fmaf(d.y, yv.y - mn.y, t2v.y);
-      t2v.z = __builtin_fmaf(d.z, yv.z - mn.z, t2v.z);
-      t2v.w = __builtin_fmaf(d.w, yv.w - mn.w, t2v.w);
-    }
-  };
-  auto put_sums = [&]() {  // scratch rows [q * RG + row group]: q = 1 s1, 2 s2
-    float* scr = reinterpret_cast<float*>(&pa[0][0]);
-    const float4 is4 = reinterpret_cast<const float4*>(bn_prev + 3 * CIN)[cy4];
-    t2v.x *= is4.x;
-    t2v.y *= is4.y;
-    t2v.z *= is4.z;
-    t2v.w *= is4.w;
-    *reinterpret_cast<float4*>(scr + (1 * RG + ry0) * CIN + 4 * cy4) = s1v;
-    *reinterpret_cast<float4*>(scr + (2 * RG + ry0) * CIN + 4 * cy4) = t2v;
-  };
-  using Half0 = std::integral_constant<int, 0>;
-  using Half1 = std::integral_constant<int, 1>;
 
   if (wave < NS) {
     // ================================================ stager waves ==========================================================
-    const int t = threadIdx.x;
+    // Besides staging, these waves finish the input gradient (see pn_bwd_q_kernel's epilogue): the thread that fetched
+    // (row, 4 columns) of Y4 for the A panel is the one that needs them again for the ReLU mask and the BatchNorm-backward
+    // sums, so the rows stay in its registers from their request (unit u - 2) to the unit's epilogue (u + 1) and Y4 is read
+    // once.  Three named register sets, ya / yb / yc = the rows of units it - 1 / it / it + 1 at the top of iteration it,
+    // handed down by register moves (a ring indexed at run time made the compiler wait for every load in flight at the
+    // loop's back edge; the loop written out three iterations at a time went to scratch).
+    const int te = threadIdx.x;  // (row group, 4 columns) of this thread in every unit
+    int cy4 = te % QC, ry0 = te / QC;
+    const float4 sc = reinterpret_cast<const float4*>(bn_prev)[cy4];
+    const float4 sh = reinterpret_cast<const float4*>(bn_prev + CIN)[cy4];
+    const float4 mn = reinterpret_cast<const float4*>(bn_prev + 2 * CIN)[cy4];
     const int T1 = (N + 31) / 32 + 1;
-    float4 ry[NLY];
+    float4 ya[NLY], yb[NLY], yc[NLY];
     float4 colsum = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float4 s1v = colsum, t2v = colsum;
     const pn_f32x2 sc01 = {sc.x, sc.y}, sc23 = {sc.z, sc.w}, sh01 = {sh.x, sh.y}, sh23 = {sh.z, sh.w}, zero2 = {0.0f, 0.0f};
-    auto fetch = [&](int it, int m) {
+    auto fetch = [&](int it, int m, float4(&ry)[NLY]) {
       const int n0 = n0_of(it);
       const long long row0 = (long long)m * N + n0;
 #pragma unroll
@@ -750,7 +699,7 @@ __global__ __launch_bounds__(64 * (NS + ND + NW), (NS + ND + NW + 3) / 4) void p
         ry[i] = reinterpret_cast<const float4*>(y_prev)[(row0 + rr) * QC + cy4];
       }
     };
-    auto stash = [&](int it, int b) {
+    auto stash = [&](int it, int b, const float4(&ry)[NLY]) {
       const int n0 = n0_of(it);
 #pragma unroll
       for (int i = 0; i < NLY; ++i) {
@@ -771,6 +720,44 @@ __global__ __launch_bounds__(64 * (NS + ND + NW), (NS + ND + NW + 3) / 4) void p
         *reinterpret_cast<pn_bf16x4*>(p + 4 * CIN) = pl;
       }
     };
+    // the epilogue of unit `it`, one barrier after the input-gradient waves left A Q + c0 raw in outp[it & 1]: one row at a
+    // time, its dense part + S W5 (rowsum[it % 3], which this same thread wrote two iterations ago), ReLU mask (the
+    // forward's own expression), dZ4 as coalesced 16-byte stores, BatchNorm-backward sums
+    auto epilogue = [&](int it, int m, const float4(&ye)[NLY]) {
+      const int n0 = n0_of(it), slot = it % 3;
+      // dZ4 rows of the unit through a buffer descriptor that ends with the part: the range check drops the rows past it, so
+      // every thread issues every store (a store under a branch leaves the number of memory operations in flight unknown,
+      // and the wait for the NEXT unit's rows then has to cover everything issued after them)
+      const auto dzr = __builtin_amdgcn_make_buffer_rsrc(dz_prev + ((long long)m * N + n0) * CIN, 0,
+                                                         (N - n0 < RB ? N - n0 : RB) * CIN * 4, 0x00020000);
+      const float* ob = &outp[it & 1][0];
+#pragma unroll
+      for (int i = 0; i < NLY; ++i) {
+        const int rl = ry0 + i * RG;
+        const bool ok = n0 + rl < N;
+        float4 o = *reinterpret_cast<const float4*>(ob + rl * CIN + 4 * cy4);
+        const float4 sp = *reinterpret_cast<const float4*>(&rowsum[slot][rl * CIN + 4 * cy4]);
+        o.x += sp.x;
+        o.y += sp.y;
+        o.z += sp.z;
+        o.w += sp.w;
+        const float4 yv = ye[i];
+        float4 d;
+        d.x = (ok && __builtin_fmaf(yv.x, sc.x, sh.x) > 0.0f) ? o.x : 0.0f;
+        d.y = (ok && __builtin_fmaf(yv.y, sc.y, sh.y) > 0.0f) ? o.y : 0.0f;
+        d.z = (ok && __builtin_fmaf(yv.z, sc.z, sh.z) > 0.0f) ? o.z : 0.0f;
+        d.w = (ok && __builtin_fmaf(yv.w, sc.w, sh.w) > 0.0f) ? o.w : 0.0f;
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(pn_u32x4, d), dzr, (rl * CIN + 4 * cy4) * 4, 0, 0);
+        s1v.x += d.x;
+        s1v.y += d.y;
+        s1v.z += d.z;
+        s1v.w += d.w;
+        t2v.x = __builtin_fmaf(d.x, yv.x - mn.x, t2v.x);  // sum d (y4 - mean): scaled by invstd at the end
+        t2v.y = __builtin_fmaf(d.y, yv.y - mn.y, t2v.y);
+        t2v.z = __builtin_fmaf(d.z, yv.z - mn.z, t2v.z);
+        t2v.w = __builtin_fmaf(d.w, yv.w - mn.w, t2v.w);
+      }
+    };
     // S W5 of a unit, per row, from the table pn_top_csr_kernel built (rtile, rsum): the same request pipeline as the Y4 rows,
     // one stage longer.  The tile record of unit u is requested at iteration u - 3; at u - 2 every thread requests its NLY rows
     // x 4 columns of the finished sums (a row of the tile that has one is found by a popcount in the record's mask: no loop,
@@ -780,14 +767,14 @@ __global__ __launch_bounds__(64 * (NS + ND + NW), (NS + ND + NW + 3) / 4) void p
     float4 rv[NLY];
     auto rt_fetch = [&](int it, int m) { rt = rtile[(long long)m * T1 + (n0_of(it) >> 5)]; };
     auto rows_fetch = [&](int m) {  // uses the record of this unit (rt holds it now)
-      const float4* rs4 = reinterpret_cast<const float4*>(rsum) + (long long)m * F * QC + cy4;
+      const int bytes = F * CIN * 4;  // the part's rows; a row without an arg-max reads past them: the range check returns zeros
+      const auto rsr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(rsum) + (long long)m * F * CIN, 0, bytes, 0x00020000);
 #pragma unroll
       for (int i = 0; i < NLY; ++i) {
         const int rl = ry0 + i * RG;
         const unsigned mask = (unsigned)rt.y;
         const int jr = rt.x + __builtin_popcount(mask & ((1u << rl) - 1u));
-        rv[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if ((mask >> rl) & 1u) rv[i] = rs4[(long long)jr * QC];
+        rv[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsr, (mask >> rl) & 1u ? (jr * CIN + 4 * cy4) * 4 : bytes, 0, 0));
       }
     };
     auto rows_stash = [&](int it) {
@@ -796,41 +783,71 @@ __global__ __launch_bounds__(64 * (NS + ND + NW), (NS + ND + NW + 3) / 4) void p
       for (int i = 0; i < NLY; ++i) *reinterpret_cast<float4*>(&rowsum[slot][(ry0 + i * RG) * CIN + 4 * cy4]) = rv[i];
     };
     int m1 = part_of(1), m2 = part_of(2), m3 = part_of(3);
+    int m_prev = 0, m_cur = part_of(0);
     if (n_it > 0) {
-      const int m0 = part_of(0);
-      rt_fetch(0, m0);
-      fetch(0, m0);
-      rows_fetch(m0);
+      rt_fetch(0, m_cur);
+      fetch(0, m_cur, yb);
+      rows_fetch(m_cur);
       if (n_it > 1) rt_fetch(1, m1);
       rows_stash(0);
-      stash(0, 0);
+      stash(0, 0, yb);
       if (n_it > 1) {
-        fetch(1, m1);
+        fetch(1, m1, yc);
         rows_fetch(m1);
       }
       if (n_it > 2) rt_fetch(2, m2);
     }
     __syncthreads();  // panel 0 and unit 0's sparse rows are complete
     PN_T_DECL
-    for (int it = 0; it < n_it; ++it) {
+    // Iteration `it`: finish unit it - 1, put unit it + 1's sparse rows and panel into LDS, request unit it + 2.  Everything
+    // that waits for rows requested an iteration ago comes before the new requests, except the conversion, which runs under
+    // them.  STEADY: 0 < it and it + 3 < n_it, every stage runs and none sits under a branch, so the compiler knows how many
+    // memory operations follow the rows it waits for and does not wait for those (the dZ4 stores of this iteration).
+    auto step = [&](int it, auto steady_tag) {
+      constexpr bool STEADY = decltype(steady_tag)::value;
       const int m4 = part_of(it + 4);
-      if (it + 1 < n_it) {
-        rows_stash(it + 1);  // (requested an iteration ago, like the unit's Y4 rows)
-        stash(it + 1, (it + 1) & 1);
+      // every address and row mask below is rebuilt from these two per iteration: hoisted out of the loop, the lot of them
+      // (LDS and global addresses of four rows in three roles, the popcount masks) cost more registers than the three sets
+      asm volatile("" : "+v"(cy4), "+v"(ry0));
+      if (STEADY || it > 0) epilogue(it - 1, m_prev, ya);
+      if (STEADY || it + 1 < n_it) rows_stash(it + 1);
+#pragma unroll
+      for (int i = 0; i < NLY; ++i) {
+        ya[i] = yb[i];
+        yb[i] = yc[i];
       }
-      if (it + 2 < n_it) {
-        fetch(it + 2, m2);
+      if (STEADY || it + 2 < n_it) {
+        fetch(it + 2, m2, yc);
         rows_fetch(m2);  // (its tile record was requested an iteration ago)
       }
-      if (it + 3 < n_it) rt_fetch(it + 3, m3);
+      if (STEADY || it + 3 < n_it) rt_fetch(it + 3, m3);
+      if (STEADY || it + 1 < n_it) stash(it + 1, (it + 1) & 1, yb);
+      m_prev = m_cur;
+      m_cur = m1;
       m1 = m2;
       m2 = m3;
       m3 = m4;
       PN_BAR
+    };
+    int it = 0;
+    for (int phase = 0; phase < 2; ++phase) {  // ramp-up (one iteration), the steady loop, ramp-down (three)
+      const int hi = phase == 0 ? (n_it < 1 ? n_it : 1) : n_it;
+      for (; it < hi; ++it) step(it, std::false_type{});
+      if (phase == 0)
+        for (; it + 3 < n_it; ++it) step(it, std::true_type{});
     }
+    if (n_it > 0) epilogue(n_it - 1, m_prev, ya);  // the last unit, after the last barrier
     PN_T_REPORT("stager")
+    // scratch rows [q * RG + row group]: q = 0 column sums of A, 1 s1, 2 s2 (the panels they alias are read by nobody any more)
     float* scr = reinterpret_cast<float*>(&pa[0][0]);
+    const float4 is4 = reinterpret_cast<const float4*>(bn_prev + 3 * CIN)[cy4];
+    t2v.x *= is4.x;
+    t2v.y *= is4.y;
+    t2v.z *= is4.z;
+    t2v.w *= is4.w;
     *reinterpret_cast<float4*>(scr + (0 * RG + ry0) * CIN + 4 * cy4) = colsum;
+    *reinterpret_cast<float4*>(scr + (1 * RG + ry0) * CIN + 4 * cy4) = s1v;
+    *reinterpret_cast<float4*>(scr + (2 * RG + ry0) * CIN + 4 * cy4) = t2v;
   } else if (wave < NS + ND) {
     // ============================================ input-gradient waves ========================================================
     const int ct = wave - NS, d0 = 32 * ct;
@@ -886,17 +903,10 @@ __global__ __launch_bounds__(64 * (NS + ND + NW), (NS + ND + NW + 3) / 4) void p
     PN_T_DECL
     auto run = [&](auto w_tag) {
       constexpr int W = decltype(w_tag)::value;
-      int m_prev = 0, m_cur = part_of(0);
       for (int it = 0; it < n_it; ++it) {
-        const int b = it & 1;
-        const int m_next = part_of(it + 1);
-        if (it > 0) epilogue(it - 1, m_prev, Half0{});
-        load_y(it, m_cur, Half0{});
-        m_prev = m_cur;
-        m_cur = m_next;
-        const unsigned char* ba = pa[b] + offa;
-        pn_bf16x8 f[4][3];  // fragments of A's four column tiles (only the ones this wave's tiles use are loaded; one
-        // k-step at a time: these waves have the slack, and the registers go to the epilogue's state)
+        const unsigned char* ba = pa[it & 1] + offa;
+        pn_bf16x8 f[4][3];  // fragments of A's four column tiles (only the ones this wave's tiles use are loaded), one
+        // k-step at a time
 #pragma unroll
         for (int ks = 0; ks < KW; ++ks) {
           pn_static_for<4>([&](auto c_tag) {
@@ -916,7 +926,6 @@ __global__ __launch_bounds__(64 * (NS + ND + NW), (NS + ND + NW + 3) / 4) void p
         }
         PN_BAR
       }
-      if (n_it > 0) epilogue(n_it - 1, m_prev, Half0{});
       float* out = dwpart + (long long)blockIdx.x * ELEMS;  // the full matrix: upper tiles and their mirror images
       pn_static_for<TPW>([&](auto i_tag) {
         constexpr int i = decltype(i_tag)::value;
@@ -936,7 +945,6 @@ __global__ __launch_bounds__(64 * (NS + ND + NW), (NS + ND + NW + 3) / 4) void p
     else if (ww == 2) run(std::integral_constant<int, 2>{});
     else run(std::integral_constant<int, 3>{});
     PN_T_REPORT("gram")
-    put_sums();
   }
   __syncthreads();  // the end-of-block scratch (aliasing the panels, which nobody reads any more) is complete
   {
