@@ -3,27 +3,32 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "arena.h"
 
 namespace mpa {
 
-// extra workspace the grid-pruned whole-shape search needs (floats / int32s)
-int64_t grid_workspace_floats(int64_t B, int64_t P, int64_t N);
-int64_t grid_workspace_ints(int64_t B);
-// inside that scratch: the per-part bounding boxes [B*P][12] (lo of shape 1, lo of shape 2, hi of shape 1, hi of shape 2)
-// and the one-word ticket of the sort launch — both written by the producer of S1 / S2 BEFORE launch_grid_shape_search
+// The region of the fused loss's workspace that the grid-pruned whole-shape search works in, carved from the float and the
+// int32 workspace.  bbox: the per-part bounding boxes [B*P][12] (lo of shape 1, lo of shape 2, hi of shape 1, hi of shape 2);
+// ticket: the one-word ticket of the sort launch — both written by the producer of S1 / S2 BEFORE launch_grid_shape_search
 // (boxes of the valid parts; ticket = 0).
-float* grid_bbox(float* fws, int64_t B, int64_t P, int64_t N);
-unsigned* grid_ticket(int32_t* iws, int64_t B);
+struct GridWs {
+  float4* records;
+  void *params, *plan;  // GridParams [B], XcdPlan (types of grid_nn.hip)
+  float *dist1, *dist2, *bbox;
+  int *starts, *batches, *worklist;
+  unsigned* ticket;
+};
+GridWs grid_carve(Arena& fa, Arena& ia, int64_t B, int64_t P, int64_t N);
 
 // Exact NN of every valid point of S1 in S2 and vice versa (whole shapes of each sample, padded parts as
 // one representative).  Writes idx1/idx2 [B,P,N] (index within the sample, -1 if none) and the per-part
-// distance sums into tile_sums[dir][m*tiles + 0].  fws/iws: scratch sized by the functions above.
+// distance sums into tile_sums[dir][m*tiles + 0].
 // before_search / after_search (nullable) are recorded around the search kernel proper.
 // route (nullable) [B]: samples with route[b] == 0 are left to the leaf search (no work, no sums written for them).
 // phases: 1 = build the grid, 2 = the search kernel, 4 = per-part distance sums (a caller that puts another search's
 // launches between the search kernel and the sums calls three times).
 int launch_grid_shape_search(const float* valids, const float* S1, const float* S2, int64_t B, int64_t P,
-                             int64_t N, int tiles, float* fws, int32_t* iws, int32_t* idx1, int32_t* idx2,
+                             int64_t N, int tiles, const GridWs& g, int32_t* idx1, int32_t* idx2,
                              float* tile_sums, hipEvent_t before_search, hipEvent_t after_search, hipStream_t s,
                              const int* route = nullptr, int phases = 7);
 
@@ -57,14 +62,19 @@ void launch_leaf_order(const float* part_pcs, const float* valids, int64_t B, in
                        hipStream_t s);
 // exact NN of cloud A's valid points in cloud B (idx1) and vice versa (idx2): shape = every point against the sample's whole
 // other shape (indices p * N + n), else every part against its own copy (indices n); per-wave distance sums into
-// wave_sums[dir][m][NW], NW = max(1, Npad / 64).  scratch: leaf_scratch_floats() floats (16-byte aligned), shared by the two
-// searches of a loss evaluation; its two counters (leaf_heavy_counters) must be zero when the first search starts.
+// wave_sums[dir][m][NW], NW = max(1, Npad / 64).  The heavy list, its keys and the two counters of `w` are scratch shared by
+// the two searches of a loss evaluation; the counters must be zero when the first search starts.
 // route (nullable) [B]: the whole-shape search skips samples with route[b] != 0 (searched by the grid, grid_nn.hip).
-int64_t leaf_scratch_floats(int64_t B, int64_t P, int64_t N);
-int* leaf_heavy_counters(float* scratch);
-int* leaf_route(float* scratch);  // [B] ints inside the scratch
+// Its region of the loss's float workspace (all null when !leaf_supported): the library's own k-d order (callers may hand
+// one in), records / leaf boxes / part boxes of R1, R2, S1, S2, the searches' wave sums and the scratch.
+struct LeafWs {
+  float *order, *rec[4], *leaf[4], *pbox[4], *wsum_part, *wsum_shape;
+  int *heavy_counters, *route, *heavy_list;
+  unsigned long long* heavy_keys;
+};
+LeafWs leaf_carve(Arena& fa, int64_t B, int64_t P, int64_t N);
 void launch_leaf_search(bool shape, const float* valids, const LeafCloud& A, const LeafCloud& B_, int64_t B, int64_t P,
-                        int64_t N, int32_t* idx1, int32_t* idx2, float* wave_sums, float* scratch, hipStream_t s,
+                        int64_t N, int32_t* idx1, int32_t* idx2, float* wave_sums, const LeafWs& w, hipStream_t s,
                         const int* route = nullptr);
 // Which search answers each sample's whole-shape term (route[b]: 1 = grid, 0 = leaf).  force < 0: by the sample itself —
 // the share of the ground-truth shape's bounding box that its parts' boxes fill (part boxes pbox [B*P][8]); many small

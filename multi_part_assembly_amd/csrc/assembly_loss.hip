@@ -868,27 +868,7 @@ __global__ void assembly_backward_finish_kernel(const float* __restrict__ go, co
   else gt[3 * m + (k - RW)] = s;
 }
 
-// floats the leaf search adds to the workspace: order + 4 record arrays (float4 per slot), 4 x leaf boxes, 4 x part boxes
-int64_t leaf_workspace_floats(int64_t B, int64_t P, int64_t N) {
-  if (!mpa::leaf_supported(P, N)) return 0;
-  const int64_t npad = mpa::leaf_npad(N), nw = npad >= 64 ? npad / 64 : 1;
-  // + per-wave distance sums (2 searches x 2 directions) + the searches' scratch
-  return 20 * B * P * npad + 32 * B * P * (npad / 32) + 32 * B * P + (4 * B * P * nw + 3) / 4 * 4 +
-         mpa::leaf_scratch_floats(B, P, N);
-}
-
 }  // namespace
-
-extern "C" int mpa_assembly_loss_workspace(int64_t B, int64_t P, int64_t N, int64_t* float_elems,
-                                           int64_t* int_elems) {
-  MPA_REQUIRE(B >= 0 && P >= 0 && N >= 0 && float_elems && int_elems, "assembly_loss_workspace: bad args");
-  const int64_t tiles = (N + kMinTile - 1) / kMinTile;
-  // 4 clouds + partial[5] + 2 tile-sum arrays (2 directions each), rounded to 16 B, + grid-search scratch
-  *float_elems = (4 * B * P * N * 3 + 5 * B * P + 4 * B * P * tiles + 3) / 4 * 4 + mpa::grid_workspace_floats(B, P, N) +
-                 leaf_workspace_floats(B, P, N);
-  *int_elems = 4 * B * P * N + mpa::grid_workspace_ints(B);
-  return MPA_OK;
-}
 
 extern "C" int mpa_assembly_order_elems(int64_t B, int64_t P, int64_t N, int64_t* float_elems) {
   MPA_REQUIRE(B >= 0 && P >= 0 && N >= 0 && float_elems, "assembly_order_elems: bad args");
@@ -908,12 +888,11 @@ extern "C" int mpa_assembly_order(const float* part_pcs, const float* valids, in
 
 namespace {
 struct Workspace {
-  float *R1, *R2, *S1, *S2, *partial, *part_tiles, *shape_tiles, *grid_f;
-  int *ip1, *ip2, *is1, *is2, *grid_i;
+  float *R1, *R2, *S1, *S2, *partial, *part_tiles, *shape_tiles;
+  int *ip1, *ip2, *is1, *is2;
   int tiles;
-  // leaf search (leaf_nn.hip): the library's own k-d order (callers may hand one in), records / leaf boxes / part boxes
-  // of the four clouds R1, R2, S1, S2
-  float *order, *rec[4], *leaf[4], *pbox[4], *wsum_part, *wsum_shape, *scratch;
+  mpa::GridWs grid;  // grid-pruned whole-shape search (grid_nn.hip)
+  mpa::LeafWs leaf;  // leaf search (leaf_nn.hip)
 };
 
 // Which searches answer the two Chamfer terms.  0: brute-force scans; 1 (default): brute-force per-part scan +
@@ -951,39 +930,41 @@ bool part_search_gate(int64_t N) {
   return mpa::gate_supported(N, N) && (N >= 64 || (e != nullptr && e[0] == 'g'));
 }
 
-Workspace carve(float* fws, int32_t* iws, int64_t B, int64_t P, int64_t N, int q) {
+// float_ws: the four posed clouds lead (include/mpa_hip.h), then partial[5], the tile sums, the grid search's region and
+// the leaf search's; int_ws: the four arg-min arrays lead, then the grid search's region.
+Workspace carve(mpa::Arena& fa, mpa::Arena& ia, int64_t B, int64_t P, int64_t N, int q) {
   Workspace w;
   const int64_t cloud = B * P * N * 3, pn = B * P * N;
   const int64_t tile = 64 * (int64_t)q;
   w.tiles = (int)((N + tile - 1) / tile);
-  w.R1 = fws;
-  w.R2 = fws + cloud;
-  w.S1 = fws + 2 * cloud;
-  w.S2 = fws + 3 * cloud;
-  w.partial = fws + 4 * cloud;
-  w.part_tiles = w.partial + 5 * B * P;
-  w.shape_tiles = w.part_tiles + 2 * B * P * w.tiles;  // (capacity was sized for the smallest tile)
-  w.ip1 = iws;
-  w.ip2 = iws + pn;
-  w.is1 = iws + 2 * pn;
-  w.is2 = iws + 3 * pn;
-  w.grid_i = iws + 4 * pn;
-  const int64_t min_tiles = (N + kMinTile - 1) / kMinTile;
-  w.grid_f = fws + (4 * cloud + 5 * B * P + 4 * B * P * min_tiles + 3) / 4 * 4;
-  float* lf = w.grid_f + mpa::grid_workspace_floats(B, P, N);
-  const int64_t npad = mpa::leaf_supported(P, N) ? mpa::leaf_npad(N) : 0;
-  w.order = lf;
-  lf += 4 * B * P * npad;
-  for (int c = 0; c < 4; ++c, lf += 4 * B * P * npad) w.rec[c] = lf;
-  for (int c = 0; c < 4; ++c, lf += 8 * B * P * (npad / 32)) w.leaf[c] = lf;
-  for (int c = 0; c < 4; ++c, lf += 8 * B * P) w.pbox[c] = lf;
-  const int64_t nw = npad >= 64 ? npad / 64 : 1;
-  w.wsum_part = lf;
-  w.wsum_shape = lf + 2 * B * P * nw;
-  w.scratch = lf + (4 * B * P * nw + 3) / 4 * 4;
+  w.R1 = fa.take<float>(cloud, 4);
+  w.R2 = fa.take<float>(cloud, 4);
+  w.S1 = fa.take<float>(cloud, 4);
+  w.S2 = fa.take<float>(cloud, 4);
+  w.partial = fa.take<float>(5 * B * P, 4);
+  // two tile-sum arrays of two directions each.  Their capacity is sized for the smallest tile any scan variant uses
+  // (kMinTile), so that the size does not depend on q; the second array starts behind the first at THIS call's tile count.
+  w.part_tiles = fa.take<float>(4 * B * P * ((N + kMinTile - 1) / kMinTile), 4);
+  w.shape_tiles = w.part_tiles ? w.part_tiles + 2 * B * P * w.tiles : nullptr;
+  w.ip1 = ia.take<int>(pn, 4);
+  w.ip2 = ia.take<int>(pn, 4);
+  w.is1 = ia.take<int>(pn, 4);
+  w.is2 = ia.take<int>(pn, 4);
+  w.grid = mpa::grid_carve(fa, ia, B, P, N);  // (starts on a multiple of 16 bytes)
+  w.leaf = mpa::leaf_carve(fa, B, P, N);
   return w;
 }
 }  // namespace
+
+extern "C" int mpa_assembly_loss_workspace(int64_t B, int64_t P, int64_t N, int64_t* float_elems,
+                                           int64_t* int_elems) {
+  MPA_REQUIRE(B >= 0 && P >= 0 && N >= 0 && float_elems && int_elems, "assembly_loss_workspace: bad args");
+  mpa::Arena fa(nullptr), ia(nullptr);
+  carve(fa, ia, B, P, N, 2);  // (the size does not depend on q)
+  *float_elems = fa.elems<float>();
+  *int_elems = ia.elems<int32_t>();
+  return MPA_OK;
+}
 
 extern "C" int mpa_assembly_loss_forward_ordered(const float* part_pcs, const float* valids,
                                                  const float* quat_pred, const float* trans_pred,
@@ -1043,7 +1024,9 @@ int loss_forward(const float* part_pcs, const float* valids, const float* quat_p
               "assembly_loss_forward: problem too large");
   hipStream_t s = mpa::as_stream(stream);
   const int q = pick_q(B, P, N);
-  const Workspace w = carve(float_ws, int_ws, B, P, N, q);
+  mpa::Arena fa(float_ws), ia(int_ws);
+  const Workspace w = carve(fa, ia, B, P, N, q);
+  const mpa::LeafWs& lw = w.leaf;
   const unsigned parts = (unsigned)(B * P);
   const int mode = search_mode(P, N, search);
   // padded parts never write their tile sums: clear them (2 directions x B*P*tiles, both arrays)
@@ -1051,62 +1034,62 @@ int loss_forward(const float* part_pcs, const float* valids, const float* quat_p
   mark(0);
   if (mode >= 2) {
     // ---- leaf search: k-d order (once per batch), pose kernel in that order, both searches over the leaves ----
-    int* route = mpa::leaf_route(w.scratch);
+    int* route = lw.route;
     const int npad = mpa::leaf_npad(N);
     MPA_REQUIRE(B * P * (int64_t)npad < (1LL << 31), "assembly_loss_forward: problem too large");
     if (order == nullptr) {
-      mpa::launch_leaf_order(part_pcs, valids, B, P, N, w.order, s);
-      order = w.order;
+      mpa::launch_leaf_order(part_pcs, valids, B, P, N, lw.order, s);
+      order = lw.order;
     }
     LeafOut lo;
     for (int c = 0; c < 4; ++c) {
-      lo.rec[c] = reinterpret_cast<float4*>(w.rec[c]);
-      lo.leaf[c] = w.leaf[c];
-      lo.part[c] = w.pbox[c];
+      lo.rec[c] = reinterpret_cast<float4*>(lw.rec[c]);
+      lo.leaf[c] = lw.leaf[c];
+      lo.part[c] = lw.pbox[c];
     }
     hipLaunchKernelGGL(assembly_pose_leaf_kernel<RW>, dim3(parts), dim3(kThreads), 0, s,
                        reinterpret_cast<const float4*>(order), valids, quat_pred, trans_pred, quat_gt, trans_gt, (int)P,
                        (int)N, npad, fill_pad_points, w.R1, w.R2, w.S1, w.S2, w.partial, lo,
-                       mpa::leaf_heavy_counters(w.scratch), mode == 3 ? mpa::grid_bbox(w.grid_f, B, P, N) : (float*)nullptr,
-                       mode == 3 ? mpa::grid_ticket(w.grid_i, B) : (unsigned*)nullptr);
-    mpa::launch_leaf_route(valids, w.pbox[3], B, P, mode == 3 ? -1 : 0, route, s);
+                       lw.heavy_counters, mode == 3 ? w.grid.bbox : (float*)nullptr,
+                       mode == 3 ? w.grid.ticket : (unsigned*)nullptr);
+    mpa::launch_leaf_route(valids, lw.pbox[3], B, P, mode == 3 ? -1 : 0, route, s);
     mark(1);
-    const mpa::LeafCloud r1{w.rec[0], w.leaf[0], w.pbox[0], w.R1}, r2{w.rec[1], w.leaf[1], w.pbox[1], w.R2};
-    const mpa::LeafCloud s1{w.rec[2], w.leaf[2], w.pbox[2], w.S1}, s2{w.rec[3], w.leaf[3], w.pbox[3], w.S2};
+    const mpa::LeafCloud r1{lw.rec[0], lw.leaf[0], lw.pbox[0], w.R1}, r2{lw.rec[1], lw.leaf[1], lw.pbox[1], w.R2};
+    const mpa::LeafCloud s1{lw.rec[2], lw.leaf[2], lw.pbox[2], w.S1}, s2{lw.rec[3], lw.leaf[3], lw.pbox[3], w.S2};
     // per-part Chamfer: the matrix-core gated search on the clouds in original order (0.10 vs 0.16 ms on the artifact mix);
     // MPA_PART_SEARCH=scan leaves it to the leaf search as in the first half of round 5
     const bool part_gate = part_search_gate(N);
     if (part_gate)
       mpa::launch_gate_part_search(valids, w.R1, w.R2, B, P, N, w.ip1, w.ip2, w.part_tiles, s);
     else
-      mpa::launch_leaf_search(false, valids, r1, r2, B, P, N, w.ip1, w.ip2, w.wsum_part, w.scratch, s);
+      mpa::launch_leaf_search(false, valids, r1, r2, B, P, N, w.ip1, w.ip2, lw.wsum_part, lw, s);
     mark(2);
     // [5] .. [6] bracket the search kernels proper of BOTH routes (grid search, leaf search + its second pass) — not the
     // grid's build and its distance sums, as in rounds 1-4.  A route no sample takes costs its launches a header each.
     if (mode == 3)
-      mpa::launch_grid_shape_search(valids, w.S1, w.S2, B, P, N, w.tiles, w.grid_f, w.grid_i, w.is1, w.is2,
+      mpa::launch_grid_shape_search(valids, w.S1, w.S2, B, P, N, w.tiles, w.grid, w.is1, w.is2,
                                     w.shape_tiles, nullptr, nullptr, s, route, 1);
     mark(5);
     if (mode == 3)
-      mpa::launch_grid_shape_search(valids, w.S1, w.S2, B, P, N, w.tiles, w.grid_f, w.grid_i, w.is1, w.is2,
+      mpa::launch_grid_shape_search(valids, w.S1, w.S2, B, P, N, w.tiles, w.grid, w.is1, w.is2,
                                     w.shape_tiles, nullptr, nullptr, s, route, 2);
-    mpa::launch_leaf_search(true, valids, s1, s2, B, P, N, w.is1, w.is2, w.wsum_shape, w.scratch, s, route);
+    mpa::launch_leaf_search(true, valids, s1, s2, B, P, N, w.is1, w.is2, lw.wsum_shape, lw, s, route);
     mark(6);
     if (mode == 3)
-      mpa::launch_grid_shape_search(valids, w.S1, w.S2, B, P, N, w.tiles, w.grid_f, w.grid_i, w.is1, w.is2,
+      mpa::launch_grid_shape_search(valids, w.S1, w.S2, B, P, N, w.tiles, w.grid, w.is1, w.is2,
                                     w.shape_tiles, nullptr, nullptr, s, route, 4);
     mark(3);
     const int nw = npad >= 64 ? npad / 64 : 1;  // every wave of a valid part leaves its distance sum
     hipLaunchKernelGGL(assembly_finalize_kernel<RW>, dim3((unsigned)B), dim3(64), 0, s, valids, quat_pred,
-                       trans_pred, quat_gt, trans_gt, w.partial, part_gate ? (const float*)w.part_tiles : (const float*)w.wsum_part,
-                       (const float*)w.wsum_shape, (int)B, (int)P, (int)N, part_gate ? mpa::gate_tiles(N, N) : nw, nw, training, losses,
+                       trans_pred, quat_gt, trans_gt, w.partial, part_gate ? (const float*)w.part_tiles : (const float*)lw.wsum_part,
+                       (const float*)lw.wsum_shape, (int)B, (int)P, (int)N, part_gate ? mpa::gate_tiles(N, N) : nw, nw, training, losses,
                        (const float*)w.shape_tiles, w.tiles, (const int*)route);
     mark(4);
     return mpa::check_launch("assembly_loss_forward");
   }
   hipLaunchKernelGGL(assembly_pose_kernel<RW>, dim3(parts), dim3(kThreads), 0, s, part_pcs, valids,
                      quat_pred, trans_pred, quat_gt, trans_gt, (int)N, fill_pad_points, w.R1, w.R2,
-                     w.S1, w.S2, w.partial, mpa::grid_bbox(w.grid_f, B, P, N), mpa::grid_ticket(w.grid_i, B));
+                     w.S1, w.S2, w.partial, w.grid.bbox, w.grid.ticket);
   mark(1);
   const dim3 grid(parts * w.tiles, 2, 1);
   // Steering a sample's blocks to one XCD (L2 affinity) loses more to the static load imbalance between
@@ -1126,7 +1109,7 @@ int loss_forward(const float* part_pcs, const float* valids, const float* quat_p
                        w.R1, w.R2, (int)B, (int)P, (int)N, w.tiles, remap, w.ip1, w.ip2, w.part_tiles);
   mark(2);
   if (mode == 1)
-    mpa::launch_grid_shape_search(valids, w.S1, w.S2, B, P, N, w.tiles, w.grid_f, w.grid_i, w.is1, w.is2,
+    mpa::launch_grid_shape_search(valids, w.S1, w.S2, B, P, N, w.tiles, w.grid, w.is1, w.is2,
                                   w.shape_tiles, events ? reinterpret_cast<hipEvent_t>(events[5]) : nullptr,
                                   events ? reinterpret_cast<hipEvent_t>(events[6]) : nullptr, s);
   else if (q == 4)
@@ -1153,8 +1136,8 @@ int loss_backward(const float* grad_losses, const float* part_pcs, const float* 
   MPA_REQUIRE(P >= 1 && P <= 64 && N >= 1, "assembly_loss_backward: need 1 <= P <= 64 and N >= 1");
   MPA_REQUIRE(grad_losses && part_pcs && valids && quat_pred && trans_pred && quat_gt && trans_gt &&
                   float_ws && int_ws && grad_quat && grad_trans, "assembly_loss_backward: null pointer");
-  const Workspace w = carve(const_cast<float*>(float_ws), const_cast<int32_t*>(int_ws), B, P, N,
-                            pick_q(B, P, N));
+  mpa::Arena fa(const_cast<float*>(float_ws)), ia(const_cast<int32_t*>(int_ws));
+  const Workspace w = carve(fa, ia, B, P, N, pick_q(B, P, N));
   // four slices of the point range per part when the (forward-only) tile-sum area (4 * B*P * tiles floats) is big enough
   // for their partials (KS per slice: 8 quaternion, 16 matrix)
   const int S = RW == 4 ? (w.tiles >= 8 ? 4 : 1) : (w.tiles >= 16 ? 4 : (w.tiles >= 8 ? 2 : 1));

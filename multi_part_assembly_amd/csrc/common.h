@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include "../../include/mpa_hip.h"
+#include "arena.h"
 
 namespace mpa {
 

@@ -1320,17 +1320,17 @@ struct KnnWs {
   unsigned char* scnt;
 };
 
-template <typename Take>
-KnnWs knn_carve(Take&& take, int64_t M, int64_t N) {
+constexpr int64_t kWsAlign = 256;  // every field starts on, and is padded to, 256 bytes
+KnnWs knn_carve(mpa::Arena& a, int64_t M, int64_t N) {
   KnnWs k;
   const int64_t R = M * N;
-  k.xs = reinterpret_cast<unsigned short*>(take(2 * R * 2 * 128));
-  k.surv = reinterpret_cast<unsigned short*>(take(2 * R * 2 * kKfCap));
-  k.nl = reinterpret_cast<float*>(take(4 * R));
-  k.nu = reinterpret_cast<float*>(take(4 * R));
-  k.theta = reinterpret_cast<float*>(take(4 * R));
-  k.scnt = reinterpret_cast<unsigned char*>(take(2 * R));
-  k.mu = reinterpret_cast<float*>(take(4 * M * 128));  // one-product form: the clouds' centres
+  k.xs = a.take<unsigned short>(R * 2 * 128, kWsAlign);
+  k.surv = a.take<unsigned short>(R * 2 * kKfCap, kWsAlign);
+  k.nl = a.take<float>(R, kWsAlign);
+  k.nu = a.take<float>(R, kWsAlign);
+  k.theta = a.take<float>(R, kWsAlign);
+  k.scnt = a.take<unsigned char>(2 * R, kWsAlign);
+  k.mu = a.take<float>(M * 128, kWsAlign);  // one-product form: the clouds' centres
   return k;
 }
 
@@ -1399,56 +1399,51 @@ struct Ws {
 
 Ws dg_carve(char* base, int64_t M, int64_t N, int64_t F) {
   Ws w;
-  char* p = base;
-  auto take = [&](int64_t bytes) {
-    char* r = p;
-    p += (bytes + 255) / 256 * 256;
-    return r;
-  };
+  mpa::Arena a(base);
   const int64_t R = M * N, tiles = (R + kTile - 1) / kTile;
-  w.hdr = reinterpret_cast<int*>(take(64));
-  w.vlist = reinterpret_cast<int*>(take(4 * M));
-  w.rank = reinterpret_cast<int*>(take(4 * M));
-  w.tickets = reinterpret_cast<unsigned*>(take(64));
-  w.x0 = reinterpret_cast<float4*>(take(16 * R));
-  w.hcat = reinterpret_cast<float*>(take(4 * R * kCat));
+  w.hdr = a.take<int>(16, kWsAlign);
+  w.vlist = a.take<int>(M, kWsAlign);
+  w.rank = a.take<int>(M, kWsAlign);
+  w.tickets = a.take<unsigned>(16, kWsAlign);
+  w.x0 = a.take<float4>(R, kWsAlign);
+  w.hcat = a.take<float>(R * kCat, kWsAlign);
   for (int l = 0; l < 4; ++l) {
-    w.uv[l] = reinterpret_cast<float*>(take(4 * R * 2 * kCO[l]));
-    w.esel[l] = reinterpret_cast<float*>(take(4 * R * kCO[l]));
-    w.s1[l] = reinterpret_cast<float*>(take(4 * R * kCO[l]));
-    w.ssel[l] = reinterpret_cast<unsigned char*>(take(R * kCO[l]));
-    w.idx[l] = reinterpret_cast<unsigned short*>(take(2 * R * kNbr));
-    w.bn[l] = reinterpret_cast<float*>(take(4 * 4 * kCO[l]));
-    w.wstk[l] = reinterpret_cast<float*>(take(4 * 2 * kCO[l] * kCinP[l]));
-    w.wstt[l] = reinterpret_cast<float*>(take(4 * 2 * kCO[l] * kCinP[l]));
+    w.uv[l] = a.take<float>(R * 2 * kCO[l], kWsAlign);
+    w.esel[l] = a.take<float>(R * kCO[l], kWsAlign);
+    w.s1[l] = a.take<float>(R * kCO[l], kWsAlign);
+    w.ssel[l] = a.take<unsigned char>(R * kCO[l], kWsAlign);
+    w.idx[l] = a.take<unsigned short>(R * kNbr, kWsAlign);
+    w.bn[l] = a.take<float>(4 * kCO[l], kWsAlign);
+    w.wstk[l] = a.take<float>(2 * kCO[l] * kCinP[l], kWsAlign);
+    w.wstt[l] = a.take<float>(2 * kCO[l] * kCinP[l], kWsAlign);
   }
-  w.y5 = reinterpret_cast<float*>(take(4 * R * F));
-  w.norm = reinterpret_cast<float*>(take(4 * R));
-  w.bn[4] = reinterpret_cast<float*>(take(4 * 4 * F));
-  w.coef = reinterpret_cast<float*>(take(4 * 3 * kCat));
+  w.y5 = a.take<float>(R * F, kWsAlign);
+  w.norm = a.take<float>(R, kWsAlign);
+  w.bn[4] = a.take<float>(4 * F, kWsAlign);
+  w.coef = a.take<float>(3 * kCat, kWsAlign);
   const int64_t prow = tiles > M ? tiles : M;  // partial table rows: row tiles or parts
-  w.partial = reinterpret_cast<float*>(take(4 * prow * kCat * 2));
-  w.w5t = reinterpret_cast<float*>(take(4 * kCat * F));
-  w.pooled = reinterpret_cast<float*>(take(4 * M * 2 * F));
-  w.dpooled = reinterpret_cast<float*>(take(4 * M * 2 * F));
-  w.arg5 = reinterpret_cast<int*>(take(4 * M * F));
+  w.partial = a.take<float>(prow * kCat * 2, kWsAlign);
+  w.w5t = a.take<float>(kCat * F, kWsAlign);
+  w.pooled = a.take<float>(M * 2 * F, kWsAlign);
+  w.dpooled = a.take<float>(M * 2 * F, kWsAlign);
+  w.arg5 = a.take<int>(M * F, kWsAlign);
   int64_t tn = (int64_t)kTnChunks * kCat * 128;  // largest weight gradient: 512 x 128 (or F x 512)
   if ((int64_t)kTnChunks * F * kCat > tn) tn = (int64_t)kTnChunks * F * kCat;
   const int64_t first = ((R + kFirstTile - 1) / kFirstTile) * 128 * 4;  // first-stage weight-gradient partials
   if (first > tn) tn = first;
-  w.tnpart = reinterpret_cast<float*>(take(4 * tn));
-  w.dhcat = reinterpret_cast<float*>(take(4 * R * kCat));
-  w.duv = reinterpret_cast<float*>(take(4 * R * 2 * kCO[3]));
-  w.dz = reinterpret_cast<float*>(take(4 * R * kCO[3]));
-  w.gstk = reinterpret_cast<float*>(take(4 * kCat * 128));
+  w.tnpart = a.take<float>(tn, kWsAlign);
+  w.dhcat = a.take<float>(R * kCat, kWsAlign);
+  w.duv = a.take<float>(R * 2 * kCO[3], kWsAlign);
+  w.dz = a.take<float>(R * kCO[3], kWsAlign);
+  w.gstk = a.take<float>(kCat * 128, kWsAlign);
   for (int l = 0; l < 4; ++l) {
-    w.rptr[l] = reinterpret_cast<int*>(take(4 * M * (N + 1)));
-    w.order[l] = reinterpret_cast<int*>(take(4 * M * N));
+    w.rptr[l] = a.take<int>(M * (N + 1), kWsAlign);
+    w.order[l] = a.take<int>(M * N, kWsAlign);
   }
-  for (int l = 0; l < 4; ++l) w.rlist[l] = reinterpret_cast<unsigned short*>(take(2 * R * kNbr));
-  w.stage = reinterpret_cast<double*>(take(8 * 2 * kCat * ((prow + kEB - 1) / kEB)));
-  w.knn = knn_carve(take, M, N);
-  w.total = p - base;
+  for (int l = 0; l < 4; ++l) w.rlist[l] = a.take<unsigned short>(R * kNbr, kWsAlign);
+  w.stage = a.take<double>(2 * kCat * ((prow + kEB - 1) / kEB), kWsAlign);
+  w.knn = knn_carve(a, M, N);
+  w.total = a.bytes();
   return w;
 }
 
@@ -1824,16 +1819,11 @@ struct KnnExactWs {
 };
 KnnExactWs knn_exact_carve(char* base, int64_t n, int64_t N) {
   KnnExactWs w;
-  char* p = base;
-  auto take = [&](int64_t bytes) {
-    char* r = p;
-    p += (bytes + 255) / 256 * 256;
-    return r;
-  };
-  w.hdr = reinterpret_cast<int*>(take(64));
-  w.norm = reinterpret_cast<float*>(take(4 * n * N));
-  w.knn = knn_carve(take, n, N);
-  w.total = p - base;
+  mpa::Arena a(base);
+  w.hdr = a.take<int>(16, kWsAlign);
+  w.norm = a.take<float>(n * N, kWsAlign);
+  w.knn = knn_carve(a, n, N);
+  w.total = a.bytes();
   return w;
 }
 }  // namespace

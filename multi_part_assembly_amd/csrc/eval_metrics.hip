@@ -323,6 +323,9 @@ __global__ __launch_bounds__(kConnThreads) void connectivity_kernel(const float*
   for (int b = threadIdx.x; b < B; b += kConnThreads) out[b] = acc;
 }
 
+// the metrics' workspace: the per-slot rows [kSlotRows][B * P] of doubles
+double* metrics_carve(mpa::Arena& a, int64_t B, int64_t P) { return a.take<double>(kSlotRows * B * P, 8); }
+
 template <bool kRmat>
 int assembly_metrics(const float* part_pcs, const float* trans_pred, const float* trans_gt, const float* rot_pred,
                      const float* rot_gt, const float* valids, int64_t B, int64_t P, int64_t N, void* workspace, float* out,
@@ -335,7 +338,8 @@ int assembly_metrics(const float* part_pcs, const float* trans_pred, const float
   MPA_REQUIRE(part_pcs && trans_pred && trans_gt && rot_pred && rot_gt && valids && workspace && out,
               "assembly_metrics: null pointer");
   MPA_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "assembly_metrics: workspace must be 8-byte aligned");
-  double* slot = static_cast<double*>(workspace);
+  mpa::Arena arena(workspace);
+  double* slot = metrics_carve(arena, B, P);
   const size_t lds = 2 * sizeof(float) * (size_t)((3 * N + 3) & ~3LL);
   hipLaunchKernelGGL(slot_metrics_kernel<kRmat>, dim3((unsigned)(B * P)), dim3(kThreads), lds, mpa::as_stream(stream), part_pcs,
                      trans_pred, trans_gt, rot_pred, rot_gt, valids, (int)N, (long long)(B * P), slot, per_part);
@@ -351,7 +355,9 @@ int assembly_metrics(const float* part_pcs, const float* trans_pred, const float
 extern "C" int mpa_assembly_metrics_workspace(int64_t B, int64_t P, int64_t* bytes) {
   MPA_REQUIRE(bytes != nullptr, "assembly_metrics_workspace: null pointer");
   MPA_REQUIRE(B >= 0 && P >= 0 && B * P < (1LL << 31) / kSlotRows, "assembly_metrics_workspace: bad size");
-  *bytes = (int64_t)sizeof(double) * kSlotRows * B * P;
+  mpa::Arena a(nullptr);
+  metrics_carve(a, B, P);
+  *bytes = a.bytes();
   return MPA_OK;
 }
 

@@ -422,11 +422,18 @@ extern "C" int mpa_narrow_linear_relu_forward(const float* x, const float* w, co
   return mpa::check_launch("narrow_linear_relu_forward");
 }
 
+struct NlWs { float* part; int64_t total; };  // the narrow linear layer's workspace: the backward's per-chunk partial sums
+static NlWs nl_carve(float* ws, int64_t R, int64_t N) {
+  mpa::Arena a(ws);
+  float* part = a.take<float>(((R + kNlRows - 1) / kNlRows) * N * (kMaxK + 1), 4);
+  return {part, a.elems<float>()};
+}
+
 extern "C" int mpa_narrow_linear_relu_workspace(int64_t R, int64_t K, int64_t N, int64_t* float_elems) {
   MPA_REQUIRE(float_elems != nullptr, "narrow_linear_relu_workspace: null pointer");
   MPA_REQUIRE(R >= 1 && R <= (1 << 24) && K >= 1 && K <= kMaxK && N >= 1 && N <= (1 << 16),
               "narrow_linear_relu: R=%lld K=%lld (1..%d) N=%lld out of range", (long long)R, (long long)K, kMaxK, (long long)N);
-  *float_elems = ((R + kNlRows - 1) / kNlRows) * N * (kMaxK + 1);  // the backward's per-chunk partial sums
+  *float_elems = nl_carve(nullptr, R, N).total;
   return MPA_OK;
 }
 
@@ -438,18 +445,27 @@ extern "C" int mpa_narrow_linear_relu_backward(const float* grad_out, const floa
   MPA_REQUIRE(grad_out && out && x && w && ws && grad_w, "narrow_linear_relu_backward: null pointer");
   hipStream_t s = mpa::as_stream(stream);
   const int chunks = (int)((R + kNlRows - 1) / kNlRows);
+  float* part = nl_carve(ws, R, N).part;
   launch(nl_bwd_kernel, dim3((unsigned)(R + ((N + 63) / 64) * chunks)), dim3(512), s, grad_out, out, x, w, (int)R, (int)K,
-         (int)N, grad_x, ws);
-  launch(nl_reduce_kernel, dim3((unsigned)((N * (K + 1) + 255) / 256)), dim3(256), s, (const float*)ws, chunks, (int)K, (int)N,
+         (int)N, grad_x, part);
+  launch(nl_reduce_kernel, dim3((unsigned)((N * (K + 1) + 255) / 256)), dim3(256), s, (const float*)part, chunks, (int)K, (int)N,
          grad_w, grad_b);
   return mpa::check_launch("narrow_linear_relu_backward");
+}
+
+struct RhWs { float *sig, *part; int64_t total; };  // the relation head's: the sigmoids, then the backward's per-block partials
+static RhWs rh_carve(float* ws, int64_t R, int64_t K) {
+  mpa::Arena a(ws);
+  float* sig = a.take<float>(R, 4);
+  float* part = a.take<float>(((R + kRhRows - 1) / kRhRows) * (K + 1), 4);
+  return {sig, part, a.elems<float>()};
 }
 
 extern "C" int mpa_relation_head_workspace(int64_t R, int64_t K, int64_t* float_elems) {
   MPA_REQUIRE(float_elems != nullptr, "relation_head_workspace: null pointer");
   MPA_REQUIRE(R >= 1 && R <= (1 << 24) && K >= 4 && K % 4 == 0 && K <= 4096,
               "relation_head: R=%lld K=%lld (a multiple of 4, <= 4096) out of range", (long long)R, (long long)K);
-  *float_elems = R + ((R + kRhRows - 1) / kRhRows) * (K + 1);  // the sigmoids, then the backward's per-block partials
+  *float_elems = rh_carve(nullptr, R, K).total;
   return MPA_OK;
 }
 
@@ -458,8 +474,8 @@ extern "C" int mpa_relation_head_forward(const float* h, const float* w, const f
   int64_t n;
   if (int st = mpa_relation_head_workspace(R, K, &n)) return st;
   MPA_REQUIRE(h && w && ws && out, "relation_head_forward: null pointer");
-  launch(rh_fwd_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), mpa::as_stream(stream), h, w, bias, mask, (int)R, (int)K, ws,
-         out);
+  launch(rh_fwd_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), mpa::as_stream(stream), h, w, bias, mask, (int)R, (int)K,
+         rh_carve(ws, R, K).sig, out);
   return mpa::check_launch("relation_head_forward");
 }
 
@@ -471,8 +487,8 @@ extern "C" int mpa_relation_head_backward(const float* grad_out, const float* h,
   MPA_REQUIRE(grad_out && h && w && ws && grad_w, "relation_head_backward: null pointer");
   hipStream_t s = mpa::as_stream(stream);
   const int nblk = (int)((R + kRhRows - 1) / kRhRows);
-  float* part = ws + R;
-  launch(rh_bwd_kernel, dim3((unsigned)nblk), dim3(256), s, grad_out, h, w, mask, (const float*)ws, (int)R, (int)K, grad_h,
+  const auto [sig, part, total] = rh_carve(ws, R, K);
+  launch(rh_bwd_kernel, dim3((unsigned)nblk), dim3(256), s, grad_out, h, w, mask, (const float*)sig, (int)R, (int)K, grad_h,
          part);
   launch(rh_reduce_kernel, dim3((unsigned)((K + 1 + 3) / 4)), dim3(256), s, (const float*)part, nblk, (int)K, grad_w, grad_b);
   return mpa::check_launch("relation_head_backward");

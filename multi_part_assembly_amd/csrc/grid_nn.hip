@@ -1349,44 +1349,42 @@ __global__ __launch_bounds__(256) void grid_part_sum_kernel(const float* __restr
 
 }  // namespace
 
-int64_t grid_workspace_floats(int64_t B, int64_t P, int64_t N) {
-  const int64_t rec = (P * N + 8) * 4;  // float4 records (+ sentinels) per slot
-  // + 2 distance arrays + boxes; a multiple of 4 floats: the leaf search's float4 arrays start right behind this region
-  // (odd B * P * N used to leave them 8-byte aligned)
-  return (4 * B * rec + B * (int64_t)(sizeof(GridParams) / 4) + 2 * B * P * N + 12 * B * P + 3) / 4 * 4;
-}
-int64_t grid_workspace_ints(int64_t B) {  // starts, batches, work list, wave table, ticket
-  return 2 * 4 * B * (int64_t)kStartStride + 4 * B * (int64_t)kWorkStride + (int64_t)(sizeof(XcdPlan) / 4) + 16;
-}
-float* grid_bbox(float* fws, int64_t B, int64_t P, int64_t N) {
-  const int64_t rec = (P * N + 8) * 4;
-  return fws + 4 * B * rec + B * (int64_t)(sizeof(GridParams) / 4) + 2 * B * P * N;
-}
-unsigned* grid_ticket(int32_t* iws, int64_t B) {
-  return reinterpret_cast<unsigned*>(iws + 2 * 4 * B * (int64_t)kStartStride + 4 * B * (int64_t)kWorkStride +
-                                     (int64_t)(sizeof(XcdPlan) / 4));
+GridWs grid_carve(Arena& fa, Arena& ia, int64_t B, int64_t P, int64_t N) {
+  static_assert(sizeof(GridParams) % 4 == 0 && sizeof(XcdPlan) % 4 == 0, "both are carved from arrays of 4-byte words");
+  GridWs g;
+  g.records = fa.take<float4>(4 * B * (P * N + 8), 16);  // float4 records (+ sentinels) per slot
+  g.params = fa.take<GridParams>(B, 4);
+  g.dist1 = fa.take<float>(B * P * N, 4);
+  g.dist2 = fa.take<float>(B * P * N, 4);
+  g.bbox = fa.take<float>(12 * B * P, 4);
+  // the region ends on a multiple of 16 bytes: the leaf search's float4 arrays start right behind it (odd B * P * N used
+  // to leave them 8-byte aligned)
+  fa.take<float>(0, 16);
+  g.starts = ia.take<int>(4 * B * (int64_t)kStartStride, 4);
+  g.batches = ia.take<int>(4 * B * (int64_t)kStartStride, 4);
+  // persistent waves (768 per (sample, direction) on average) walk a pair's work list of (super-cell, 64-query batch) items
+  g.worklist = ia.take<int>(4 * B * (int64_t)kWorkStride, 4);
+  g.plan = ia.take<XcdPlan>(1, 4);
+  g.ticket = ia.take<unsigned>(16, 4);
+  return g;
 }
 
 int launch_grid_shape_search(const float* valids, const float* S1, const float* S2, int64_t B, int64_t P,
-                             int64_t N, int tiles, float* fws, int32_t* iws, int32_t* idx1, int32_t* idx2,
+                             int64_t N, int tiles, const GridWs& g, int32_t* idx1, int32_t* idx2,
                              float* tile_sums, hipEvent_t before_search, hipEvent_t after_search, hipStream_t s,
                              const int* route, int phases) {
   const int rec_stride = (int)(P * N + 8);
-  float4* records = reinterpret_cast<float4*>(fws);
-  GridParams* params = reinterpret_cast<GridParams*>(fws + 4 * B * (int64_t)rec_stride * 4);
-  float* dist1 = reinterpret_cast<float*>(params + B);
-  float* dist2 = dist1 + B * P * N;
-  int* starts = iws;
-  int* batches = iws + 4 * B * (int64_t)kStartStride;
-  int* worklist = batches + 4 * B * (int64_t)kStartStride;
-  // persistent waves (768 per (sample, direction) on average) walk a pair's work list of (super-cell, 64-query batch) items
-  XcdPlan* plan = reinterpret_cast<XcdPlan*>(worklist + 4 * B * (int64_t)kWorkStride);
+  float4* records = g.records;
+  GridParams* params = static_cast<GridParams*>(g.params);
+  float *dist1 = g.dist1, *dist2 = g.dist2;
+  int *starts = g.starts, *batches = g.batches, *worklist = g.worklist;
+  XcdPlan* plan = static_cast<XcdPlan*>(g.plan);
   const bool xcd_table = 2 * B >= 8 && 2 * B <= kMaxPairs;
   const int nwaves = (int)(MPA_GRID_WAVES * 2 * B);
   if (phases & 1)
     hipLaunchKernelGGL(grid_sort_kernel, dim3((unsigned)(4 * B)), dim3(1024), 0, s, valids, S1, S2, (int)P, (int)N,
-                       (const float*)grid_bbox(fws, B, P, N), params, starts, batches, worklist, records, rec_stride,
-                       grid_ticket(iws, B), xcd_table ? plan : (XcdPlan*)nullptr, nwaves, route);
+                       (const float*)g.bbox, params, starts, batches, worklist, records, rec_stride, g.ticket,
+                       xcd_table ? plan : (XcdPlan*)nullptr, nwaves, route);
   if (phases & 2) {
     if (before_search != nullptr) (void)hipEventRecord(before_search, s);
     if (xcd_table)
@@ -1422,23 +1420,19 @@ CloudWs cloud_ws(void* base, int64_t B, int64_t n1, int64_t n2) {
   CloudWs w;
   w.rec_stride = (int)(nmax + 8);
   w.work_stride = (int)(kMaxSuper + nmax / kBatch + 64);
-  char* p = static_cast<char*>(base);
-  auto take = [&p](int64_t bytes) {
-    char* q = p;
-    p += (bytes + 255) / 256 * 256;
-    return q;
-  };
-  w.records = reinterpret_cast<float4*>(take(4 * B * (int64_t)w.rec_stride * 16));
-  w.params = reinterpret_cast<GridParams*>(take(B * (int64_t)sizeof(GridParams)));
-  w.starts = reinterpret_cast<int*>(take(4 * B * (int64_t)kStartStride * 4));
-  w.batches = reinterpret_cast<int*>(take(4 * B * (int64_t)kStartStride * 4));
-  w.worklist = reinterpret_cast<int*>(take(4 * B * (int64_t)w.work_stride * 4));
-  w.plan = reinterpret_cast<XcdPlan*>(take(sizeof(XcdPlan)));
-  w.ticket = reinterpret_cast<unsigned*>(take(64));
-  w.fallback = reinterpret_cast<int*>(take(B * 4));
-  w.heads = reinterpret_cast<int*>(take(2 * B * nmax * 4));
-  w.boxes = reinterpret_cast<CloudBox*>(take(2 * B * (int64_t)sizeof(CloudBox)));
-  w.bytes = p - static_cast<char*>(base);
+  Arena a(base);
+  constexpr int64_t kAlign = 256;
+  w.records = a.take<float4>(4 * B * (int64_t)w.rec_stride, kAlign);
+  w.params = a.take<GridParams>(B, kAlign);
+  w.starts = a.take<int>(4 * B * (int64_t)kStartStride, kAlign);
+  w.batches = a.take<int>(4 * B * (int64_t)kStartStride, kAlign);
+  w.worklist = a.take<int>(4 * B * (int64_t)w.work_stride, kAlign);
+  w.plan = a.take<XcdPlan>(1, kAlign);
+  w.ticket = a.take<unsigned>(16, kAlign);
+  w.fallback = a.take<int>(B, kAlign);
+  w.heads = a.take<int>(2 * B * nmax, kAlign);
+  w.boxes = a.take<CloudBox>(2 * B, kAlign);
+  w.bytes = a.bytes();
   return w;
 }
 }  // namespace

@@ -341,12 +341,21 @@ extern "C" int mpa_gru_resident(int64_t D, int64_t B, int64_t H, int* ok) {
   return MPA_OK;
 }
 
+// saved gates [D][B][T][4][H] | exchange words [D][2][H/kU][B][H] of 8 bytes (the backward's partials; the forward
+// uses the first [D][2][B][H] of them) | padding
+struct GruWs { float* saved; tagged_t* xch; int64_t total; };
+static GruWs gru_carve(float* ws, int64_t D, int64_t B, int64_t T, int64_t H) {
+  mpa::Arena a(ws);
+  float* saved = a.take<float>(D * B * T * 4 * H, 4);
+  tagged_t* xch = a.take<tagged_t>(D * 2 * (H / kU) * B * H, 4);  // (8-byte aligned when the workspace is: the launchers check)
+  a.take<float>(64, 4);
+  return {saved, xch, a.elems<float>()};
+}
+
 extern "C" int mpa_gru_workspace(int64_t D, int64_t B, int64_t T, int64_t H, int64_t* float_elems) {
   if (int st = gru_check(D, B, T, H, "gru_workspace")) return st;
   MPA_REQUIRE(float_elems != nullptr, "gru_workspace: null pointer");
-  // saved gates [D][B][T][4][H] | exchange words [D][2][H/kU][B][H] of 8 bytes (the backward's partials; the forward
-  // uses the first [D][2][B][H] of them) | padding
-  *float_elems = D * B * T * 4 * H + 2 * D * 2 * (H / kU) * B * H + 64;
+  *float_elems = gru_carve(nullptr, D, B, T, H).total;
   return MPA_OK;
 }
 
@@ -355,8 +364,7 @@ extern "C" int mpa_gru_forward(const float* gi, const float* h0, const float* wh
   if (int st = gru_check(D, B, T, H, "gru_forward")) return st;
   MPA_REQUIRE(gi && h0 && whh && bhh && ws && out, "gru_forward: null pointer");
   hipStream_t s = mpa::as_stream(stream);
-  float* saved = ws;
-  tagged_t* xch = reinterpret_cast<tagged_t*>(ws + D * B * T * 4 * H);
+  const auto [saved, xch, total] = gru_carve(ws, D, B, T, H);
   MPA_REQUIRE((uintptr_t)xch % 8 == 0, "gru_forward: workspace must be 8-byte aligned");
   const size_t smem = sizeof(float) * (3 * kU * (H + 4) + B * (H + 4));
   MPA_REQUIRE(smem <= 160 * 1024, "gru_forward: batch x hidden size does not fit the 160 KB of LDS");
@@ -385,8 +393,7 @@ extern "C" int mpa_gru_backward(const float* grad_out, const float* h0, const fl
   if (int st = gru_check(D, B, T, H, "gru_backward")) return st;
   MPA_REQUIRE(grad_out && h0 && whh && out && ws && grad_gi && grad_whh && grad_bhh, "gru_backward: null pointer");
   hipStream_t s = mpa::as_stream(stream);
-  const float* saved = ws;
-  tagged_t* part = reinterpret_cast<tagged_t*>(ws + D * B * T * 4 * H);
+  const auto [saved, part, total] = gru_carve(ws, D, B, T, H);
   MPA_REQUIRE((uintptr_t)part % 8 == 0, "gru_backward: workspace must be 8-byte aligned");
   const size_t smem = sizeof(float) * (3 * kU * H + B * H + B * 3 * kU + B * kU);
   MPA_REQUIRE(smem <= 160 * 1024, "gru_backward: batch x hidden size does not fit the 160 KB of LDS");

@@ -678,12 +678,22 @@ void launch_leaf_order(const float* part_pcs, const float* valids, int64_t B, in
                      npad, reinterpret_cast<float4*>(sorted));
 }
 
-int64_t leaf_scratch_floats(int64_t B, int64_t P, int64_t N) {  // heavy list + keys + counters, shared by both searches
-  const int64_t nw = leaf_npad(N) >= 64 ? leaf_npad(N) / 64 : 1, items = 2 * B * P * nw;
-  return 16 + (B + 3) / 4 * 4 + (items + 3) / 4 * 4 + items * 64 * 2;  // counters, route, list, keys
+LeafWs leaf_carve(Arena& fa, int64_t B, int64_t P, int64_t N) {
+  LeafWs w{};
+  if (!leaf_supported(P, N)) return w;  // (no leaf region: the loss takes its grid search)
+  const int64_t npad = leaf_npad(N), nw = npad >= 64 ? npad / 64 : 1, items = 2 * B * P * nw;
+  w.order = fa.take<float>(4 * B * P * npad, 16);
+  for (int c = 0; c < 4; ++c) w.rec[c] = fa.take<float>(4 * B * P * npad, 16);
+  for (int c = 0; c < 4; ++c) w.leaf[c] = fa.take<float>(8 * B * P * (npad / 32), 16);
+  for (int c = 0; c < 4; ++c) w.pbox[c] = fa.take<float>(8 * B * P, 16);
+  w.wsum_part = fa.take<float>(2 * B * P * nw, 4);  // per-wave distance sums: 2 directions of each search
+  w.wsum_shape = fa.take<float>(2 * B * P * nw, 4);
+  w.heavy_counters = fa.take<int>(16, 16);
+  w.route = fa.take<int>(B, 16);
+  w.heavy_list = fa.take<int>(items, 16);
+  w.heavy_keys = fa.take<unsigned long long>(items * 64, 16);
+  return w;
 }
-int* leaf_heavy_counters(float* scratch) { return reinterpret_cast<int*>(scratch); }
-int* leaf_route(float* scratch) { return reinterpret_cast<int*>(scratch) + 16; }
 
 namespace {
 constexpr float kRouteFill = 0.075f;  // parts' boxes fill at least this share of the shape's box: the grid answers
@@ -723,7 +733,7 @@ void launch_leaf_route(const float* valids, const float* pbox, int64_t B, int64_
 }
 
 void launch_leaf_search(bool shape, const float* valids, const LeafCloud& A, const LeafCloud& Bc, int64_t B, int64_t P,
-                        int64_t N, int32_t* idx1, int32_t* idx2, float* wave_sums, float* scratch, hipStream_t s,
+                        int64_t N, int32_t* idx1, int32_t* idx2, float* wave_sums, const LeafWs& w, hipStream_t s,
                         const int* route) {
   LeafArgs g;
   g.route = route;
@@ -739,9 +749,9 @@ void launch_leaf_search(bool shape, const float* valids, const LeafCloud& A, con
   g.wave_sums = wave_sums;
   g.total_parts = (int)(B * P);
   const int64_t items = 2 * B * P * g.NW;
-  g.heavy_count = leaf_heavy_counters(scratch) + (shape ? 1 : 0);  // (zeroed by the producer of the records)
-  g.heavy_list = reinterpret_cast<int*>(scratch) + 16 + (B + 3) / 4 * 4;
-  g.heavy_keys = reinterpret_cast<unsigned long long*>(scratch + 16 + (B + 3) / 4 * 4 + (items + 3) / 4 * 4);
+  g.heavy_count = w.heavy_counters + (shape ? 1 : 0);  // (zeroed by the producer of the records)
+  g.heavy_list = w.heavy_list;
+  g.heavy_keys = w.heavy_keys;
   const dim3 grid((unsigned)((B * P * g.NW + 3) / 4), 2);
   const unsigned heavy_blocks = (unsigned)(items < 4096 ? items : 4096);  // (blocks beyond the list's length leave at once)
   if (shape) {

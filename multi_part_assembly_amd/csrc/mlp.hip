@@ -439,28 +439,20 @@ struct MlWs {
   unsigned* tickets;
   float *ypre, *bn, *coef, *partial, *tnpart, *dy;
   double* stage;
-  int64_t total;
 };
 
-MlWs ml_carve(char* base, int64_t R, int64_t K, int64_t N) {
+constexpr int64_t kWsAlign = 256;  // every field starts on, and is padded to, 256 bytes
+MlWs ml_carve(mpa::Arena& a, int64_t R, int64_t K, int64_t N) {
   MlWs w;
-  char* p = base;
-  auto take = [&](int64_t bytes) {
-    char* r = p;
-    p += (bytes + 255) / 256 * 256;
-    return r;
-  };
   const int64_t tiles = (R + kRT - 1) / kRT;
-  take(64);  // (unused: keeps the layout and size of the workspace)
-  w.tickets = reinterpret_cast<unsigned*>(take(256));
-  w.ypre = reinterpret_cast<float*>(take(4 * R * N));
-  w.bn = reinterpret_cast<float*>(take(4 * 4 * N));
-  w.coef = reinterpret_cast<float*>(take(4 * 3 * N));
-  w.partial = reinterpret_cast<float*>(take(4 * tiles * N * 2));
-  w.tnpart = reinterpret_cast<float*>(take(4 * (int64_t)kChunks * N * K));
-  w.dy = reinterpret_cast<float*>(take(4 * R * N));
-  w.stage = reinterpret_cast<double*>(take(8 * 2 * N * ((tiles + kEB - 1) / kEB)));
-  w.total = p - base;
+  w.tickets = a.take<unsigned>(64, kWsAlign);
+  w.ypre = a.take<float>(R * N, kWsAlign);
+  w.bn = a.take<float>(4 * N, kWsAlign);
+  w.coef = a.take<float>(3 * N, kWsAlign);
+  w.partial = a.take<float>(tiles * N * 2, kWsAlign);
+  w.tnpart = a.take<float>((int64_t)kChunks * N * K, kWsAlign);
+  w.dy = a.take<float>(R * N, kWsAlign);
+  w.stage = a.take<double>(2 * N * ((tiles + kEB - 1) / kEB), kWsAlign);
   return w;
 }
 
@@ -501,7 +493,9 @@ void ml_gemm(const float* A, int lda, const float* W, int K, float* C, int ldc, 
 extern "C" int mpa_mlp_layer_workspace(int64_t R, int64_t K, int64_t N, int64_t* bytes) {
   if (int st = ml_check(R, K, N, "mlp_layer_workspace")) return st;
   MPA_REQUIRE(bytes != nullptr, "mlp_layer_workspace: null pointer");
-  *bytes = ml_carve(nullptr, R, K, N).total;
+  mpa::Arena a(nullptr);
+  ml_carve(a, R, K, N);
+  *bytes = a.bytes();
   return MPA_OK;
 }
 
@@ -514,7 +508,8 @@ extern "C" int mpa_mlp_layer_forward(const float* x, int64_t ldx, const float* w
   MPA_REQUIRE(gamma == nullptr || (beta && running_mean && running_var), "mlp_layer_forward: incomplete BatchNorm");
   MPA_REQUIRE((uintptr_t)ws % 256 == 0, "mlp_layer_forward: workspace must be 256-byte aligned");
   hipStream_t s = mpa::as_stream(stream);
-  const MlWs m = ml_carve(static_cast<char*>(ws), R, K, N);
+  mpa::Arena arena(ws);
+  const MlWs m = ml_carve(arena, R, K, N);
   const long long total4 = R * N / 4;
   const CoopWs cw{m.stage, m.tickets};
   if (R <= kSmallRows) {
@@ -591,7 +586,8 @@ extern "C" int mpa_mlp_layer_backward(const float* grad_out, const float* x, int
   MPA_REQUIRE(grad_out && x && w && out && ws && grad_w, "mlp_layer_backward: null pointer");
   MPA_REQUIRE(gamma == nullptr || (grad_gamma && grad_beta), "mlp_layer_backward: BatchNorm gradients missing");
   hipStream_t s = mpa::as_stream(stream);
-  const MlWs m = ml_carve(static_cast<char*>(ws), R, K, N);
+  mpa::Arena arena(ws);
+  const MlWs m = ml_carve(arena, R, K, N);
   const int tiles = (int)((R + kRT - 1) / kRT);
   const CoopWs cw{m.stage, m.tickets};
   int bias_tiles = tiles;  // rows of the column-sum table the bias gradient is reduced from
@@ -660,24 +656,16 @@ namespace {
 struct PairWs {
   MlWs m;                       // the layer's workspace over the R = B P P pair rows (K = 2 F)
   float *pa, *pb, *dpa, *dpb;   // [B P, N] each
-  int64_t total;
 };
 
-PairWs pair_carve(char* base, int64_t B, int64_t P, int64_t F, int64_t N) {
+PairWs pair_carve(mpa::Arena& a, int64_t B, int64_t P, int64_t F, int64_t N) {
   PairWs w;
-  w.m = ml_carve(base, B * P * P, 2 * F, N);
-  char* p = base + w.m.total;
-  auto take = [&](int64_t bytes) {
-    char* r = p;
-    p += (bytes + 255) / 256 * 256;
-    return r;
-  };
-  const int64_t mn = 4 * B * P * N;
-  w.pa = reinterpret_cast<float*>(take(mn));
-  w.pb = reinterpret_cast<float*>(take(mn));
-  w.dpa = reinterpret_cast<float*>(take(mn));
-  w.dpb = reinterpret_cast<float*>(take(mn));
-  w.total = p - base;
+  w.m = ml_carve(a, B * P * P, 2 * F, N);
+  const int64_t mn = B * P * N;
+  w.pa = a.take<float>(mn, kWsAlign);
+  w.pb = a.take<float>(mn, kWsAlign);
+  w.dpa = a.take<float>(mn, kWsAlign);
+  w.dpb = a.take<float>(mn, kWsAlign);
   return w;
 }
 
@@ -692,7 +680,9 @@ int pair_check(int64_t B, int64_t P, int64_t F, int64_t N, const char* who) {
 extern "C" int mpa_pair_layer_workspace(int64_t B, int64_t P, int64_t F, int64_t N, int64_t* bytes) {
   if (int st = pair_check(B, P, F, N, "pair_layer_workspace")) return st;
   MPA_REQUIRE(bytes != nullptr, "pair_layer_workspace: null pointer");
-  *bytes = pair_carve(nullptr, B, P, F, N).total;
+  mpa::Arena a(nullptr);
+  pair_carve(a, B, P, F, N);
+  *bytes = a.bytes();
   return MPA_OK;
 }
 
@@ -705,7 +695,8 @@ extern "C" int mpa_pair_layer_forward(const float* a, const float* b, const floa
               "pair_layer_forward: null pointer (the layer has a BatchNorm)");
   MPA_REQUIRE((uintptr_t)ws % 256 == 0, "pair_layer_forward: workspace must be 256-byte aligned");
   hipStream_t s = mpa::as_stream(stream);
-  const PairWs pw = pair_carve(static_cast<char*>(ws), B, P, F, N);
+  mpa::Arena arena(ws);
+  const PairWs pw = pair_carve(arena, B, P, F, N);
   const MlWs& m = pw.m;
   const int64_t M = B * P, R = M * P;
   const int tiles = (int)((R + kRT - 1) / kRT);
@@ -749,7 +740,8 @@ extern "C" int mpa_pair_layer_backward(const float* grad_out, const float* a, co
   MPA_REQUIRE(grad_out && a && b && w && gamma && out && ws && grad_w && grad_gamma && grad_beta,
               "pair_layer_backward: null pointer");
   hipStream_t s = mpa::as_stream(stream);
-  const PairWs pw = pair_carve(static_cast<char*>(ws), B, P, F, N);
+  mpa::Arena arena(ws);
+  const PairWs pw = pair_carve(arena, B, P, F, N);
   const MlWs& m = pw.m;
   const int64_t M = B * P, R = M * P;
   const int tiles = (int)((R + kRT - 1) / kRT);

@@ -697,7 +697,6 @@ struct PnWs {
   CoopWs coop;    // fp64 group sums + tickets of the cooperative reductions
   float* topv;    // [M*splits][F][2] top-2 records of the last layer (values)
   float* ybest;   // [M][F] pre-BatchNorm value at the arg-max
-  float* eval;    // [M][F] retired (the arg-max entries live in pn_top_csr_kernel's LDS); kept: the fields behind it stay put
   float* q;       // [129][128] Q then c0
   float* gram;    // [129][128] Gram matrix then column sums of A4
   float* ql[5];   // Q form of conv2..conv4: [CIN + 1][CIN] Q then c0 of layer l
@@ -709,9 +708,6 @@ struct PnWs {
 struct PnIws {
   int* argmax;  // [M][F]
   int* topn;    // [M*splits][F][2]
-  int* erow;    // [M][F], [M][F], [M][T+1]: retired with `eval` (the CSR by 32-row tile that the last layer's backward
-  int* ech;     // pass walked entry by entry); kept so that the fields behind them stay put
-  int* tptr;
   int* vlist;   // [4 + M] number of valid parts, then (from [4]) their ids
   int2* rtile;  // [M][T+1] {first distinct arg-max row, mask of the rows that have one} of part m's 32-row tile t
   int64_t total;
@@ -719,67 +715,53 @@ struct PnIws {
 
 PnWs carve(float* base, const Dims& d) {
   PnWs w;
-  float* p = base;
-  auto take = [&](int64_t n) {
-    float* r = p;
-    p += (n + 3) / 4 * 4;  // keep 16-byte alignment for float4 accesses
-    return r;
-  };
+  mpa::Arena a(base);  // every field 16-byte aligned for float4 accesses
   w.Y[1] = nullptr;  // never stored: recomputed from the points by its consumers (pn_fwd_first_kernel)
-  for (int l = 2; l <= 4; ++l) w.Y[l] = take(d.rows * d.C[l]);
+  for (int l = 2; l <= 4; ++l) w.Y[l] = a.take<float>(d.rows * d.C[l], 16);
   w.Y[5] = nullptr;
   w.dZ[1] = nullptr;  // never leaves the conv2 kernel (pn_bwd_q.h)
-  for (int l = 2; l <= 4; ++l) w.dZ[l] = take(d.rows * d.C[l]);
-  w.Wt1 = take(192);
-  for (int l = 1; l <= 5; ++l) w.bn[l] = take(4LL * d.C[l]);
-  for (int l = 1; l <= 5; ++l) w.coef[l] = take(4LL * d.C[l]);
+  for (int l = 2; l <= 4; ++l) w.dZ[l] = a.take<float>(d.rows * d.C[l], 16);
+  w.Wt1 = a.take<float>(192, 16);
+  for (int l = 1; l <= 5; ++l) w.bn[l] = a.take<float>(4LL * d.C[l], 16);
+  for (int l = 1; l <= 5; ++l) w.coef[l] = a.take<float>(4LL * d.C[l], 16);
   const int64_t maxc = d.F > 128 ? d.F : 128;
   // rows of `partial`: one per (part, row split) or per (part, tile) of the row-split kernels, one per block of the
   // persistent ones
   int64_t blocks = d.M * (d.tiles1 > d.splits_top ? d.tiles1 : d.splits_top);
   if (blocks < kWsBlocks) blocks = kWsBlocks;
-  w.partial = take(blocks * maxc * 2);
+  w.partial = a.take<float>(blocks * maxc * 2, 16);
   // the Gram partials of the last layer (reduced at once), then — in the same storage — the partial tables of layers 4..2,
   // which wait for ONE grouped reduction at the end of the backward pass
   {
     const int64_t gram = (int64_t)kWsBlocks * (128 * 128 + 128);
     const int64_t wait =
         (int64_t)kWsBlocks * (pn_bwd_q_elems(128, 64, false) + pn_bwd_q_elems(64, 64, false) + pn_bwd_q_elems(64, 64, true));
-    w.dwpart = take(gram > wait ? gram : wait);
+    w.dwpart = a.take<float>(gram > wait ? gram : wait, 16);
   }
   for (int l = 2; l <= 4; ++l) {
-    w.ql[l] = take((int64_t)(d.C[l - 1] + 1) * d.C[l - 1]);
-    w.red[l] = take(pn_bwd_q_elems(d.C[l], d.C[l - 1], l == 2));
+    w.ql[l] = a.take<float>((int64_t)(d.C[l - 1] + 1) * d.C[l - 1], 16);
+    w.red[l] = a.take<float>(pn_bwd_q_elems(d.C[l], d.C[l - 1], l == 2), 16);
   }
-  w.count = take(4);
-  w.coop.ticket = reinterpret_cast<unsigned*>(take(4));
-  w.coop.stage = reinterpret_cast<double*>(take(2 * 2 * maxc * ((blocks + kEB - 1) / kEB)));
-  w.topv = take(d.M * d.splits_top * d.F * 2);
-  w.ybest = take(d.M * d.F);
-  w.eval = take(d.M * d.F);
-  w.q = take(129 * 128);
-  w.gram = take(129 * 128);
-  w.rsum = take(d.M * d.F * 128);
-  w.total = p - base;
+  w.count = a.take<float>(4, 16);
+  w.coop.ticket = a.take<unsigned>(4, 16);
+  w.coop.stage = a.take<double>(2 * maxc * ((blocks + kEB - 1) / kEB), 16);
+  w.topv = a.take<float>(d.M * d.splits_top * d.F * 2, 16);
+  w.ybest = a.take<float>(d.M * d.F, 16);
+  w.q = a.take<float>(129 * 128, 16);
+  w.gram = a.take<float>(129 * 128, 16);
+  w.rsum = a.take<float>(d.M * d.F * 128, 16);
+  w.total = a.elems<float>();
   return w;
 }
 
 PnIws carve_int(int32_t* base, const Dims& d) {
   PnIws w;
-  int32_t* p = base;
-  auto take = [&](int64_t n) {
-    int32_t* r = p;
-    p += (n + 3) / 4 * 4;
-    return r;
-  };
-  w.argmax = take(d.M * d.F);
-  w.topn = take(d.M * d.splits_top * d.F * 2);
-  w.erow = take(d.M * d.F);
-  w.ech = take(d.M * d.F);
-  w.tptr = take(d.M * ((d.N + 31) / 32 + 1));
-  w.vlist = take(d.M + 4);
-  w.rtile = reinterpret_cast<int2*>(take(2 * d.M * ((d.N + 31) / 32 + 1)));
-  w.total = p - base;
+  mpa::Arena a(base);
+  w.argmax = a.take<int32_t>(d.M * d.F, 16);
+  w.topn = a.take<int32_t>(d.M * d.splits_top * d.F * 2, 16);
+  w.vlist = a.take<int32_t>(d.M + 4, 16);
+  w.rtile = a.take<int2>(d.M * ((d.N + 31) / 32 + 1), 16);
+  w.total = a.elems<int32_t>();
   return w;
 }
 

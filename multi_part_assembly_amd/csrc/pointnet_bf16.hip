@@ -959,42 +959,39 @@ struct Ws {
   float* partw;
   float4* pool;      // [tiles][2][F] extrema records of the last layer's tiles
   unsigned* bitmap;  // one word per row (backward of the last layer)
+  int64_t total;
 };
 
 constexpr int kC[6] = {3, 64, 64, 64, 128, 0};
 
-char* take(char*& p, int64_t bytes) {
-  char* r = p;
-  p += (bytes + 255) / 256 * 256;
-  return r;
-}
-
-Ws carve(void* base, int64_t M, int64_t N, int64_t F, int64_t* total) {
+constexpr int64_t kAlign = 256;  // every field starts on, and is padded to, 256 bytes
+Ws carve(void* base, int64_t M, int64_t N, int64_t F) {
   Ws w{};
-  char* p = static_cast<char*>(base);
+  mpa::Arena a(base);
   const int64_t R = M * N, tiles = (R + kRows - 1) / kRows;
   int C[6];
   for (int l = 0; l < 5; ++l) C[l] = kC[l];
   C[5] = (int)F;
-  w.hdr = reinterpret_cast<int*>(take(p, 256));
-  w.vlist = reinterpret_cast<int*>(take(p, 4 * M));
-  w.rank = reinterpret_cast<int*>(take(p, 4 * M));
-  w.arg = reinterpret_cast<int*>(take(p, 4 * M * F));
+  w.hdr = a.take<int>(64, kAlign);
+  w.vlist = a.take<int>(M, kAlign);
+  w.rank = a.take<int>(M, kAlign);
+  w.arg = a.take<int>(M * F, kAlign);
   for (int l = 0; l < 5; ++l) {
-    w.coef[l] = reinterpret_cast<float*>(take(p, 4 * 4 * C[l + 1]));
-    w.bc[l] = reinterpret_cast<float*>(take(p, 4 * 3 * C[l + 1]));
-    w.wb[l] = reinterpret_cast<unsigned short*>(take(p, 2 * (int64_t)C[l + 1] * (l == 0 ? 64 : C[l])));
-    w.wt[l] = reinterpret_cast<unsigned short*>(take(p, 2 * (int64_t)C[l + 1] * (l == 0 ? 64 : C[l])));
-    w.y[l] = reinterpret_cast<unsigned short*>(take(p, 2 * R * C[l + 1]));
-    if (l < 4) w.g[l] = reinterpret_cast<unsigned short*>(take(p, 2 * R * C[l + 1]));
+    const int64_t wn = (int64_t)C[l + 1] * (l == 0 ? 64 : C[l]);
+    w.coef[l] = a.take<float>(4 * C[l + 1], kAlign);
+    w.bc[l] = a.take<float>(3 * C[l + 1], kAlign);
+    w.wb[l] = a.take<unsigned short>(wn, kAlign);
+    w.wt[l] = a.take<unsigned short>(wn, kAlign);
+    w.y[l] = a.take<unsigned short>(R * C[l + 1], kAlign);
+    if (l < 4) w.g[l] = a.take<unsigned short>(R * C[l + 1], kAlign);
   }
-  w.part = reinterpret_cast<float*>(take(p, 4 * (tiles > M ? tiles : M) * 2 * (F > 128 ? F : 128)));  // rows: row tiles or parts
+  w.part = a.take<float>((tiles > M ? tiles : M) * 2 * (F > 128 ? F : 128), kAlign);  // rows: row tiles or parts
   int64_t pw = (int64_t)kChunks * F * 128;
   if (tiles * 192 > pw) pw = tiles * 192;
-  w.partw = reinterpret_cast<float*>(take(p, 4 * pw));
-  w.bitmap = reinterpret_cast<unsigned*>(take(p, 4 * R));
-  w.pool = reinterpret_cast<float4*>(take(p, 16 * tiles * 2 * F));
-  if (total) *total = p - static_cast<char*>(base);
+  w.partw = a.take<float>(pw, kAlign);
+  w.bitmap = a.take<unsigned>(R, kAlign);
+  w.pool = a.take<float4>(tiles * 2 * F, kAlign);
+  w.total = a.bytes();
   return w;
 }
 
@@ -1015,9 +1012,7 @@ void launch(K k, dim3 g, dim3 b, hipStream_t s, A... a) {
 extern "C" int mpa_pointnet_workspace_bf16(int64_t M, int64_t N, int64_t F, int64_t* bytes) {
   if (int st = check_dims(M, N, F, "pointnet_workspace_bf16")) return st;
   MPA_REQUIRE(bytes != nullptr, "pointnet_workspace_bf16: null pointer");
-  int64_t total = 0;
-  carve(nullptr, M, N, F, &total);
-  *bytes = total + 256;
+  *bytes = carve(nullptr, M, N, F).total + 256;
   return MPA_OK;
 }
 
@@ -1032,7 +1027,7 @@ extern "C" int mpa_pointnet_forward_bf16(const float* points, const float* valid
               "pointnet_forward_bf16: null pointer");
   MPA_REQUIRE((uintptr_t)ws % 256 == 0, "pointnet_forward_bf16: workspace must be 256-byte aligned");
   hipStream_t s = mpa::as_stream(stream);
-  const Ws w = carve(ws, M, N, F, nullptr);
+  const Ws w = carve(ws, M, N, F);
   const int64_t R = M * N;
   const unsigned tiles = (unsigned)((R + kRows - 1) / kRows);
   const int C[6] = {3, 64, 64, 64, 128, (int)F};
@@ -1088,7 +1083,7 @@ extern "C" int mpa_pointnet_backward_bf16(const float* grad_feat, const float* p
   if (M == 0) return MPA_OK;
   MPA_REQUIRE(grad_feat && points && ws && grad_conv_w && grad_bn_w && grad_bn_b, "pointnet_backward_bf16: null pointer");
   hipStream_t s = mpa::as_stream(stream);
-  const Ws w = carve(ws, M, N, F, nullptr);
+  const Ws w = carve(ws, M, N, F);
   const int64_t R = M * N;
   const unsigned tiles = (unsigned)((R + kRows - 1) / kRows);
   const int* hdr = w.hdr;

@@ -354,10 +354,15 @@ int dec_check(int64_t B, int64_t T, const char* who) {
   return MPA_OK;
 }
 
-// the exchange words follow the saved gates in the workspace: forward [2][B][H + Z + C], backward [2][nblk][B][H]
-int64_t dec_tag_words(int64_t B) {
+// saved gates | 8-byte tagged exchange words: forward [2][B][H + Z + C], backward [2][nblk][B][H] | padding
+struct DecWs { float* saved; tagged_t* xch; int64_t total; };
+DecWs dec_carve(float* ws, int64_t B, int64_t T) {
+  mpa::Arena a(ws);
   const int64_t fwd = 2 * B * (kDH + kDZ + kDC), bwd = 2LL * kDBlocks * B * kDH;
-  return fwd > bwd ? fwd : bwd;
+  float* saved = a.take<float>(T * B * 4 * kDH, 4);
+  tagged_t* xch = a.take<tagged_t>(fwd > bwd ? fwd : bwd, 4);  // (8-byte aligned when the workspace is: the launchers check)
+  a.take<float>(64, 4);
+  return {saved, xch, a.elems<float>()};
 }
 
 }  // namespace
@@ -375,7 +380,7 @@ extern "C" int mpa_seq2seq_decoder_resident(int64_t B, int* ok) {
 extern "C" int mpa_seq2seq_decoder_workspace(int64_t B, int64_t T, int64_t* float_elems) {
   if (int st = dec_check(B, T, "seq2seq_decoder_workspace")) return st;
   MPA_REQUIRE(float_elems != nullptr, "seq2seq_decoder_workspace: null pointer");
-  *float_elems = T * B * 4 * kDH + 2 * dec_tag_words(B) + 64;  // saved gates | 8-byte tagged words | padding
+  *float_elems = dec_carve(nullptr, B, T).total;
   return MPA_OK;
 }
 
@@ -387,8 +392,7 @@ extern "C" int mpa_seq2seq_decoder_forward(const float* gi, const float* mask, c
   MPA_REQUIRE(h0 && wih && bih && whh && bhh && w1 && b1 && w2 && b2 && ws && hs && z1 && y,
               "seq2seq_decoder_forward: null pointer");
   hipStream_t s = mpa::as_stream(stream);
-  float* saved = ws;
-  tagged_t* xh = reinterpret_cast<tagged_t*>(ws + T * B * 4 * kDH);
+  const auto [saved, xh, total] = dec_carve(ws, B, T);
   MPA_REQUIRE((uintptr_t)xh % 8 == 0, "seq2seq_decoder_forward: workspace must be 8-byte aligned");
   tagged_t* xz = xh + 2 * B * kDH;
   tagged_t* xy = xz + 2 * B * kDZ;
@@ -411,8 +415,7 @@ extern "C" int mpa_seq2seq_decoder_backward(const float* dh, const float* h0, co
   if (int st = dec_check(B, T, "seq2seq_decoder_backward")) return st;
   MPA_REQUIRE(dh && h0 && whh && hs && ws && dgi && dwhh && dbhh && dh0, "seq2seq_decoder_backward: null pointer");
   hipStream_t s = mpa::as_stream(stream);
-  const float* saved = ws;
-  tagged_t* part = reinterpret_cast<tagged_t*>(ws + T * B * 4 * kDH);
+  const auto [saved, part, total] = dec_carve(ws, B, T);
   MPA_REQUIRE((uintptr_t)part % 8 == 0, "seq2seq_decoder_backward: workspace must be 8-byte aligned");
   const size_t smem = dec_bwd_smem((int)B);
   MPA_REQUIRE(smem <= 160 * 1024, "seq2seq_decoder_backward: the batch does not fit the 160 KB of LDS");

@@ -1579,40 +1579,35 @@ struct TfLayout {
 
 TfLayout tf_carve(float* base, const TfDims& d) {
   TfLayout w;
-  float* p = base;
-  auto take = [&](int64_t n) {
-    float* r = p;
-    p += (n + 3) / 4 * 4;
-    return r;
-  };
+  mpa::Arena a(base);
   for (int l = 0; l < d.L; ++l) {
-    w.layer[l].x_in = take(d.M * d.D);
-    w.layer[l].stats1 = take(2 * d.M);
-    w.layer[l].h1 = take(d.M * d.D);
-    w.layer[l].qkv = take(d.M * 3 * d.D);
-    w.layer[l].probs = take(d.B * d.H * d.P * d.P);
-    w.layer[l].o = take(d.M * d.D);
-    w.layer[l].x_mid = take(d.M * d.D);
-    w.layer[l].stats2 = take(2 * d.M);
-    w.layer[l].h2 = take(d.M * d.D);
-    w.layer[l].f = take(d.M * d.FF);
+    w.layer[l].x_in = a.take<float>(d.M * d.D, 16);
+    w.layer[l].stats1 = a.take<float>(2 * d.M, 16);
+    w.layer[l].h1 = a.take<float>(d.M * d.D, 16);
+    w.layer[l].qkv = a.take<float>(d.M * 3 * d.D, 16);
+    w.layer[l].probs = a.take<float>(d.B * d.H * d.P * d.P, 16);
+    w.layer[l].o = a.take<float>(d.M * d.D, 16);
+    w.layer[l].x_mid = a.take<float>(d.M * d.D, 16);
+    w.layer[l].stats2 = a.take<float>(2 * d.M, 16);
+    w.layer[l].h2 = a.take<float>(d.M * d.D, 16);
+    w.layer[l].f = a.take<float>(d.M * d.FF, 16);
   }
-  w.x_final = take(d.M * d.D);
-  w.stats_f = take(2 * d.M);
-  w.g_a = take(d.M * d.D);
-  w.g_b = take(d.M * d.D);
-  w.g_c = take(d.M * d.D);
-  w.g_d = take(d.M * d.D);  // d(attention output): the fused LayerNorm backward reads g_c while this is written
-  w.gd_out = take(d.M * d.D);  // dropout-masked copies of the gradients at the two residual branches' outputs
-  w.gd_mid = take(d.M * d.D);
-  w.dz = take(d.M * d.FF);
-  w.dqkv = take(d.M * 3 * d.D);
-  w.lnpart = take((2 * d.L + 1) * ((d.M + 3) / 4) * 2 * d.D);  // one partial table per LayerNorm
-  w.gd_alt = take(d.M * d.D);
-  w.hp = take(d.B * d.H * 32 * d.D);
-  w.sk_buf = take((int64_t)tfg::kSkTiles * 2048);
-  w.sk_ticket = reinterpret_cast<unsigned*>(take(tfg::kSkTiles));
-  w.total = p - base;
+  w.x_final = a.take<float>(d.M * d.D, 16);
+  w.stats_f = a.take<float>(2 * d.M, 16);
+  w.g_a = a.take<float>(d.M * d.D, 16);
+  w.g_b = a.take<float>(d.M * d.D, 16);
+  w.g_c = a.take<float>(d.M * d.D, 16);
+  w.g_d = a.take<float>(d.M * d.D, 16);  // d(attention output): the fused LayerNorm backward reads g_c while this is written
+  w.gd_out = a.take<float>(d.M * d.D, 16);  // dropout-masked copies of the gradients at the two residual branches' outputs
+  w.gd_mid = a.take<float>(d.M * d.D, 16);
+  w.dz = a.take<float>(d.M * d.FF, 16);
+  w.dqkv = a.take<float>(d.M * 3 * d.D, 16);
+  w.lnpart = a.take<float>((2 * d.L + 1) * ((d.M + 3) / 4) * 2 * d.D, 16);  // one partial table per LayerNorm
+  w.gd_alt = a.take<float>(d.M * d.D, 16);
+  w.hp = a.take<float>(d.B * d.H * 32 * d.D, 16);
+  w.sk_buf = a.take<float>((int64_t)tfg::kSkTiles * 2048, 16);
+  w.sk_ticket = a.take<unsigned>(tfg::kSkTiles, 16);
+  w.total = a.elems<float>();
   return w;
 }
 
@@ -1908,18 +1903,32 @@ extern "C" int mpa_transformer_backward(const float* grad_out, const float* vali
 // ws: h1 [M,256] | h2 [M,128] | rot_raw [M,4] | dqt [M,8] | d2 [M,128] | d1 [M,256]
 //     and, when F is not a multiple of the GEMM panels' 64 columns (labels / noise appended to the features), zero-padded
 //     copies of x and fc1.w and the padded gradients of both: x' [M,F'] | w' [256,F'] | dx' [M,F'] | dw' [256,F']
-struct HeadPad {
-  int64_t Fp;  // F rounded up to a multiple of 64
-  float *x, *w, *dx, *dw;
+//     The quaternion head has rot_raw / dqt rows of 4 / 8 floats, the 6D head (mpa_pose_head6_*) rows of 8 / 16.
+struct HeadWs {
+  float *h1, *h2, *rot_raw, *dqt, *d2, *d1;
+  int64_t Fp;              // F rounded up to a multiple of 64
+  float *x, *w, *dx, *dw;  // null when F is one already
+  int64_t total;
 };
 
-static HeadPad head_pad(float* ws, int64_t M, int64_t F) {
-  HeadPad h;
+static HeadWs head_carve(float* ws, int64_t M, int64_t F, int rot_w, int dqt_w) {
+  HeadWs h{};
+  mpa::Arena a(ws);
+  h.h1 = a.take<float>(M * 256, 4);
+  h.h2 = a.take<float>(M * 128, 4);
+  h.rot_raw = a.take<float>(M * rot_w, 4);
+  h.dqt = a.take<float>(M * dqt_w, 4);
+  h.d2 = a.take<float>(M * 128, 4);
+  h.d1 = a.take<float>(M * 256, 4);
+  a.take<float>(64, 4);  // spare
   h.Fp = (F + 63) / 64 * 64;
-  h.x = ws + M * (256 + 128 + 4 + 8 + 128 + 256) + 64;
-  h.w = h.x + M * h.Fp;
-  h.dx = h.w + 256 * h.Fp;
-  h.dw = h.dx + M * h.Fp;
+  if (F % 64 != 0) {
+    h.x = a.take<float>(M * h.Fp, 4);
+    h.w = a.take<float>(256 * h.Fp, 4);
+    h.dx = a.take<float>(M * h.Fp, 4);
+    h.dw = a.take<float>(256 * h.Fp, 4);
+  }
+  h.total = a.elems<float>();
   return h;
 }
 
@@ -1950,8 +1959,7 @@ static void launch_pad2(const float* s0, float* d0, int64_t rows0, const float* 
 
 extern "C" int mpa_pose_head_workspace(int64_t M, int64_t F, int64_t* float_elems) {
   MPA_REQUIRE(M >= 0 && F >= 1 && F <= 4096 && float_elems, "pose_head_workspace: need 1 <= F <= 4096");
-  *float_elems = M * (256 + 128 + 4 + 8 + 128 + 256) + 64;
-  if (F % 64 != 0) *float_elems += 2 * (M + 256) * ((F + 63) / 64 * 64);
+  *float_elems = head_carve(nullptr, M, F, 4, 8).total;
   return MPA_OK;
 }
 
@@ -1961,12 +1969,10 @@ extern "C" int mpa_pose_head_forward(const float* x, const float* const* params,
   if (M == 0) return MPA_OK;
   MPA_REQUIRE(x && params && ws && rot && trans, "pose_head_forward: null pointer");
   hipStream_t s = mpa::as_stream(stream);
-  float* h1 = ws;
-  float* h2 = h1 + M * 256;
-  float* rot_raw = h2 + M * 128;
+  const HeadWs hp = head_carve(ws, M, F, 4, 8);
+  float *h1 = hp.h1, *h2 = hp.h2, *rot_raw = hp.rot_raw;
   const float* w1 = params[0];
   if (F % 64 != 0) {
-    const HeadPad hp = head_pad(ws, M, F);
     launch_pad2(x, hp.x, M, w1, hp.w, 256, F, hp.Fp, s);
     x = hp.x, w1 = hp.w, F = hp.Fp;
   }
@@ -1984,15 +1990,10 @@ extern "C" int mpa_pose_head_backward(const float* grad_rot, const float* grad_t
   if (M == 0) return MPA_OK;
   MPA_REQUIRE(grad_rot && grad_trans && x && params && ws && grad_x && grad_params, "pose_head_backward: null pointer");
   hipStream_t s = mpa::as_stream(stream);
-  float* h1 = ws;
-  float* h2 = h1 + M * 256;
-  float* rot_raw = h2 + M * 128;
-  float* dqt = rot_raw + M * 4;
-  float* d2 = dqt + M * 8;
-  float* d1 = d2 + M * 128;
+  const HeadWs hp = head_carve(ws, M, F, 4, 8);  // (the forward call left x' and w' there; fc1.w has not changed since)
+  float *h1 = hp.h1, *h2 = hp.h2, *rot_raw = hp.rot_raw, *dqt = hp.dqt, *d2 = hp.d2, *d1 = hp.d1;
   const int Mi = (int)M;
   const bool padded = F % 64 != 0;
-  const HeadPad hp = head_pad(ws, M, F);  // (the forward call left x' and w' there; fc1.w has not changed since)
   const float* w1 = padded ? hp.w : params[0];
   const float* xin = padded ? hp.x : x;
   float* gx = padded ? hp.dx : grad_x;
@@ -2015,21 +2016,10 @@ extern "C" int mpa_pose_head_backward(const float* grad_rot, const float* grad_t
 
 // ---- pose head with the 6D rotation head (rot_type='rmat') ---------------------------------------------------------------------
 // params as mpa_pose_head_* with rot.w [6,128], rot.b [6].  ws: h1 [M,256] | h2 [M,128] | rot_raw [M,8] (6 used) | dqt [M,16] | d2 [M,128]
-// | d1 [M,256] | 64, then the padded copies as in head_pad.  The two GEMMs each way are the quaternion head's.
-static HeadPad head6_pad(float* ws, int64_t M, int64_t F) {
-  HeadPad h;
-  h.Fp = (F + 63) / 64 * 64;
-  h.x = ws + M * (256 + 128 + 8 + 16 + 128 + 256) + 64;
-  h.w = h.x + M * h.Fp;
-  h.dx = h.w + 256 * h.Fp;
-  h.dw = h.dx + M * h.Fp;
-  return h;
-}
-
+// | d1 [M,256] | 64, then the padded copies as in head_carve.  The two GEMMs each way are the quaternion head's.
 extern "C" int mpa_pose_head6_workspace(int64_t M, int64_t F, int64_t* float_elems) {
   MPA_REQUIRE(M >= 0 && F >= 1 && F <= 4096 && float_elems, "pose_head6_workspace: need 1 <= F <= 4096");
-  *float_elems = M * (256 + 128 + 8 + 16 + 128 + 256) + 64;
-  if (F % 64 != 0) *float_elems += 2 * (M + 256) * ((F + 63) / 64 * 64);
+  *float_elems = head_carve(nullptr, M, F, 8, 16).total;
   return MPA_OK;
 }
 
@@ -2040,12 +2030,10 @@ extern "C" int mpa_pose_head6_forward(const float* x, const float* const* params
   MPA_REQUIRE(M < (1LL << 31), "pose_head6_forward: too many rows");
   MPA_REQUIRE(x && params && ws && rot6d && trans, "pose_head6_forward: null pointer");
   hipStream_t s = mpa::as_stream(stream);
-  float* h1 = ws;
-  float* h2 = h1 + M * 256;
-  float* rot_raw = h2 + M * 128;
+  const HeadWs hp = head_carve(ws, M, F, 8, 16);
+  float *h1 = hp.h1, *h2 = hp.h2, *rot_raw = hp.rot_raw;
   const float* w1 = params[0];
   if (F % 64 != 0) {
-    const HeadPad hp = head6_pad(ws, M, F);
     launch_pad2(x, hp.x, M, w1, hp.w, 256, F, hp.Fp, s);
     x = hp.x, w1 = hp.w, F = hp.Fp;
   }
@@ -2065,15 +2053,11 @@ extern "C" int mpa_pose_head6_backward(const float* grad_rot6d, const float* gra
   MPA_REQUIRE(grad_rot6d && grad_trans && x && params && ws && grad_x && grad_params,
               "pose_head6_backward: null pointer");
   hipStream_t s = mpa::as_stream(stream);
-  float* h1 = ws;
-  float* h2 = h1 + M * 256;
-  float* rot_raw = h2 + M * 128;
-  float* dqt = rot_raw + M * 8;  // (rows of 8: every region stays 16-byte aligned for odd M)
-  float* d2 = dqt + M * 16;
-  float* d1 = d2 + M * 128;
+  // (rot_raw / dqt rows of 8 / 16: every region stays 16-byte aligned for odd M)
+  const HeadWs hp = head_carve(ws, M, F, 8, 16);  // (the forward call left x' and w' there; fc1.w has not changed since)
+  float *h1 = hp.h1, *h2 = hp.h2, *rot_raw = hp.rot_raw, *dqt = hp.dqt, *d2 = hp.d2, *d1 = hp.d1;
   const int Mi = (int)M;
   const bool padded = F % 64 != 0;
-  const HeadPad hp = head6_pad(ws, M, F);  // (the forward call left x' and w' there; fc1.w has not changed since)
   const float* w1 = padded ? hp.w : params[0];
   const float* xin = padded ? hp.x : x;
   float* gx = padded ? hp.dx : grad_x;

@@ -314,7 +314,7 @@ def test_leaf_search_point_counts_and_masks(cuda_device, monkeypatch, N, P):
 @pytest.mark.parametrize("B,P,N", [(1, 3, 33), (1, 5, 101), (3, 1, 7)])
 def test_leaf_search_with_odd_total_point_count(cuda_device, monkeypatch, B, P, N):
     """B * P * N odd: the grid region of the workspace used to end 8 bytes past a 16-byte boundary, which left the leaf
-    search's float4 arrays behind it misaligned (now rounded up in grid_workspace_floats) — leaf and auto against the scan."""
+    search's float4 arrays behind it misaligned (the region now ends on 16 bytes in grid_carve) — leaf and auto against the scan."""
     from multi_part_assembly_amd import synthetic
 
     assert (B * P * N) % 2 == 1

@@ -129,11 +129,14 @@ _BEFORE = {(640, 1000, 256): (348294676, 3134724), (12, 1000, 128): (21267988, 2
 
 @pytest.mark.parametrize("shape", sorted(_BEFORE))
 def test_workspace_grows_by_the_row_table(shape):
-    """Appended behind the earlier fields, each rounded up to 16 bytes: rsum [M][F][128] floats, rtile [M][T + 1] int2."""
+    """Appended behind the earlier fields, each rounded up to 16 bytes: rsum [M][F][128] floats, rtile [M][T + 1] int2.
+    The fields they made dead have since been retired from the layout: eval [M][F] floats, and erow [M][F], ech [M][F],
+    tptr [M][T + 1] ints."""
     M, N, F = shape
     nf, ni = ctypes.c_int64(), ctypes.c_int64()
     _lib.check(_lib.lib().mpa_pointnet_workspace(M, N, F, ctypes.byref(nf), ctypes.byref(ni)), "mpa_pointnet_workspace")
     pad = lambda n: (n + 3) // 4 * 4
-    assert nf.value - _BEFORE[shape][0] == pad(M * F * 128)
-    assert ni.value - _BEFORE[shape][1] == pad(2 * M * ((N + 31) // 32 + 1))
+    T = (N + 31) // 32
+    assert nf.value - _BEFORE[shape][0] == pad(M * F * 128) - pad(M * F)
+    assert ni.value - _BEFORE[shape][1] == pad(2 * M * (T + 1)) - 2 * pad(M * F) - pad(M * (T + 1))
     assert nf.value % 4 == 0 and ni.value % 4 == 0 and _BEFORE[shape][0] % 4 == 0 and _BEFORE[shape][1] % 4 == 0
