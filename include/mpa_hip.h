@@ -482,6 +482,37 @@ int mpa_seq2seq_decoder_forward(const float* gi, const float* mask, const float*
 int mpa_seq2seq_decoder_backward(const float* dh, const float* h0, const float* whh, const float* hs, int64_t B,
                                  int64_t T, float* ws, float* dgi, float* dwhh, float* dbhh, float* dh0, int32_t* status,
                                  void* stream);
+/* mpa_seq2seq_decoder_forward_sel: the forward with the mode read ON THE DEVICE.  `teacher` (int32 [1], device memory,
+ * written by an earlier launch of the same stream — mpa_seq2seq_draw) picks it: nonzero = teacher forcing, the launch is
+ * bit-equal to mpa_seq2seq_decoder_forward with the same gi; zero = free running, bit-equal to it with gi = NULL and the
+ * same mask.  gi and teacher are always given (NULL: MPA_EINVAL), mask as for free running.  Every block reads the word
+ * once in front of its step loop; nothing else about the launch changes (same grid, exchange, workspace, status word), so
+ * one captured launch serves both outcomes of the coin.  Backward is mpa_seq2seq_decoder_backward. */
+int mpa_seq2seq_decoder_forward_sel(const float* gi, const float* mask, const int32_t* teacher, const float* h0,
+                                    const float* wih, const float* bih, const float* whh, const float* bhh,
+                                    const float* w1, const float* b1, const float* w2, const float* b2, int64_t B,
+                                    int64_t T, float* ws, float* hs, float* z1, float* y, int32_t* status, void* stream);
+/* mpa_seq2seq_draw (csrc/seq2seq_draw.hip): the per-forward draws of the seq2seq module in one launch — what the
+ * reference draws on the host with np.random.normal, random.random() and LockedDropout's bernoulli_ (seq2seq.py:165-220,
+ * 226-241).  multi_part_assembly_amd/seq2seq_draw_ref.py restates the definition in numpy.
+ *   Randomness: Philox4x32-10, stateless.  key = (seed low word, seed high word); counter = (i, 0x73320000 | kind, c low
+ * word, c high word), c = (counter_dev != NULL ? *counter_dev : counter) + salt (mod 2^64), with counter / counter_dev /
+ * salt as in mpa_match_sample_indices.  Word 1 of the counter is one no other user of the generator produces (the list
+ * is at mpa_epoch_order).  u24(w) = float(w >> 8) * 2^-24, exact, in [0, 1).
+ *   teacher [1] int32: kind 0, block i = 0, word 0 = w: teacher = u24(w) < ratio (float32 comparison) — ratio >= 1 always
+ * forces, ratio <= 0 never does; the meaning of `random.random() < ratio`.
+ *   noise [B,16] float32: kind 1, block i = 0 .. 4 B - 1 with words (w0, w1, w2, w3) gives elements 4 i .. 4 i + 3 of the
+ * flat array by Box-Muller: from a word pair (wa, wb), u1 = (float(wa >> 9) + 0.5f) * 2^-23 (exact, in (0, 1)), u2 =
+ * u24(wb), r = sqrtf(-2 logf(u1)), the pair is (r cosf(a), r sinf(a)) with a = float32(2 pi) * u2 rounded to float32;
+ * (w0, w1) gives elements 4 i, 4 i + 1 and (w2, w3) elements 4 i + 2, 4 i + 3.  The accurate library logf / sincosf.
+ *   mask [T,B,128] float32, or NULL (outside training mode: not drawn): kind 2, flat element e takes word e % 4 of block
+ * i = e / 4; value = u24(w) >= p ? 1.0f / (1.0f - p) : 0.0f, the quotient rounded once to float32.
+ *   Every byte of every non-NULL output is written on every call; no memset / memcpy nodes: capturable.
+ *   MPA_EINVAL (before any launch, no device needed): B outside [1, 64], T outside [1, 4096] (checked with or without a
+ * mask), p outside [0, 1) or NaN, NULL noise or teacher. */
+int mpa_seq2seq_draw(int64_t B, int64_t T, float p, float ratio, uint64_t seed, uint64_t counter,
+                     const uint64_t* counter_dev, uint64_t salt, float* noise, int32_t* teacher, float* mask,
+                     void* stream);
 /* Test support: `blocks` workgroups that each hold `lds_bytes` of LDS and do nothing for `usec` microseconds — CUs no other
  * stream can use meanwhile (how tests/test_gru_gpu.py provokes the co-residency failure above). */
 int mpa_debug_occupy(int64_t blocks, int64_t lds_bytes, int64_t usec, void* stream);
@@ -671,7 +702,8 @@ int mpa_mesh_slot_table(const int64_t* shape_part_off, int64_t S, const int64_t*
  *   key_i, i = 0..S-1, is the 64-bit word x | (y << 32) of the Philox4x32-10 block with key = (seed low word, seed high
  * word) and counter = (i, 0x65700000, e low word, e high word), e = (epoch_dev != NULL ? *epoch_dev : epoch) as an unsigned
  * 64-bit number.  Word 1 of the counter is one no other user of the generator produces (mpa_mesh_sample_batch: below 4;
- * mpa_match_sample_indices: 0x6D61xxxx; mpa_partnet_gather_batch: 0x706Exxxx), so equal seeds give unrelated streams.
+ * mpa_match_sample_indices: 0x6D61xxxx; mpa_partnet_gather_batch: 0x706Exxxx; mpa_seq2seq_draw: 0x7332xxxx), so equal seeds
+ * give unrelated streams.
  *   perm = 0..S-1 sorted ascending by (key_i, i): a stable argsort, ties cannot make it ambiguous.
  *   Sharding as torch.utils.data.DistributedSampler(shuffle=True, drop_last=False): total = ceil(S / world) * world;
  * padded[q] = perm[q mod S] for q < total (perm followed by its first total - S entries, repeated where world > 2 S);

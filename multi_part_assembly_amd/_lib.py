@@ -97,7 +97,9 @@ SIGNATURES: dict[str, tuple] = {
     "mpa_seq2seq_decoder_workspace": (_INT, [_I64, _I64, _P]),
     "mpa_seq2seq_decoder_resident": (_INT, [_I64, _P]),
     "mpa_seq2seq_decoder_forward": (_INT, [_P] * 11 + [_I64, _I64] + [_P] * 6),
+    "mpa_seq2seq_decoder_forward_sel": (_INT, [_P] * 12 + [_I64, _I64] + [_P] * 6),
     "mpa_seq2seq_decoder_backward": (_INT, [_P] * 4 + [_I64, _I64] + [_P] * 7),
+    "mpa_seq2seq_draw": (_INT, [_I64, _I64, _F32, _F32, _U64, _U64, _P, _U64, _P, _P, _P, _P]),
     "mpa_debug_occupy": (_INT, [_I64, _I64, _I64, _P]),
     "mpa_transformer_workspace": (_INT, [_I64] * 6 + [_P]),
     "mpa_transformer_forward": (_INT, [_P, _P, _P] + [_I64] * 6 + [_F32, _U64, _P, _P, _P, _P]),

@@ -58,6 +58,11 @@ class BaseModel(nn.Module):
             raise ValueError(f"cfg.loss.match_sample must be 'host' or 'device', got {self.match_sample!r}")
         if self.match_sample == "device" and self.semantic:
             self.match_sampler = MatchSampler()
+        # where B-LSTM's per-forward draws (teacher-forcing coin, decoder noise, LockedDropout masks) come from: "host" = the
+        # reference's generators; "device" = csrc/seq2seq_draw.hip (lstm.py).  Other models ignore the key.
+        self.lstm_draws = cfg.model.get("lstm_draws", "host")
+        if self.lstm_draws not in ("host", "device"):
+            raise ValueError(f"cfg.model.lstm_draws must be 'host' or 'device', got {self.lstm_draws!r}")
         # fused HIP loss path for geometric data (csrc/assembly_loss.hip); the per-function path is
         # kept for the semantic datasets and as a cross-check.  keep_pts: also return the transformed
         # clouds (`sample_assembly` poses its own: csrc/assemble.hip).  Quaternions and rotation matrices alike.
@@ -282,6 +287,9 @@ class BaseModel(nn.Module):
         data_dict = self._start_part_order(data_dict)
         if self.semantic and self.match_sample == "device":
             self.match_sampler.begin_step(self.training)
+        draw_counter = getattr(self, "draw_counter", None)  # (B-LSTM on device draws)
+        if draw_counter is not None:
+            draw_counter.begin_step(self.training)
         try:
             return self._loss_function_impl(data_dict, optimizer_idx)
         finally:

@@ -42,6 +42,8 @@ size_t dec_fwd_smem(int B) { return sizeof(float) * (size_t)(3 * kDU + kDZU + B)
 size_t dec_bwd_smem(int B) { return sizeof(float) * (size_t)(3 * kDU * kDH + B * kDH + B * 3 * kDU + B * kDU); }
 
 // gi [T][B][3H] (teacher forcing) or null (free running; mask [T][B][C] or null = no dropout), h0 [B][H],
+// teacher: null, or a device word an earlier launch of the stream wrote that picks the mode instead (0 = free running,
+// gi then given but unread): every block reads it once, in front of the step loop, so all of them agree,
 // wih [3H][C], bih [3H], whh [3H][H], bhh [3H], w1 [Z][H], b1 [Z], w2 [C][Z], b2 [C]
 // -> hs [T][B][H], saved [T][B][4][H] (r, z, n, W_hn h + b_hn), z1 [T][B][Z], y [T][B][C].
 // xh [2][B][H], xz [2][B][Z], xy [2][B][C]: tagged words by step parity, zeroed before the launch; tag = step + 1.
@@ -54,7 +56,8 @@ __global__ __launch_bounds__(kDT) void dec_fwd_kernel(const float* __restrict__ 
                                                       float* __restrict__ saved, float* __restrict__ z1,
                                                       float* __restrict__ y, tagged_t* __restrict__ xh,
                                                       tagged_t* __restrict__ xz, tagged_t* __restrict__ xy,
-                                                      int* __restrict__ status, int poll_limit) {
+                                                      int* __restrict__ status, int poll_limit,
+                                                      const int* __restrict__ teacher) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int H = kDH, C = kDC, Z = kDZ;
   float* W = smem;                     // [3 * kDU][H]: rows r(u0..), z(..), n(..)
@@ -62,7 +65,7 @@ __global__ __launch_bounds__(kDT) void dec_fwd_kernel(const float* __restrict__ 
   float* hp = W1s + kDZU * H;          // [B][H]: h_{t-1} during the GRU phase, h_t after the gather
   __shared__ float red[kDT];
   const int blk = blockIdx.x, u0 = blk * kDU;
-  const bool head = blk < kDHead, free_run = gi == nullptr;
+  const bool head = blk < kDHead, free_run = teacher != nullptr ? *teacher == 0 : gi == nullptr;
   for (int e = threadIdx.x; e < 3 * kDU * H; e += kDT) {
     const int row = e / H, k = e % H, gate = row / kDU, u = row % kDU;
     W[e] = whh[(long long)(gate * H + u0 + u) * H + k];
@@ -384,29 +387,51 @@ extern "C" int mpa_seq2seq_decoder_workspace(int64_t B, int64_t T, int64_t* floa
   return MPA_OK;
 }
 
+namespace {
+
+int dec_forward(const char* who, const float* gi, const float* mask, const int32_t* teacher, const float* h0,
+                const float* wih, const float* bih, const float* whh, const float* bhh, const float* w1, const float* b1,
+                const float* w2, const float* b2, int64_t B, int64_t T, float* ws, float* hs, float* z1, float* y,
+                int32_t* status, void* stream) {
+  if (int st = dec_check(B, T, who)) return st;
+  MPA_REQUIRE(h0 && wih && bih && whh && bhh && w1 && b1 && w2 && b2 && ws && hs && z1 && y, "%s: null pointer", who);
+  hipStream_t s = mpa::as_stream(stream);
+  const auto [saved, xh, total] = dec_carve(ws, B, T);
+  MPA_REQUIRE((uintptr_t)xh % 8 == 0, "%s: workspace must be 8-byte aligned", who);
+  tagged_t* xz = xh + 2 * B * kDH;
+  tagged_t* xy = xz + 2 * B * kDZ;
+  const size_t smem = dec_fwd_smem((int)B);
+  MPA_REQUIRE(smem <= 160 * 1024, "%s: the batch does not fit the 160 KB of LDS", who);
+  mpa::zero_words_async(xh, 2 * 2 * B * (kDH + kDZ + kDC), s);  // load-bearing: tags run 1..T in every launch
+  static size_t checked = 0;  // LDS request + co-residency of the whole grid, once per footprint
+  if (smem != checked) {
+    if (int st = gru_resident(dec_fwd_kernel, smem, kDBlocks, who, kDT)) return st;
+    checked = smem;
+  }
+  hipLaunchKernelGGL(dec_fwd_kernel, dim3(kDBlocks), dim3(kDT), smem, s, gi, mask, h0, wih, bih, whh, bhh, w1, b1, w2, b2,
+                     (int)B, (int)T, hs, saved, z1, y, xh, xz, xy, (int*)status, poll_limit(), (const int*)teacher);
+  return mpa::check_launch(who);
+}
+
+}  // namespace
+
 extern "C" int mpa_seq2seq_decoder_forward(const float* gi, const float* mask, const float* h0, const float* wih,
                                            const float* bih, const float* whh, const float* bhh, const float* w1,
                                            const float* b1, const float* w2, const float* b2, int64_t B, int64_t T,
                                            float* ws, float* hs, float* z1, float* y, int32_t* status, void* stream) {
-  if (int st = dec_check(B, T, "seq2seq_decoder_forward")) return st;
-  MPA_REQUIRE(h0 && wih && bih && whh && bhh && w1 && b1 && w2 && b2 && ws && hs && z1 && y,
-              "seq2seq_decoder_forward: null pointer");
-  hipStream_t s = mpa::as_stream(stream);
-  const auto [saved, xh, total] = dec_carve(ws, B, T);
-  MPA_REQUIRE((uintptr_t)xh % 8 == 0, "seq2seq_decoder_forward: workspace must be 8-byte aligned");
-  tagged_t* xz = xh + 2 * B * kDH;
-  tagged_t* xy = xz + 2 * B * kDZ;
-  const size_t smem = dec_fwd_smem((int)B);
-  MPA_REQUIRE(smem <= 160 * 1024, "seq2seq_decoder_forward: the batch does not fit the 160 KB of LDS");
-  mpa::zero_words_async(xh, 2 * 2 * B * (kDH + kDZ + kDC), s);  // load-bearing: tags run 1..T in every launch
-  static size_t checked = 0;  // LDS request + co-residency of the whole grid, once per footprint
-  if (smem != checked) {
-    if (int st = gru_resident(dec_fwd_kernel, smem, kDBlocks, "seq2seq_decoder_forward", kDT)) return st;
-    checked = smem;
-  }
-  hipLaunchKernelGGL(dec_fwd_kernel, dim3(kDBlocks), dim3(kDT), smem, s, gi, mask, h0, wih, bih, whh, bhh, w1, b1, w2, b2,
-                     (int)B, (int)T, hs, saved, z1, y, xh, xz, xy, (int*)status, poll_limit());
-  return mpa::check_launch("seq2seq_decoder_forward");
+  return dec_forward("seq2seq_decoder_forward", gi, mask, nullptr, h0, wih, bih, whh, bhh, w1, b1, w2, b2, B, T, ws, hs,
+                     z1, y, status, stream);
+}
+
+extern "C" int mpa_seq2seq_decoder_forward_sel(const float* gi, const float* mask, const int32_t* teacher,
+                                               const float* h0, const float* wih, const float* bih, const float* whh,
+                                               const float* bhh, const float* w1, const float* b1, const float* w2,
+                                               const float* b2, int64_t B, int64_t T, float* ws, float* hs, float* z1,
+                                               float* y, int32_t* status, void* stream) {
+  MPA_REQUIRE(gi != nullptr && teacher != nullptr, "seq2seq_decoder_forward_sel: null pointer (gi and teacher are both "
+              "given: the mode is read on the device)");
+  return dec_forward("seq2seq_decoder_forward_sel", gi, mask, teacher, h0, wih, bih, whh, bhh, w1, b1, w2, b2, B, T, ws,
+                     hs, z1, y, status, stream);
 }
 
 extern "C" int mpa_seq2seq_decoder_backward(const float* dh, const float* h0, const float* whh, const float* hs,

@@ -17,7 +17,13 @@ grid, MPA_GRU=library) the same equations run on library operators, step by step
 
 Host randomness is drawn like the reference, in its order and on its generators: the decoder noise with
 `np.random.normal`, the teacher-forcing coin with `random.random()`, once per forward — in eval mode too.  The
-LockedDropout masks (training mode) are one `bernoulli_` of [P, B, C] per forward on the input's device."""
+LockedDropout masks (training mode) are one `bernoulli_` of [P, B, C] per forward on the input's device.
+
+`cfg.model.lstm_draws = "device"` draws all three with one launch of csrc/seq2seq_draw.hip instead (`draw`; the numpy
+restatement seq2seq_draw_ref.py is its definition) and lets the decoder launch read the coin from device memory
+(`mpa_seq2seq_decoder_forward_sel`): no host generator, no host-to-device copy, nothing read back — the step can be
+captured into a HIP graph, and `DrawCounter` keeps the position of the stream as `matching.MatchSampler` does for the
+matching's draws.  That mode has no library path: outside the kernels' envelope it raises."""
 from __future__ import annotations
 
 import ctypes
@@ -32,10 +38,12 @@ from . import _lib
 from . import gru as _gru
 from .base_model import BaseModel
 from .encoder import build_encoder
+from .matching import MatchSampler
 from .regressor import StocasticPoseRegressor
 
 _H, _C, _Z = 528, 128, 256  # the decoder shapes csrc/seq2seq.hip is built for
 _DEC_RESIDENT: dict = {}
+_U64 = 0xFFFFFFFFFFFFFFFF
 
 
 def _decoder_resident(batch):
@@ -80,30 +88,98 @@ class _DecoderFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        h0, x, w_hh, w1, w2, hs, z1, ws = ctx.saved_tensors
-        P, B, _ = hs.shape
-        dev = hs.device
-        dy2 = dy.reshape(P * B, _C).float()
-        # the head over all P * B rows: batched GEMMs (its gradient w.r.t. h_t of every step is known up front)
-        dw2 = dy2.t() @ z1.reshape(P * B, _Z)
-        db2 = dy2.sum(0)
-        dz1 = dy2 @ w2
-        dw1 = dz1.t() @ hs.reshape(P * B, _H)
-        db1 = dz1.sum(0)
-        dh = (dz1 @ w1).reshape(P, B, _H).contiguous()
-        dgi = torch.empty((P, B, 3 * _H), dtype=torch.float32, device=dev)
-        dwhh = torch.empty_like(w_hh)
-        dbhh = torch.empty((3 * _H,), dtype=torch.float32, device=dev)
-        dh0 = torch.empty((B, _H), dtype=torch.float32, device=dev)
+        dh0, *rest = _decoder_backward(ctx, dy)
+        return (dh0, None, None, None, *rest)
+
+
+def _decoder_backward(ctx, dy):
+    """(dh0, dwih, dbih, dwhh, dbhh, dw1, db1, dw2, db2) from what either decoder function saved."""
+    h0, x, w_hh, w1, w2, hs, z1, ws = ctx.saved_tensors
+    P, B, _ = hs.shape
+    dev = hs.device
+    dy2 = dy.reshape(P * B, _C).float()
+    # the head over all P * B rows: batched GEMMs (its gradient w.r.t. h_t of every step is known up front)
+    dw2 = dy2.t() @ z1.reshape(P * B, _Z)
+    db2 = dy2.sum(0)
+    dz1 = dy2 @ w2
+    dw1 = dz1.t() @ hs.reshape(P * B, _H)
+    db1 = dz1.sum(0)
+    dh = (dz1 @ w1).reshape(P, B, _H).contiguous()
+    dgi = torch.empty((P, B, 3 * _H), dtype=torch.float32, device=dev)
+    dwhh = torch.empty_like(w_hh)
+    dbhh = torch.empty((3 * _H,), dtype=torch.float32, device=dev)
+    dh0 = torch.empty((B, _H), dtype=torch.float32, device=dev)
+    _gru.raise_if_failed(dev)
+    word, host = _gru._status(dev)
+    _lib.launch("mpa_seq2seq_decoder_backward", dev, dh, h0, w_hh, hs, B, P, ws, dgi, dwhh, dbhh, dh0, word,
+                timer=f"seq2seq_decoder_backward[{B}x{P}]")
+    host.copy_(word, non_blocking=True)
+    dgi2 = dgi.reshape(P * B, 3 * _H)
+    dwih = dgi2.t() @ x.reshape(P * B, _C)
+    dbih = dgi2.sum(0)
+    return dh0, dwih, dbih, dwhh, dbhh, dw1, db1, dw2, db2
+
+
+class _DecoderSelFn(torch.autograd.Function):
+    """`_DecoderFn` with the mode read on the device: `teacher` (int32 [1] on the device, from `draw`) picks teacher forcing
+    (nonzero) or free running (zero) inside the launch.  `target` is always given and its projections always computed (one
+    GEMM: cheap beside a launch shape the host would have to choose); the flag is never read back."""
+
+    @staticmethod
+    def forward(ctx, h0, target, mask, teacher, P, w_ih, b_ih, w_hh, b_hh, w1, b1, w2, b2):
+        B = h0.shape[0]
+        dev = h0.device
+        h0 = h0.detach().float().contiguous()
+        xt = torch.cat([torch.zeros_like(target[:1]), target[:-1]], dim=0)
+        if mask is not None:
+            xt = xt * mask
+        gi = F.linear(xt, w_ih, b_ih).contiguous()
+        ws = torch.empty(_lib.query("mpa_seq2seq_decoder_workspace", B, P), dtype=torch.float32, device=dev)
+        hs = torch.empty((P, B, _H), dtype=torch.float32, device=dev)
+        z1 = torch.empty((P, B, _Z), dtype=torch.float32, device=dev)
+        y = torch.empty((P, B, _C), dtype=torch.float32, device=dev)
         _gru.raise_if_failed(dev)
         word, host = _gru._status(dev)
-        _lib.launch("mpa_seq2seq_decoder_backward", dev, dh, h0, w_hh, hs, B, P, ws, dgi, dwhh, dbhh, dh0, word,
-                    timer=f"seq2seq_decoder_backward[{B}x{P}]")
+        _lib.launch("mpa_seq2seq_decoder_forward_sel", dev, gi, mask, teacher, h0, w_ih, b_ih, w_hh, b_hh, w1, b1, w2, b2,
+                    B, P, ws, hs, z1, y, word, timer=f"seq2seq_decoder_forward[{B}x{P}]")
         host.copy_(word, non_blocking=True)
-        dgi2 = dgi.reshape(P * B, 3 * _H)
-        dwih = dgi2.t() @ x.reshape(P * B, _C)
-        dbih = dgi2.sum(0)
-        return dh0, None, None, None, dwih, dbih, dwhh, dbhh, dw1, db1, dw2, db2
+        # the step inputs behind dW_ih: the targets, or the launch's own outputs (the same values it fed back)
+        xy = torch.cat([torch.zeros_like(y[:1]), y[:-1]], dim=0)
+        if mask is not None:
+            xy = xy * mask
+        x = torch.where(teacher != 0, xt, xy)
+        ctx.save_for_backward(h0, x, w_hh, w1, w2, hs, z1, ws)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dh0, *rest = _decoder_backward(ctx, dy)
+        return (dh0, None, None, None, None, *rest)
+
+
+def draw(B, T, p, ratio, training, seed=0, counter=0, counter_dev=None, salt=0, device="cuda"):
+    """One launch of csrc/seq2seq_draw.hip: (noise float32 [B, 16], teacher int32 [1], mask float32 [T, B, 128] — the
+    scaled LockedDropout mask, None unless `training`) on the HIP device, Philox4x32-10 keyed by `seed`, stream
+    counter + salt (seq2seq_draw_ref.py restates the layout).  `counter_dev` (int64 [1] on the device) is read by the
+    kernel instead of `counter`: a captured step passes it and rewrites the word between replays."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("lstm.draw: HIP device only — no CPU fallback")
+    if counter_dev is not None:
+        assert counter_dev.dtype == torch.int64 and counter_dev.device == dev and counter_dev.numel() == 1
+    noise = torch.empty((B, 16), dtype=torch.float32, device=dev)
+    teacher = torch.empty((1,), dtype=torch.int32, device=dev)
+    mask = torch.empty((T, B, _C), dtype=torch.float32, device=dev) if training else None
+    _lib.launch("mpa_seq2seq_draw", dev, B, T, float(p), float(ratio), int(seed) & _U64, int(counter) & _U64, counter_dev,
+                int(salt) & _U64, noise, teacher, mask, timer=f"seq2seq_draw[{B}x{T}]")
+    return noise, teacher, mask
+
+
+class DrawCounter(MatchSampler):
+    """Seed and step counter of a model's device-side seq2seq draws (`cfg.model.lstm_draws = "device"`): the protocol of
+    `matching.MatchSampler` — `begin_step` once per `loss_function`, the k-th forward of the step draws from the stream
+    (counter, k), by value in eager launches and through the device word while a step is captured, evaluation passes on
+    the `1 << 62` stream — with `draw_args` feeding `draw`.  No parameters, no buffers."""
 
 
 class LockedDropout(nn.Module):
@@ -163,9 +239,12 @@ class DecoderRNN(nn.Module):
 class Seq2Seq(nn.Module):
     """seq2seq.py:140-223."""
 
-    def __init__(self, enc_input_size, dec_input_size, hidden_size):
+    def __init__(self, enc_input_size, dec_input_size, hidden_size, draws="host"):
         super().__init__()
         self.n_layer = 2
+        self.draws = draws  # "host": the reference's generators; "device": csrc/seq2seq_draw.hip
+        if draws == "device":
+            self.draw_counter = DrawCounter()
         self.encoder = _RNNWrapper(EncoderRNN(enc_input_size, hidden_size, n_layer=self.n_layer, bidirectional=True))
         self.decoder = DecoderRNN(dec_input_size, hidden_size * 2 + 16, n_layer=self.n_layer, bidirectional=False)
         self.teacher_forcing_ratio = 0.5
@@ -243,6 +322,27 @@ class Seq2Seq(nn.Module):
                                 g.weight_ih_l0, g.bias_ih_l0, g.weight_hh_l0, g.bias_hh_l0, l1.weight, l1.bias,
                                 l2.weight, l2.bias)
 
+    def _forward_device(self, input_seq, target_seq, valids, ratio, return_stop_signs, masks, hip):
+        """The forward with coin, noise and masks drawn by one launch and the coin read by the decoder launch."""
+        if hip is False or self.hip is False or return_stop_signs or not self._hip_ok(input_seq):
+            raise RuntimeError(f"Seq2Seq: lstm_draws = 'device' needs the HIP kernels, and {tuple(input_seq.shape)} "
+                               f"{input_seq.device.type} input with lstm_hidden_size = {self.encoder.rnn.hidden_size} "
+                               "(or a forced library path / stop signs) is outside their envelope; use lstm_draws = 'host'")
+        P, B, _ = target_seq.shape
+        dev = input_seq.device
+        noise, teacher, drawn = draw(B, P, self.decoder.dropout_i, ratio, self.training,
+                                     **self.draw_counter.draw_args(dev), device=dev)
+        if masks is None:
+            masks = drawn
+        h_f, h_b = self.infer_encoder(input_seq, valids, True)
+        h0 = torch.cat([h_f, h_b, noise], dim=1)                                        # decoder layer 0's state
+        d = self.decoder
+        g = d.gru
+        l1, l2 = d.linear1[0], d.linear1[2]
+        return _DecoderSelFn.apply(h0, target_seq.detach().float().contiguous(),
+                                   None if masks is None else masks.float().contiguous(), teacher, P, g.weight_ih_l0,
+                                   g.bias_ih_l0, g.weight_hh_l0, g.bias_hh_l0, l1.weight, l1.bias, l2.weight, l2.bias)
+
     def draw_masks(self, target_seq):
         """The LockedDropout masks of one forward, scaled: [P, B, C] (None outside training mode or at p = 0)."""
         p = self.decoder.dropout_i
@@ -257,6 +357,8 @@ class Seq2Seq(nn.Module):
         `masks` [P, B, C]: the scaled dropout masks to use instead of drawing them (tests compare the two paths with
         them); `hip` forces a path (None: the HIP kernels inside their envelope)."""
         ratio = self.teacher_forcing_ratio if teacher_forcing_ratio is None else teacher_forcing_ratio
+        if self.draws == "device":
+            return self._forward_device(input_seq, target_seq, valids, ratio, return_stop_signs, masks, hip), None
         B = target_seq.size(1)
         noise = np.random.normal(loc=0.0, scale=1.0, size=[self.n_layer * 1, B, 16]).astype(np.float32)
         noise = torch.tensor(noise).to(input_seq.device, non_blocking=True).type_as(input_seq)
@@ -282,7 +384,9 @@ class LSTMModel(BaseModel):
     def __init__(self, cfg):
         super().__init__(cfg)
         self.encoder = build_encoder(cfg.model.encoder, feat_dim=self.pc_feat_dim, global_feat=True)
-        self.seq2seq = Seq2Seq(self.pc_feat_dim, self.pc_feat_dim, cfg.model.lstm_hidden_size)
+        self.seq2seq = Seq2Seq(self.pc_feat_dim, self.pc_feat_dim, cfg.model.lstm_hidden_size, draws=self.lstm_draws)
+        if self.lstm_draws == "device":  # nothing is drawn on the host: Trainer may capture the step
+            self.host_draws_per_forward = False
         dim = self.pc_feat_dim
         if self.semantic:
             dim += self.max_num_part
@@ -292,6 +396,11 @@ class LSTMModel(BaseModel):
 
     # the coin and the noise are host draws of every forward: a captured step would replay one draw for ever
     host_draws_per_forward = True
+
+    @property
+    def draw_counter(self):
+        """The counter of the device-side draws (None on host draws): `BaseModel.loss_function` begins its steps."""
+        return getattr(self.seq2seq, "draw_counter", None)
 
     def _extract_part_feats(self, part_pcs, part_valids):
         B, P, N, _ = part_pcs.shape

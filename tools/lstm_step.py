@@ -1,9 +1,28 @@
 """B-LSTM training step (everyday preset, B = 32, P = 20, N = 1000) on the HIP path and on the library path of the
 seq2seq module, alternating in one process and timed with device events; prints the aten-op and kernel-launch counts
-of one step of each.  GPU only:  python tools/lstm_step.py [--steps 20]"""
+of one step of each.  GPU only:  python tools/lstm_step.py [--steps 20]
+
+`--draws` instead measures where the per-forward draws come from (one JSON line, profiles/r15_lstm_step_rate.json):
+
+  models   lstm_everyday on `synthetic.make_batch`, lstm_partnet_chair on `make_partnet_like_batch` (its matching draws on
+           the device in every arm: `cfg.loss.match_sample = "device"`), both at B = 32, P = 20, N = 1000
+  arms     a  coin, noise and masks from the host generators, eager launches — the path of `lstm_draws = "host"`
+           b  cfg.model.lstm_draws = "device" (csrc/seq2seq_draw.hip + the coin read by the decoder launch), eager
+           c  arm b captured as one HIP graph (Trainer(use_graph=True))
+  *_ms     ms per `Trainer.train_step`: a host clock around a window of steps that ends in a device synchronise; the arms
+           run in ONE process in alternating windows after a warm-up of every arm (the capture included); the median of
+           the windows, the windows themselves beside it; spread_a = max - min of arm a's windows, the margin of
+           `b_not_slower` (b_ms <= a_ms + spread_a)
+  draw_us  device time of one `mpa_seq2seq_draw` kernel at B = 32, T = 20 with a mask (the profiler's kernel records)
+  launches_fwd_a / _b   kernel launches of one training-mode seq2seq forward (profiler count), host and device draws
+
+  python tools/lstm_step.py --draws [--steps 10] [--windows 5] [--models everyday,partnet] [--arms a,b,c]"""
 import argparse
+import json
 import os
+import statistics
 import sys
+import time
 import warnings
 
 import torch
@@ -25,13 +44,121 @@ class OpCount(TorchDispatchMode):
         return func(*args, **(kwargs or {}))
 
 
+DRAW_PRESETS = {"everyday": config.lstm_everyday, "partnet": config.lstm_partnet_chair}
+
+
+def _draws_arm(name, arm, dev, P):
+    cfg = DRAW_PRESETS[name]()
+    cfg.data.max_num_part = P
+    if cfg.data.dataset != "geometry":
+        cfg.loss.match_sample = "device"
+    if arm != "a":
+        cfg.model.lstm_draws = "device"
+    torch.manual_seed(0)
+    return Trainer(build_model(cfg).to(dev), cfg, use_graph=arm == "c", graph_warmup=2)
+
+
+def _window(trainer, batches, steps):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i in range(steps):
+        trainer.train_step(batches[i % len(batches)], i)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / steps
+
+
+def _forward_launches(trainer, batch):
+    """Kernel launches of one training-mode seq2seq forward on the trainer's model."""
+    model = trainer.model.train()
+    P = batch["part_valids"].shape[1]
+    x = torch.randn(P, batch["part_valids"].shape[0], 128, device=batch["part_valids"].device)
+    with torch.no_grad():
+        model.seq2seq(x, x, valids=batch["part_valids"])
+        torch.cuda.synchronize()
+        with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
+            model.seq2seq(x, x, valids=batch["part_valids"])
+            torch.cuda.synchronize()
+    return sum(e.count for e in prof.key_averages() if e.device_type == torch.autograd.DeviceType.CUDA)
+
+
+def _draw_us(dev, B, P, reps=50):
+    """Device time of one draw kernel, from the profiler's kernel records (events around back-to-back launches would
+    measure the host's launch rate: the kernel is shorter than a launch)."""
+    from multi_part_assembly_amd import lstm
+    for _ in range(10):
+        lstm.draw(B, P, 0.2, 0.5, True, seed=1, counter=1, device=dev)
+    torch.cuda.synchronize()
+    with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
+        for k in range(reps):
+            lstm.draw(B, P, 0.2, 0.5, True, seed=1, counter=k, device=dev)
+        torch.cuda.synchronize()
+    rows = [e for e in prof.key_averages() if "seq2seq_draw" in e.key]
+    total = sum(getattr(e, "device_time_total", None) or getattr(e, "cuda_time_total", 0.0) for e in rows)
+    count = sum(e.count for e in rows)
+    return total / max(count, 1)
+
+
+def measure_draws(name, dev, args):
+    B, P, N = 32, 20, 1000
+    if name == "partnet":
+        batches = [synthetic.make_partnet_like_batch(B, P, N, seed=1234 + i, device=dev) for i in range(2)]
+    else:
+        batches = [synthetic.make_batch(B, P, N, seed=1234 + i, device=dev) for i in range(2)]
+    for b in batches:
+        b.pop("num_parts", None)
+    trainers = {arm: _draws_arm(name, arm, dev, P) for arm in args.arms}
+    for tr in trainers.values():  # warm-up of every arm: first launches, allocator, the capture of arm c
+        _window(tr, batches, 4)
+    times = {arm: [] for arm in trainers}
+    for _ in range(args.windows):
+        for arm, tr in trainers.items():
+            times[arm].append(_window(tr, batches, args.steps))
+    out = {"B": B, "P": P, "N": N, "steps_per_window": args.steps, "sample_iter": trainers[args.arms[0]].model.sample_iter}
+    for arm, ts in times.items():
+        out[f"{arm}_ms"] = round(statistics.median(ts), 4)
+        out[f"{arm}_ms_windows"] = [round(t, 4) for t in ts]
+    if "c" in trainers:
+        out["c_captured"] = trainers["c"]._graph is not None
+    if "a" in times:
+        out["spread_a"] = round(max(times["a"]) - min(times["a"]), 4)
+        if "b" in times:
+            out["b_not_slower"] = out["b_ms"] <= out["a_ms"] + out["spread_a"]
+    for arm in ("a", "b"):
+        if arm in trainers:
+            out[f"launches_fwd_{arm}"] = _forward_launches(trainers[arm], batches[0])
+    for tr in trainers.values():
+        tr.check_health(synchronize=True)
+    return out
+
+
+def main_draws(args):
+    dev = torch.device("cuda:0")
+    warnings.simplefilter("ignore")
+    args.arms = [a for a in args.arms.split(",") if a]
+    result = {"windows": args.windows}
+    for name in args.models.split(","):
+        result[name] = measure_draws(name, dev, args)
+    result["draw_us"] = round(_draw_us(dev, 32, 20), 3)
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--draws", action="store_true", help="time host draws / device draws / device draws captured")
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--models", default="everyday,partnet")
+    ap.add_argument("--arms", default="a,b,c")
+    ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-counts", action="store_true", help="skip the op / launch counts (under an outside profiler)")
     ap.add_argument("--paths", default="hip,library", help="comma-separated subset of hip,library")
     args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("lstm_step: needs the GPU (a host timing says nothing about the step)")
+    if args.draws:
+        args.steps = 10 if args.steps is None else args.steps
+        return main_draws(args)
+    args.steps = 20 if args.steps is None else args.steps
     dev = torch.device("cuda:0")
     warnings.simplefilter("ignore")
     cfg = config.lstm_everyday()

@@ -2,6 +2,7 @@
 
   python tools/train.py --preset pn_transformer_everyday --data-dir data/breaking_bad --data-fn everyday.train.txt \\
       --val-fn everyday.val.txt [--category Bottle] [--epochs 400] [--graph] [--ckpt-dir ckpt] [--resume]
+  python tools/train.py --preset lstm_everyday --lstm-draws device --graph ...      (B-LSTM captured: its draws on the device)
   python tools/train.py --preset dgl_partnet_chair --data-dir data/partnet --data-fn Chair.train.npy --val-fn Chair.val.npy
   python tools/train.py --preset pn_transformer_everyday --synthetic --epochs 2
   torchrun --nproc-per-node 8 tools/train.py ...      (one rank per GPU; every rank keeps its stride of the epoch's order)
@@ -31,6 +32,9 @@ def parser():
     ap.add_argument("--epochs", type=int, default=-1, help="cfg.exp.num_epochs (the cosine schedule spans it)")
     ap.add_argument("--batch-size", type=int, default=-1, help="per rank; default cfg.exp.batch_size")
     ap.add_argument("--graph", action="store_true", help="capture the step as a HIP graph")
+    ap.add_argument("--lstm-draws", choices=("host", "device"), default=None,
+                    help="cfg.model.lstm_draws: B-LSTM's coin, noise and masks from the host generators (the presets' "
+                         "default) or from a kernel — what --graph needs for the lstm presets")
     ap.add_argument("--ckpt-dir", default="")
     ap.add_argument("--resume", action="store_true")
     ap.add_argument("--synthetic", action="store_true")
@@ -111,6 +115,8 @@ def main(argv=None):
         cfg.exp.batch_size = args.batch_size
     if cfg.data.dataset != "geometry":
         cfg.loss.match_sample = "device"  # the matching's point sample drawn by a kernel: no host copy in the step
+    if args.lstm_draws is not None:
+        cfg.model.lstm_draws = args.lstm_draws
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", 1), ("RANK", 0), ("LOCAL_RANK", 0)))
     device = torch.device("cuda", local)
     torch.cuda.set_device(device)
