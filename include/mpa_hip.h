@@ -939,6 +939,48 @@ int mpa_contact_points_rmat(const float* part_pcs, const float* valids, const fl
                             float thre_sq, int64_t B, int64_t P, int64_t N, float* contact_points, float* min_dist,
                             int32_t* index, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * PointNet++ sampling and grouping (csrc/pointnet2_ops.hip) -- the operators of the reference's CUDA-only extension
+ * `pointnet2_ops` that its set-abstraction modules use (pointnet2_ops/pointnet2_utils.py: furthest_point_sample,
+ * ball_query, grouping_operation, gather_operation; kernels in _ext-src/src/sampling_gpu.cu, ball_query_gpu.cu,
+ * group_points_gpu.cu).  multi_part_assembly_amd/pointnet2_ref.py restates every definition below in numpy.
+ * All arithmetic is IEEE fp32, one operation at a time in the written order, no fused multiply-add.  Inputs are
+ * contiguous; indices are int32.  No call synchronises, every launch configuration depends on the sizes only
+ * (capturable), every output element is written on every call, two calls give the same bits.
+ *
+ * mpa_furthest_point_sample: xyz [M, N, 3] -> idx [M, npoint].  idx[0] = 0; the running distance temp[k] of every point
+ *   starts at 1e10.  Round j takes old = idx[j-1]; a point k with (double)((x*x + y*y) + z*z) <= 1e-3 is skipped (never
+ *   updated, never chosen); every other point gets d = (dx*dx + dy*dy) + dz*dz against `old`, temp[k] = min(d, temp[k]),
+ *   and idx[j] is the point of largest temp, 0 when every point is skipped.  Equal distances are decided as the
+ *   reference's block reduction decides them under ITS block size T = min(512, 2^floor(log2 N)): the point whose
+ *   reference thread k mod T, read with its log2 T bits reversed, is smallest; inside one thread the smallest k.
+ *   npoint > N is legal (indices repeat).  Non-finite coordinates: unspecified indices inside [0, N), and the call
+ *   terminates.  N <= 4096: no workspace (points and distances stay in registers and LDS); above, the distances live in
+ *   the workspace, mpa_furthest_point_sample_workspace bytes, 256-byte aligned.  N >= 1 unless M or npoint is 0.
+ * mpa_ball_query: xyz [M, N, 3], new_xyz [M, S, 3] -> idx [M, S, nsample]: the first nsample indices k, ascending, with
+ *   (cx-x)^2 + (cy-y)^2 + (cz-z)^2 < radius * radius (fp32, strict; the sum left to right); the remaining slots repeat
+ *   the first hit; a ball without a hit is all zeros.
+ * mpa_group_points_forward: features [M, C, N], idx [M, S, K] -> out [M, C, S, K], out[m,c,j,l] = features[m,c,idx[m,j,l]].
+ *   gather_operation is the call with K = 1.  An index outside [0, N) is never dereferenced: it reads as 0.
+ * mpa_group_points_backward: grad_out [M, C, S, K] -> grad_features [M, C, N]: every element the fp32 sum of its
+ *   contributions, added one after the other in ascending flat position j K + l, starting from 0; an index outside
+ *   [0, N) contributes nothing.  No floating-point atomics.  Workspace: mpa_group_points_workspace bytes (the inverted
+ *   index of every cloud), 256-byte aligned.
+ * Sizes: every product of sizes that addresses a tensor (3 M N, M npoint, M S nsample, M C S K, M C N) stays below 2^31,
+ * otherwise MPA_EINVAL.  Negative sizes and null pointers are refused before the device is touched; empty problems
+ * return MPA_OK.
+ * ---------------------------------------------------------------------------------------------- */
+int mpa_furthest_point_sample_workspace(int64_t M, int64_t N, int64_t* bytes);
+int mpa_furthest_point_sample(const float* xyz, int64_t M, int64_t N, int64_t npoint, void* workspace, int32_t* idx,
+                              void* stream);
+int mpa_ball_query(const float* xyz, const float* new_xyz, float radius, int64_t M, int64_t N, int64_t S,
+                   int64_t nsample, int32_t* idx, void* stream);
+int mpa_group_points_forward(const float* features, const int32_t* idx, int64_t M, int64_t C, int64_t N, int64_t S,
+                             int64_t K, float* out, void* stream);
+int mpa_group_points_workspace(int64_t M, int64_t N, int64_t S, int64_t K, int64_t* bytes);
+int mpa_group_points_backward(const float* grad_out, const int32_t* idx, int64_t M, int64_t C, int64_t N, int64_t S,
+                              int64_t K, void* workspace, float* grad_features, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

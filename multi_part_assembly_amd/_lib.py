@@ -132,6 +132,12 @@ SIGNATURES: dict[str, tuple] = {
     "mpa_mesh_pose_parts": (_INT, [_P, _P, _I64, _P, _P, _I64, _I64, _I64] + [_P] * 8),
     "mpa_contact_points": (_INT, [_P, _P, _P, _P, _F32, _I64, _I64, _I64, _P, _P, _P, _P]),
     "mpa_contact_points_rmat": (_INT, [_P, _P, _P, _P, _F32, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "mpa_furthest_point_sample_workspace": (_INT, [_I64, _I64, _P]),
+    "mpa_furthest_point_sample": (_INT, [_P, _I64, _I64, _I64, _P, _P, _P]),
+    "mpa_ball_query": (_INT, [_P, _P, _F32, _I64, _I64, _I64, _I64, _P, _P]),
+    "mpa_group_points_forward": (_INT, [_P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P]),
+    "mpa_group_points_workspace": (_INT, [_I64, _I64, _I64, _I64, _P]),
+    "mpa_group_points_backward": (_INT, [_P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P]),
 }
 
 ABI_VERSION = 10

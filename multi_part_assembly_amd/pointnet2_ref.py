@@ -1,0 +1,137 @@
+"""numpy restatement of the PointNet++ sampling and grouping operators (include/mpa_hip.h, csrc/pointnet2_ops.hip): what the
+reference's CUDA-only `pointnet2_ops` extension computes (its `_ext-src/src/sampling_gpu.cu`, `ball_query_gpu.cu`,
+`group_points_gpu.cu`), written as definitions instead of as thread programs.  Every operation is one IEEE float32
+operation in the written order, with no contraction.  It is the specification the device kernels are held to, and what
+`pointnet2_utils` runs for host tensors.  Imports nothing but numpy.
+
+Furthest point sampling needs one remark.  The reference reduces (distance, index) pairs over a block of T threads with a
+tree whose `max` keeps the LOWER thread on equal distances, strides T/2 ... 1.  The winner among equal distances is
+therefore the thread whose index, read with its log2 T bits REVERSED, is smallest (the last level decides bit 0, the level
+before it bit 1, ...); inside one thread (points k = r, r + T, ...) the strict `>` keeps the smallest k.  `fps_key` is
+that order as one integer; the restatement and the kernel take the maximum of (distance, -key), whatever block they use.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+_f32 = np.float32
+FPS_START = _f32(1e10)       # the running distance of every point before the first round
+FPS_SKIP_BELOW = 1e-3        # a point with |p|^2 <= this (the float32 sum widened to double) is never looked at
+MAX_THREADS = 512
+
+
+def fps_threads(n: int) -> int:
+    """The reference's block size for a cloud of n points: max(min(1 << int(log(n) / log(2)), 512), 1) in double
+    precision (include/cuda_utils.h's `opt_n_threads`)."""
+    pow_2 = int(math.log(float(n)) / math.log(2.0))
+    return max(min(1 << pow_2, MAX_THREADS), 1)
+
+
+def fps_threads_closed_form(n: int) -> int:
+    """min(512, 2^floor(log2 n)) in integers: what the kernel computes.  Equal to `fps_threads` for n = 1 ... 4096
+    (tests/test_pointnet2_ops.py keeps the table)."""
+    return min(MAX_THREADS, 1 << (int(n).bit_length() - 1))
+
+
+def bit_reverse(r, bits: int):
+    r = np.asarray(r, dtype=np.int64)
+    out = np.zeros_like(r)
+    for b in range(bits):
+        out |= ((r >> b) & 1) << (bits - 1 - b)
+    return out
+
+
+def fps_key(n: int, threads: int | None = None):
+    """int64 [n]: the tie order of the reference's reduction — on equal distances the point with the smallest key wins.
+    High part: the bit-reversed reference thread k mod T; low part: k div T (the order inside one thread)."""
+    T = fps_threads_closed_form(n) if threads is None else threads
+    bits = T.bit_length() - 1
+    k = np.arange(n, dtype=np.int64)
+    return (bit_reverse(k % T, bits) << 22) | (k // T)
+
+
+def furthest_point_sample(xyz, npoint: int, threads: int | None = None):
+    """xyz [M, N, 3] float32 -> int32 [M, npoint].  `threads` overrides the reference's block size T(N) (tests).
+    Every cloud at once; the points are visited in winning order (ascending key), so that the first maximum along that
+    axis is the winner."""
+    xyz = np.asarray(xyz, dtype=_f32)
+    M, N, _ = xyz.shape
+    out = np.zeros((M, max(npoint, 0)), dtype=np.int32)
+    if M == 0 or N == 0 or npoint <= 1:
+        return out
+    order = np.argsort(fps_key(N, threads), kind="stable")
+    first = int(np.flatnonzero(order == 0)[0])      # where point 0 sits in that order
+    x, y, z = (np.ascontiguousarray(xyz[:, order, a]) for a in range(3))
+    mag = (x * x + y * y) + z * z
+    live = ~(mag.astype(np.float64) <= FPS_SKIP_BELOW)
+    some = live.any(axis=1)
+    temp = np.full((M, N), FPS_START, dtype=_f32)
+    rows = np.arange(M)
+    pos = np.full(M, first)
+    for j in range(1, npoint):
+        dx, dy, dz = x - x[rows, pos, None], y - y[rows, pos, None], z - z[rows, pos, None]
+        d = (dx * dx + dy * dy) + dz * dz
+        d2 = np.minimum(d, temp)                    # (non-finite coordinates are outside the specification)
+        temp = np.where(live, d2, temp)
+        pos = np.where(some, np.argmax(np.where(live, d2, _f32(-1.0)), axis=1), first)
+        out[:, j] = order[pos]
+    return out
+
+
+def ball_query(radius: float, nsample: int, xyz, new_xyz):
+    """xyz [M, N, 3], new_xyz [M, S, 3] -> int32 [M, S, nsample]: the first nsample indices k, ascending, with
+    (cx-x)^2 + (cy-y)^2 + (cz-z)^2 < radius^2 (float32, strict); the remaining slots repeat the first hit; a ball without
+    a hit is all zeros."""
+    xyz, new_xyz = np.asarray(xyz, dtype=_f32), np.asarray(new_xyz, dtype=_f32)
+    M, N, _ = xyz.shape
+    S = new_xyz.shape[1]
+    r2 = _f32(radius) * _f32(radius)
+    out = np.zeros((M, S, nsample), dtype=np.int32)
+    for m in range(M):
+        c, p = new_xyz[m][:, None, :], xyz[m][None, :, :]
+        dx, dy, dz = c[..., 0] - p[..., 0], c[..., 1] - p[..., 1], c[..., 2] - p[..., 2]
+        hit = ((dx * dx + dy * dy) + dz * dz) < r2            # [S, N]
+        if N == 0 or nsample == 0:
+            continue
+        out[m] = np.argmax(hit, axis=1)[:, None]              # the first hit everywhere (0 for an empty ball) ...
+        rank = np.cumsum(hit, axis=1) - 1
+        j, k = np.nonzero(hit & (rank < nsample))
+        out[m, j, rank[j, k]] = k                             # ... then the first nsample hits in their slots
+    return out
+
+
+def grouping_operation(features, idx):
+    """features [M, C, N], idx [M, S, K] -> [M, C, S, K], a copy; an index outside [0, N) reads as 0."""
+    features, idx = np.asarray(features, dtype=_f32), np.asarray(idx)
+    M, C, N = features.shape
+    ok = (idx >= 0) & (idx < N)
+    safe = np.where(ok, idx, 0).astype(np.int64)
+    out = np.take_along_axis(features[:, :, None, :], safe.reshape(M, 1, 1, -1), axis=3).reshape(M, C, *idx.shape[1:])
+    return np.where(ok[:, None], out, _f32(0)).astype(_f32)
+
+
+def grouping_backward(grad_out, idx, N: int):
+    """grad_out [M, C, S, K], idx [M, S, K] -> [M, C, N]: every element the float32 sum of its contributions, added one
+    after the other in ascending flat position j K + l (`np.add.at` on float32 rows); indices outside [0, N) contribute
+    nothing."""
+    grad_out, idx = np.asarray(grad_out, dtype=_f32), np.asarray(idx)
+    M, C = grad_out.shape[:2]
+    out = np.zeros((M, C, N), dtype=_f32)
+    for m in range(M):
+        flat = idx[m].reshape(-1).astype(np.int64)
+        ok = (flat >= 0) & (flat < N)
+        g = grad_out[m].reshape(C, -1)
+        for c in range(C):
+            np.add.at(out[m, c], flat[ok], g[c, ok])
+    return out
+
+
+def gather_operation(features, idx):
+    """features [M, C, N], idx [M, S] -> [M, C, S]: grouping with K = 1."""
+    return grouping_operation(features, np.asarray(idx)[:, :, None])[..., 0]
+
+
+def gather_backward(grad_out, idx, N: int):
+    return grouping_backward(np.asarray(grad_out)[..., None], np.asarray(idx)[:, :, None], N)

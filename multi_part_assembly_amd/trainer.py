@@ -51,6 +51,13 @@ class Trainer:
             warnings.warn(f"Trainer: use_graph=True is not available for {type(model).__name__} (its teacher-forcing coin "
                           "and decoder noise are drawn on the host every forward); running eager launches")
             use_graph = False
+        if use_graph and any(getattr(mod, "host_sync_per_forward", False) for mod in model.modules()):
+            # the PointNet++ encoder compacts the valid parts on the host in every forward (pointnet2.py: BatchNorm must
+            # see valid parts only): the synchronisation is illegal under capture.  Eager launches instead.
+            import warnings
+            warnings.warn(f"Trainer: use_graph=True is not available for {type(model).__name__} (its encoder synchronises "
+                          "with the host in every forward to compact the valid parts); running eager launches")
+            use_graph = False
         self.use_graph, self.graph_warmup = use_graph, graph_warmup
         self._fit_pending = None  # what `resume` read for the next `fit` (fit.py)
         self._graph, self._static_batch, self._static_loss, self._eager_steps = None, None, None, 0

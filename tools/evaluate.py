@@ -65,6 +65,8 @@ def parse_args(argv=None):
     ap.add_argument("--category", default="")
     ap.add_argument("--min-num-part", type=int, default=-1)
     ap.add_argument("--max-num-part", type=int, default=-1)
+    ap.add_argument("--encoder", choices=("pointnet", "dgcnn", "pointnet2_ssg"), default=None,
+                    help="cfg.model.encoder: the part encoder the weights were trained with (default: the preset's)")
     ap.add_argument("--connectivity", action="store_true",
                     help="compute every batch's contact table and report the connectivity accuracy")
     return ap.parse_args(argv)
@@ -79,6 +81,8 @@ def main(argv=None):
         cfg.data.min_num_part = args.min_num_part
     if args.max_num_part > 0:
         cfg.data.max_num_part = args.max_num_part
+    if args.encoder is not None:
+        cfg.model.encoder = args.encoder
     if args.connectivity and "contact_points" not in cfg.data.data_keys:
         cfg.data.data_keys = tuple(cfg.data.data_keys) + ("contact_points",)
     device = torch.device("cuda:0")

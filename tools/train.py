@@ -35,6 +35,8 @@ def parser():
     ap.add_argument("--lstm-draws", choices=("host", "device"), default=None,
                     help="cfg.model.lstm_draws: B-LSTM's coin, noise and masks from the host generators (the presets' "
                          "default) or from a kernel — what --graph needs for the lstm presets")
+    ap.add_argument("--encoder", choices=("pointnet", "dgcnn", "pointnet2_ssg"), default=None,
+                    help="cfg.model.encoder: the part encoder (default: the preset's)")
     ap.add_argument("--ckpt-dir", default="")
     ap.add_argument("--resume", action="store_true")
     ap.add_argument("--synthetic", action="store_true")
@@ -117,6 +119,8 @@ def main(argv=None):
         cfg.loss.match_sample = "device"  # the matching's point sample drawn by a kernel: no host copy in the step
     if args.lstm_draws is not None:
         cfg.model.lstm_draws = args.lstm_draws
+    if args.encoder is not None:
+        cfg.model.encoder = args.encoder
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", 1), ("RANK", 0), ("LOCAL_RANK", 0)))
     device = torch.device("cuda", local)
     torch.cuda.set_device(device)
