@@ -63,6 +63,11 @@ class BaseModel(nn.Module):
         self.lstm_draws = cfg.model.get("lstm_draws", "host")
         if self.lstm_draws not in ("host", "device"):
             raise ValueError(f"cfg.model.lstm_draws must be 'host' or 'device', got {self.lstm_draws!r}")
+        # how a PointNet++ part encoder evaluates (eval() under no_grad): "library" = its Conv2d / BatchNorm2d chain, "fused" =
+        # csrc/pointnet2_sa_mlp.hip (pointnet2_fused.py).  The models hand it to `build_encoder`; other encoders ignore it.
+        self.pointnet2_eval = cfg.model.get("pointnet2_eval", "library")
+        if self.pointnet2_eval not in ("library", "fused"):
+            raise ValueError(f"cfg.model.pointnet2_eval must be 'library' or 'fused', got {self.pointnet2_eval!r}")
         # fused HIP loss path for geometric data (csrc/assembly_loss.hip); the per-function path is
         # kept for the semantic datasets and as a cross-check.  keep_pts: also return the transformed
         # clouds (`sample_assembly` poses its own: csrc/assemble.hip).  Quaternions and rotation matrices alike.

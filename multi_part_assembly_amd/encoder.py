@@ -382,7 +382,8 @@ class DGCNN(nn.Module):
 def build_encoder(arch, feat_dim, global_feat=True, **kwargs):
     """Registry of reference encoder/__init__.py:6-21: `pointnet` and `dgcnn` (whole encoders on HIP kernels) and
     `pointnet2_ssg` (pointnet2.py: HIP sampling and grouping, the shared MLPs on library operators; global feature
-    only, as upstream).  `pointnet2_msg`, the multi-scale variant, is not built."""
+    only, as upstream; `pointnet2_eval` = cfg.model.pointnet2_eval picks its evaluation path, other encoders ignore it).
+    `pointnet2_msg`, the multi-scale variant, is not built."""
     if arch == "pointnet":
         return PointNet(feat_dim, global_feat=global_feat)
     if arch == "dgcnn":
@@ -391,7 +392,7 @@ def build_encoder(arch, feat_dim, global_feat=True, **kwargs):
         if not global_feat:
             raise ValueError("pointnet2_ssg gives a global feature only (global_feat=True), as in the reference")
         from .pointnet2 import PointNet2SSG
-        return PointNet2SSG(feat_dim)
+        return PointNet2SSG(feat_dim).set_eval_mlp(kwargs.get("pointnet2_eval", "library"))
     if arch == "pointnet2_msg":
         raise NotImplementedError("pointnet2_msg is not supported: the multi-scale-grouping PointNet++ encoder (MSG) is not "
                                   "built; use pointnet2_ssg")

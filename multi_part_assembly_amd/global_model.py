@@ -18,8 +18,10 @@ from .regressor import StocasticPoseRegressor
 class GlobalModel(BaseModel):
     def __init__(self, cfg):
         super().__init__(cfg)
-        self.encoder = build_encoder(cfg.model.encoder, feat_dim=self.pc_feat_dim, global_feat=True)
-        self.global_encoder = build_encoder(cfg.model.encoder, feat_dim=self.pc_feat_dim, global_feat=True)
+        self.encoder = build_encoder(cfg.model.encoder, feat_dim=self.pc_feat_dim, global_feat=True,
+                                     pointnet2_eval=self.pointnet2_eval)
+        self.global_encoder = build_encoder(cfg.model.encoder, feat_dim=self.pc_feat_dim, global_feat=True,
+                                            pointnet2_eval=self.pointnet2_eval)
         dim = 2 * self.pc_feat_dim
         if self.semantic:
             dim += self.max_num_part

@@ -159,7 +159,8 @@ class DGLModel(BaseModel):
         # equivalent parts merged by csrc/gnn_glue.hip (no host copy of part_valids / part_ids, no Python loop); False: the
         # host loop of the reference (`_gather_same_class` + `_merge_nodes`), kept as the cross-check
         self.merge_on_device = True
-        self.encoder = build_encoder(cfg.model.encoder, feat_dim=self.pc_feat_dim, global_feat=True)
+        self.encoder = build_encoder(cfg.model.encoder, feat_dim=self.pc_feat_dim, global_feat=True,
+                                     pointnet2_eval=self.pointnet2_eval)
         self.edge_mlps = _clones(_PairMLP(2 * self.pc_feat_dim, self.pc_feat_dim), self.iter)
         self.node_mlps = self._init_node_mlps()
         dim = self.pc_feat_dim + self.pose_dim

@@ -383,7 +383,8 @@ class LSTMModel(BaseModel):
 
     def __init__(self, cfg):
         super().__init__(cfg)
-        self.encoder = build_encoder(cfg.model.encoder, feat_dim=self.pc_feat_dim, global_feat=True)
+        self.encoder = build_encoder(cfg.model.encoder, feat_dim=self.pc_feat_dim, global_feat=True,
+                                     pointnet2_eval=self.pointnet2_eval)
         self.seq2seq = Seq2Seq(self.pc_feat_dim, self.pc_feat_dim, cfg.model.lstm_hidden_size, draws=self.lstm_draws)
         if self.lstm_draws == "device":  # nothing is drawn on the host: Trainer may capture the step
             self.host_draws_per_forward = False

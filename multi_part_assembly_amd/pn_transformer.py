@@ -21,7 +21,8 @@ class PNTransformer(BaseModel):
     def __init__(self, cfg):
         super().__init__(cfg)
         m = cfg.model
-        self.encoder = build_encoder(m.encoder, feat_dim=self.pc_feat_dim, global_feat=True)
+        self.encoder = build_encoder(m.encoder, feat_dim=self.pc_feat_dim, global_feat=True,
+                                     pointnet2_eval=self.pointnet2_eval)
         self.corr_module = self._init_corr_module()
         self.pose_predictor = self._init_pose_predictor()
 

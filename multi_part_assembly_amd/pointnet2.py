@@ -4,8 +4,10 @@ same constructor argument, forward contract ([n, N, 3] -> [n, feat_dim]) and sta
 (`SA_modules.{i}.mlps.0.{0,1,3,4,6,7}.*`), so a reference checkpoint loads unchanged.
 
 Sampling and grouping run on csrc/pointnet2_ops.hip through `pointnet2_utils`; the shared MLPs run on the module's own
-Conv2d / BatchNorm2d / ReLU sub-modules — library operators, the reference's own op sequence.  A fused grouped-MLP kernel
-is the follow-up that would make this encoder fast; `pointnet2_msg` is not built.
+Conv2d / BatchNorm2d / ReLU sub-modules — library operators, the reference's own op sequence.  In evaluation
+(`eval()` under `no_grad`) `set_eval_mlp("fused")` routes the levels through csrc/pointnet2_sa_mlp.hip instead
+(pointnet2_fused.py): gather, the three layers and the max in one kernel, no [n, C, S, K] tensor.  The training-mode
+fused path (statistics passes and a backward) is the follow-up; `pointnet2_msg` is not built.
 """
 from __future__ import annotations
 
@@ -63,6 +65,11 @@ class PointNet2SSG(nn.Module):
     module advertises (`host_sync_per_forward`): `Trainer(use_graph=True)` keeps such a model on eager launches."""
 
     host_sync_per_forward = True
+    # "library": the shared MLPs on Conv2d / BatchNorm2d / ReLU / max_pool2d, always.  "fused": in eval() mode without
+    # gradients the levels run on csrc/pointnet2_sa_mlp.hip (pointnet2_fused.py); training and grad-enabled calls are the
+    # library path either way.  Opt-in: `set_eval_mlp`, or cfg.model.pointnet2_eval through the models.
+    EVAL_MLP_MODES = ("library", "fused")
+    eval_mlp = "library"
 
     def __init__(self, feat_dim):
         super().__init__()
@@ -73,9 +80,37 @@ class PointNet2SSG(nn.Module):
             PointnetSAModule(mlp=[256, 256, 512, feat_dim], use_xyz=True),
         ])
 
+    def set_eval_mlp(self, mode):
+        if mode not in self.EVAL_MLP_MODES:
+            raise ValueError(f"PointNet2SSG.eval_mlp must be 'library' or 'fused', got {mode!r}")
+        self.eval_mlp = mode
+        return self
+
+    def _forward_fused_eval(self, xyz, record):
+        """The levels on pointnet2_fused.sa_level_eval, features point-major in between; a level outside the kernel's
+        envelope runs its library chain (one warning per encoder)."""
+        from . import pointnet2_fused
+        from .encoder import _warn_library_path
+        feats_pm = None                                                       # [n, N, C]
+        for module in self.SA_modules:
+            miss = pointnet2_fused.envelope_miss(module)
+            if miss is None:
+                xyz, feats_pm = pointnet2_fused.sa_level_eval(module, xyz, feats_pm)
+                if record is not None:
+                    record.append((xyz, feats_pm.transpose(1, 2).contiguous()))
+            else:
+                _warn_library_path(self, f"a set-abstraction level with {miss}")
+                xyz, features = module(xyz, None if feats_pm is None else feats_pm.transpose(1, 2).contiguous())
+                if record is not None:
+                    record.append((xyz, features))
+                feats_pm = features.transpose(1, 2).contiguous()
+        return feats_pm.squeeze(1)
+
     def forward(self, pointcloud, record=None):
         """pointcloud [n, N, 3 + ...] -> [n, feat_dim]; `record`: a list that receives (new_xyz, features) of each level."""
         xyz, features = pointcloud[..., 0:3].contiguous(), None
+        if self.eval_mlp == "fused" and not self.training and not torch.is_grad_enabled():
+            return self._forward_fused_eval(xyz, record)
         for module in self.SA_modules:
             xyz, features = module(xyz, features)
             if record is not None:

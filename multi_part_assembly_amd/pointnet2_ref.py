@@ -4,6 +4,9 @@ reference's CUDA-only `pointnet2_ops` extension computes (its `_ext-src/src/samp
 operation in the written order, with no contraction.  It is the specification the device kernels are held to, and what
 `pointnet2_utils` runs for host tensors.  Imports nothing but numpy.
 
+`sa_mlp_max` / `sa_scale_shift` at the end restate the evaluation kernel of a whole set-abstraction level
+(csrc/pointnet2_sa_mlp.hip) the same way, in the dtype of their inputs: the float64 evaluation is the anchor of its tests.
+
 Furthest point sampling needs one remark.  The reference reduces (distance, index) pairs over a block of T threads with a
 tree whose `max` keeps the LOWER thread on equal distances, strides T/2 ... 1.  The winner among equal distances is
 therefore the thread whose index, read with its log2 T bits REVERSED, is smallest (the last level decides bit 0, the level
@@ -135,3 +138,42 @@ def gather_operation(features, idx):
 
 def gather_backward(grad_out, idx, N: int):
     return grouping_backward(np.asarray(grad_out)[..., None], np.asarray(idx)[:, :, None], N)
+
+
+def sa_scale_shift(gamma, beta, running_mean, running_var, eps):
+    """The per-channel affine map of a BatchNorm in eval() mode, as `mpa_sa_mlp_pack` stores it:
+    scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale, in the dtype of `gamma`."""
+    gamma = np.asarray(gamma)
+    dt = gamma.dtype.type
+    scale = gamma / np.sqrt(np.asarray(running_var, dtype=dt) + dt(eps))
+    return scale, np.asarray(beta, dtype=dt) - np.asarray(running_mean, dtype=dt) * scale
+
+
+def sa_mlp_max(xyz, new_xyz, features, idx, layers):
+    """One set-abstraction level in evaluation (`mpa_sa_mlp_max_forward`), in the dtype of `xyz` (float32 or float64):
+    xyz [M, N, 3], new_xyz [M, S, 3], features [M, N, C] point-major | None, idx [M, S, K]; new_xyz and idx both None: one
+    group of every point (S = 1, K = N).  layers: three (W [Cout, Cin], scale [Cout], shift [Cout]).  -> [M, S, C3].
+    Row (m, j, l) is [xyz[m, idx[m,j,l]] - new_xyz[m, j] ; features[m, idx[m,j,l]]]; an index outside [0, N) reads a zero
+    point and zero features; a_l = relu(scale_l * (W_l a_{l-1}) + shift_l); the result is the max over l of a_3."""
+    xyz = np.asarray(xyz)
+    dt = xyz.dtype
+    M, N, _ = xyz.shape
+    if (new_xyz is None) != (idx is None):
+        raise ValueError("sa_mlp_max: new_xyz and idx are given together, or both None")
+    if idx is None:
+        rows = xyz[:, None]                                                    # [M, 1, N, 3]
+        if features is not None:
+            rows = np.concatenate([rows, np.asarray(features, dtype=dt)[:, None]], axis=-1)
+    else:
+        idx = np.asarray(idx)
+        ok = (idx >= 0) & (idx < N)
+        safe = np.where(ok, idx, 0).astype(np.int64)
+        m = np.arange(M)[:, None, None]
+        rows = np.where(ok[..., None], xyz[m, safe], dt.type(0)) - np.asarray(new_xyz, dtype=dt)[:, :, None, :]
+        if features is not None:
+            f = np.where(ok[..., None], np.asarray(features, dtype=dt)[m, safe], dt.type(0))
+            rows = np.concatenate([rows, f], axis=-1)
+    a = rows.astype(dt)
+    for W, scale, shift in layers:
+        a = np.maximum(np.asarray(scale, dtype=dt) * (a @ np.asarray(W, dtype=dt).T) + np.asarray(shift, dtype=dt), dt.type(0))
+    return a.max(axis=2).astype(dt)

@@ -3,7 +3,7 @@
 
   python tools/evaluate.py --preset pn_transformer_everyday --weight ckpt.pt --data-dir data/breaking_bad \\
       --data-fn everyday.val.txt [--category Bottle | --category all] [--min-num-part 2] [--max-num-part 20]
-      [--connectivity]
+      [--connectivity] [--encoder pointnet2_ssg [--pointnet2-eval fused]]
 
 `--preset` names a function of multi_part_assembly_amd.config; `--weight` a file written by `torch.save` holding either
 `Trainer.state_dict()`, a Lightning-style `{"state_dict": ...}` or a bare model state dict (not needed for the identity
@@ -67,6 +67,9 @@ def parse_args(argv=None):
     ap.add_argument("--max-num-part", type=int, default=-1)
     ap.add_argument("--encoder", choices=("pointnet", "dgcnn", "pointnet2_ssg"), default=None,
                     help="cfg.model.encoder: the part encoder the weights were trained with (default: the preset's)")
+    ap.add_argument("--pointnet2-eval", choices=("library", "fused"), default=None,
+                    help="cfg.model.pointnet2_eval: how a pointnet2_ssg encoder evaluates — its library Conv2d / BatchNorm2d "
+                         "chain (default) or the fused set-abstraction kernel; other encoders ignore it")
     ap.add_argument("--connectivity", action="store_true",
                     help="compute every batch's contact table and report the connectivity accuracy")
     return ap.parse_args(argv)
@@ -83,6 +86,8 @@ def main(argv=None):
         cfg.data.max_num_part = args.max_num_part
     if args.encoder is not None:
         cfg.model.encoder = args.encoder
+    if args.pointnet2_eval is not None:
+        cfg.model.pointnet2_eval = args.pointnet2_eval
     if args.connectivity and "contact_points" not in cfg.data.data_keys:
         cfg.data.data_keys = tuple(cfg.data.data_keys) + ("contact_points",)
     device = torch.device("cuda:0")

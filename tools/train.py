@@ -37,6 +37,9 @@ def parser():
                          "default) or from a kernel — what --graph needs for the lstm presets")
     ap.add_argument("--encoder", choices=("pointnet", "dgcnn", "pointnet2_ssg"), default=None,
                     help="cfg.model.encoder: the part encoder (default: the preset's)")
+    ap.add_argument("--pointnet2-eval", choices=("library", "fused"), default=None,
+                    help="cfg.model.pointnet2_eval: how a pointnet2_ssg encoder evaluates — its library Conv2d / BatchNorm2d "
+                         "chain (default) or the fused set-abstraction kernel; other encoders ignore it")
     ap.add_argument("--ckpt-dir", default="")
     ap.add_argument("--resume", action="store_true")
     ap.add_argument("--synthetic", action="store_true")
@@ -121,6 +124,8 @@ def main(argv=None):
         cfg.model.lstm_draws = args.lstm_draws
     if args.encoder is not None:
         cfg.model.encoder = args.encoder
+    if args.pointnet2_eval is not None:
+        cfg.model.pointnet2_eval = args.pointnet2_eval  # (the validation passes; training is the library chain either way)
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", 1), ("RANK", 0), ("LOCAL_RANK", 0)))
     device = torch.device("cuda", local)
     torch.cuda.set_device(device)

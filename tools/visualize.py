@@ -88,7 +88,7 @@ def export(model, cfg, data_dir, folders, out_dir, vis, device):
     return written
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--preset", required=True)
     ap.add_argument("--weight", default="")
@@ -100,7 +100,16 @@ def main(argv=None):
     ap.add_argument("--num-points", type=int, default=-1, help="points sampled per part (default: the preset's)")
     ap.add_argument("--vis", type=int, default=-1, help="how many of the best assemblies to write (default: all)")
     ap.add_argument("--out", required=True, help="directory to write below")
-    args = ap.parse_args(argv)
+    ap.add_argument("--encoder", choices=("pointnet", "dgcnn", "pointnet2_ssg"), default=None,
+                    help="cfg.model.encoder: the part encoder the weights were trained with (default: the preset's)")
+    ap.add_argument("--pointnet2-eval", choices=("library", "fused"), default=None,
+                    help="cfg.model.pointnet2_eval: how a pointnet2_ssg encoder evaluates — its library Conv2d / BatchNorm2d "
+                         "chain (default) or the fused set-abstraction kernel; other encoders ignore it")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(argv)
     cfg = getattr(config, args.preset)()
     if cfg.data.dataset != "geometry":
         raise SystemExit("tools/visualize.py reads the Breaking-Bad folder layout (part meshes); semantic presets have none")
@@ -110,6 +119,10 @@ def main(argv=None):
         cfg.data.max_num_part = args.max_num_part
     if args.num_points > 0:
         cfg.data.num_pc_points = args.num_points
+    if args.encoder is not None:
+        cfg.model.encoder = args.encoder
+    if args.pointnet2_eval is not None:
+        cfg.model.pointnet2_eval = args.pointnet2_eval
     device = torch.device("cuda:0")
     model = build_model(cfg).to(device)
     if args.weight:
