@@ -40,15 +40,21 @@ constexpr int kChunks = 64;      // most row chunks of the weight-gradient GEMM 
 __global__ __launch_bounds__(64 * kSlices) void ml_bn_finalize_kernel(
     const float* __restrict__ partial, int rows, int C, double count, const float* __restrict__ gamma,
     const float* __restrict__ beta, float* __restrict__ running_mean, float* __restrict__ running_var, float momentum,
-    float eps, float* __restrict__ bn, const CoopWs cw) {
+    float eps, float* __restrict__ bn, const CoopWs cw, int tile_rows) {
   const int c = blockIdx.x * 64 + (threadIdx.x & 63);
   double s, ss;
+  // tile_rows > 0: table row e covers tile_rows data rows (the last one what is left of `count`) and its second entry is
+  // the sum of squares about the TILE's mean (pair_sum_stats_kernel); the raw sum of squares is that + s^2 / n, in double
   const bool last = coop_colsum(rows, C, c, cw,
                                 [&](int e, bool& ok, double& x, double& y) {
                                   const float2 t = *reinterpret_cast<const float2*>(partial + ((long long)e * C + c) * 2);
                                   ok = true;
                                   x = (double)t.x;
                                   y = (double)t.y;
+                                  if (tile_rows > 0) {
+                                    const double left = count - (double)e * (double)tile_rows;
+                                    y += x * x / (left < (double)tile_rows ? left : (double)tile_rows);
+                                  }
                                 },
                                 s, ss);
   if (!last || threadIdx.x >= 64) return;
@@ -363,8 +369,8 @@ __global__ __launch_bounds__(kSbT) void ml_small_bn_bwd_kernel(
 // ---- first layer of the P x P edge MLP without the pair tensor --------------------------------------------------------------
 // The layer's input row (b, i, j) is [a_i ; b_j], so  x w^T = pa[(b, i)] + pb[(b, j)]  with  pa = a Wa^T + bias,
 // pb = b Wb^T  (Wa | Wb = the column halves of w): two GEMMs over the B*P part rows instead of one over the B*P*P pair rows.
-// ypre[(b,i,j)][c] = pa[(b,i)][c] + pb[(b,j)][c] and the per-tile column sums (sum, sum of squares; rows ascending) of kRT
-// rows.  grid = tiles of kRT rows, block 256.
+// ypre[(b,i,j)][c] = pa[(b,i)][c] + pb[(b,j)][c] and the per-tile column sums (sum, sum of squares about the tile's mean;
+// rows ascending) of kRT rows.  grid = tiles of kRT rows, block 256.
 __global__ __launch_bounds__(256) void pair_sum_stats_kernel(const float* __restrict__ pa, const float* __restrict__ pb, int P,
                                                              int R, int C, float* __restrict__ ypre,
                                                              float* __restrict__ partial) {
@@ -390,14 +396,26 @@ __global__ __launch_bounds__(256) void pair_sum_stats_kernel(const float* __rest
         }
       }
     }
-    float s = 0.0f, ss = 0.0f;
+    float s = 0.0f;
 #pragma unroll
     for (int i = 0; i < kRT; ++i) {
       if (i < rows) {
         const float t = va[i] + vb[i];
         ypre[(r0 + i) * C + c] = t;
         s += t;
-        ss = __builtin_fmaf(t, t, ss);
+        va[i] = t;
+      }
+    }
+    // squares CENTRED on the tile's own mean (the values are in registers): a raw fp32 sum of squares carries a rounding of
+    // 2^-24 * sum t^2, which the finalize's  ss / n - mean^2  magnifies by mean^2 / var — 800 with the 4 pair rows of two
+    // parts (tests/test_mlp_anchored_gpu.py); ml_bn_finalize_kernel adds the tile's  s^2 / rows  back in double
+    const float tm = s / (float)rows;
+    float ss = 0.0f;
+#pragma unroll
+    for (int i = 0; i < kRT; ++i) {
+      if (i < rows) {
+        const float dv = va[i] - tm;
+        ss = __builtin_fmaf(dv, dv, ss);
       }
     }
     float* d = partial + ((long long)blockIdx.x * C + c) * 2;
@@ -541,7 +559,7 @@ extern "C" int mpa_mlp_layer_forward(const float* x, int64_t ldx, const float* w
       }
       launch(ml_bn_finalize_kernel, dim3((unsigned)(N / 64), (unsigned)((tiles32 + kEB - 1) / kEB)), dim3(64 * kSlices), s,
              (const float*)m.partial, tiles32, (int)N, (double)R, gamma, beta, running_mean, running_var, momentum, eps,
-             m.bn, cw);
+             m.bn, cw, 0);
     } else {
       tfg::launch_gemm<tfg::EPI_BIAS_ACT>(g, s);  // (g.relu = 0: bias only)
       launch(ml_bn_from_running_kernel, dim3((unsigned)(N / 64)), dim3(64), s, (int)N, gamma, beta,
@@ -567,7 +585,7 @@ extern "C" int mpa_mlp_layer_forward(const float* x, int64_t ldx, const float* w
     ml_gemm<1, false>(x, (int)ldx, w, (int)K, m.ypre, (int)N, (int)N, R, epi, 0, s);
     launch(ml_bn_finalize_kernel, dim3((unsigned)(N / 64), (unsigned)((tiles128 + kEB - 1) / kEB)), dim3(64 * kSlices), s,
            (const float*)m.partial, tiles128, (int)N, (double)R, gamma, beta, running_mean, running_var, momentum, eps, m.bn,
-           cw);
+           cw, 0);
   } else {
     ml_gemm<2, false>(x, (int)ldx, w, (int)K, m.ypre, (int)N, (int)N, R, epi, 0, s);
     launch(ml_bn_from_running_kernel, dim3((unsigned)(N / 64)), dim3(64), s, (int)N, gamma, beta,
@@ -723,7 +741,8 @@ extern "C" int mpa_pair_layer_forward(const float* a, const float* b, const floa
          (int)N, m.ypre, m.partial);
   if (training)
     launch(ml_bn_finalize_kernel, dim3((unsigned)(N / 64), (unsigned)((tiles + kEB - 1) / kEB)), dim3(64 * kSlices), s,
-           (const float*)m.partial, tiles, (int)N, (double)R, gamma, beta, running_mean, running_var, momentum, eps, m.bn, cw);
+           (const float*)m.partial, tiles, (int)N, (double)R, gamma, beta, running_mean, running_var, momentum, eps, m.bn, cw,
+           (int)kRT);
   else
     launch(ml_bn_from_running_kernel, dim3((unsigned)(N / 64)), dim3(64), s, (int)N, gamma, beta, (const float*)running_mean,
            (const float*)running_var, eps, m.bn);

@@ -110,8 +110,13 @@ def supported(hidden, batch, directions=2):
 
 def gru_recurrent(gi, h0, whh, bhh):
     """gi [D, B, T, 3H] (input projections incl. b_ih, gate order r|z|n), h0 [D, B, H], whh [D, 3H, H], bhh [D, 3H]
-    -> hidden states of every step [D, B, T, H] (torch.nn.GRU's equations)."""
+    -> hidden states of every step [D, B, T, H] (torch.nn.GRU's equations).
+    The initial state is DATA: `h0` is detached and takes no gradient (the callers' initial states are random draws or
+    zeros); an `h0` that requires one is an error instead of a silently missing gradient."""
     if not gi.is_cuda:
         raise RuntimeError("gru_recurrent: only CUDA (HIP) tensors are supported — no CPU fallback")
+    if h0.requires_grad:
+        raise RuntimeError("gru_recurrent: the backward pass does not compute the initial state's gradient — pass "
+                           "h0.detach() (csrc/gru.hip treats h0 as data)")
     return _GRURecurrentFn.apply(gi.float().contiguous(), h0.detach().float().contiguous(), whh.contiguous(),
                                  bhh.contiguous())

@@ -70,6 +70,45 @@ def packed_bigru(x, hidden, valids, sd, prefix, training):
     return out
 
 
+def gru_recurrent(gi, h0, whh, bhh):
+    """Recurrent half of a single-layer GRU, one independent direction per leading index: gi [D, B, T, 3H] (the input
+    projections W_ih x_t + b_ih, gate order r|z|n), h0 [D, B, H], whh [D, 3H, H], bhh [D, 3H] -> the hidden state of
+    every step [D, B, T, H].  torch.nn.GRU's equations — b_hn inside the `r *` product — as a plain loop over t, in the
+    dtype of its inputs:
+        r = sigmoid(gi_r + W_hr h + b_hr), z = sigmoid(gi_z + W_hz h + b_hz), n = tanh(gi_n + r * (W_hn h + b_hn)),
+        h' = (1 - z) * n + z * h."""
+    H = h0.shape[-1]
+    h, out = h0, []
+    for t in range(gi.shape[2]):
+        gh = torch.matmul(h, whh.transpose(1, 2)) + bhh[:, None]
+        g = gi[:, :, t]
+        r = torch.sigmoid(g[..., :H] + gh[..., :H])
+        z = torch.sigmoid(g[..., H:2 * H] + gh[..., H:2 * H])
+        n = torch.tanh(g[..., 2 * H:] + r * gh[..., 2 * H:])
+        h = (1.0 - z) * n + z * h
+        out.append(h)
+    return torch.stack(out, dim=2)
+
+
+def mlp_layer(x, sd, prefix, bn=True, relu=True, training=True, stats_out=None, return_preact=False):
+    """One layer of the graph networks' MLPs over rows: x [R, K] -> [R, N] = relu?(bn?(x W^T + b)) with the state-dict
+    entries `<prefix>lin.weight` [N, K], `<prefix>lin.bias` (optional) and, with `bn`, `<prefix>bn.*` (oracle.nets._bn:
+    batch statistics in training mode, the updated running statistics into `stats_out`).  `return_preact`: also the value
+    in front of the ReLU — BatchNorm's output, or the linear map's without `bn`."""
+    pre = F.linear(x, sd[prefix + "lin.weight"], sd.get(prefix + "lin.bias"))
+    if bn:
+        pre = on._bn(pre, sd, prefix + "bn", training, stats_out)
+    out = F.relu(pre) if relu else pre
+    return (out, pre) if return_preact else out
+
+
+def pair_rows(a, b):
+    """a, b [B, P, F] -> the materialised rows [a_i ; b_j] of all part pairs [B*P*P, 2F], row (s, i, j) at (s*P + i)*P + j
+    (the pair tensor of dgl/network.py:135-144)."""
+    B, P, Fd = a.shape
+    return torch.cat([a[:, :, None].expand(B, P, P, Fd), b[:, None].expand(B, P, P, Fd)], dim=-1).reshape(B * P * P, 2 * Fd)
+
+
 def dgl_forward(sd, batch, iters, encoder="dgcnn", training=True, stats_out=None, recurrent=False, merge_node=False):
     """DGL.forward for geometric data (dgl/network.py:154-243; no semantic labels, merge_node without effect):
     -> list of (rot [B,P,4], trans [B,P,3]) per GNN iteration.

@@ -16,7 +16,9 @@ below rounding.  A gradient that is structurally zero (a bias in front of a norm
 its layer's weight-gradient scale) is held to the absolute rule of tests/test_callers_gpu.py: 1e-5 of that scale.
 
 tests/test_anchored.py shows on the CPU that these bars accept a re-associated float32 evaluation and reject a weight that
-lost the third term of its bf16 split, a wrong epsilon and one gradient tensor off by 2e-5.
+lost the third term of its bf16 split, a wrong epsilon and one gradient tensor off by 2e-5; for the single layers of
+csrc/gru.hip and csrc/mlp.hip (the cases at the end of this file, whose only ReLU is pinned by `_pin_relu`) a GRU with b_hn
+outside the reset product, a running variance from the biased variance and swapped weight halves of the pair layer.
 """
 import math
 import statistics
@@ -118,10 +120,10 @@ def summary(label, rows, r32, r64):
     e32, _, med32 = bars(r32, r64, [r[3] for r in rows])
     worst, w32 = max(rows), max(e32, key=e32.get)
     med = statistics.median(r[0] for r in rows)
-    ratio = max(r[0] / max(r[1], med32, 1e-300) for r in rows)
+    ratio, at = max((r[0] / max(r[1], med32, 1e-300), r[3]) for r in rows)
     return (f"{label}: {len(rows)} tensors vs float64: worst {worst[0]:.2e} ({worst[3]}; e32 there {worst[1]:.2e}, bar "
             f"{worst[2]:.2e}), median {med:.2e}; float32 oracle: worst e32 {e32[w32]:.2e} ({w32}), median {med32:.2e}; "
-            f"largest hip / max(e32, median e32) {ratio:.2f} of {MULT:g}")
+            f"largest hip / max(e32, median e32) {ratio:.2f} of {MULT:g} ({at})")
 
 
 def assert_anchored(got, r32, r64, label="", capsys=None):
@@ -269,3 +271,167 @@ def pose_head_fn(sd, inp):
 def valid_rows(t, valid):
     """Rows of the valid tokens of a [B, P, ...] tensor."""
     return t.detach().cpu()[valid.cpu()]
+
+
+# ---- the graph networks' workhorses: csrc/gru.hip and csrc/mlp.hip -------------------------------------------------------
+
+FLIP_PREACT = 5e-6  # the constant of tests/test_callers_gpu.py (tests/test_anchored.py holds the two equal)
+PIN_SHARE = 1e-3    # at most this share of a case's output entries may be taken out of the loss by the ReLU pinning
+
+# (D, B, T, H): the smallest shapes that reach each edge of csrc/gru.hip; see tests/test_gru_anchored_gpu.py
+GRU_CASES = [(2, 1, 1, 128), (1, 1, 2, 256), (1, 32, 4, 128), (2, 32, 3, 256), (2, 33, 3, 256), (2, 64, 2, 128),
+             (2, 64, 5, 256), (2, 7, 33, 128)]
+GRU_WRAPPER_CASES = [(33, 6, 256), (64, 4, 128)]  # (B, T, H) of the masked bidirectional wrapper
+
+# (R, K, N, mode) of one layer of csrc/mlp.hip; see tests/test_mlp_anchored_gpu.py.  Modes: "bn" Linear + bias ->
+# BatchNorm -> ReLU, "bn-norelu" the same without the ReLU; without BatchNorm "bias-relu", "bias", "nobias" (ReLU, no
+# bias) and "data" (bias + ReLU, x takes no gradient).
+MLP_SMALL_CASES = [(5, 64, 64, "bn"), (31, 192, 320, "bn"), (33, 384, 192, "bn"), (257, 768, 64, "bn"),
+                   (2048, 1024, 128, "bn"), (257, 128, 768, "bn"), (2048, 384, 192, "bn"), (33, 128, 768, "bn"),
+                   (257, 192, 320, "bn-norelu")]
+MLP_BIG_CASES = [(2049, 64, 64, "bn"), (2177, 192, 320, "bn"), (2049, 320, 192, "bn"), (2177, 128, 128, "bn"),
+                 (2177, 64, 64, "bn"), (2049, 128, 128, "bn"), (2177, 192, 320, "bn-norelu")]
+MLP_NOBN_MODES = ("bias-relu", "bias", "nobias", "data")
+MLP_NOBN_CASES = [(R, K, N, mode) for R in (1, 33, 2049) for K, N in ((256, 512), (192, 64)) for mode in MLP_NOBN_MODES]
+MLP_LAYER_CASES = MLP_SMALL_CASES + MLP_BIG_CASES + MLP_NOBN_CASES
+
+# (B, P, F, N, mode) of the pair layer; modes: "distinct" a and b, "same" one tensor in both roles, "data" b takes no gradient
+PAIR_MODES = ("distinct", "same", "data")
+PAIR_LAYER_CASES = [(B, P, F, N, mode) for B, P, F, N in ((1, 2, 64, 64), (3, 5, 192, 192), (2, 7, 64, 320), (2, 46, 64, 128),
+                                                         (5, 13, 128, 512)) for mode in PAIR_MODES]
+
+
+def case_id(case):
+    return "x".join(str(c) for c in case)
+
+
+def gru_case(dims, seed=0):
+    """(sd, inputs) of the recurrence: gi ~ N(0,1), h0 ~ N(0,1), whh ~ N(0,1)/sqrt(H), bhh ~ 0.1 N(0,1), loss weights w."""
+    D, B, T, H = dims
+    g = torch.Generator().manual_seed(1000 * D + 100 * B + 10 * T + H + seed)
+    sd = {"whh": torch.randn(D, 3 * H, H, generator=g) / H ** 0.5, "bhh": 0.1 * torch.randn(D, 3 * H, generator=g)}
+    inputs = {"gi": torch.randn(D, B, T, 3 * H, generator=g), "h0": torch.randn(D, B, H, generator=g),
+              "w": torch.randn(D, B, T, H, generator=g)}
+    return sd, inputs
+
+
+def gru_fn(sd, inp):
+    """oracle.callers.gru_recurrent; loss = sum(h w)."""
+    from oracle import callers as oc
+    h = oc.gru_recurrent(inp["gi"], inp["h0"], sd["whh"], sd["bhh"])
+    return {"h": h}, (h * inp["w"]).sum()
+
+
+GRU_WRT = ("gi",)
+
+
+def gru_wrapper_case(dims, seed=0):
+    """A _MaskedBiGRU (on the CPU) over nn.GRU(H, H, bidirectional), x [B, T, H], a non-zero initial state [2, B, H], the
+    validity matrix (valid lengths drawn in 1..T; the first sample has length 1, the last one T) and the loss weights."""
+    from multi_part_assembly_amd.gnn import _MaskedBiGRU
+    B, T, H = dims
+    torch.manual_seed(B + 10 * T + H + seed)
+    mod = _MaskedBiGRU(torch.nn.GRU(input_size=H, hidden_size=H, num_layers=1, batch_first=True, bidirectional=True))
+    g = torch.Generator().manual_seed(7 * B + 3 * T + H + seed)
+    lengths = torch.randint(1, T + 1, (B,), generator=g)
+    lengths[0], lengths[-1] = 1, T
+    valids = (torch.arange(T)[None] < lengths[:, None]).float()
+    inputs = {"x": torch.randn(B, T, H, generator=g), "hidden": torch.randn(2, B, H, generator=g), "valids": valids,
+              "w": torch.randn(B, T, 2 * H, generator=g)}
+    return mod, inputs
+
+
+def gru_wrapper_fn(sd, inp):
+    """oracle.callers.packed_bigru (pack_padded_sequence -> GRU -> pad_packed_sequence); loss = sum(out w)."""
+    from oracle import callers as oc
+    out = oc.packed_bigru(inp["x"], inp["hidden"], inp["valids"], sd, "", True)
+    return {"y": out}, (out * inp["w"]).sum()
+
+
+def _layer_sd(K, N, bn, bias, g):
+    """lin.* (+ bn.*) of one layer: gamma in 0.5..1.5 with a few negative entries and one exact zero, beta ~ 0.1 N,
+    non-trivial running statistics."""
+    sd = {"lin.weight": torch.randn(N, K, generator=g) / K ** 0.5}
+    if bias:
+        sd["lin.bias"] = 0.1 * torch.randn(N, generator=g)
+    if bn:
+        gamma = 0.5 + torch.rand(N, generator=g)
+        gamma[::9] *= -1.0
+        gamma[5] = 0.0
+        sd.update({"bn.weight": gamma, "bn.bias": 0.1 * torch.randn(N, generator=g),
+                   "bn.running_mean": 0.1 * torch.randn(N, generator=g), "bn.running_var": 0.5 + torch.rand(N, generator=g)})
+    return sd
+
+
+def _pin_relu(fn, sd, inputs):
+    """The ReLU pinning of a single layer: evaluate `fn` in float64, find the output entries whose pre-activation lies
+    within FLIP_PREACT of zero relative to its channel's largest |pre-activation| — a float32-grade evaluation may land
+    on the other side of the ReLU there — and zero the loss weight `w` at them (in place).  Their gradient contribution
+    is then zero on either side of the flip and their output within any bar of zero.  Returns their share."""
+    cast = lambda v: v.double() if torch.is_tensor(v) and v.is_floating_point() else v
+    with torch.no_grad():
+        outs, _ = fn({k: cast(v) for k, v in sd.items()}, {k: cast(v) for k, v in inputs.items()})
+    pre = outs["pre"]
+    near = pre.abs() < FLIP_PREACT * pre.abs().amax(dim=0, keepdim=True)
+    inputs["w"][near] = 0.0
+    return float(near.double().mean())
+
+
+def mlp_layer_case(case, seed=0):
+    """(sd, inputs, wrt, share) of one MLP-layer case: x ~ N(0,1) [R, K], weight ~ N(0,1)/sqrt(K), bias ~ 0.1 N, the
+    BatchNorm parameters of `_layer_sd`, the loss weights w [R, N] with the ReLU pinning applied (share: the entries it
+    zeroed; 0 without a ReLU)."""
+    R, K, N, mode = case
+    modes = ("bn", "bn-norelu") + MLP_NOBN_MODES
+    g = torch.Generator().manual_seed(100000 * modes.index(mode) + 1000 * R + 10 * K + N + seed)
+    sd = _layer_sd(K, N, mode.startswith("bn"), mode != "nobias", g)
+    inputs = {"x": torch.randn(R, K, generator=g), "w": torch.randn(R, N, generator=g)}
+    relu = mode in ("bn", "bias-relu", "nobias", "data")
+    share = _pin_relu(mlp_layer_fn(case, preact=True), sd, inputs) if relu else 0.0
+    return sd, inputs, (() if mode == "data" else ("x",)), share
+
+
+def mlp_layer_fn(case, training=True, preact=False):
+    """oracle.callers.mlp_layer: the output and (training-mode BatchNorm) the updated running statistics; loss = sum(y w).
+    `preact`: also the value in front of the ReLU (as `pre`; for `_pin_relu`, not a compared tensor)."""
+    R, K, N, mode = case
+    bn, relu = mode.startswith("bn"), mode in ("bn", "bias-relu", "nobias", "data")
+
+    def fn(sd, inp):
+        from oracle import callers as oc
+        stats = {} if bn and training else None
+        y, pre = oc.mlp_layer(inp["x"], sd, "", bn, relu, training, stats, return_preact=True)
+        outs = {"y": y}
+        if stats:
+            outs.update({"stat." + k: v for k, v in stats.items()})
+        if preact:
+            outs["pre"] = pre
+        return outs, (y * inp["w"]).sum()
+    return fn
+
+
+def pair_layer_case(case, seed=0):
+    """(sd, inputs, wrt, share) of one pair-layer case: a, b ~ N(0,1) [B, P, F] ("same": a alone, in both roles), the
+    layer's parameters over the 2F-wide pair rows, the loss weights w [B P P, N] with the ReLU pinning applied."""
+    B, P, F, N, mode = case
+    g = torch.Generator().manual_seed(100000 * PAIR_MODES.index(mode) + 1000 * B + 100 * P + 10 * F + N + seed)
+    sd = _layer_sd(2 * F, N, True, True, g)
+    inputs = {"a": torch.randn(B, P, F, generator=g), "w": torch.randn(B * P * P, N, generator=g)}
+    if mode != "same":
+        inputs["b"] = torch.randn(B, P, F, generator=g)
+    share = _pin_relu(pair_layer_fn(case, preact=True), sd, inputs)
+    return sd, inputs, (("a", "b") if mode == "distinct" else ("a",)), share
+
+
+def pair_layer_fn(case, preact=False):
+    """oracle.callers.mlp_layer over the materialised pair rows cat([a_i ; b_j]) (oracle.callers.pair_rows)."""
+    def fn(sd, inp):
+        from oracle import callers as oc
+        stats = {}
+        rows = oc.pair_rows(inp["a"], inp.get("b", inp["a"]))
+        y, pre = oc.mlp_layer(rows, sd, "", True, True, True, stats, return_preact=True)
+        outs = {"y": y, **{"stat." + k: v for k, v in stats.items()}}
+        if preact:
+            outs["pre"] = pre
+        return outs, (y * inp["w"]).sum()
+    return fn

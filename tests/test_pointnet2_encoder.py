@@ -86,6 +86,37 @@ def test_running_statistics_and_gradients_match_the_reference_records(fixture, c
         param_fill.compare(fixture, "f32.", f"grad.{k}", p.grad.numpy(), REL, floor=floor)
 
 
+def test_pinned_relu_decisions_reproduce_the_pass_and_follow_a_flip(fixture):
+    """tests/pointnet2_pinned.py, the anchor of the GPU test where the device decides a ReLU the other way: in float64
+    the free pass is the fixture's float64 pass (records stored in float32), pinned at its own decisions it reproduces
+    itself bit for bit, every level has a pre-activation below float32 rounding, and ONE decision flipped at the smallest
+    pre-activation of SA2's first ReLU moves that layer's BatchNorm bias gradient by more than 1e-3 — the distance a
+    float32-grade run that takes that decision shows against the unpinned records."""
+    import anchored
+    import pointnet2_pinned as pp
+    from test_pointnet2_encoder_gpu import picked, records
+    r64 = records(fixture, "f64.")
+    g64, z64 = pp.cpu_pass(fixture, torch.float64)
+    assert len(z64) == 9 and set(g64) == {k for k in r64 if k.startswith("grad.")}
+    for k, v in g64.items():
+        if anchored._zero_scale(k, r64) is None:
+            assert anchored.err(picked(v), r64[k]) <= 2e-7, k
+    own = [z > 0 for z in z64]
+    assert pp.sites_off(own, z64) == (0, 0.0)
+    again, _ = pp.cpu_pass(fixture, torch.float64, own)
+    assert all(torch.equal(again[k], g64[k]) for k in g64)
+    rel = z64[3].abs() / z64[3].abs().amax(dim=(0, 2, 3), keepdim=True)
+    assert float(rel.min()) < 2.0 ** -24
+    flipped = list(own)
+    flipped[3] = own[3].clone()
+    flipped[3].view(-1)[rel.flatten().argmin()] ^= True
+    assert pp.sites_off(flipped, z64) == (1, float(rel.min()))
+    moved, _ = pp.cpu_pass(fixture, torch.float64, flipped)
+    assert anchored.err(moved["grad.SA_modules.1.mlps.0.1.bias"], g64["grad.SA_modules.1.mlps.0.1.bias"]) > 1e-3
+    for k in ("grad.SA_modules.1.mlps.0.3.weight", "grad.SA_modules.2.mlps.0.0.weight"):  # above the site: the value did not move
+        assert anchored.err(moved[k], g64[k]) < 1e-6, k
+
+
 def test_forward_parts_runs_the_valid_parts_only():
     enc = PointNet2SSG(64).train()
     twin = copy.deepcopy(enc)
