@@ -982,6 +982,40 @@ int mpa_group_points_backward(const float* grad_out, const int32_t* idx, int64_t
                               int64_t K, void* workspace, float* grad_features, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * PointNet++ feature propagation (csrc/pointnet2_interp.hip) -- the remaining operators of `pointnet2_ops`
+ * (pointnet2_ops/pointnet2_utils.py: three_nn, three_interpolate; kernels in _ext-src/src/interpolate_gpu.cu), which its
+ * `PointnetFPModule` uses.  The rules of the block above hold: IEEE fp32, one operation at a time in the written order, no
+ * fused multiply-add; contiguous inputs, int32 indices; no call synchronises, every launch configuration depends on the
+ * sizes only (capturable), every output element is written on every call, two calls give the same bits, no floating-point
+ * atomics.  multi_part_assembly_amd/pointnet2_ref.py restates every definition in numpy.
+ *
+ * mpa_three_nn: unknown [M, n, 3], known [M, m, 3] -> dist [M, n, 3], idx [M, n, 3].  For every unknown point the known
+ *   points are walked in ascending k with d = ((ux-x)*(ux-x) + (uy-y)*(uy-y)) + (uz-z)*(uz-z); three running bests start
+ *   at (+inf, index 0) and take d through the strict cascade: d < best1 shifts best1, best2 down and takes the first slot,
+ *   else d < best2 shifts best2 down and takes the second, else d < best3 takes the third.  Equal distances therefore keep
+ *   the lower index first, and a NaN d is never inserted.  dist holds the correctly rounded fp32 square roots of the three
+ *   bests (the reference's wrapper takes them in a second launch), idx their indices; with m < 3 the unused slots stay
+ *   (inf, 0).  m >= 1 and n >= 1 unless M is 0.
+ * mpa_three_interpolate_forward: features [M, C, m], idx [M, n, 3], weight [M, n, 3] -> out [M, C, n],
+ *   out[b,c,j] = (f1*w1 + f2*w2) + f3*w3 with fk = features[b,c,idx[b,j,k]]; an index outside [0, m) is never
+ *   dereferenced: its fk reads as 0, the rule of mpa_group_points_forward.
+ * mpa_three_interpolate_backward: grad_out [M, C, n] -> grad_features [M, C, m]: every element the fp32 sum, started at
+ *   0, of the products grad_out[b,c,j] * weight[b,j,k] over the pairs (j, k) with idx[b,j,k] == i, added one after the
+ *   other in ascending flat position 3 j + k; an index outside [0, m) contributes nothing.  Workspace:
+ *   mpa_three_interpolate_workspace bytes (the inverted index of every cloud: mpa_group_points_backward's, over 3 n
+ *   positions), 256-byte aligned.
+ * Sizes: 3 M n, 3 M m, M C n and M C m stay below 2^31, otherwise MPA_EINVAL.  Negative sizes and null pointers are refused
+ * before the device is touched; empty problems return MPA_OK.
+ * ---------------------------------------------------------------------------------------------- */
+int mpa_three_nn(const float* unknown, const float* known, int64_t M, int64_t n, int64_t m, float* dist, int32_t* idx,
+                 void* stream);
+int mpa_three_interpolate_forward(const float* features, const int32_t* idx, const float* weight, int64_t M, int64_t C,
+                                  int64_t m, int64_t n, float* out, void* stream);
+int mpa_three_interpolate_workspace(int64_t M, int64_t n, int64_t m, int64_t* bytes);
+int mpa_three_interpolate_backward(const float* grad_out, const int32_t* idx, const float* weight, int64_t M, int64_t C,
+                                   int64_t n, int64_t m, void* workspace, float* grad_features, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * PointNet++ set-abstraction level for evaluation (csrc/pointnet2_sa_mlp.hip): gather, three (GEMM, per-channel scale and
  * shift, ReLU) layers, max over the samples of every centre, in one kernel -- the shared MLP of a `PointnetSAModule` whose
  * BatchNorms are in eval() mode, without the [M, C, S, K] tensors.  `sa_mlp_max` of multi_part_assembly_amd/pointnet2_ref.py

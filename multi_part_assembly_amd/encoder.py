@@ -383,7 +383,8 @@ def build_encoder(arch, feat_dim, global_feat=True, **kwargs):
     """Registry of reference encoder/__init__.py:6-21: `pointnet` and `dgcnn` (whole encoders on HIP kernels) and
     `pointnet2_ssg` (pointnet2.py: HIP sampling and grouping, the shared MLPs on library operators; global feature
     only, as upstream; `pointnet2_eval` = cfg.model.pointnet2_eval picks its evaluation path, other encoders ignore it).
-    `pointnet2_msg`, the multi-scale variant, is not built."""
+    `pointnet2_msg`, the multi-scale variant, is not in the registry yet: the class exists (pointnet2.PointNet2MSG), the
+    refusal below is what tests/test_pointnet2_encoder.py pins."""
     if arch == "pointnet":
         return PointNet(feat_dim, global_feat=global_feat)
     if arch == "dgcnn":

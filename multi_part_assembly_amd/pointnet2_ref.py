@@ -1,6 +1,7 @@
-"""numpy restatement of the PointNet++ sampling and grouping operators (include/mpa_hip.h, csrc/pointnet2_ops.hip): what the
-reference's CUDA-only `pointnet2_ops` extension computes (its `_ext-src/src/sampling_gpu.cu`, `ball_query_gpu.cu`,
-`group_points_gpu.cu`), written as definitions instead of as thread programs.  Every operation is one IEEE float32
+"""numpy restatement of the PointNet++ sampling, grouping and interpolation operators (include/mpa_hip.h,
+csrc/pointnet2_ops.hip, csrc/pointnet2_interp.hip): what the reference's CUDA-only `pointnet2_ops` extension computes (its
+`_ext-src/src/sampling_gpu.cu`, `ball_query_gpu.cu`, `group_points_gpu.cu`, `interpolate_gpu.cu`), written as definitions
+instead of as thread programs.  Every operation is one IEEE float32
 operation in the written order, with no contraction.  It is the specification the device kernels are held to, and what
 `pointnet2_utils` runs for host tensors.  Imports nothing but numpy.
 
@@ -138,6 +139,75 @@ def gather_operation(features, idx):
 
 def gather_backward(grad_out, idx, N: int):
     return grouping_backward(np.asarray(grad_out)[..., None], np.asarray(idx)[:, :, None], N)
+
+
+def three_nn(unknown, known):
+    """unknown [M, n, 3], known [M, m, 3] -> dist [M, n, 3], idx int32 [M, n, 3], in the dtype of `unknown` (float32 or
+    float64).  Every unknown point walks the known points in ascending k with
+    d = ((ux-x)(ux-x) + (uy-y)(uy-y)) + (uz-z)(uz-z); three running bests start at (+inf, index 0) and take d through the
+    strict cascade `d < best1` / `else d < best2` / `else d < best3` (equal distances keep the lower index first, a NaN d
+    is never inserted); dist is the square root of the bests.  With m < 3 the unused slots stay (inf, 0)."""
+    unknown = np.asarray(unknown)
+    dt = unknown.dtype.type
+    known = np.asarray(known, dtype=dt)
+    M, n, _ = unknown.shape
+    m = known.shape[1]
+    best = [np.full((M, n), np.inf, dtype=dt) for _ in range(3)]
+    besti = [np.zeros((M, n), dtype=np.int32) for _ in range(3)]
+    ux, uy, uz = unknown[..., 0], unknown[..., 1], unknown[..., 2]
+    with np.errstate(invalid="ignore", over="ignore"):
+        for k in range(m):
+            x, y, z = known[:, k, 0, None], known[:, k, 1, None], known[:, k, 2, None]
+            d = ((ux - x) * (ux - x) + (uy - y) * (uy - y)) + (uz - z) * (uz - z)
+            first = d < best[0]
+            second = ~first & (d < best[1])
+            third = ~first & ~second & (d < best[2])
+            down = first | second
+            best[2], besti[2] = np.where(down, best[1], np.where(third, d, best[2])), \
+                np.where(down, besti[1], np.where(third, np.int32(k), besti[2]))
+            best[1], besti[1] = np.where(first, best[0], np.where(second, d, best[1])), \
+                np.where(first, besti[0], np.where(second, np.int32(k), besti[1]))
+            best[0], besti[0] = np.where(first, d, best[0]), np.where(first, np.int32(k), besti[0])
+    return np.sqrt(np.stack(best, axis=-1)).astype(dt), np.stack(besti, axis=-1).astype(np.int32)
+
+
+def three_interpolate(features, idx, weight):
+    """features [M, C, m], idx [M, n, 3], weight [M, n, 3] -> [M, C, n] in the dtype of `features`:
+    out[b,c,j] = (f1 w1 + f2 w2) + f3 w3 with fk = features[b,c,idx[b,j,k]]; an index outside [0, m) reads as 0."""
+    features, idx = np.asarray(features), np.asarray(idx)
+    dt = features.dtype.type
+    weight = np.asarray(weight, dtype=dt)
+    M, C, m = features.shape
+    n = idx.shape[1]
+    ok = (idx >= 0) & (idx < m)
+    safe = np.where(ok, idx, 0).astype(np.int64)
+    if m == 0:
+        f = np.zeros((M, C, n, 3), dtype=dt)
+    else:
+        f = np.take_along_axis(features[:, :, None, :], safe.reshape(M, 1, 1, -1), axis=3).reshape(M, C, n, 3)
+        f = np.where(ok[:, None], f, dt(0))
+    w = weight[:, None]
+    with np.errstate(invalid="ignore", over="ignore"):
+        return ((f[..., 0] * w[..., 0] + f[..., 1] * w[..., 1]) + f[..., 2] * w[..., 2]).astype(dt)
+
+
+def three_interpolate_backward(grad_out, idx, weight, m: int):
+    """grad_out [M, C, n], idx [M, n, 3], weight [M, n, 3] -> [M, C, m] in the dtype of `grad_out`: every element the sum,
+    started at 0, of grad_out[b,c,j] * weight[b,j,k] over the pairs with idx[b,j,k] == i, added one after the other in
+    ascending flat position 3 j + k (`np.add.at`); indices outside [0, m) contribute nothing."""
+    grad_out, idx = np.asarray(grad_out), np.asarray(idx)
+    dt = grad_out.dtype.type
+    weight = np.asarray(weight, dtype=dt)
+    M, C, n = grad_out.shape
+    out = np.zeros((M, C, m), dtype=dt)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for b in range(M):
+            flat = idx[b].reshape(-1).astype(np.int64)
+            ok = (flat >= 0) & (flat < m)
+            terms = (np.repeat(grad_out[b], 3, axis=1) * weight[b].reshape(1, -1)).astype(dt)    # [C, 3 n]
+            for c in range(C):
+                np.add.at(out[b, c], flat[ok], terms[c, ok])
+    return out
 
 
 def sa_scale_shift(gamma, beta, running_mean, running_var, eps):

@@ -1,12 +1,12 @@
 """The operator module of the reference's `pointnet2_ops` extension (pointnet2_ops/pointnet2_utils.py) over
-csrc/pointnet2_ops.hip: the same function and class names and argument orders, so the reference's
-`pointnet2_modules.py` binds to it unchanged.  `three_nn` / `three_interpolate` are not here: no encoder
-of the reference uses them.
+csrc/pointnet2_ops.hip and csrc/pointnet2_interp.hip: the same function and class names and argument orders, so the
+reference's `pointnet2_modules.py` binds to it unchanged — the set-abstraction modules and, through
+`three_nn` / `three_interpolate`, its `PointnetFPModule`.
 
 Inputs are cast to float32, as `custom_fwd(cast_inputs=torch.float32)` does upstream.  The wrappers check shapes, never
 index values, and never synchronise.  CUDA tensors run the HIP kernels; CPU tensors run the numpy restatement
 `pointnet2_ref` — slow, and the one exception to the package's "no CPU fallback" rule: it exists for the tests and for the
-fixture generator (tests/golden/make_golden_pointnet2.py), which drives the reference's own modules on the host.
+fixture generators (tests/golden/make_golden_pointnet2*.py), which drive the reference's own modules on the host.
 """
 from __future__ import annotations
 
@@ -15,8 +15,9 @@ import torch.nn as nn
 
 from . import _lib, pointnet2_ref
 
-__all__ = ["furthest_point_sample", "gather_operation", "grouping_operation", "ball_query", "QueryAndGroup", "GroupAll",
-           "FurthestPointSampling", "GatherOperation", "GroupingOperation", "BallQuery"]
+__all__ = ["furthest_point_sample", "gather_operation", "grouping_operation", "ball_query", "three_nn", "three_interpolate",
+           "QueryAndGroup", "GroupAll", "FurthestPointSampling", "GatherOperation", "GroupingOperation", "BallQuery",
+           "ThreeNN", "ThreeInterpolate"]
 
 
 def _f32(t):
@@ -106,6 +107,85 @@ class GatherOperation(torch.autograd.Function):
 
 
 gather_operation = GatherOperation.apply
+
+
+class ThreeNN(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, unknown, known):
+        """unknown [M, n, 3], known [M, m, 3] -> dist [M, n, 3] (l2 distances to the three nearest known points, nearest
+        first), idx int32 [M, n, 3]; neither is differentiable."""
+        _check("three_nn", unknown, 3, 3)
+        _check("three_nn", known, 3, 3)
+        unknown, known = _f32(unknown), _f32(known)
+        M, n, _ = unknown.shape
+        m = known.shape[1]
+        if known.shape[0] != M:
+            raise ValueError(f"three_nn: unknown {tuple(unknown.shape)} and known {tuple(known.shape)} differ in clouds")
+        if not unknown.is_cuda:
+            dist, idx = (torch.from_numpy(a) for a in pointnet2_ref.three_nn(unknown.numpy(), known.numpy()))
+        else:
+            dist = torch.empty((M, n, 3), dtype=torch.float32, device=unknown.device)
+            idx = torch.empty((M, n, 3), dtype=torch.int32, device=unknown.device)
+            _lib.launch("mpa_three_nn", unknown.device, unknown, known, M, n, m, dist, idx, timer=f"three_nn[{M}x{n}x{m}]")
+        ctx.mark_non_differentiable(dist, idx)
+        return dist, idx
+
+    @staticmethod
+    def backward(ctx, grad_dist, grad_idx):
+        return None, None
+
+
+three_nn = ThreeNN.apply
+
+
+def _interpolate_forward(features, idx, weight):
+    """features [M, C, m] float32, idx [M, n, 3] int32, weight [M, n, 3] float32, all contiguous -> [M, C, n]."""
+    M, C, m = features.shape
+    n = idx.shape[1]
+    if not features.is_cuda:
+        return torch.from_numpy(pointnet2_ref.three_interpolate(features.numpy(), idx.numpy(), weight.numpy()))
+    out = torch.empty((M, C, n), dtype=torch.float32, device=features.device)
+    _lib.launch("mpa_three_interpolate_forward", features.device, features, idx, weight, M, C, m, n, out,
+                timer=f"three_interpolate_forward[{M}x{C}x{m}->{n}]")
+    return out
+
+
+def _interpolate_backward(grad_out, idx, weight, m):
+    """grad_out [M, C, n] float32 -> [M, C, m], summed in ascending position 3 j + k."""
+    M, C, n = grad_out.shape
+    if not grad_out.is_cuda:
+        return torch.from_numpy(pointnet2_ref.three_interpolate_backward(grad_out.numpy(), idx.numpy(), weight.numpy(), m))
+    dev = grad_out.device
+    grad = torch.empty((M, C, m), dtype=torch.float32, device=dev)
+    ws = _workspace("mpa_three_interpolate_workspace", dev, M, n, m)
+    _lib.launch("mpa_three_interpolate_backward", dev, grad_out, idx, weight, M, C, n, m, ws, grad,
+                timer=f"three_interpolate_backward[{M}x{C}x{n}->{m}]")
+    return grad
+
+
+class ThreeInterpolate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, features, idx, weight):
+        """features [M, C, m], idx [M, n, 3], weight [M, n, 3] -> [M, C, n]: the weighted sum of three feature columns;
+        the gradient goes to `features` only."""
+        _check("three_interpolate", features, 3)
+        _check("three_interpolate", idx, 3, 3)
+        _check("three_interpolate", weight, 3, 3)
+        if idx.shape != weight.shape or idx.shape[0] != features.shape[0]:
+            raise ValueError(f"three_interpolate: features {tuple(features.shape)}, idx {tuple(idx.shape)} and weight "
+                             f"{tuple(weight.shape)} do not belong together")
+        features, idx, weight = _f32(features), _i32(idx), _f32(weight)
+        ctx.save_for_backward(idx, weight)
+        ctx.m = features.shape[2]
+        return _interpolate_forward(features, idx, weight)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        idx, weight = ctx.saved_tensors
+        return _interpolate_backward(_f32(grad_out), idx, weight, ctx.m), None, None
+
+
+three_interpolate = ThreeInterpolate.apply
 
 
 class GroupingOperation(torch.autograd.Function):
