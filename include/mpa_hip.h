@@ -1050,6 +1050,50 @@ int mpa_sa_mlp_max_forward(const float* xyz, const float* new_xyz, const float* 
                            int64_t N, int64_t S, int64_t K, int64_t C, const void* layer1, const void* layer2,
                            const void* layer3, int64_t C1, int64_t C2, int64_t C3, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Repulsion loss (csrc/repulsion.hip) -- `repulsion_cd_loss` of the reference (multi_part_assembly/utils/loss.py:205-225):
+ * the Chamfer distance of every pair of parts of a shape, hinged at `thre`, without the two [B P P, N, 3] expansions.
+ * multi_part_assembly_amd/repulsion_ref.py restates every definition below in numpy, in float32 and float64.
+ *
+ * Inputs, contiguous fp32: part_pcs [B, P, N, 3], the POSED clouds (the operator is the same for every rotation form);
+ * valids [B, P] (a part is valid iff its entry == 1); thre by value.  Valid parts hold finite coordinates; padded slots are
+ * never read (NaN there changes no output bit).  With nv the number of valid parts of sample b:
+ *   loss_b = [nv thre + 2 sum_{i<j, both valid} max(0, thre - cd_ij)] / nv^2,    cd_ij = mean_n d1[n] + mean_m d2[m],
+ *   d1[n] = min_m d(a_n, b_m), d2[m] = min_n d(a_n, b_m) over the points a of part i and b of part j, with the Chamfer
+ *   contract above: d = (dx*dx + dy*dy) + dz*dz, every operation rounded, strict `<` in index order, (1e32, -1) for a point
+ *   that never sees d < 1e32 -- d1, d2 and both index lists are those of mpa_chamfer_forward for the pair, bit for bit.
+ *   (The reference sums all P x P pairs: every unordered pair twice, and `thre` per valid part for the diagonal, whose cd
+ *   is 0.)  A mean is `ordered_sum` / N: 256 partial sums over the points t, t + 256, ... in ascending order, six butterfly
+ *   steps p[t] += p[t ^ off] (off = 32 ... 1) in every group of 64, the four groups left to right.  The hinges are added in
+ *   slot order (i ascending, then j), started at 0.  nv = 0 gives NaN (0 / 0), as the reference does.
+ * Outputs: loss [B]; cd [B, P, P] (NULL: skipped) symmetric, 0 on the diagonal and for a pair with a padded member; dists
+ * [B, P (P - 1) / 2, 2, N] (NULL: skipped; a diagnostic) d1 and d2 of every searched pair, other rows unwritten.
+ * The prune: when cd is not requested, a pair whose bounding boxes are at least `thre` apart -- the gap g evaluated with
+ * the rounded formula of mpa_contact_points, a lower bound of every computed d -- is not searched.  Then each mean is at
+ * least g (1 - N 2^-24) and cd >= 2 g (1 - N 2^-24) >= thre, the hinge is exactly zero: the prune never changes loss or
+ * gradient.
+ * Workspace: mpa_repulsion_cd_workspace bytes, 256-byte aligned, written by the forward and read by the backward: per pair
+ * slot a flag byte (0 not searched: padded member or pruned; 1 searched, thre - cd < 0; 2 hinged, thre - cd >= 0 -- the
+ * rule of torch's clamp_min) at flag_offset, and for every searched pair the two 16-bit arg-min lists [B, slots, N] at
+ * idx1_offset (points of i -> part j) and idx2_offset (points of j -> part i), 0xffff for -1; the lists of other pairs
+ * are unwritten.  The offset pointers may be NULL.
+ * Backward: grad_loss [B] -> grad_pcs [B, P, N, 3], every element written.  c_b = (-grad_loss[b] * 2) / ((nv * nv) * N).
+ * Point n of part i takes, over its hinged partners j in ascending order, first c_b * (2 (a_n - b_{idx[n]})) for its own
+ * minimum and then c_b * (2 (a_n - b_m)) for every point m of j whose minimum lands on it, in ascending m; every product
+ * and sum rounded, per coordinate, no floating-point atomics.  Padded slots, pairs that are not hinged and a sample
+ * without a valid part get exact zeros (the reference's gradient of such a sample is NaN).
+ * Forward: two launches (one block per pair slot, one per sample); backward: one (one block per part).  No atomics, no
+ * host synchronisation, launch configurations that depend on the sizes only: capturable, bit-identical from run to run.
+ * Envelope: 1 <= N <= 2048 (both parts live in LDS, 24 N bytes), 1 <= P <= 64, B >= 0, B P P N < 2^31; outside it
+ * MPA_EINVAL.  Negative sizes and null pointers are refused before the device is touched; B = 0 returns MPA_OK.
+ * ---------------------------------------------------------------------------------------------- */
+int mpa_repulsion_cd_workspace(int64_t B, int64_t P, int64_t N, int64_t* bytes, int64_t* flag_offset, int64_t* idx1_offset,
+                               int64_t* idx2_offset);
+int mpa_repulsion_cd_forward(const float* part_pcs, const float* valids, float thre, int64_t B, int64_t P, int64_t N,
+                             void* workspace, float* loss, float* cd, float* dists, void* stream);
+int mpa_repulsion_cd_backward(const float* grad_loss, const float* part_pcs, const float* valids, int64_t B, int64_t P,
+                              int64_t N, const void* workspace, float* grad_pcs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,9 @@ SIGNATURES: dict[str, tuple] = {
     "mpa_sa_mlp_packed_bytes": (_INT, [_I64, _I64, _P]),
     "mpa_sa_mlp_pack": (_INT, [_P] * 5 + [_F32, _I64, _I64, _P, _P]),
     "mpa_sa_mlp_max_forward": (_INT, [_P] * 4 + [_I64] * 5 + [_P] * 3 + [_I64] * 3 + [_P, _P]),
+    "mpa_repulsion_cd_workspace": (_INT, [_I64, _I64, _I64, _P, _P, _P, _P]),
+    "mpa_repulsion_cd_forward": (_INT, [_P, _P, _F32, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
+    "mpa_repulsion_cd_backward": (_INT, [_P, _P, _P, _I64, _I64, _I64, _P, _P, _P]),
 }
 
 ABI_VERSION = 10

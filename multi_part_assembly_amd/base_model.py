@@ -20,8 +20,8 @@ import torch.nn as nn
 from .chamfer import chamfer_distance
 from .eval_utils import assembly_metrics, calc_connectivity_acc, calc_part_acc, rot_metrics, trans_metrics
 from .matching import SUBSAMPLE, MatchSampler, match_parts
-from .loss import (LossTerms, geometric_assembly_loss, part_order, search_mode, rot_cosine_loss, rot_points_cd_loss,
-                   rot_points_l2_loss, shape_cd_loss, trans_l2_loss)
+from .loss import (LossTerms, geometric_assembly_loss, part_order, repulsion_cd_loss, search_mode, rot_cosine_loss,
+                   rot_points_cd_loss, rot_points_l2_loss, shape_cd_loss, trans_l2_loss)
 from .rotation import Rotation3D
 from .transforms import transform_pc
 
@@ -73,6 +73,13 @@ class BaseModel(nn.Module):
         # clouds (`sample_assembly` poses its own: csrc/assemble.hip).  Quaternions and rotation matrices alike.
         self.fused_loss = True
         self.keep_pts = False
+        # opt-in repulsion term (loss.repulsion_cd_loss on the posed prediction, weighted by repulsion_loss_w like every
+        # `<term>_w`): the reference ships neither a threshold nor a weight, so there is no default to fall back on
+        self.use_repulsion_loss = bool(cfg.loss.get("use_repulsion_loss", False))
+        if self.use_repulsion_loss:
+            for key in ("repulsion_thre", "repulsion_loss_w"):
+                if key not in cfg.loss:
+                    raise ValueError(f"cfg.loss.use_repulsion_loss is set but cfg.loss.{key} is missing (no default exists)")
         # evaluation metrics by csrc/eval_metrics.hip (two launches + one for the connectivity accuracy) instead of the
         # per-function composition; off by default, `evaluate.Evaluator` switches it on for its run
         self.fused_metrics = False
@@ -171,6 +178,7 @@ class BaseModel(nn.Module):
                 loss_dict["rot_loss"] = terms["rot_loss"]
             if self.cfg.loss.use_rot_pt_l2_loss:
                 loss_dict["rot_pt_l2_loss"] = terms["rot_pt_l2_loss"]
+            self._add_repulsion_loss(loss_dict, pred_trans, pred_rot, part_pcs, valids)
             if self.training and tuple(loss_dict) == terms.stacked[0]:
                 loss_dict.stacked = terms.stacked  # every row is used, in order: no select / re-stack
             if not self.training:
@@ -190,11 +198,20 @@ class BaseModel(nn.Module):
             loss_dict["rot_loss"] = rot_cosine_loss(pred_rot, new_rot, valids)
         if self.cfg.loss.use_rot_pt_l2_loss:
             loss_dict["rot_pt_l2_loss"] = rot_points_l2_loss(part_pcs, pred_rot, new_rot, valids)
+        self._add_repulsion_loss(loss_dict, pred_trans, pred_rot, part_pcs, valids)
         if not self.training:
             loss_dict.update(self._calc_metrics(data_dict, out_dict, new_trans, new_rot))
         out_dict = {"pred_trans": pred_trans, "pred_rot": pred_rot, "gt_trans_pts": gt_pts,
                     "pred_trans_pts": pred_pts}
         return loss_dict, out_dict
+
+    def _add_repulsion_loss(self, loss_dict, pred_trans, pred_rot, part_pcs, valids):
+        """`repulsion_loss` [B] of the posed prediction when cfg.loss.use_repulsion_loss is set: csrc/repulsion.hip on the
+        fused-loss path, the reference's composition otherwise.  Without the key `loss_dict` is left as it is."""
+        if not self.use_repulsion_loss:
+            return
+        posed = transform_pc(pred_trans, pred_rot, part_pcs)
+        loss_dict["repulsion_loss"] = repulsion_cd_loss(posed, valids, self.cfg.loss.repulsion_thre, fused=self.fused_loss)
 
     @torch.no_grad()
     def _calc_metrics(self, data_dict, out_dict, gt_trans, gt_rot):

@@ -14,7 +14,7 @@ from .chamfer import chamfer_distance
 from .transforms import pose_apply, pose_apply_rmat, rot_pc
 
 __all__ = ["geometric_assembly_loss", "part_order", "search_mode", "SEARCH_MODES", "LOSS_TERMS", "trans_l2_loss", "rot_l2_loss", "rot_cosine_loss", "rot_points_l2_loss",
-           "rot_points_cd_loss", "shape_cd_loss", "repulsion_cd_loss"]
+           "rot_points_cd_loss", "shape_cd_loss", "repulsion_cd_loss", "repulsion_cd_search", "repulsion_supported"]
 
 PAD_FILL = 1e3  # coordinate given to the points of padded parts in shape_cd_loss (loss.py:173-175)
 
@@ -102,15 +102,156 @@ def shape_cd_loss(pts, trans1, trans2, rot1, rot2, valids, ret_pts=False, traini
     return (loss, pts1, pts2) if ret_pts else loss
 
 
-def repulsion_cd_loss(part_pcs, valids, thre):
-    """max(0, thre - CD(part_i, part_j)) averaged over valid pairs (unused by the shipped configs)."""
+def _repulsion_composed(part_pcs, valids, thre):
+    """The reference's composition (loss.py:205-225): all P x P pairs through the Chamfer operator.  (loss [B], raw
+    Chamfer distances [B, P, P]; the rows and columns of padded slots hold whatever their points give.)"""
     B, P, N, _ = part_pcs.shape
     a = part_pcs[:, :, None].expand(B, P, P, N, 3).reshape(-1, N, 3)
     b = part_pcs[:, None].expand(B, P, P, N, 3).reshape(-1, N, 3)
     dist1, dist2 = chamfer_distance(a.contiguous(), b.contiguous())
-    cd = (thre - (dist1.mean(1) + dist2.mean(1)).view(B, P, P)).clamp_min(0.0)
+    raw = (dist1.mean(1) + dist2.mean(1)).view(B, P, P)
+    cd = (thre - raw).clamp_min(0.0)
     pair = (valids[:, :, None] * valids[:, None, :]).type_as(cd)
-    return (cd * pair).sum([1, 2]) / pair.sum([1, 2])
+    return (cd * pair).sum([1, 2]) / pair.sum([1, 2]), raw
+
+
+def repulsion_supported(part_pcs):
+    """The envelope of csrc/repulsion.hip (include/mpa_hip.h): float32 CUDA clouds [B, P, N, 3] with 1 <= N <= 2048,
+    1 <= P <= 64 and B P P N < 2^31."""
+    from . import repulsion_ref
+    return (part_pcs.is_cuda and part_pcs.dtype == torch.float32 and part_pcs.dim() == 4 and part_pcs.shape[3] == 3
+            and 1 <= part_pcs.shape[2] <= repulsion_ref.MAX_POINTS and 1 <= part_pcs.shape[1] <= repulsion_ref.MAX_PARTS
+            and part_pcs.shape[0] * part_pcs.shape[1] ** 2 * part_pcs.shape[2] < 2 ** 31)
+
+
+class _RepulsionCD(torch.autograd.Function):
+    """The repulsion loss over the unordered pairs of valid parts: two launches forward, one backward (csrc/repulsion.hip).
+    The workspace carries the pair flags and the 16-bit arg-min lists from the forward to the backward."""
+
+    @staticmethod
+    def forward(ctx, part_pcs, valids, thre, ret_cd):
+        B, P, N, _ = part_pcs.shape
+        dev = part_pcs.device
+        nbytes = _lib.query("mpa_repulsion_cd_workspace", B, P, N)[0]
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        loss = torch.empty(B, dtype=torch.float32, device=dev)
+        cd = torch.empty((B, P, P), dtype=torch.float32, device=dev) if ret_cd else None
+        _lib.launch("mpa_repulsion_cd_forward", dev, part_pcs, valids, thre, B, P, N, ws, loss, cd, None,
+                    timer=f"repulsion_cd_forward[{B}x{P}x{N}]")
+        ctx.save_for_backward(part_pcs, valids, ws)
+        ctx.set_materialize_grads(False)
+        if cd is None:
+            return loss, None
+        ctx.mark_non_differentiable(cd)
+        return loss, cd
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_cd):
+        if grad_loss is None:
+            return None, None, None, None
+        part_pcs, valids, ws = ctx.saved_tensors
+        B, P, N, _ = part_pcs.shape
+        grad = torch.empty_like(part_pcs)
+        _lib.launch("mpa_repulsion_cd_backward", part_pcs.device, grad_loss.to(torch.float32).contiguous(), part_pcs, valids,
+                    B, P, N, ws, grad, timer=f"repulsion_cd_backward[{B}x{P}x{N}]")
+        return grad, None, None, None
+
+
+@torch.no_grad()
+def repulsion_cd_search(part_pcs, valids, thre, ret_cd=False, out=None):
+    """What `mpa_repulsion_cd_forward` leaves behind, for tests and tools: a dict with loss [B], flag [B, P (P - 1) / 2]
+    uint8 (0 not searched, 1 searched, 2 hinged), idx1 / idx2 [B, slots, N] int32 (-1 for none; rows of pairs that were not
+    searched are unwritten), dist1 / dist2 [B, slots, N] and, with `ret_cd`, cd [B, P, P].  `out`: a dict of preallocated
+    `loss`, `workspace`, `dists` (and `cd`) tensors to write into, as an earlier call returned them."""
+    if not repulsion_supported(part_pcs):
+        raise ValueError(f"repulsion_cd_search: {tuple(part_pcs.shape)} {part_pcs.dtype} {part_pcs.device.type} clouds are "
+                         "outside csrc/repulsion.hip")
+    import numpy as np
+    B, P, N, _ = part_pcs.shape
+    dev, slots = part_pcs.device, P * (P - 1) // 2
+    nbytes, o_flag, o_idx1, o_idx2 = _lib.query("mpa_repulsion_cd_workspace", B, P, N)
+    out = dict(out or {})
+    ws = out.get("workspace")
+    if ws is None:
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    loss = out.get("loss")
+    if loss is None:
+        loss = torch.empty(B, dtype=torch.float32, device=dev)
+    dists = out.get("dists")
+    if dists is None:
+        dists = torch.empty((B, slots, 2, N), dtype=torch.float32, device=dev)
+    cd = out.get("cd") if ret_cd else None
+    if ret_cd and cd is None:
+        cd = torch.empty((B, P, P), dtype=torch.float32, device=dev)
+    _lib.launch("mpa_repulsion_cd_forward", dev, part_pcs.contiguous(), valids.to(torch.float32).contiguous(),
+                float(np.float32(thre)), B, P, N, ws, loss, cd, dists)
+    lists = lambda off: ws[off:off + 2 * B * slots * N].view(torch.int16).view(B, slots, N).to(torch.int32)
+    res = {"loss": loss, "flag": ws[o_flag:o_flag + B * slots].view(B, slots), "idx1": lists(o_idx1), "idx2": lists(o_idx2),
+           "dist1": dists[:, :, 0], "dist2": dists[:, :, 1], "workspace": ws, "dists": dists}
+    if ret_cd:
+        res["cd"] = cd
+    return res
+
+
+class _RepulsionHost(torch.autograd.Function):
+    """The float32 restatement (repulsion_ref.py) for host tensors."""
+
+    @staticmethod
+    def forward(ctx, part_pcs, valids, thre, ret_cd):
+        from . import repulsion_ref
+        loss, cd, _ = repulsion_ref.repulsion_cd(part_pcs.detach().numpy(), valids.detach().numpy(), thre, prune=not ret_cd)
+        ctx.save_for_backward(part_pcs, valids)
+        ctx.thre, ctx.prune = thre, not ret_cd
+        ctx.set_materialize_grads(False)
+        if not ret_cd:
+            return torch.from_numpy(loss), None
+        cd = torch.from_numpy(cd)
+        ctx.mark_non_differentiable(cd)
+        return torch.from_numpy(loss), cd
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_cd):
+        if grad_loss is None:
+            return None, None, None, None
+        from . import repulsion_ref
+        part_pcs, valids = ctx.saved_tensors
+        grad = repulsion_ref.repulsion_cd_grad(part_pcs.detach().numpy(), valids.detach().numpy(), ctx.thre,
+                                               grad_loss.detach().numpy(), prune=ctx.prune)
+        return torch.from_numpy(grad), None, None, None
+
+
+def repulsion_cd_loss(part_pcs, valids, thre, fused=False, ret_cd=False):
+    """max(0, thre - CD(part_i, part_j)) averaged over the valid pairs of every sample, [B, P, N, 3] posed clouds -> [B]
+    (reference loss.py:205-225): pushes apart parts that sit inside each other.
+
+    fused=False is the reference's composition: the batch expanded to two [B P P, N, 3] tensors and one Chamfer call over
+    all P x P pairs.  fused=True runs csrc/repulsion.hip: one block per unordered pair of valid parts, pairs whose bounding
+    boxes are at least `thre` apart not searched, nothing expanded; the values are those of `repulsion_ref` (the same
+    nearest neighbours as the composition, bit for bit; the sums in another order), the gradient flows to `part_pcs`.
+    Float32 CUDA clouds with N <= 2048 and P <= 64; anything else leaves the kernel with one warning -- CUDA tensors for
+    the composition, host tensors for the numpy restatement.  `ret_cd`: also the Chamfer distances [B, P, P] (no gradient);
+    the fused path writes 0 on the diagonal and for pairs with a padded member, and then searches every valid pair."""
+    if part_pcs.dim() != 4 or part_pcs.shape[-1] != 3 or tuple(valids.shape) != tuple(part_pcs.shape[:2]):
+        raise ValueError(f"repulsion_cd_loss: part_pcs must be [B, P, N, 3] and valids [B, P], got "
+                         f"{tuple(part_pcs.shape)} and {tuple(valids.shape)}")
+    if fused and not repulsion_supported(part_pcs):
+        from .eval_utils import _warn_once
+        from . import repulsion_ref
+        _warn_once("repulsion_cd_loss", f"{tuple(part_pcs.shape)} {part_pcs.dtype} {part_pcs.device.type} clouds are outside "
+                   f"csrc/repulsion.hip (float32 CUDA, at most {repulsion_ref.MAX_POINTS} points per part and "
+                   f"{repulsion_ref.MAX_PARTS} part slots)")
+        if not part_pcs.is_cuda:
+            import numpy as np
+            loss, cd = _RepulsionHost.apply(part_pcs.float(), valids.detach().float(), float(np.float32(thre)), bool(ret_cd))
+            return (loss, cd) if ret_cd else loss
+        fused = False
+    if fused:
+        import numpy as np
+        loss, cd = _RepulsionCD.apply(part_pcs.contiguous(), valids.detach().to(torch.float32).contiguous(),
+                                      float(np.float32(thre)), bool(ret_cd))
+        return (loss, cd) if ret_cd else loss
+    loss, raw = _repulsion_composed(part_pcs, valids, thre)
+    return (loss, raw.detach()) if ret_cd else loss
 
 
 # ---- fused path ------------------------------------------------------------------------------------

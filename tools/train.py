@@ -2,6 +2,7 @@
 
   python tools/train.py --preset pn_transformer_everyday --data-dir data/breaking_bad --data-fn everyday.train.txt \\
       --val-fn everyday.val.txt [--category Bottle] [--epochs 400] [--graph] [--ckpt-dir ckpt] [--resume]
+  python tools/train.py --preset pn_transformer_everyday --repulsion 0.01 1.0 ...   (the opt-in repulsion term: THRE W)
   python tools/train.py --preset lstm_everyday --lstm-draws device --graph ...      (B-LSTM captured: its draws on the device)
   python tools/train.py --preset dgl_partnet_chair --data-dir data/partnet --data-fn Chair.train.npy --val-fn Chair.val.npy
   python tools/train.py --preset pn_transformer_everyday --synthetic --epochs 2
@@ -40,6 +41,9 @@ def parser():
     ap.add_argument("--pointnet2-eval", choices=("library", "fused"), default=None,
                     help="cfg.model.pointnet2_eval: how a pointnet2_ssg encoder evaluates — its library Conv2d / BatchNorm2d "
                          "chain (default) or the fused set-abstraction kernel; other encoders ignore it")
+    ap.add_argument("--repulsion", nargs=2, type=float, default=None, metavar=("THRE", "W"),
+                    help="add the repulsion term: cfg.loss.use_repulsion_loss = True, repulsion_thre = THRE (the Chamfer "
+                         "distance below which a pair of parts is pushed apart), repulsion_loss_w = W; no default exists")
     ap.add_argument("--ckpt-dir", default="")
     ap.add_argument("--resume", action="store_true")
     ap.add_argument("--synthetic", action="store_true")
@@ -103,15 +107,9 @@ def producer(cfg, store, device, seed, train):
                                           device=device)
 
 
-def main(argv=None):
-    args = parse_args(argv)
-    import torch
-    import torch.distributed as dist
-
+def configure(args):
+    """The preset's configuration with the command line's overrides applied."""
     from multi_part_assembly_amd import config
-    from multi_part_assembly_amd.pn_transformer import build_model
-    from multi_part_assembly_amd.sampler import EpochSampler
-    from multi_part_assembly_amd.trainer import Trainer
 
     cfg = getattr(config, args.preset)()
     if args.epochs > 0:
@@ -126,6 +124,22 @@ def main(argv=None):
         cfg.model.encoder = args.encoder
     if args.pointnet2_eval is not None:
         cfg.model.pointnet2_eval = args.pointnet2_eval  # (the validation passes; training is the library chain either way)
+    if args.repulsion is not None:
+        cfg.loss.use_repulsion_loss = True
+        cfg.loss.repulsion_thre, cfg.loss.repulsion_loss_w = args.repulsion
+    return cfg
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    import torch
+    import torch.distributed as dist
+
+    from multi_part_assembly_amd.pn_transformer import build_model
+    from multi_part_assembly_amd.sampler import EpochSampler
+    from multi_part_assembly_amd.trainer import Trainer
+
+    cfg = configure(args)
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", 1), ("RANK", 0), ("LOCAL_RANK", 0)))
     device = torch.device("cuda", local)
     torch.cuda.set_device(device)
