@@ -2,7 +2,12 @@
 """Benchmark of the hot path: one full training step (forward + losses + backward + gradient all-reduce + fused
 Adam) on synthetic part clouds, B = 32 per GPU, P = 20, N = 1000 (weak scaling over GPUs).
 
-    python bench.py [--gpus N --steps K --warmup W] [--config c1|c2|c3|c4|c5 | global_partnet|pn_transformer|dgl_dgcnn|rgl_net_dgcnn]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--config c1|c2|c3|c4|c5 | global_partnet|pn_transformer|dgl_dgcnn|rgl_net_dgcnn]
+
+A plain run does what the headline figure needs and nothing else: set-up, W warm-up steps, the K timed steps, the dump of
+`--dump-outputs`, the result line.  `--full` adds every leg that takes runs of its own after the timed region - the per-phase
+pass behind `kernels` / `kernel_table` (and behind the `roofline` of a `--graph` run), `cpu_baseline`, `chamfer_standalone`, and with several ranks `collectives` - and
+changes nothing of the timed region: `value`, `ms_per_step` and the dumped arrays are measured the same way either way.
 
 With --gpus N > 1 and no torch.distributed environment the script re-launches itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (one rank per GPU over
@@ -22,12 +27,14 @@ steps (a generation-2 collection inside K steps of 3 ms was measured as +1.6 ms 
 
 `roofline` describes the dominant kernel of the workload — c1/c2/c4: the whole-shape Chamfer search of the fused
 loss; c3/c5: the kNN graph kernel of the DGCNN encoder — timed per launch with HIP events that the library records
-around it on its launch stream inside the timed region.  It carries the mandated HBM comparison (algorithmic bytes of
+around it on its launch stream inside the timed region, so a plain eager run has it too; a `--graph` replay records no
+events, its `roofline` comes from the eager per-phase pass and needs `--full` (a plain `--graph` line carries `"roofline":
+null` and empty `kernels`).  It carries the mandated HBM comparison (algorithmic bytes of
 SURVEY.md §8d per launch / time / 8 TB/s) AND the bound that actually binds (`binding`), plus a per-kernel table
-(`kernel_table`) with MFMA / VALU / HBM fractions of the other large kernels.  `cpu_baseline` is the oracle's
+(`kernel_table`, `--full`) with MFMA / VALU / HBM fractions of the other large kernels.  `cpu_baseline` (`--full`) is the oracle's
 reference-equivalent PyTorch-CPU step of the SAME workload timed on this host (rank 0, N = 1) on a bounded sample: c1 at
 full size, c2 / c4 at B = 4, c3 / c5 at B = 2 (scaled linearly in B, labelled), on all physical cores and on one thread.
-With several ranks the line carries `collectives`: bytes of each gradient bucket, its stand-alone all-reduce time, the step
+With several ranks and `--full` the line carries `collectives`: bytes of each gradient bucket, its stand-alone all-reduce time, the step
 time without any collective, and the fraction of the collective time that backward hid (`overlap_frac`).
 `--self-check N` appends N more timed steps and reports whether the K-step mean holds over them.
 `--dump-outputs DIR` writes what the last timed step computed (rank 0) as DIR/<name>.npy, float32: `loss` (what
@@ -68,11 +75,14 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="c2", choices=["c1", "c2", "c3", "c4", "c5"] + sorted(CONFIG_ALIASES))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the per-phase pass (`kernels`, "
+                         "`kernel_table`), `cpu_baseline`, `chamfer_standalone`, and with several ranks `collectives`")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the `cpu_baseline` leg")
     ap.add_argument("--batches", type=int, default=N_BATCHES,
                     help="distinct synthetic batches rotated through the steps (1: one static batch, as rounds 1-3 did)")
     ap.add_argument("--no-chamfer-standalone", action="store_true",
-                    help="skip the stand-alone timing of the drop-in Chamfer operator (the `chamfer_standalone` object)")
+                    help="with --full: skip the stand-alone timing of the drop-in Chamfer operator (the `chamfer_standalone` object)")
     ap.add_argument("--graph", action="store_true",
                     help="replay the step as one HIP graph (default: eager launches; see trainer.py)")
     ap.add_argument("--eager", action="store_true", help="(the default; accepted for symmetry)")
@@ -561,7 +571,7 @@ def main():
     fence()
     # Inside the timed region only the roofline kernel is bracketed by HIP events (recorded by the library right around
     # it: two records per step); the per-phase table of every entry point (~60 records per step, 0.1 ms of gaps in a
-    # 2.7 ms step) is taken in a second, untimed pass over the same K steps.
+    # 2.7 ms step) is taken in a second, untimed pass over the same K steps, which only a --full run makes.
     roof_timer = _lib.KernelTimer(only=("shape_search_kernel", "dgcnn_knn") + (("chamfer_forward[",) if args.config == "c1" else ()))
     if not use_graph:
         _lib.KernelTimer.active = roof_timer
@@ -590,7 +600,7 @@ def main():
         self_check = {"steps": args.self_check, "ms_per_step": long_ms, "ratio_to_timed_mean": long_ms / short_ms,
                       "holds": abs(long_ms / short_ms - 1.0) < 0.05}
     collectives = None
-    if distributed:
+    if distributed and args.full:
         from multi_part_assembly_amd.dp import measure_collectives
         collectives = measure_collectives(trainer, batch, steps=min(args.steps, 10), fence=fence)
         if collectives is not None and collectives["local_ms_per_step"] is not None:
@@ -600,7 +610,7 @@ def main():
             collectives["overlap_frac"] = (max(0.0, min(1.0, hidden / sum(collectives["allreduce_ms"])))
                                            if sum(collectives["allreduce_ms"]) > 0 else None)
     timer = _lib.KernelTimer()
-    if rank == 0 and not distributed:  # (with several ranks the backward hooks of this pass would start collectives)
+    if args.full and rank == 0 and not distributed:  # (with several ranks the backward hooks of this pass would start collectives)
         # per-phase timing pass (not timed): the same K steps launched eagerly with every entry point instrumented
         _lib.KernelTimer.active = timer
         for i in range(args.steps):
@@ -623,8 +633,8 @@ def main():
         N = POINTS
         timing = ("HIP events recorded by libmpa_hip.so right before/after the kernel on its launch stream, "
                   + ("in an eager pass over the same K steps right after the timed graph replays"
-                     if use_graph else "inside the timed region (the other entries of `kernels` come from a second, "
-                     "untimed pass over the same K steps with every entry point instrumented)"))
+                     if use_graph else "inside the timed region (with --full the other entries of `kernels` come from a "
+                     "second, untimed pass over the same K steps with every entry point instrumented)"))
         roofline = None
         if cfg.model.encoder == "dgcnn":
             # kNN graph of the first EdgeConv stage (C = 3): SURVEY.md §8d — n*N*(4C read + 20*8 index write)
@@ -775,12 +785,14 @@ def main():
             "final_loss": final_loss,
             "kernels": kernels,
             "roofline": roofline,
-            "kernel_table": kernel_table(kernels, valid_parts, cfg, B, P),
+            "full": args.full,
         }
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(args.config, args.cpu_batch, dev)
-        if world == 1 and not args.no_chamfer_standalone:
-            line["chamfer_standalone"] = chamfer_standalone(dev)
+        if args.full:
+            line["kernel_table"] = kernel_table(kernels, valid_parts, cfg, B, P)
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(args.config, args.cpu_batch, dev)
+            if world == 1 and not args.no_chamfer_standalone:
+                line["chamfer_standalone"] = chamfer_standalone(dev)
         if self_check is not None:
             line["self_check"] = self_check
         if collectives is not None:

@@ -1,6 +1,7 @@
 """The bench contract (task statement §4, bench.py's docstring) checked on a short run: ONE JSON line on stdout with the
 mandated keys, the `roofline` object of the dominant kernel measured with HIP events over exactly the K timed steps, the
-bounded CPU baseline — and the KernelTimer scoping that keeps every other event out of the timed region.
+bounded CPU baseline and the other legs of a `--full` run, their absence from a plain one — and the KernelTimer scoping
+that keeps every other event out of the timed region.
 
 Collected LAST (file name + the hook in conftest.py) so that no bench run can stop `pytest -x` before a parity test, and
 every wall-clock figure here is RECORDED (printed into the run's log), never asserted: a stopwatch must not be able to
@@ -26,8 +27,40 @@ def _run(*flags):
     return json.loads(lines[0])
 
 
+def test_plain_run_carries_the_headline_and_no_leg_of_its_own(cuda_device):
+    """Without `--full` the line has the headline keys and the roofline kernel's in-region measurement (its events are
+    part of the timed steps either way), and nothing that takes a run of its own after the timed region."""
+    d = _run("--gpus", "1", "--steps", "3", "--warmup", "1")
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "roofline", "final_loss"):
+        assert k in d, k
+    assert d["full"] is False and d["metric"] == "train-step parts/sec (BxP) at N=1000 pts" and d["unit"] == "parts/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32" and d["steps"] == 3 and d["warmup"] == 1
+    assert abs(d["value"] - 640.0 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    for k in ("cpu_baseline", "chamfer_standalone", "kernel_table", "collectives", "self_check"):
+        assert k not in d, k
+    assert d["kernels"] and all(k.startswith("shape_search_kernel[") for k in d["kernels"])  # no per-phase pass ran
+    r = d["roofline"]
+    assert r["launches"] == 3 and 0.0 < r["avg_launch_ms"] < d["ms_per_step"] and r["whole_phase_avg_ms"] is None
+
+
+@pytest.mark.parametrize("full", [False, True])
+def test_graph_replay_has_its_roofline_only_in_a_full_run(cuda_device, full):
+    """A graph replay records no events inside the timed region, so the roofline of a `--graph` run comes from the eager
+    per-phase pass: present with `--full` (timed over that pass's K steps), null in a plain run, whose headline stands."""
+    d = _run("--steps", "3", "--warmup", "1", "--graph",
+             *(("--full", "--no-cpu-baseline", "--no-chamfer-standalone") if full else ()))
+    assert d["config"]["launch"] == "hip-graph replay" and d["full"] is full
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 640.0 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    if full:
+        assert d["roofline"]["launches"] == 3 and "eager pass" in d["roofline"]["timing"] and "kernel_table" in d
+    else:
+        assert d["roofline"] is None and d["kernels"] == {} and "kernel_table" not in d
+
+
 def test_bench_line_has_the_contract_keys(cuda_device):
-    d = _run("--steps", "3", "--warmup", "1", "--cpu-batch", "1")
+    d = _run("--full", "--steps", "3", "--warmup", "1", "--cpu-batch", "1")
+    assert d["full"] is True
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -66,7 +99,7 @@ def test_one_stdout_line_under_the_drivers_launcher(cuda_device):
     RCCL, whose version banner goes to stdout when the first communicator comes up — the bench keeps it off ITS stdout."""
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                           "--master-addr", "127.0.0.1", "--master-port", "29617", os.path.join(ROOT, "bench.py"),
-                          "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-chamfer-standalone"],
+                          "--gpus", "1", "--steps", "3", "--warmup", "1"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -82,7 +115,7 @@ def test_two_rank_branch_runs_on_one_gpu_over_gloo(cuda_device):
     env = dict(os.environ, MPA_DP_BACKEND="gloo")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", "29631", os.path.join(ROOT, "bench.py"),
-                          "--gpus", "2", "--steps", "3", "--warmup", "2"],
+                          "--gpus", "2", "--steps", "3", "--warmup", "2", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -114,7 +147,7 @@ def test_other_configs_hold_their_committed_step_time(cuda_device, capsys, tag, 
     """BASELINE.json configs[2] / configs[4] and the bf16 variant line, 10 timed steps each under the driver's own GPU
     test run: the JSON line is printed (so the run's log witnesses the number) next to the builder-run line committed
     under profiles/ and their ratio.  Only the structure of the line is asserted."""
-    d = _run("--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-chamfer-standalone", *flags)
+    d = _run("--steps", "10", "--warmup", "3", *flags)
     want, src = _committed_ms(tag)
     with capsys.disabled():
         slim = {k: d[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "ms_per_step", "dtype")}
@@ -137,7 +170,7 @@ def test_other_configs_hold_their_committed_step_time(cuda_device, capsys, tag, 
 def test_plumbing_config_with_its_cpu_baseline_and_self_check(cuda_device, capsys):
     """configs[0] (B-Global, semantic flags, P = 2, B = 4) with its full-size CPU baseline on all physical cores.  The
     step time and CPU rate are printed, not judged."""
-    d = _run("--config", "c1", "--steps", "10", "--warmup", "5", "--no-chamfer-standalone")
+    d = _run("--full", "--config", "c1", "--steps", "10", "--warmup", "5", "--no-chamfer-standalone")
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["value"] > 0 and c["cores"] >= 1 and "B=4," in c["sample"]
     r = d["roofline"]  # the whole-shape search of the fused loss (round 6: semantic models use it too): 5 min-of-N samples per step
@@ -151,7 +184,7 @@ def test_self_check_leg_reports_the_ratio(cuda_device, capsys):
     """`--self-check M` on the headline config (c2, device-bound) after 20 warm-up steps: the leg runs M further steps
     and reports their mean against the K timed ones.  The ratio is printed for the record; only its presence and the
     step count are asserted."""
-    d = _run("--steps", "20", "--warmup", "20", "--self-check", "40", "--no-cpu-baseline", "--no-chamfer-standalone")
+    d = _run("--steps", "20", "--warmup", "20", "--self-check", "40")
     sc = d["self_check"]
     assert sc["steps"] == 40 and sc["ms_per_step"] > 0 and sc["ratio_to_timed_mean"] > 0
     with capsys.disabled():
@@ -163,7 +196,7 @@ def test_dump_outputs_of_the_last_timed_step(cuda_device, tmp_path):
     the one the line reports, and two runs with the same arguments dump the same outputs (same seeded inputs and weights;
     compared by relative norm: the kernels' float atomics leave the order of some sums open)."""
     import numpy as np
-    flags = ("--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-chamfer-standalone", "--dump-outputs")
+    flags = ("--steps", "2", "--warmup", "1", "--dump-outputs")
     runs = []
     for r in ("a", "b"):
         d = _run(*flags, str(tmp_path / r))

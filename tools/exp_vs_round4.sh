@@ -9,6 +9,6 @@ print(round(d['ms_per_step'],4), 'ms/step | roofline', round(r.get('avg_launch_m
 for cfg in "$@"; do
   for rep in 1 2 3; do
     echo -n "$cfg r04 : "; (cd $R/build_variants/r04_tree && python bench.py --config $cfg --no-cpu-baseline --no-chamfer-standalone 2>/dev/null | line)
-    echo -n "$cfg HEAD: "; (cd $R && python bench.py --config $cfg --no-cpu-baseline --no-chamfer-standalone 2>/dev/null | line)
+    echo -n "$cfg HEAD: "; (cd $R && python bench.py --full --config $cfg --no-cpu-baseline --no-chamfer-standalone 2>/dev/null | line)
   done
 done

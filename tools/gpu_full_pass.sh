@@ -9,7 +9,7 @@ mkdir -p $O
 if [ "${3:-1}" = "1" ]; then
   timeout 1500 python -m pytest tests -q -m gpu 2>&1 | grep -E "passed|failed|Error|error" | tail -5 > $O/pytest_gpu.txt
 fi
-python bench.py --config $CFG > $O/bench.json 2> $O/bench.err
+python bench.py --full --config $CFG > $O/bench.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o st -- python $R/bench.py --config $CFG --no-cpu-baseline > $O/bench_under_rocprof.json 2>/dev/null

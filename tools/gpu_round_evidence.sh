@@ -4,10 +4,12 @@
 #   the SQ counter passes of c2 / c3 / c5, the HIP-graph lines, the stand-alone Chamfer operator profile.
 R=$PWD
 for c in c2 c3 c5 c1; do bash tools/gpu_full_pass.sh $c full_$c 0; cd $R; done
-mkdir -p gpurun_out/full_c2_bf16
-python bench.py --dtype bf16 --no-chamfer-standalone > gpurun_out/full_c2_bf16/bench.json 2> gpurun_out/full_c2_bf16/bench.err
+O=$(dirname "$(find $R -maxdepth 2 -type d -name full_c2 | head -1)")  # the folder tools/gpu_full_pass.sh just wrote full_c2/ under
+mkdir -p $O/full_c2_bf16
+python bench.py --full --dtype bf16 --no-chamfer-standalone > $O/full_c2_bf16/bench.json 2> $O/full_c2_bf16/bench.err
 for c in c2 c3 c5; do
-  python bench.py --config $c --graph --no-cpu-baseline --no-chamfer-standalone > gpurun_out/full_$c/bench_graph.json 2>/dev/null
+  # (--full: a graph replay records no events in the timed region, its roofline comes from the eager per-phase pass)
+  python bench.py --full --config $c --graph --no-cpu-baseline --no-chamfer-standalone > $O/full_$c/bench_graph.json 2>/dev/null
   bash tools/gpu_pmc_sq.sh $c full_$c; cd $R
 done
 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-chamfer-standalone > gpurun_out/full_c2/bench_driver_protocol.json 2>/dev/null

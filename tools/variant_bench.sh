@@ -8,7 +8,7 @@ cp multi_part_assembly_amd/libmpa_hip.so /tmp/orig.so
 for v in /tmp/orig.so $R/build_variants/*.so; do
   cp $v $R/multi_part_assembly_amd/libmpa_hip.so
   echo "== $(basename $v)" >> $R/gpurun_out/variant_bench.txt
-  python bench.py --config $CFG --no-cpu-baseline 2>/dev/null | python -c "
+  python bench.py --full --config $CFG --no-cpu-baseline 2>/dev/null | python -c "
 import json, sys, re
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('  ms/step', round(d['ms_per_step'], 3))
