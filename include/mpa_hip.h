@@ -201,7 +201,13 @@ int mpa_assembly_loss_forward_ordered(const float* part_pcs, const float* valids
                                       const float* order, int search, float* float_ws, int32_t* int_ws, float* losses,
                                       void* const* events, void* stream);
 /* grad_losses [5,B] = d(objective)/d(losses); writes grad_quat [B,P,4] and grad_trans [B,P,3] of the
- * PREDICTED pose.  Deterministic (no atomics). */
+ * PREDICTED pose.  Deterministic (no atomics).  Every row is written.  A padded part takes the gradient the reference gives
+ * it: exactly zero unless its fill point R (1e3,1e3,1e3) + t is the nearest predicted point of some valid ground-truth point
+ * of its sample (whole-shape term, GT -> prediction direction), and then that term's gradient through the fill point, to
+ * its rotation and its translation.  A sample without a valid part: the loss terms that are means over its valid parts are NaN (0 / 0, as
+ * the reference gives) -- all but transform_pt_cd_loss with training != 0, which divides by P N and is 0 -- and the
+ * gradients of all its parts are exactly zero, whatever grad_losses holds for it.  A stored index of -1
+ * (no candidate below 1e32) contributes no gradient. */
 int mpa_assembly_loss_backward(const float* grad_losses, const float* part_pcs, const float* valids,
                                const float* quat_pred, const float* trans_pred, const float* quat_gt,
                                const float* trans_gt, int64_t B, int64_t P, int64_t N, int training,
@@ -784,7 +790,8 @@ int mpa_partnet_gather_batch(const float* pcs, const float* poses, const float* 
 int mpa_quat_to_rmat(const float* quat, int64_t count, float* rmat, void* stream);
 
 /* The fused assembly loss (mpa_assembly_loss_*) with rotation matrices: rmat_pred / rmat_gt [B,P,3,3] row-major in place
- * of the quaternions, same workspace (mpa_assembly_loss_workspace), same searches and routes, same outputs.  The clouds
+ * of the quaternions, same workspace (mpa_assembly_loss_workspace), same searches and routes, same outputs.  Padded
+ * parts and samples without a valid part take the gradients documented at mpa_assembly_loss_backward.  The clouds
  * are transformed as in mpa_pose_apply_rmat_forward; rot_loss = mean over the nine entries of (I - R1^T R2)^2
  * (utils/loss.py:76-82); the backward writes grad_rmat [B,P,3,3] as fixed-order sums dL/dR = sum g p^T plus the closed
  * form of rot_loss (no atomics, deterministic). */
