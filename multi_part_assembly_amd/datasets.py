@@ -25,6 +25,12 @@ the same keys, shapes and dtypes, batched `[B, ...]` and already on the device.
 * Device-resident PartNet data: `PartNetStore` reads a split once and packs it into flat arrays; `DevicePartNetProducer.batch`
   gathers a batch from them and derives every label in ONE launch (`mpa_partnet_gather_batch`, csrc/partnet_gather.hip).
   Same `data_dict` as `PartNetBatchProducer`, which stays the yardstick.
+
+What the four producers and the two stores have in common is written once, ahead of them: `_hip_device` (the "HIP device
+only" refusal and the resolved device index), `_check_data_keys`, `_geometry_batch` (the geometry `data_dict` and its key
+order, for all three geometry paths), `_StatusWord` (the device word behind `.check()`) and `_ResidentStore` (`.npz`
+writer and reader, byte limit, one upload per array and device); `read_partnet_split` is the one reader of a PartNet
+split.  `DeviceGeometryProducer` has one launch path (`_run`) fed by a host and a device builder of its slot tables.
 """
 from __future__ import annotations
 
@@ -159,6 +165,128 @@ def _to_device(arr: np.ndarray, device) -> torch.Tensor:
     return t
 
 
+# ---- what the producers and the stores share ----------------------------------------------------------------------
+def _hip_device(device, who):
+    """`device` with its index resolved; RuntimeError, in the name of `who` (the caller and what it runs there: "MeshStore:
+    the mesh sampler"), unless it is a HIP device."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"{who} runs on the HIP device only (there is no CPU fallback)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+def _check_data_keys(allowed, data_keys):
+    """The reference's refusal of a data key it does not know (geometry_data.py:189-201, partnet_data.py:210-241)."""
+    for key in data_keys:
+        if key not in allowed:
+            raise ValueError(f"ERROR: unknown data {key}")
+
+
+def _geometry_batch(part_pcs, part_quat, part_trans, part_valids, part_ids, data_id, data_keys, contact_thre=0.01):
+    """The geometry `data_dict` from its device tensors, in the one key order every geometry producer returns.
+    `part_ids` may be None where `data_keys` does not ask for it."""
+    (B, P), dev = part_valids.shape, part_valids.device
+    out = {
+        "part_pcs": part_pcs,
+        "part_quat": part_quat,
+        "part_trans": part_trans,
+        "part_valids": part_valids,
+        "data_id": data_id,
+        # zero-width labels keep the semantic models' concatenations valid (geometry_data.py:181-187)
+        "instance_label": torch.zeros((B, P, 0), dtype=torch.float32, device=dev),
+        "part_label": torch.zeros((B, P, 0), dtype=torch.float32, device=dev),
+    }
+    if "part_ids" in data_keys:
+        out["part_ids"] = part_ids
+    if "valid_matrix" in data_keys:
+        out["valid_matrix"] = part_valids[:, :, None] * part_valids[:, None, :]
+    if "contact_points" in data_keys:  # the table of the batch's own clouds and ground-truth poses
+        from .contacts import contact_points
+        out["contact_points"] = contact_points(part_pcs, part_valids, part_quat, part_trans, thre=contact_thre)
+    return out
+
+
+class _StatusWord:
+    """The int32 device word through which a kernel reports what it could not read.  It is allocated at the first launch
+    that needs it — outside a graph capture, hence the rule to call `.batch()` once before capturing — and `check` reads
+    it, clears it and raises."""
+
+    def __init__(self):
+        self.word = None
+
+    def on(self, device):
+        if self.word is None:
+            self.word = torch.zeros(1, dtype=torch.int32, device=device)
+        return self.word
+
+    def check(self, template, what):
+        """RuntimeError `template.format(what[code])` if the word holds a code; synchronises."""
+        if self.word is None:
+            return
+        code = int(self.word.item())
+        if code:
+            self.word.zero_()
+            raise RuntimeError(template.format(what.get(code, f"status {code}")))
+
+
+def _check_store_bytes(nbytes, max_bytes, who, noun):
+    if max_bytes is not None and nbytes > max_bytes:
+        raise ValueError(f"{who}: {nbytes} bytes of {noun} data exceed max_bytes={max_bytes}")
+
+
+class _ResidentStore:
+    """What `MeshStore` and `PartNetStore` share.  A store names its host arrays in `ARRAYS` (`shape_part_off` among them)
+    and those that may be None in `OPTIONAL`; `_meta` / `_from_meta` carry whatever else its .npz holds."""
+
+    ARRAYS, OPTIONAL = (), ()
+
+    def _names(self):
+        return self.ARRAYS + tuple(n for n in self.OPTIONAL if getattr(self, n) is not None)
+
+    @property
+    def nbytes(self):
+        return sum(getattr(self, n).nbytes for n in self._names())
+
+    @property
+    def num_shapes(self):
+        return len(self.shape_part_off) - 1
+
+    def __len__(self):
+        return self.num_shapes
+
+    def _meta(self):
+        return {}
+
+    @staticmethod
+    def _from_meta(z):
+        return {}
+
+    def save(self, path):
+        """One .npz of plain arrays (no pickle): the per-file parse is paid once per dataset."""
+        with open(path, "wb") as fh:
+            np.savez(fh, **{n: getattr(self, n) for n in self._names()}, **self._meta())
+
+    @classmethod
+    def load(cls, path, max_bytes=None):
+        with np.load(path, allow_pickle=False) as z:
+            arrays = [z[n] for n in cls.ARRAYS] + [z[n] if n in z.files else None for n in cls.OPTIONAL]
+            return cls(*arrays, **cls._from_meta(z), max_bytes=max_bytes)
+
+    def _on_device(self, device, names):
+        """The arrays `names` as tensors on `device` (resolved by `_hip_device`), each uploaded at its first use there;
+        None for an optional array the store does not hold."""
+        cache = self._device.setdefault(device, {})  # `_device`: {} from the store's __init__
+        if names not in cache:  # the first call for this tuple of names: later ones are this one lookup
+            for n in names:
+                if n not in cache:
+                    a = getattr(self, n)
+                    cache[n] = None if a is None else torch.from_numpy(a).to(device)
+            cache[names] = tuple(cache[n] for n in names)
+        return cache[names]
+
+
 class GeometryBatchProducer:
     """`GeometryPartDataset` + default collate, one HIP launch per batch for the per-part transforms."""
 
@@ -169,9 +297,7 @@ class GeometryBatchProducer:
         self.max_num_part = max_num_part
         self.rot_range = rot_range
         self.data_keys = tuple(data_keys)
-        for key in self.data_keys:  # geometry_data.py:189-201
-            if key not in ("part_ids", "valid_matrix"):
-                raise ValueError(f"ERROR: unknown data {key}")
+        _check_data_keys(("part_ids", "valid_matrix"), self.data_keys)
         self.device = torch.device(device)
         self.sampler = sampler or _no_sampler
         self.data_list = list(data_list)
@@ -215,33 +341,17 @@ class GeometryBatchProducer:
                 rot[b, i] = rot_mat.reshape(9)
                 quat[b, i] = q
                 perm[b, i] = self._draw_order(N)
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("GeometryBatchProducer: the transform runs on the HIP device only")
+        dev = _hip_device(self.device, "GeometryBatchProducer: the transform")
         with torch.cuda.device(dev):
             d_raw, d_rot, d_perm, d_val = (_to_device(a, dev) for a in (raw, rot, perm, valids))
             part_pcs = torch.empty((B, P, N, 3), dtype=torch.float32, device=dev)
             part_trans = torch.empty((B, P, 3), dtype=torch.float32, device=dev)
             _lib.launch("mpa_part_batch_transform", dev, d_raw, d_rot, d_perm, d_val, B * P, N, part_pcs, part_trans)
-        out = {
-            "part_pcs": part_pcs,
-            "part_quat": _to_device(quat, dev),
-            "part_trans": part_trans,
-            "part_valids": d_val,
-            "data_id": torch.as_tensor(list(range(B)) if data_ids is None else list(data_ids), dtype=torch.int64),
-            # zero-width labels keep the semantic models' concatenations valid (geometry_data.py:181-187)
-            "instance_label": torch.zeros((B, P, 0), dtype=torch.float32, device=dev),
-            "part_label": torch.zeros((B, P, 0), dtype=torch.float32, device=dev),
-        }
-        num_parts = valids.sum(1).astype(np.int64)
+        part_ids = None
         if "part_ids" in self.data_keys:
-            ids = np.zeros((B, P), dtype=np.float32)
-            for b, p in enumerate(num_parts):
-                ids[b, :p] = np.arange(p)
-            out["part_ids"] = _to_device(ids, dev)
-        if "valid_matrix" in self.data_keys:
-            out["valid_matrix"] = d_val[:, :, None] * d_val[:, None, :]
-        return out
+            part_ids = _to_device(np.arange(P, dtype=np.float32)[None] * valids, dev)  # 0..p-1, 0 in padded slots
+        data_id = torch.as_tensor(list(range(B)) if data_ids is None else list(data_ids), dtype=torch.int64)
+        return _geometry_batch(part_pcs, _to_device(quat, dev), part_trans, d_val, part_ids, data_id, self.data_keys)
 
     def batch(self, indices: Sequence[int]) -> dict:
         """Sample the fracture folders `data_list[i]` with the configured sampler and produce the batch."""
@@ -249,7 +359,7 @@ class GeometryBatchProducer:
 
 
 # ---- device-resident meshes ---------------------------------------------------------------------------------------
-class MeshStore:
+class MeshStore(_ResidentStore):
     """Every part mesh of a list of shapes, parsed once and packed into four flat arrays the device sampler reads
     (csrc/mesh_sample.hip):
 
@@ -261,7 +371,9 @@ class MeshStore:
     float64 like the reference pipeline up to its final cast: 80 B per face, `nbytes` in total; with `max_bytes` a store
     that would be larger raises instead of exhausting device memory (stores larger than the device are out of scope).
     Zero-area faces inside a part stay and are never picked (`searchsorted`), except a degenerate FIRST face at a pick of
-    exactly 0.  The arrays live on the host; `device_arrays(device)` uploads them once per device."""
+    exactly 0.  The arrays live on the host; each is uploaded once per device, when a batch first needs it there."""
+
+    ARRAYS = ("tri", "cum_area", "part_face_off", "shape_part_off")
 
     def __init__(self, tri, cum_area, part_face_off, shape_part_off, max_bytes=None):
         self.tri = np.ascontiguousarray(tri, dtype=np.float64).reshape(-1, 9)
@@ -276,24 +388,12 @@ class MeshStore:
         last = self.cum_area[pf[1:] - 1]
         if not (np.isfinite(last) & (last > 0.0)).all():
             raise ValueError("MeshStore: a part with zero (or non-finite) total area cannot be sampled")
-        _check_store_bytes(self.nbytes, max_bytes)
+        _check_store_bytes(self.nbytes, max_bytes, "MeshStore", "mesh")
         self._device = {}
-        self._device_off = {}
-
-    @property
-    def nbytes(self):
-        return self.tri.nbytes + self.cum_area.nbytes + self.part_face_off.nbytes + self.shape_part_off.nbytes
-
-    @property
-    def num_shapes(self):
-        return len(self.shape_part_off) - 1
 
     @property
     def num_parts(self):
         return len(self.part_face_off) - 1
-
-    def __len__(self):
-        return self.num_shapes
 
     @classmethod
     def from_arrays(cls, shapes, min_num_part=2, max_num_part=20, max_bytes=None):
@@ -301,7 +401,7 @@ class MeshStore:
         shapes = [list(parts) for parts in shapes]
         faces_total = sum(len(f) for parts in shapes for _, f in parts)
         parts_total = sum(len(parts) for parts in shapes)
-        _check_store_bytes(80 * faces_total + 8 * (parts_total + 1) + 8 * (len(shapes) + 1), max_bytes)
+        _check_store_bytes(80 * faces_total + 8 * (parts_total + 1) + 8 * (len(shapes) + 1), max_bytes, "MeshStore", "mesh")
         tri, cum, pf, sp = [], [], [0], [0]
         for s, parts in enumerate(shapes):
             if not min_num_part <= len(parts) <= max_num_part:
@@ -337,45 +437,14 @@ class MeshStore:
             shapes.append([load_obj(os.path.join(folder, name)) for name in mesh_files])
         return cls.from_arrays(shapes, min_num_part, max_num_part, max_bytes)
 
-    def save(self, path):
-        """One .npz with the four arrays: the per-part parse is paid once per dataset."""
-        with open(path, "wb") as fh:
-            np.savez(fh, tri=self.tri, cum_area=self.cum_area, part_face_off=self.part_face_off,
-                     shape_part_off=self.shape_part_off)
-
-    @classmethod
-    def load(cls, path, max_bytes=None):
-        with np.load(path) as z:
-            return cls(z["tri"], z["cum_area"], z["part_face_off"], z["shape_part_off"], max_bytes=max_bytes)
-
     def device_arrays(self, device):
         """(tri, cum_area, part_face_off) as tensors on `device`, uploaded at the first call."""
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("MeshStore: the mesh sampler runs on the HIP device only (there is no CPU fallback)")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        if device not in self._device:
-            self._device[device] = tuple(torch.from_numpy(a).to(device)
-                                         for a in (self.tri, self.cum_area, self.part_face_off))
-        return self._device[device]
+        device = _hip_device(device, "MeshStore: the mesh sampler")
+        return self._on_device(device, ("tri", "cum_area", "part_face_off"))
 
     def device_shape_part_off(self, device):
         """`shape_part_off` on `device`, uploaded at the first call: what builds a batch's slot table from device indices."""
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("MeshStore: the mesh sampler runs on the HIP device only (there is no CPU fallback)")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        if device not in self._device_off:
-            self._device_off[device] = torch.from_numpy(self.shape_part_off).to(device)
-        return self._device_off[device]
-
-
-def _check_store_bytes(nbytes, max_bytes, what="MeshStore"):
-    if max_bytes is not None and nbytes > max_bytes:
-        raise ValueError(f"{what}: {nbytes} bytes of {'mesh' if what == 'MeshStore' else 'part'} data exceed "
-                         f"max_bytes={max_bytes}")
+        return self._on_device(_hip_device(device, "MeshStore: the mesh sampler"), ("shape_part_off",))[0]
 
 
 MAX_DEVICE_SAMPLE_POINTS = 2048  # the sampled float64 cloud of a part lives in LDS (csrc/mesh_sample.hip)
@@ -410,22 +479,13 @@ class DeviceGeometryProducer:
         self.num_points, self.min_num_part, self.max_num_part = num_points, min_num_part, max_num_part
         self.rot_range = float(rot_range)
         self.data_keys = tuple(data_keys)
-        for key in self.data_keys:
-            if key not in ("part_ids", "valid_matrix", "contact_points"):
-                raise ValueError(f"ERROR: unknown data {key}")
+        _check_data_keys(("part_ids", "valid_matrix", "contact_points"), self.data_keys)
         self.contact_thre = float(contact_thre)
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.device = torch.device(device)
         self.shuffle_parts = shuffle_parts
         self.batch_counter = 0  # the default `batch_counter` of the next batch() call
-        self._status = None     # device word of the device-index path (csrc/mesh_sample.hip, mesh_slot_table)
-
-    def _add_contacts(self, out):
-        """The `contact_points` entry of a finished batch: the table of its own clouds and ground-truth poses."""
-        if "contact_points" in self.data_keys:
-            from .contacts import contact_points
-            out["contact_points"] = contact_points(out["part_pcs"], out["part_valids"], out["part_quat"], out["part_trans"],
-                                                   thre=self.contact_thre)
+        self._status = _StatusWord()  # of the device-index path (csrc/mesh_sample.hip, mesh_slot_table)
 
     def __len__(self):
         return self.store.num_shapes
@@ -459,115 +519,74 @@ class DeviceGeometryProducer:
                                "in every call, so the table would not describe any batch")
         return self._slots(indices)[0]
 
-    def _run(self, indices, stream_ids=None, uniforms=None, rot=None, perm=None, quat=None, return_raw=False):
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("DeviceGeometryProducer: the mesh sampler runs on the HIP device only "
-                               "(there is no CPU fallback)")
-        indices = list(indices)
+    def _host_tables(self, dev, indices, stream_ids):
+        """The [2, B, P] int64 (slot_part, stream) and float32 (valids, part ids) tables of the host sequence `indices`,
+        filled on the host in one pinned buffer and sent in one asynchronous copy."""
         slot, valid = self._slots(indices)
-        B, P, N = len(indices), self.max_num_part, self.num_points
+        B, P = len(indices), self.max_num_part
         M = B * P
-        replay = uniforms is not None
-        with torch.cuda.device(dev):
-            tri, cum, pf = self.store.device_arrays(dev)
-            # one pinned buffer, one asynchronous copy: int64 [2, M] (slot_part, stream) | float32 [2, M] (valids, ids)
-            host = torch.empty(24 * M, dtype=torch.uint8, pin_memory=True)
-            h64 = host[: 16 * M].view(torch.int64).view(2, B, P).numpy()
-            h32 = host[16 * M:].view(torch.float32).view(2, B, P).numpy()
-            h64[0] = slot
-            h64[1] = 0 if stream_ids is None else stream_ids
-            h32[0] = valid
-            h32[1] = np.arange(P)[None] * valid
-            buf = host.to(dev, non_blocking=True)
-            d64 = buf[: 16 * M].view(torch.int64).view(2, B, P)
-            d32 = buf[16 * M:].view(torch.float32).view(2, B, P)
-            part_pcs = torch.empty((B, P, N, 3), dtype=torch.float32, device=dev)
-            part_trans = torch.empty((B, P, 3), dtype=torch.float32, device=dev)
-            raw = torch.empty((B, P, N, 3), dtype=torch.float64, device=dev) if return_raw else None
-            if replay:
-                d_uni, d_rot, d_perm = (_to_device(a, dev) for a in (uniforms, rot, perm))
-                part_quat = _to_device(quat, dev)
-                args = (d_uni, d_rot, d_perm, 0, None, 0.0, part_pcs, part_trans, None)
-            else:
-                part_quat = torch.empty((B, P, 4), dtype=torch.float32, device=dev)
-                args = (None, None, None, self.seed, d64[1], self.rot_range, part_pcs, part_trans, part_quat)
-            _lib.launch("mpa_mesh_sample_batch", dev, tri, cum, pf, self.store.num_parts, d64[0], M, N, *args, raw)
-        d_val = d32[0]
-        out = {
-            "part_pcs": part_pcs,
-            "part_quat": part_quat,
-            "part_trans": part_trans,
-            "part_valids": d_val,
-            "data_id": torch.as_tensor(indices, dtype=torch.int64),
-            "instance_label": torch.zeros((B, P, 0), dtype=torch.float32, device=dev),
-            "part_label": torch.zeros((B, P, 0), dtype=torch.float32, device=dev),
-        }
-        if "part_ids" in self.data_keys:
-            out["part_ids"] = d32[1]
-        if "valid_matrix" in self.data_keys:
-            out["valid_matrix"] = d_val[:, :, None] * d_val[:, None, :]
-        self._add_contacts(out)
-        return (out, raw) if return_raw else out
+        host = torch.empty(24 * M, dtype=torch.uint8, pin_memory=True)
+        h64 = host[: 16 * M].view(torch.int64).view(2, B, P).numpy()
+        h32 = host[16 * M:].view(torch.float32).view(2, B, P).numpy()
+        h64[0] = slot
+        h64[1] = stream_ids
+        h32[0] = valid
+        h32[1] = np.arange(P)[None] * valid
+        buf = host.to(dev, non_blocking=True)
+        return buf[: 16 * M].view(torch.int64).view(2, B, P), buf[16 * M:].view(torch.float32).view(2, B, P)
 
-    def _run_device(self, indices, batch_counter, return_raw=False):
-        """`batch` for a device index vector: the slot table is built by `mpa_mesh_slot_table` from the store's
-        `shape_part_off`, the sampler launch behind it is the host path's."""
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("DeviceGeometryProducer: the mesh sampler runs on the HIP device only "
-                               "(there is no CPU fallback)")
+    def _device_tables(self, dev, indices, batch_counter):
+        """The same tables for a device index vector, built by `mpa_mesh_slot_table` from the store's `shape_part_off`;
+        what the host builder refuses with an exception is left in the status word here."""
         if indices.dtype != torch.int64 or indices.dim() != 1 or not indices.is_contiguous():
             raise ValueError("DeviceGeometryProducer: device indices must be a contiguous int64 vector")
         if self.shuffle_parts:
             raise ValueError("DeviceGeometryProducer: shuffle_parts draws its part orders on the host (random.shuffle) "
                              "and is not available with device indices")
-        B, P, N = indices.numel(), self.max_num_part, self.num_points
-        M = B * P
+        B, P = indices.numel(), self.max_num_part
+        off, = self.store._on_device(dev, ("shape_part_off",))
+        d64 = torch.empty((2, B, P), dtype=torch.int64, device=dev)
+        d32 = torch.empty((2, B, P), dtype=torch.float32, device=dev)
+        _lib.launch("mpa_mesh_slot_table", dev, off, self.store.num_shapes, indices, B, P, self.min_num_part,
+                    self.max_num_part, (int(batch_counter) * B * P) & 0xFFFFFFFFFFFFFFFF, d64[0], d64[1], d32[0], d32[1],
+                    self._status.on(dev))
+        return d64, d32
+
+    def _run(self, indices, batch_counter=None, replay=None, return_raw=False):
+        """One batch: the tables of `indices`, the sampler launch, the `data_dict`.  `replay`: the caller's (uniforms,
+        rot, perm, quat) instead of the device's draws."""
+        dev = _hip_device(self.device, "DeviceGeometryProducer: the mesh sampler")
         with torch.cuda.device(dev):
-            tri, cum, pf = self.store.device_arrays(dev)
-            off = self.store.device_shape_part_off(dev)
-            if self._status is None:
-                self._status = torch.zeros(1, dtype=torch.int32, device=dev)
-            d64 = torch.empty((2, B, P), dtype=torch.int64, device=dev)
-            d32 = torch.empty((2, B, P), dtype=torch.float32, device=dev)
+            if isinstance(indices, torch.Tensor) and indices.device.type == "cuda":
+                data_id = indices
+                d64, d32 = self._device_tables(dev, indices, batch_counter)
+            else:
+                indices = list(indices)
+                data_id = torch.as_tensor(indices, dtype=torch.int64)
+                B, P = len(indices), self.max_num_part
+                streams = 0 if replay else (int(batch_counter) * B * P + np.arange(B * P, dtype=np.int64)).reshape(B, P)
+                d64, d32 = self._host_tables(dev, indices, streams)
+            (_, B, P), N = d64.shape, self.num_points
+            tri, cum, pf = self.store._on_device(dev, ("tri", "cum_area", "part_face_off"))
             part_pcs = torch.empty((B, P, N, 3), dtype=torch.float32, device=dev)
             part_trans = torch.empty((B, P, 3), dtype=torch.float32, device=dev)
-            part_quat = torch.empty((B, P, 4), dtype=torch.float32, device=dev)
             raw = torch.empty((B, P, N, 3), dtype=torch.float64, device=dev) if return_raw else None
-            _lib.launch("mpa_mesh_slot_table", dev, off, self.store.num_shapes, indices, B, P, self.min_num_part,
-                        self.max_num_part, (int(batch_counter) * M) & 0xFFFFFFFFFFFFFFFF, d64[0], d64[1], d32[0], d32[1],
-                        self._status)
-            _lib.launch("mpa_mesh_sample_batch", dev, tri, cum, pf, self.store.num_parts, d64[0], M, N, None, None, None,
-                        self.seed, d64[1], self.rot_range, part_pcs, part_trans, part_quat, raw)
-        d_val = d32[0]
-        out = {
-            "part_pcs": part_pcs,
-            "part_quat": part_quat,
-            "part_trans": part_trans,
-            "part_valids": d_val,
-            "data_id": indices,
-            "instance_label": torch.zeros((B, P, 0), dtype=torch.float32, device=dev),
-            "part_label": torch.zeros((B, P, 0), dtype=torch.float32, device=dev),
-        }
-        if "part_ids" in self.data_keys:
-            out["part_ids"] = d32[1]
-        if "valid_matrix" in self.data_keys:
-            out["valid_matrix"] = d_val[:, :, None] * d_val[:, None, :]
-        self._add_contacts(out)
+            if replay:
+                d_uni, d_rot, d_perm, part_quat = (_to_device(a, dev) for a in replay)
+                args = (d_uni, d_rot, d_perm, 0, None, 0.0, part_pcs, part_trans, None)
+            else:
+                part_quat = torch.empty((B, P, 4), dtype=torch.float32, device=dev)
+                args = (None, None, None, self.seed, d64[1], self.rot_range, part_pcs, part_trans, part_quat)
+            _lib.launch("mpa_mesh_sample_batch", dev, tri, cum, pf, self.store.num_parts, d64[0], B * P, N, *args, raw)
+        out = _geometry_batch(part_pcs, part_quat, part_trans, d32[0], d32[1], data_id, self.data_keys, self.contact_thre)
         return (out, raw) if return_raw else out
 
     def check(self):
         """RuntimeError if a device-index batch since the last check held a shape index outside the store or a shape whose
         part count is outside [min_num_part, max_num_part]; synchronises.  The word is cleared as it is reported."""
-        if self._status is None:
-            return
-        code = int(self._status.item())
-        if code:
-            self._status.zero_()
-            what = "a shape index outside the store" if code == 1 else \
-                f"a shape with a part count outside [{self.min_num_part}, {self.max_num_part}]"
-            raise RuntimeError(f"DeviceGeometryProducer: a batch met {what}; that shape was written as padding")
+        self._status.check("DeviceGeometryProducer: a batch met {}; that shape was written as padding",
+                           {1: "a shape index outside the store",
+                            2: f"a shape with a part count outside [{self.min_num_part}, {self.max_num_part}]"})
 
     def batch(self, indices: Sequence[int], batch_counter: int | None = None, return_raw=False):
         """The `data_dict` of the shapes `indices`, sampled, rotated and cast on the device.  `batch_counter` selects the
@@ -578,18 +597,10 @@ class DeviceGeometryProducer:
         slot table is built on the device too, `data_id` is that vector, the bits are those of the host sequence with
         the same values, and a bad index is reported by `check()` instead of an exception here (the host never sees
         the values).  `shuffle_parts` is refused with device indices."""
-        if isinstance(indices, torch.Tensor) and indices.device.type == "cuda":
-            if batch_counter is None:
-                batch_counter = self.batch_counter
-                self.batch_counter += 1
-            return self._run_device(indices, batch_counter, return_raw=return_raw)
-        indices = list(indices)
         if batch_counter is None:
             batch_counter = self.batch_counter
             self.batch_counter += 1
-        M = len(indices) * self.max_num_part
-        streams = (int(batch_counter) * M + np.arange(M, dtype=np.int64)).reshape(len(indices), self.max_num_part)
-        return self._run(indices, stream_ids=streams, return_raw=return_raw)
+        return self._run(indices, batch_counter, return_raw=return_raw)
 
     def replay(self, indices: Sequence[int], uniforms, rot, perm, quat, return_raw=False):
         """Replay mode: uniforms float64 [B, P, N, 3], rot float64 [B, P, 9], perm int32 [B, P, N] and quat float32
@@ -607,7 +618,7 @@ class DeviceGeometryProducer:
                 raise ValueError(f"replay: {name} must be {shape}, got {arr.shape}")
         if perm.size and (perm.min() < 0 or perm.max() >= N):
             raise ValueError(f"replay: perm entries outside [0, {N})")
-        return self._run(indices, uniforms=uniforms, rot=rot, perm=perm, quat=quat, return_raw=return_raw)
+        return self._run(indices, replay=(uniforms, rot, perm, quat), return_raw=return_raw)
 
 
 # ---- PartNet ---------------------------------------------------------------------------------------------------
@@ -638,6 +649,32 @@ def match_ids(geo_part_ids: np.ndarray, max_num_part: int) -> np.ndarray:
     return out
 
 
+PARTNET_KEYS = ("part_label", "part_ids", "match_ids", "contact_points", "sym", "valid_matrix")
+
+
+def _load_partnet(data_dir, shape_id, contacts=False):
+    """A shape's `shape_data` dict, or with `contacts` its [p, p, 4] contact table, from the reference's files."""
+    level = PartNetBatchProducer.LEVEL
+    if contacts:
+        fn = os.path.join(data_dir, "contact_points", f"pairs_with_contact_points_{shape_id}_level{level}.npy")
+        return np.load(fn, allow_pickle=True)
+    return np.load(os.path.join(data_dir, "shape_data", f"{shape_id}_level{level}.npy"), allow_pickle=True).item()
+
+
+def read_partnet_split(data_dir, data_fn, min_num_part=2, max_num_part=20, overfit=-1):
+    """`PartNetPartDataset._read_data` and the `overfit` cut (partnet_data.py:36-54): yields (shape id, `shape_data`
+    dict) of the split `data_dir/data_fn` in its order, for the shapes with a part count in [min_num_part, max_num_part]
+    — the others are skipped, not an error — and with `overfit > 0` the first `overfit` of them only."""
+    kept = 0
+    for shape_id in np.load(os.path.join(data_dir, data_fn)):
+        cur = _load_partnet(data_dir, shape_id)
+        if min_num_part <= np.asarray(cur["part_pcs"]).shape[0] <= max_num_part:
+            yield shape_id, cur
+            kept += 1
+            if kept == overfit:
+                return
+
+
 class PartNetBatchProducer:
     """`PartNetPartDataset` + default collate; reads the reference's on-disk format."""
 
@@ -652,17 +689,14 @@ class PartNetBatchProducer:
         self.shuffle_parts = shuffle_parts
         self.data_keys = tuple(data_keys)
         self.device = torch.device(device)
-        self.shape_ids = [s for s in np.load(os.path.join(data_dir, data_fn))
-                          if min_num_part <= self._load(s)["part_pcs"].shape[0] <= max_num_part]
-        if overfit > 0:
-            self.shape_ids = self.shape_ids[:overfit]
+        # only the ids are kept: `item` reads a shape's file again, as the reference does
+        self.shape_ids = [s for s, _ in read_partnet_split(data_dir, data_fn, min_num_part, max_num_part, overfit)]
 
     def __len__(self):
         return len(self.shape_ids)
 
     def _load(self, shape_id) -> dict:
-        fn = os.path.join(self.data_dir, "shape_data", f"{shape_id}_level{self.LEVEL}.npy")
-        return np.load(fn, allow_pickle=True).item()
+        return _load_partnet(self.data_dir, shape_id)
 
     def _pad(self, data) -> np.ndarray:
         data = np.asarray(data)
@@ -698,25 +732,20 @@ class PartNetBatchProducer:
             d["part_label"] = self._pad(one_hot)
         else:
             d["part_label"] = np.zeros((P, 0), dtype=np.float32)
+        _check_data_keys(PARTNET_KEYS, self.data_keys)  # raised per item, as the reference does
         for key in self.data_keys:
-            if key == "part_label":
-                continue
             if key == "part_ids":
                 d[key] = self._pad(geo)
             elif key == "match_ids":
                 d[key] = match_ids(geo, P)
             elif key == "contact_points":
-                fn = os.path.join(self.data_dir, "contact_points",
-                                  f"pairs_with_contact_points_{shape_id}_level{self.LEVEL}.npy")
                 out = np.zeros((P, P, 4), dtype=np.float32)
-                out[:p, :p] = np.load(fn, allow_pickle=True)
+                out[:p, :p] = _load_partnet(self.data_dir, shape_id, contacts=True)
                 d[key] = out
             elif key == "sym":
                 d[key] = self._pad(cur["sym"])
             elif key == "valid_matrix":
                 d[key] = valids[:, None] * valids[None, :]
-            else:
-                raise ValueError(f"ERROR: unknown data {key}")
         return d
 
     def batch(self, indices: Sequence[int]) -> dict:
@@ -733,12 +762,11 @@ class PartNetBatchProducer:
 
 
 # ---- device-resident PartNet data ---------------------------------------------------------------------------------
-PARTNET_KEYS = ("part_label", "part_ids", "match_ids", "contact_points", "sym", "valid_matrix")
 MAX_DEVICE_PARTS = 64        # one lane per part in csrc/partnet_gather.hip
 _MAX_EXACT_ID = 1 << 24      # `part_ids` travels as float32: every id below 2^24 survives the cast
 
 
-class PartNetStore:
+class PartNetStore(_ResidentStore):
     """Every shape of a PartNet split, read once and packed into flat arrays the gather kernel reads
     (csrc/partnet_gather.hip) — the `MeshStore` of the semantic data:
 
@@ -754,6 +782,8 @@ class PartNetStore:
     `MeshStore`.  The arrays live on the host; `device_arrays(device)` uploads them once per device."""
 
     ARRAYS = ("pcs", "poses", "sym", "geo_ids", "sem_ids", "shape_part_off", "shape_ids")
+    OPTIONAL = ("contacts", "contact_off")
+    EVERY = ARRAYS + OPTIONAL
 
     def __init__(self, pcs, poses, sym, geo_ids, sem_ids, shape_part_off, shape_ids, contacts=None, contact_off=None,
                  min_num_part=2, max_num_part=20, max_bytes=None):
@@ -795,19 +825,8 @@ class PartNetStore:
             want = np.concatenate([[0], np.cumsum(count * count)])
             if len(self.contact_off) != len(want) or (self.contact_off != want).any() or len(self.contacts) != want[-1]:
                 raise ValueError("PartNetStore: inconsistent offsets (contact_off must be the running sum of p * p)")
-        _check_store_bytes(self.nbytes, max_bytes, "PartNetStore")
+        _check_store_bytes(self.nbytes, max_bytes, "PartNetStore", "part")
         self._device = {}
-
-    @property
-    def nbytes(self):
-        arrays = [getattr(self, n) for n in self.ARRAYS]
-        if self.contacts is not None:
-            arrays += [self.contacts, self.contact_off]
-        return sum(a.nbytes for a in arrays)
-
-    @property
-    def num_shapes(self):
-        return len(self.shape_ids)
 
     @property
     def num_parts(self):
@@ -820,9 +839,6 @@ class PartNetStore:
     @property
     def has_contacts(self):
         return self.contacts is not None
-
-    def __len__(self):
-        return self.num_shapes
 
     @classmethod
     def from_arrays(cls, shapes, shape_ids=None, contacts=None, min_num_part=2, max_num_part=20, max_bytes=None):
@@ -839,7 +855,7 @@ class PartNetStore:
         count = np.array([len(a) for a in pcs], dtype=np.int64)
         if (count < min_num_part).any() or (count > max_num_part).any():
             raise ValueError(f"PartNetStore: a shape has a part count outside [{min_num_part}, {max_num_part}]")
-        _check_store_bytes(int(count.sum()) * (12 * pcs[0].shape[1] + 48), max_bytes, "PartNetStore")
+        _check_store_bytes(int(count.sum()) * (12 * pcs[0].shape[1] + 48), max_bytes, "PartNetStore", "part")
         cat = lambda key, width: np.concatenate(
             [np.asarray(d[key]).reshape((len(a),) + width) for d, a in zip(shapes, pcs)])
         c = co = None
@@ -860,21 +876,13 @@ class PartNetStore:
         """The split `data_dir/data_fn` in the reference's on-disk format, with the shape filter, the order and the
         `overfit` cut of `PartNetBatchProducer.__init__`; every file is read once.  `with_contacts`: None reads the
         contact files when the `contact_points` folder exists, True requires them, False leaves them out."""
-        level = PartNetBatchProducer.LEVEL
         ids, shapes = [], []
-        for s in np.load(os.path.join(data_dir, data_fn)):
-            cur = np.load(os.path.join(data_dir, "shape_data", f"{s}_level{level}.npy"), allow_pickle=True).item()
-            if min_num_part <= np.asarray(cur["part_pcs"]).shape[0] <= max_num_part:
-                ids.append(int(s))
-                shapes.append(cur)
-        if overfit > 0:
-            ids, shapes = ids[:overfit], shapes[:overfit]
+        for s, cur in read_partnet_split(data_dir, data_fn, min_num_part, max_num_part, overfit):
+            ids.append(int(s))
+            shapes.append(cur)
         if with_contacts is None:
             with_contacts = os.path.isdir(os.path.join(data_dir, "contact_points"))
-        contacts = None
-        if with_contacts:
-            contacts = [np.load(os.path.join(data_dir, "contact_points", f"pairs_with_contact_points_{s}_level{level}.npy"),
-                                allow_pickle=True) for s in ids]
+        contacts = [_load_partnet(data_dir, s, contacts=True) for s in ids] if with_contacts else None
         return cls.from_arrays(shapes, ids, contacts, min_num_part, max_num_part, max_bytes)
 
     def with_computed_contacts(self, device="cuda", thre=0.01, batch=64):
@@ -883,9 +891,7 @@ class PartNetStore:
         `contacts.contact_points` (csrc/contact_points.hip) with `thre` as the bound on the squared distance, and the
         p x p x 4 block of every shape is kept.  Contacts the store already holds are replaced.  `save`, `load` and
         `DevicePartNetProducer` then work as they do for file-borne contacts."""
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("PartNetStore: the contact search runs on the HIP device only (there is no CPU fallback)")
+        device = _hip_device(device, "PartNetStore: the contact search")
         if batch < 1:
             raise ValueError(f"PartNetStore.with_computed_contacts: batch={batch} must be positive")
         from .contacts import contact_points
@@ -909,37 +915,18 @@ class PartNetStore:
                             np.concatenate(blocks), np.concatenate([[0], np.cumsum(count * count)]),
                             min_num_part=self.min_num_part, max_num_part=self.max_num_part)
 
-    def save(self, path):
-        """One .npz of plain arrays (no pickle): the per-file parse is paid once per split."""
-        arrays = {n: getattr(self, n) for n in self.ARRAYS}
-        arrays["part_limits"] = np.array([self.min_num_part, self.max_num_part], dtype=np.int64)
-        if self.contacts is not None:
-            arrays.update(contacts=self.contacts, contact_off=self.contact_off)
-        with open(path, "wb") as fh:
-            np.savez(fh, **arrays)
+    def _meta(self):
+        return {"part_limits": np.array([self.min_num_part, self.max_num_part], dtype=np.int64)}
 
-    @classmethod
-    def load(cls, path, max_bytes=None):
-        with np.load(path, allow_pickle=False) as z:
-            lo, hi = (int(x) for x in z["part_limits"])
-            extra = (z["contacts"], z["contact_off"]) if "contacts" in z.files else (None, None)
-            return cls(*(z[n] for n in cls.ARRAYS), *extra, min_num_part=lo, max_num_part=hi, max_bytes=max_bytes)
+    @staticmethod
+    def _from_meta(z):
+        lo, hi = (int(x) for x in z["part_limits"])
+        return {"min_num_part": lo, "max_num_part": hi}
 
     def device_arrays(self, device):
         """name -> tensor on `device` for every array of the store (`contacts` / `contact_off`: None without contact
         points), uploaded at the first call."""
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("PartNetStore: the gather runs on the HIP device only (there is no CPU fallback)")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        if device not in self._device:
-            names = self.ARRAYS + (("contacts", "contact_off") if self.contacts is not None else ())
-            arrays = {n: torch.from_numpy(getattr(self, n)).to(device) for n in names}
-            arrays.setdefault("contacts", None)
-            arrays.setdefault("contact_off", None)
-            self._device[device] = arrays
-        return self._device[device]
+        return dict(zip(self.EVERY, self._on_device(_hip_device(device, "PartNetStore: the gather"), self.EVERY)))
 
 
 class DevicePartNetProducer:
@@ -963,9 +950,7 @@ class DevicePartNetProducer:
                  shuffle_parts=False, seed=0, device="cuda"):
         self.store = store
         self.data_keys = tuple(data_keys)
-        for key in self.data_keys:  # partnet_data.py:210-241
-            if key not in PARTNET_KEYS:
-                raise ValueError(f"ERROR: unknown data {key}")
+        _check_data_keys(PARTNET_KEYS, self.data_keys)
         self.num_part_category = int(num_part_category)
         self.min_num_part, self.max_num_part = int(min_num_part), int(max_num_part)
         if not 1 <= self.max_num_part <= MAX_DEVICE_PARTS:
@@ -984,7 +969,7 @@ class DevicePartNetProducer:
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.device = torch.device(device)
         self.batch_counter = 0  # the default `batch_counter` of the next batch() call
-        self._status = None
+        self._status = _StatusWord()
 
     def __len__(self):
         return self.store.num_shapes
@@ -1004,46 +989,64 @@ class DevicePartNetProducer:
                 spec[key] = (extra[key], f32)
         return spec
 
+    def _indices(self, dev, indices):
+        """(the index vector on the device, the batch's `data_id`, the host's copy of the values): a device vector is
+        used as it is, and the host never sees its values (None); a host sequence is checked and sent in one pinned copy."""
+        if isinstance(indices, torch.Tensor) and indices.device.type == "cuda":
+            if indices.dtype != torch.int64 or indices.dim() != 1 or not indices.is_contiguous():
+                raise ValueError("DevicePartNetProducer: device indices must be a contiguous int64 vector")
+            return indices, indices, None
+        host_idx = np.asarray(indices.numpy() if isinstance(indices, torch.Tensor) else list(indices),
+                              dtype=np.int64).reshape(-1)
+        S = self.store.num_shapes
+        if ((host_idx < 0) | (host_idx >= S)).any():
+            raise IndexError(f"DevicePartNetProducer: shape index outside [0, {S})")
+        pinned = torch.empty(len(host_idx), dtype=torch.int64, pin_memory=True)
+        pinned.numpy()[:] = host_idx
+        return pinned.to(dev, non_blocking=True), torch.as_tensor(host_idx, dtype=torch.int64), host_idx
+
+    def _replayed_order(self, dev, perm, B, host_idx):
+        """The caller's part orders as the int32 [B, P] device table the kernel replays."""
+        P = self.max_num_part
+        if isinstance(perm, torch.Tensor) and perm.device.type == "cuda":
+            if perm.dtype != torch.int32 or tuple(perm.shape) != (B, P) or not perm.is_contiguous():
+                raise ValueError(f"replay: a device perm must be contiguous int32 [{B}, {P}]")
+            return perm
+        h_perm = np.ascontiguousarray(perm, dtype=np.int32)
+        if h_perm.shape != (B, P):
+            raise ValueError(f"replay: perm must be ({B}, {P}), got {h_perm.shape}")
+        if host_idx is not None:  # what the wrapper can see: every row permutes 0..p-1
+            count = np.diff(self.store.shape_part_off)[host_idx]
+            for b, p in enumerate(count):
+                if not np.array_equal(np.sort(h_perm[b, :p]), np.arange(p)):
+                    raise ValueError(f"replay: perm[{b}, :{p}] is not a permutation of 0..{p - 1}")
+        return _to_device(h_perm, dev)
+
+    def _output_slots(self, dev, B, out):
+        """(key -> tensor of the batch, key -> what the kernel writes: None for an empty entry, passed as NULL).  The
+        device tensors of `out` that fit are taken as they are, the others are allocated."""
+        result, slots = {}, {}
+        for key, (shape, dtype) in self._spec(B).items():
+            t = None if out is None else out.get(key)
+            if t is not None and t.device.type != "cuda":
+                t = None  # (a host tensor of a host-built batch, `shape_id`: the kernel cannot write it)
+            if t is None:
+                t = torch.empty(shape, dtype=dtype, device=dev)
+            elif tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"DevicePartNetProducer: out[{key!r}] must be a contiguous {dtype} tensor of shape "
+                                 f"{shape} on {dev}")
+            result[key] = t
+            slots[key] = t if t.numel() else None
+        return result, slots
+
     def _run(self, indices, perm=None, counter=None, out=None, return_order=False):
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("DevicePartNetProducer: the gather runs on the HIP device only (there is no CPU fallback)")
-        S, P, N = self.store.num_shapes, self.max_num_part, self.store.num_points
+        """One batch: the indices, the replayed order if there is one, the output slots, the launch."""
+        dev = _hip_device(self.device, "DevicePartNetProducer: the gather")
+        P = self.max_num_part
         with torch.cuda.device(dev):
-            arrays = self.store.device_arrays(dev)
-            host_idx = None
-            if isinstance(indices, torch.Tensor) and indices.device.type == "cuda":
-                if indices.dtype != torch.int64 or indices.dim() != 1 or not indices.is_contiguous():
-                    raise ValueError("DevicePartNetProducer: device indices must be a contiguous int64 vector")
-                d_idx = data_id = indices
-            else:
-                host_idx = np.asarray(indices.numpy() if isinstance(indices, torch.Tensor) else list(indices),
-                                      dtype=np.int64).reshape(-1)
-                if ((host_idx < 0) | (host_idx >= S)).any():
-                    raise IndexError(f"DevicePartNetProducer: shape index outside [0, {S})")
-                pinned = torch.empty(len(host_idx), dtype=torch.int64, pin_memory=True)
-                pinned.numpy()[:] = host_idx
-                d_idx = pinned.to(dev, non_blocking=True)
-                data_id = torch.as_tensor(host_idx, dtype=torch.int64)
+            d_idx, data_id, host_idx = self._indices(dev, indices)
             B = d_idx.numel()
-            if self._status is None:
-                self._status = torch.zeros(1, dtype=torch.int32, device=dev)
-            d_perm = None
-            if perm is not None:
-                if isinstance(perm, torch.Tensor) and perm.device.type == "cuda":
-                    d_perm = perm
-                    if d_perm.dtype != torch.int32 or tuple(d_perm.shape) != (B, P) or not d_perm.is_contiguous():
-                        raise ValueError(f"replay: a device perm must be contiguous int32 [{B}, {P}]")
-                else:
-                    h_perm = np.ascontiguousarray(perm, dtype=np.int32)
-                    if h_perm.shape != (B, P):
-                        raise ValueError(f"replay: perm must be ({B}, {P}), got {h_perm.shape}")
-                    if host_idx is not None:  # what the wrapper can see: every row permutes 0..p-1
-                        count = np.diff(self.store.shape_part_off)[host_idx]
-                        for b, p in enumerate(count):
-                            if not np.array_equal(np.sort(h_perm[b, :p]), np.arange(p)):
-                                raise ValueError(f"replay: perm[{b}, :{p}] is not a permutation of 0..{p - 1}")
-                    d_perm = _to_device(h_perm, dev)
+            d_perm = None if perm is None else self._replayed_order(dev, perm, B, host_idx)
             counter_val, counter_dev = 0, None
             if isinstance(counter, torch.Tensor):
                 if counter.dtype != torch.int64 or counter.numel() != 1 or counter.device.type != "cuda":
@@ -1051,27 +1054,15 @@ class DevicePartNetProducer:
                 counter_dev = counter
             elif counter is not None:
                 counter_val = int(counter) & 0xFFFFFFFFFFFFFFFF
-            random_order = 1 if (self.shuffle_parts and perm is None) else 0
-            result, slots = {}, {}  # slots: what the kernel writes (None: an empty entry, passed as NULL)
-            for key, (shape, dtype) in self._spec(B).items():
-                t = None if out is None else out.get(key)
-                if t is not None and t.device.type != "cuda":
-                    t = None  # (a host tensor of a host-built batch, `shape_id`: the kernel cannot write it)
-                if t is None:
-                    t = torch.empty(shape, dtype=dtype, device=dev)
-                elif tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != d_idx.device:
-                    raise ValueError(f"DevicePartNetProducer: out[{key!r}] must be a contiguous {dtype} tensor of shape "
-                                     f"{shape} on {d_idx.device}")
-                result[key] = t
-                slots[key] = t if t.numel() else None
+            result, slots = self._output_slots(dev, B, out)
             order = torch.empty((B, P), dtype=torch.int32, device=dev) if return_order else None
-            _lib.launch(
-                "mpa_partnet_gather_batch", dev, *(arrays[n] for n in PartNetStore.ARRAYS), arrays["contacts"],
-                arrays["contact_off"], S, d_idx, B, P, N, result["part_label"].shape[2], d_perm, random_order, self.seed,
-                counter_val, counter_dev, slots["part_pcs"], slots["part_trans"], slots["part_quat"],
-                slots["part_valids"], slots.get("part_ids"), slots["instance_label"], slots.get("match_ids"),
-                slots["part_label"], slots.get("contact_points"), slots.get("sym"), slots.get("valid_matrix"),
-                slots["shape_id"], order, self._status)
+            _lib.launch(  # the store's arrays lead the kernel's arguments, in the order of `EVERY`
+                "mpa_partnet_gather_batch", dev, *self.store._on_device(dev, PartNetStore.EVERY), self.store.num_shapes,
+                d_idx, B, P, self.store.num_points, result["part_label"].shape[2], d_perm,
+                1 if (self.shuffle_parts and perm is None) else 0, self.seed, counter_val, counter_dev,
+                slots["part_pcs"], slots["part_trans"], slots["part_quat"], slots["part_valids"], slots.get("part_ids"),
+                slots["instance_label"], slots.get("match_ids"), slots["part_label"], slots.get("contact_points"),
+                slots.get("sym"), slots.get("valid_matrix"), slots["shape_id"], order, self._status.on(dev))
         if out is not None and host_idx is not None:  # the host-side entries of a host-built batch, filled in place
             for key, val in (("data_id", data_id), ("shape_id", self.store.shape_ids[host_idx])):
                 t = out.get(key)
@@ -1111,10 +1102,5 @@ class DevicePartNetProducer:
     def check(self):
         """RuntimeError if a launch since the last check met a shape index outside the store (or a replayed order that
         is no permutation); synchronises.  The word is cleared as it is reported."""
-        if self._status is None:
-            return
-        code = int(self._status.item())
-        if code:
-            self._status.zero_()
-            what = "a shape index outside the store" if code == 1 else "a replayed part order that is no permutation"
-            raise RuntimeError(f"DevicePartNetProducer: a gather launch met {what}; that sample was written as padding")
+        self._status.check("DevicePartNetProducer: a gather launch met {}; that sample was written as padding",
+                           {1: "a shape index outside the store", 2: "a replayed part order that is no permutation"})

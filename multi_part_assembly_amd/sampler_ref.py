@@ -1,23 +1,15 @@
 """numpy restatement of `mpa_epoch_order` (include/mpa_hip.h): the Philox keys, the stable argsort and the
 `DistributedSampler` sharding.  It is the oracle of the device kernel and what `EpochSampler(device="cpu")` runs, so that
-CPU tests and host-fed producers follow the order the device draws.  Imports nothing but numpy."""
+CPU tests and host-fed producers follow the order the device draws.  Imports nothing but numpy (and `philox_ref`, which
+does the same)."""
 from __future__ import annotations
 
 import numpy as np
 
+from .philox_ref import philox4x32_10
+
 ORDER_TAG = 0x65700000   # counter word 1 of the epoch order (csrc/epoch_order.hip)
 MAX_SHAPES = 1 << 18     # the kernel's cap on S
-
-
-def philox4x32_10(c0, c1, c2, c3, k0, k1):
-    """Philox4x32-10 on numpy uint64 arrays holding 32-bit words (broadcast); returns the four output words."""
-    c = [np.asarray(x, dtype=np.uint64) for x in (c0, c1, c2, c3)]
-    k0, k1, mask, s32 = np.uint64(k0), np.uint64(k1), np.uint64(0xFFFFFFFF), np.uint64(32)
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]  # 32 x 32 bits: fits in 64
-        c = [(p1 >> s32) ^ c[1] ^ k0, p1 & mask, (p0 >> s32) ^ c[3] ^ k1, p0 & mask]
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & mask, (k1 + np.uint64(0xBB67AE85)) & mask
-    return c
 
 
 def epoch_keys(num_shapes, seed, epoch):

@@ -1,10 +1,13 @@
 """numpy restatement of `mpa_seq2seq_draw` (include/mpa_hip.h): the teacher-forcing coin, the decoder noise and the
 LockedDropout mask of one B-LSTM forward, from Philox4x32-10 blocks.  This file is the specification the kernel
 (csrc/seq2seq_draw.hip) is tested against.  Philox runs on plain integers (numpy uint64 arrays holding 32-bit words); the
-coin and the mask are integer comparisons, the normals are evaluated in float64.  Imports nothing but numpy."""
+coin and the mask are integer comparisons, the normals are evaluated in float64.  Imports nothing but numpy (and
+`philox_ref`, which does the same)."""
 from __future__ import annotations
 
 import numpy as np
+
+from .philox_ref import philox4x32_10
 
 TAG = 0x73320000          # counter word 1 = TAG | kind (csrc/seq2seq_draw.hip); the taken values: include/mpa_hip.h
 KIND_TEACHER, KIND_NOISE, KIND_MASK = 0, 1, 2
@@ -12,17 +15,6 @@ NOISE_DIM = 16            # noise channels of the decoder's initial state
 CHANNELS = 128            # decoder input width: the mask's channels
 MAX_BATCH, MAX_STEPS = 64, 4096
 _U64 = 0xFFFFFFFFFFFFFFFF
-
-
-def philox4x32_10(c0, c1, c2, c3, k0, k1):
-    """Philox4x32-10 on numpy uint64 arrays holding 32-bit words (broadcast); returns the four output words."""
-    c = [np.asarray(x, dtype=np.uint64) for x in (c0, c1, c2, c3)]
-    k0, k1, mask, s32 = np.uint64(k0), np.uint64(k1), np.uint64(0xFFFFFFFF), np.uint64(32)
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]  # 32 x 32 bits: fits in 64
-        c = [(p1 >> s32) ^ c[1] ^ k0, p1 & mask, (p0 >> s32) ^ c[3] ^ k1, p0 & mask]
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & mask, (k1 + np.uint64(0xBB67AE85)) & mask
-    return c
 
 
 def step_value(counter=0, salt=0):

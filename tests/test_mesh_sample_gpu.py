@@ -68,7 +68,7 @@ def test_replay_is_numpy_and_the_transform_kernel_bit_for_bit(tmp_path, cuda_dev
     for b, pcs in enumerate(clouds):
         assert np.array_equal(raw[b, :len(pcs)], pcs), f"sampled cloud of batch entry {b} differs from numpy"
         assert not raw[b, len(pcs):].any()
-    assert set(got) == set(want)
+    assert list(got) == list(want)
     for k in want:
         assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape and got[k].device == want[k].device, k
         assert torch.equal(got[k], want[k]), f"{k} differs from GeometryBatchProducer.produce"
@@ -251,7 +251,7 @@ def test_batch_has_the_data_dict_of_the_host_producer(cuda_device, data_keys):
     want = host.produce(_numpy_clouds(shapes, indices, u), data_ids=indices)
     dev = DeviceGeometryProducer(store, num_points=N, max_num_part=P, data_keys=data_keys, seed=1, device=cuda_device)
     got = dev.batch(indices)
-    assert set(got) == set(want)
+    assert list(got) == list(want)
     for k in want:
         assert got[k].shape == want[k].shape and got[k].dtype == want[k].dtype and got[k].device == want[k].device, k
         assert got[k].is_contiguous(), k

@@ -6,7 +6,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from multi_part_assembly_amd import _build, _lib, datasets, synthetic
+from multi_part_assembly_amd import _build, _lib, datasets, philox_ref, synthetic
 from multi_part_assembly_amd.datasets import MeshStore, load_obj, sample_surface, sample_surface_from_uniforms
 
 
@@ -21,15 +21,9 @@ def philox4x32_10(ctr, key):
     return c
 
 
-def philox4x32_10_np(c0, c1, c2, c3, k0, k1):
-    """The same rounds on numpy uint64 arrays holding 32-bit words (broadcast): fast enough for whole batches."""
-    c = [np.asarray(x, dtype=np.uint64) for x in (c0, c1, c2, c3)]
-    k0, k1, mask = np.uint64(k0), np.uint64(k1), np.uint64(0xFFFFFFFF)
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]   # 32 x 32 bits: fits in 64
-        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k0, p1 & mask, (p0 >> np.uint64(32)) ^ c[3] ^ k1, p0 & mask]
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & mask, (k1 + np.uint64(0xBB67AE85)) & mask
-    return c
+# The same rounds on numpy uint64 arrays holding 32-bit words (broadcast), fast enough for whole batches: the package's
+# function, which `test_philox_restatement_reproduces_the_published_vectors` holds to the plain-int statement above.
+philox4x32_10_np = philox_ref.philox4x32_10
 
 
 def uniform53(hi, lo):
