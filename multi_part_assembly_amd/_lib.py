@@ -235,6 +235,14 @@ def query(name: str, *sizes, slot=ctypes.c_int64):
     return outs[0].value if len(outs) == 1 else tuple(o.value for o in outs)
 
 
+def require_hip(who: str, *tensors: torch.Tensor) -> None:
+    """The package's one refusal of host tensors: RuntimeError under the operator's name `who` unless every tensor is on
+    a device."""
+    for t in tensors:
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: only CUDA (HIP) tensors are supported — no CPU fallback")
+
+
 class KernelTimer:
     """Optional per-launch HIP-event timing of named kernels, on the stream they are launched on.
 

@@ -21,12 +21,6 @@ __all__ = ["AssembledClouds", "assemble_clouds", "rows_to_lists", "assembly_figu
 _HEADER_ALIGN = 256  # the clouds start on this boundary behind the offsets of the packed buffer
 
 
-def _need_cuda(what, *tensors):
-    for t in tensors:
-        if not t.is_cuda:
-            raise RuntimeError(f"{what}: only CUDA (HIP) tensors are supported (there is no CPU fallback)")
-
-
 class AssembledClouds:
     """What `assemble_clouds` wrote: `clouds` fp32 [S + 1, B P N, 6] (slab s < S = prediction s, slab S = ground truth;
     rows (x, y, z, r, g, b); only the first `offsets[B]` rows of a slab are defined), `offsets` int64 [B + 1] (shape b owns
@@ -105,7 +99,7 @@ def assemble_clouds(part_pcs, valids, rot, trans, gt_rot, gt_trans, colors, rot_
     g, gkind = _rot_tensor(gt_rot, rot_type)
     if kind != gkind or kind not in ("quat", "rmat"):
         raise NotImplementedError(f"assemble_clouds: rotations {kind!r} / {gkind!r} are not supported together")
-    _need_cuda("assemble_clouds", part_pcs, valids, r, trans, g, gt_trans, colors)
+    _lib.require_hip("assemble_clouds", part_pcs, valids, r, trans, g, gt_trans, colors)
     if part_pcs.dim() != 4 or part_pcs.shape[-1] != 3:
         raise RuntimeError(f"assemble_clouds: part_pcs must be [B, P, N, 3], got {tuple(part_pcs.shape)}")
     B, P, N, _ = part_pcs.shape
@@ -170,10 +164,7 @@ def rank_assemblies(model, batches, top=None):
     cols = {k: [] for k in _RECORD_FIELDS}
     try:
         for batch in batches:
-            batch = dict(batch)
-            if "part_rot" not in batch:
-                part_rot = Rotation3D(batch["part_quat"], rot_type="quat")
-                batch["part_rot"] = part_rot if model.rot_type == "quat" else part_rot.convert(model.rot_type)
+            batch = model._with_part_rot(batch)
             out = model.forward(batch)
             loss, _ = model._calc_loss(out, batch)
             if "rot_pt_l2_loss" not in loss or "trans_mae" not in loss:

@@ -21,7 +21,7 @@ from .chamfer import chamfer_distance
 from .eval_utils import assembly_metrics, calc_connectivity_acc, calc_part_acc, rot_metrics, trans_metrics
 from .matching import SUBSAMPLE, MatchSampler, match_parts
 from .loss import (LossTerms, geometric_assembly_loss, part_order, repulsion_cd_loss, search_mode, rot_cosine_loss,
-                   rot_points_cd_loss, rot_points_l2_loss, shape_cd_loss, trans_l2_loss)
+                   rot_points_cd_loss, rot_points_l2_loss, shape_cd_loss, sum_loss_rounds, trans_l2_loss)
 from .rotation import Rotation3D
 from .transforms import transform_pc
 
@@ -96,11 +96,21 @@ class BaseModel(nn.Module):
     def forward_pass(self, data_dict, mode="train", optimizer_idx=-1):
         """data_dict as produced by the reference datasets (geometry_data.py:173-207); `part_quat` is
         wrapped into `part_rot` here, like base_model.py:128-132 (non-destructively)."""
+        return self.loss_function(self._with_part_rot(data_dict), optimizer_idx=optimizer_idx)
+
+    def _with_part_rot(self, data_dict):
+        """Shallow copy of a batch whose `part_quat` has become `part_rot`, a Rotation3D of the model's rot_type."""
         data_dict = dict(data_dict)
         if "part_rot" not in data_dict:
             part_rot = Rotation3D(data_dict.pop("part_quat"), rot_type="quat")
             data_dict["part_rot"] = part_rot if self.rot_type == "quat" else part_rot.convert(self.rot_type)
-        return self.loss_function(data_dict, optimizer_idx=optimizer_idx)
+        return data_dict
+
+    def _extract_part_feats(self, part_pcs, part_valids):
+        """[B, P, N, 3] -> [B, P, C] through `self.encoder`; padded slots get zeros (mask in, zeros out: the valid parts
+        are counted and compacted on the device, no host sync)."""
+        B, P, N, _ = part_pcs.shape
+        return self.encoder.forward_parts(part_pcs.reshape(B * P, N, 3), part_valids.reshape(-1)).view(B, P, -1)
 
     # ---- GT <-> prediction matching (semantic datasets only) --------------------------------------
     @torch.no_grad()
@@ -151,22 +161,26 @@ class BaseModel(nn.Module):
         return new_trans, Rotation3D(new_rot, rot_type=self.rot_type)
 
     # ---- loss assembly ------------------------------------------------------------------------------
+    def _takes_fused_loss(self):
+        """Whether `_calc_loss` evaluates csrc/assembly_loss.hip (MPA_FUSED_SEMANTIC=0 keeps semantic data on the
+        per-function composition; read at call time)."""
+        return self.fused_loss and (not self.semantic or os.environ.get("MPA_FUSED_SEMANTIC", "1") != "0")
+
     def _calc_loss(self, out_dict, data_dict):
         """Loss terms of one prediction, each [B] (base_model.py:240-314)."""
         pred_trans, pred_rot = out_dict["trans"], out_dict["rot"]
         part_pcs, valids = data_dict["part_pcs"], data_dict["part_valids"]
         gt_trans, gt_rot = data_dict["part_trans"], data_dict["part_rot"]
-        if self.semantic and self.match_sample == "device":
-            new_trans, new_rot = self._match_parts(part_pcs, pred_trans, pred_rot, gt_trans, gt_rot,
-                                                   data_dict["match_ids"])
-        elif self.semantic:
-            if "_match_ids_host" not in data_dict:  # one copy per batch, shared by the min-of-N samples
+        if not self.semantic:
+            new_trans, new_rot = gt_trans.detach(), gt_rot.detach()
+        else:
+            if self.match_sample != "device" and "_match_ids_host" not in data_dict:
+                # one copy per batch, shared by the min-of-N samples
                 data_dict["_match_ids_host"] = data_dict["match_ids"].long().cpu().numpy()
             new_trans, new_rot = self._match_parts(part_pcs, pred_trans, pred_rot, gt_trans, gt_rot,
-                                                   data_dict["match_ids"], data_dict["_match_ids_host"])
-        else:
-            new_trans, new_rot = gt_trans.detach(), gt_rot.detach()
-        if self.fused_loss and (not self.semantic or os.environ.get("MPA_FUSED_SEMANTIC", "1") != "0"):
+                                                   data_dict["match_ids"], data_dict.get("_match_ids_host"))
+        stacked = None
+        if self._takes_fused_loss():
             # one fused forward/backward pair instead of the per-function composition below (semantic data: the matched
             # poses are plain inputs of the same five terms; its whole-shape term always normalises as in training,
             # base_model.py:281 of the reference)
@@ -178,32 +192,27 @@ class BaseModel(nn.Module):
                 loss_dict["rot_loss"] = terms["rot_loss"]
             if self.cfg.loss.use_rot_pt_l2_loss:
                 loss_dict["rot_pt_l2_loss"] = terms["rot_pt_l2_loss"]
-            self._add_repulsion_loss(loss_dict, pred_trans, pred_rot, part_pcs, valids)
-            if self.training and tuple(loss_dict) == terms.stacked[0]:
-                loss_dict.stacked = terms.stacked  # every row is used, in order: no select / re-stack
-            if not self.training:
-                loss_dict.update(self._calc_metrics(data_dict, out_dict, new_trans, new_rot))
-            out_dict = {"pred_trans": pred_trans, "pred_rot": pred_rot,
-                        "pred_trans_pts": pts[0] if pts else None, "gt_trans_pts": pts[1] if pts else None}
-            return loss_dict, out_dict
-
-        loss_dict = {
-            "trans_loss": trans_l2_loss(pred_trans, new_trans, valids),
-            "rot_pt_cd_loss": rot_points_cd_loss(part_pcs, pred_rot, new_rot, valids),
-        }
-        loss_dict["transform_pt_cd_loss"], pred_pts, gt_pts = shape_cd_loss(
-            part_pcs, pred_trans, new_trans, pred_rot, new_rot, valids, ret_pts=True,
-            training=self.semantic or self.training)
-        if self.cfg.loss.use_rot_loss:
-            loss_dict["rot_loss"] = rot_cosine_loss(pred_rot, new_rot, valids)
-        if self.cfg.loss.use_rot_pt_l2_loss:
-            loss_dict["rot_pt_l2_loss"] = rot_points_l2_loss(part_pcs, pred_rot, new_rot, valids)
+            stacked = terms.stacked
+            pts_out = {"pred_trans_pts": pts[0] if pts else None, "gt_trans_pts": pts[1] if pts else None}
+        else:
+            loss_dict = {
+                "trans_loss": trans_l2_loss(pred_trans, new_trans, valids),
+                "rot_pt_cd_loss": rot_points_cd_loss(part_pcs, pred_rot, new_rot, valids),
+            }
+            loss_dict["transform_pt_cd_loss"], pred_pts, gt_pts = shape_cd_loss(
+                part_pcs, pred_trans, new_trans, pred_rot, new_rot, valids, ret_pts=True,
+                training=self.semantic or self.training)
+            if self.cfg.loss.use_rot_loss:
+                loss_dict["rot_loss"] = rot_cosine_loss(pred_rot, new_rot, valids)
+            if self.cfg.loss.use_rot_pt_l2_loss:
+                loss_dict["rot_pt_l2_loss"] = rot_points_l2_loss(part_pcs, pred_rot, new_rot, valids)
+            pts_out = {"gt_trans_pts": gt_pts, "pred_trans_pts": pred_pts}
         self._add_repulsion_loss(loss_dict, pred_trans, pred_rot, part_pcs, valids)
+        if self.training and stacked is not None and tuple(loss_dict) == stacked[0]:
+            loss_dict.stacked = stacked  # every row is used, in order: no select / re-stack
         if not self.training:
             loss_dict.update(self._calc_metrics(data_dict, out_dict, new_trans, new_rot))
-        out_dict = {"pred_trans": pred_trans, "pred_rot": pred_rot, "gt_trans_pts": gt_pts,
-                    "pred_trans_pts": pred_pts}
-        return loss_dict, out_dict
+        return loss_dict, {"pred_trans": pred_trans, "pred_rot": pred_rot, **pts_out}
 
     def _add_repulsion_loss(self, loss_dict, pred_trans, pred_rot, part_pcs, valids):
         """`repulsion_loss` [B] of the posed prediction when cfg.loss.use_repulsion_loss is set: csrc/repulsion.hip on the
@@ -221,24 +230,18 @@ class BaseModel(nn.Module):
         geometric data."""
         part_pcs, valids = data_dict["part_pcs"], data_dict["part_valids"]
         pred_trans, pred_rot = out_dict["trans"], out_dict["rot"]
-        if self.fused_metrics:
-            fused = assembly_metrics(part_pcs, pred_trans, gt_trans, pred_rot, gt_rot, valids)
-            metrics = {"part_acc": fused["part_acc"]}
-            if "contact_points" in data_dict:
-                metrics["connectivity_acc"] = calc_connectivity_acc(pred_trans, pred_rot, data_dict["contact_points"],
-                                                                    fused=True)
-            if not self.semantic:
-                for m in ("mse", "rmse", "mae"):  # (the key order of the composition below)
-                    metrics[f"trans_{m}"] = fused[f"trans_{m}"]
-                    metrics[f"rot_{m}"] = fused[f"rot_{m}"]
-            return metrics
-        metrics = {"part_acc": calc_part_acc(part_pcs, pred_trans, gt_trans, pred_rot, gt_rot, valids)}
+        # csrc/eval_metrics.hip computes all of them at once; the composition one by one, only those that are asked for
+        fused = assembly_metrics(part_pcs, pred_trans, gt_trans, pred_rot, gt_rot, valids) if self.fused_metrics else None
+        metrics = {"part_acc": fused["part_acc"] if fused else
+                   calc_part_acc(part_pcs, pred_trans, gt_trans, pred_rot, gt_rot, valids)}
         if "contact_points" in data_dict:
-            metrics["connectivity_acc"] = calc_connectivity_acc(pred_trans, pred_rot, data_dict["contact_points"])
+            metrics["connectivity_acc"] = calc_connectivity_acc(pred_trans, pred_rot, data_dict["contact_points"],
+                                                                fused=self.fused_metrics)
         if not self.semantic:
             for m in ("mse", "rmse", "mae"):
-                metrics[f"trans_{m}"] = trans_metrics(pred_trans, gt_trans, valids, metric=m)
-                metrics[f"rot_{m}"] = rot_metrics(pred_rot, gt_rot, valids, metric=m)
+                metrics[f"trans_{m}"] = (fused[f"trans_{m}"] if fused else
+                                         trans_metrics(pred_trans, gt_trans, valids, metric=m))
+                metrics[f"rot_{m}"] = fused[f"rot_{m}"] if fused else rot_metrics(pred_rot, gt_rot, valids, metric=m)
         return metrics
 
     @staticmethod
@@ -251,6 +254,24 @@ class BaseModel(nn.Module):
 
     def _loss_function(self, data_dict, out_dict={}, optimizer_idx=-1):
         raise NotImplementedError
+
+    def _sample_loss(self, data_dict, out_dict, batch_keys, cache_keys):
+        """One min-of-N sample: `forward` on the batch's `batch_keys` plus what the previous sample left under
+        `cache_keys` (the features in front of the stochastic part of the model, computed once), then `_calc_loss`; the
+        cached entries travel on in the returned out_dict."""
+        pred = self.forward({k: data_dict[k] for k in batch_keys} | {k: out_dict.get(k, None) for k in cache_keys})
+        loss_dict, new_out = self._calc_loss(pred, data_dict)
+        new_out.update((k, pred[k]) for k in cache_keys)
+        return loss_dict, new_out
+
+    def _rounds_loss(self, rounds, data_dict):
+        """Loss of every round's prediction `(rot, trans)`, summed (`loss.sum_loss_rounds`) -> (terms, the last round's
+        out_dict)."""
+        per_round = []
+        for rot, trans in rounds:
+            loss_dict, out = self._calc_loss({"rot": rot, "trans": trans}, data_dict)
+            per_round.append(loss_dict)
+        return sum_loss_rounds(per_round), out
 
     def _shape_search(self):
         """`cfg.loss.shape_search` ("brute" | "grid" | "leaf" | "auto"; None: MPA_SHAPE_SEARCH, else "grid"): the exact
@@ -274,7 +295,7 @@ class BaseModel(nn.Module):
         Returns a shallow copy of `data_dict` carrying the pending order; the caller's dict is never touched (a cached
         order would go stale when a loader refills its batch tensors in place)."""
         pcs = data_dict["part_pcs"]
-        if not (self.fused_loss and not self.semantic and pcs.is_cuda) or search_mode(self._shape_search()) < 2:
+        if not (self._takes_fused_loss() and pcs.is_cuda) or search_mode(self._shape_search()) < 2:
             return data_dict  # (the grid / brute-force searches need no order)
         dev = pcs.device
         side = getattr(self, "_order_stream", None)
@@ -362,12 +383,9 @@ class BaseModel(nn.Module):
             if k.endswith("_loss"):
                 total = total + v * self.cfg.loss[f"{k}_w"]
         stacked["loss"] = total
-        if self.sample_iter == 1:
-            result = {k: v[0].mean() for k, v in stacked.items()}
-        else:
-            best = total.argmin(0)
-            cols = torch.arange(best.shape[0], device=best.device)
-            result = {k: v[best, cols].mean() for k, v in stacked.items()}
+        best = total.argmin(0)
+        cols = torch.arange(best.shape[0], device=best.device)
+        result = {k: v[best, cols].mean() for k, v in stacked.items()}
         if not self.training:
             result["batch_size"] = total.shape[1]
         return result
@@ -401,10 +419,7 @@ class BaseModel(nn.Module):
         call and the result reaches the host in one copy.  The caller's dict keeps its `part_quat`."""
         from .assemble import assemble_clouds
 
-        data_dict = dict(data_dict)
-        if "part_rot" not in data_dict:
-            part_rot = Rotation3D(data_dict.pop("part_quat"), rot_type="quat")
-            data_dict["part_rot"] = part_rot if self.rot_type == "quat" else part_rot.convert(self.rot_type)
+        data_dict = self._with_part_rot(data_dict)
         part_pcs = data_dict["part_pcs"]
         rots, trans = [], []
         for _ in range(self.sample_iter):

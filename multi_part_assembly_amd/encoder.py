@@ -16,17 +16,6 @@ from . import _lib
 from .gradsink import DeferredBackward, GradSink
 
 
-def _deliver(params, returned, skip):
-    """A parked backward ran outside autograd: add the gradients it RETURNED (the non-direct path; with a GradSink they
-    were written in place and the entries are None) to the parameters' .grad."""
-    for p, g in zip(params, returned[skip:]):
-        if g is not None:
-            if p.grad is None:
-                p.grad = g
-            else:
-                p.grad.add_(g)
-
-
 class _PointNetFn(torch.autograd.Function):
     """PointNet forward/backward on the HIP library (csrc/pointnet.hip).  The bf16 performance variant
     (csrc/pointnet_bf16.hip, `_PointNetBF16Fn`) differs in the entry points' suffix and in its workspace only."""
@@ -51,8 +40,7 @@ class _PointNetFn(torch.autograd.Function):
                     training, float(momentum), float(eps), M, N, F_, *ws, feat,
                     timer=f"pointnet_forward{cls.SUFFIX}[{M}x{N}x{F_}]")
         ctx.training = bool(training)
-        ctx.params = params
-        GradSink.note_use(params)
+        GradSink.register(ctx, params)
         ctx.save_for_backward(points, valids, *ws)
         return feat
 
@@ -62,25 +50,25 @@ class _PointNetFn(torch.autograd.Function):
             raise RuntimeError(f"{cls.LABEL}: backward is implemented for training-mode BatchNorm only")
         if DeferredBackward.active is not None:  # graph-mode data parallelism: run later, behind the first all-reduce
             saved = ctx.saved_tensors  # (autograd releases them when its own pass is over)
-            DeferredBackward.park(lambda g: _deliver(ctx.params, cls._run_backward(ctx, g, saved), 6), grad_feat, ctx.params)
-            return (None,) * (6 + len(ctx.params))
-        return cls._run_backward(ctx, grad_feat, ctx.saved_tensors)
+            DeferredBackward.park(lambda g: cls._run_backward(ctx, g, saved).accumulate(), grad_feat, ctx.params)
+            return (None,) * len(ctx.needs_input_grad)
+        grads = cls._run_backward(ctx, grad_feat, ctx.saved_tensors)
+        return (None, None, None, None, None, None, *grads.handed_back())
 
     @classmethod
     def _run_backward(cls, ctx, grad_feat, saved):
+        """The launch -> the parameter gradients it wrote (`gradsink.ParamGrads`)."""
         points, valids, *ws = saved
         params = ctx.params
         conv_w, bn_w = params[0:5], params[5:10]
         M, N, _ = points.shape
         F_ = conv_w[4].shape[0]
-        grads, direct = GradSink.outputs(params)
-        g_conv, g_bnw, g_bnb = grads[0:5], grads[5:10], grads[10:15]
+        grads = GradSink.outputs(params)
+        g = grads.buffers
         _lib.launch("mpa_pointnet_backward" + cls.SUFFIX, points.device, grad_feat.contiguous(), points, valids, conv_w,
-                    bn_w, M, N, F_, *ws, g_conv, g_bnw, g_bnb, timer=f"pointnet_backward{cls.SUFFIX}[{M}x{N}x{F_}]")
-        if direct:
-            GradSink.delivered(params)
-            return (None,) * (6 + len(params))
-        return (None, None, None, None, None, None, *grads)
+                    bn_w, M, N, F_, *ws, g[0:5], g[5:10], g[10:15],
+                    timer=f"pointnet_backward{cls.SUFFIX}[{M}x{N}x{F_}]")
+        return grads
 
 
 class _PointNetBF16Fn(_PointNetFn):
@@ -142,8 +130,7 @@ class PointNet(nn.Module):
 
     def forward_parts(self, part_pcs, valids):
         """part_pcs [M, N, 3], valids [M] (1/0) -> [M, feat_dim]; rows of padded parts are zero."""
-        if not part_pcs.is_cuda:
-            raise RuntimeError("PointNet: only CUDA (HIP) tensors are supported — no CPU fallback")
+        _lib.require_hip("PointNet", part_pcs)
         if not self._fused_ok():
             _warn_library_path(self, f"feat_dim = {self.feat_dim}, global_feat = {self.global_feat}")
             return _run_valid_parts(self._library_forward, part_pcs, valids, self.feat_dim, not self.global_feat)
@@ -243,8 +230,7 @@ class _DGCNNFn(torch.autograd.Function):
                 _lib.KernelTimer.add_phases([n], p)
         ctx.training = bool(training)
         ctx.want_point_grad = bool(want_point_grad)
-        ctx.params = params
-        GradSink.note_use(params)
+        GradSink.register(ctx, params)
         ctx.save_for_backward(pts, ws)
         return feat
 
@@ -254,9 +240,10 @@ class _DGCNNFn(torch.autograd.Function):
             raise RuntimeError("DGCNN: backward is implemented for training-mode BatchNorm only")
         if DeferredBackward.active is not None and not ctx.want_point_grad:
             saved = ctx.saved_tensors
-            DeferredBackward.park(lambda g: _deliver(ctx.params, _DGCNNFn._run_backward(ctx, g, saved), 8), grad_feat, ctx.params)
-            return (None,) * (8 + len(ctx.params))
-        return _DGCNNFn._run_backward(ctx, grad_feat, ctx.saved_tensors)
+            DeferredBackward.park(lambda g: _DGCNNFn._run_backward(ctx, g, saved)[1].accumulate(), grad_feat, ctx.params)
+            return (None,) * len(ctx.needs_input_grad)
+        gpts, grads = _DGCNNFn._run_backward(ctx, grad_feat, ctx.saved_tensors)
+        return (gpts, None, None, None, None, None, None, None, *grads.handed_back())
 
     @staticmethod
     def _run_backward(ctx, grad_feat, saved):
@@ -273,14 +260,12 @@ class _DGCNNFn(torch.autograd.Function):
         dev = pts.device
         # with a GradSink the kernels write the parameter gradients straight into the flat gradient buffer (every output
         # is overwritten in full) instead of 17 AccumulateGrad `add_` launches
-        grads, direct = GradSink.outputs(params)
+        grads = GradSink.outputs(params)
+        g = grads.buffers
         gpts = torch.empty_like(pts) if ctx.want_point_grad else None
-        _lib.launch("mpa_dgcnn_backward", dev, grad_feat.contiguous(), conv_w, bn_w, fc_w, M, N, F_, ws, grads[0:5],
-                    grads[5:10], grads[10:15], grads[15], grads[16], gpts, timer=f"dgcnn_backward[{M}x{N}x{F_}]")
-        if direct:
-            GradSink.delivered(params)
-            return (gpts,) + (None,) * (7 + len(params))
-        return (gpts, None, None, None, None, None, None, None, *grads)
+        _lib.launch("mpa_dgcnn_backward", dev, grad_feat.contiguous(), conv_w, bn_w, fc_w, M, N, F_, ws, g[0:5],
+                    g[5:10], g[10:15], g[15], g[16], gpts, timer=f"dgcnn_backward[{M}x{N}x{F_}]")
+        return gpts, grads
 
 
 class DGCNN(nn.Module):
@@ -355,8 +340,7 @@ class DGCNN(nn.Module):
 
     def forward_parts(self, part_pcs, valids):
         """part_pcs [M, N, 3], valids [M] (1/0) -> [M, feat_dim]; rows of padded parts are zero."""
-        if not part_pcs.is_cuda:
-            raise RuntimeError("DGCNN: only CUDA (HIP) tensors are supported — no CPU fallback")
+        _lib.require_hip("DGCNN", part_pcs)
         M, N, _ = part_pcs.shape
         if not self._fused_ok(N):
             _warn_library_path(self, f"N = {N}, feat_dim = {self.feat_dim}, global_feat = {self.global_feat}")
@@ -374,8 +358,7 @@ class DGCNN(nn.Module):
 
     def forward(self, x):
         """x [n, N, 3] -> [n, feat_dim] (global feature) or [n, N, feat_dim]; the reference's signature."""
-        if not x.is_cuda:
-            raise RuntimeError("DGCNN: only CUDA (HIP) tensors are supported — no CPU fallback")
+        _lib.require_hip("DGCNN", x)
         return self.forward_parts(x, torch.ones(x.shape[0], device=x.device))
 
 

@@ -30,10 +30,6 @@ class GlobalModel(BaseModel):
         self.pose_predictor = StocasticPoseRegressor(feat_dim=dim, noise_dim=cfg.loss.noise_dim,
                                                      rot_type=self.rot_type)
 
-    def _extract_part_feats(self, part_pcs, part_valids):
-        B, P, N, _ = part_pcs.shape
-        return self.encoder.forward_parts(part_pcs.reshape(B * P, N, 3), part_valids.reshape(-1)).view(B, P, -1)
-
     def forward(self, data_dict):
         feats = data_dict.get("pre_pose_feats", None)
         if feats is None:
@@ -48,9 +44,5 @@ class GlobalModel(BaseModel):
 
     def _loss_function(self, data_dict, out_dict={}, optimizer_idx=-1):
         """One MoN sample; the features in front of the stochastic pose head are computed once and reused."""
-        pred = self.forward({"part_pcs": data_dict["part_pcs"], "part_valids": data_dict["part_valids"],
-                             "part_label": data_dict["part_label"], "instance_label": data_dict["instance_label"],
-                             "pre_pose_feats": out_dict.get("pre_pose_feats", None)})
-        loss_dict, new_out = self._calc_loss(pred, data_dict)
-        new_out["pre_pose_feats"] = pred["pre_pose_feats"]
-        return loss_dict, new_out
+        return self._sample_loss(data_dict, out_dict, ("part_pcs", "part_valids", "part_label", "instance_label"),
+                                 ("pre_pose_feats",))

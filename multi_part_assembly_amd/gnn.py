@@ -31,7 +31,6 @@ from .encoder import build_encoder
 from .gnn_ops import (MERGE_MAX_PARTS, NARROW_MAX_IN, RELATION_MEAN_MAX_PARTS, merge_equal_parts, narrow_linear_relu,
                       pair_rows, pair_rows_supported, relation_head, relation_head_supported, relation_mean)
 from .gru import gru_recurrent, supported as gru_supported
-from .loss import LossTerms
 from .mlp import bn_counter_batch, mlp_layer, pair_layer, pair_layer_supported, supported as mlp_supported
 from .regressor import StocasticPoseRegressor
 
@@ -179,10 +178,6 @@ class DGLModel(BaseModel):
         return _clones(_PairMLP(2 * self.pc_feat_dim, self.pc_feat_dim), self.iter)
 
     # ---- pieces of one GNN iteration -----------------------------------------------------------------------
-    def _extract_part_feats(self, part_pcs, part_valids):
-        B, P, N, _ = part_pcs.shape
-        return self.encoder.forward_parts(part_pcs.reshape(B * P, N, 3), part_valids.reshape(-1)).view(B, P, -1)
-
     def _gather_same_class(self, data_dict):
         """Index groups of geometrically equivalent parts per sample (dgl/network.py:75-88); host-side, once per
         step, semantic datasets only."""
@@ -285,40 +280,13 @@ class DGLModel(BaseModel):
     def _loss_function(self, data_dict, out_dict={}, optimizer_idx=-1):
         """Loss of every iteration's prediction, summed (dgl/network.py:245-297); `part_feats` / `class_list` are
         reused across MoN samples."""
-        pred = self.forward({k: data_dict[k] for k in ("part_pcs", "part_valids", "part_label", "instance_label",
-                                                      "part_ids", "valid_matrix")}
-                            | {"part_feats": out_dict.get("part_feats", None),
-                               "class_list": out_dict.get("class_list", None)})
-        keep = {"part_feats": pred["part_feats"], "class_list": pred["class_list"]}
+        batch_keys = ("part_pcs", "part_valids", "part_label", "instance_label", "part_ids", "valid_matrix")
+        cache_keys = ("part_feats", "class_list")
         if not self.training:
-            loss_dict, out = self._calc_loss(pred, data_dict)
-            out.update(keep)
-            return loss_dict, out
-        per_iter, out = [], {}
-        iters = pred.get("_iters") or [(pred["rot"][i], pred["trans"][i]) for i in range(self.iter)]
-        for rot, trans in iters:
-            loss_dict, out = self._calc_loss({"rot": rot, "trans": trans}, data_dict)
-            per_iter.append(loss_dict)
-        out.update(keep)
-        names = list(per_iter[0])
-        stacks = [getattr(d, "stacked", None) for d in per_iter]
-        if all(st is not None and list(st[0]) == names for st in stacks):
-            # the fused loss hands every iteration's terms over as ONE [K, B] tensor: sum those (iter - 1 launches), and
-            # let `loss_function` weight the [K (iter + 1), B] concatenation directly — summing and re-stacking the
-            # terms one by one was ~100 small launches per step, forward and backward
-            summed = stacks[0][1]
-            for st in stacks[1:]:
-                summed = summed + st[1]
-            full = torch.cat([summed] + [st[1] for st in stacks], dim=0)
-            keys = names + [f"{k}_{i}" for i in range(self.iter) for k in names]
-            total = LossTerms((k, full[j]) for j, k in enumerate(keys))
-            total.stacked = (tuple(keys), full)
-            return total, out
-        total = {k: 0.0 for k in names}
-        for i, loss_dict in enumerate(per_iter):
-            for k, v in loss_dict.items():
-                total[k] = total[k] + v
-                total[f"{k}_{i}"] = v
+            return self._sample_loss(data_dict, out_dict, batch_keys, cache_keys)
+        pred = self.forward({k: data_dict[k] for k in batch_keys} | {k: out_dict.get(k, None) for k in cache_keys})
+        total, out = self._rounds_loss(pred["_iters"], data_dict)
+        out.update((k, pred[k]) for k in cache_keys)
         return total, out
 
 

@@ -23,9 +23,7 @@ class _NarrowLinearReLU(torch.autograd.Function):
         out = torch.empty((R, N), dtype=torch.float32, device=x.device)
         _lib.launch("mpa_narrow_linear_relu_forward", x.device, x, weight, bias, R, K, N, out,
                     timer=f"narrow_linear_relu_forward[{R}x{K}x{N}]")
-        ctx.params = [p for p in (weight, bias) if p is not None]
-        ctx.has_bias = bias is not None
-        GradSink.note_use(ctx.params)
+        GradSink.register(ctx, (weight, bias))
         ctx.save_for_backward(x, weight, out)
         return out
 
@@ -35,17 +33,12 @@ class _NarrowLinearReLU(torch.autograd.Function):
         R, K = x.shape
         N = weight.shape[0]
         gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        bufs, direct = GradSink.outputs(ctx.params)
-        gw = bufs[0]
-        gb = bufs[1] if ctx.has_bias else None
+        grads = GradSink.outputs(ctx.params)
         grad_out = grad_out.contiguous()
         ws = torch.empty(_lib.query("mpa_narrow_linear_relu_workspace", R, K, N), dtype=torch.float32, device=x.device)
-        _lib.launch("mpa_narrow_linear_relu_backward", x.device, grad_out, out, x, weight, R, K, N, ws, gx, gw, gb,
+        _lib.launch("mpa_narrow_linear_relu_backward", x.device, grad_out, out, x, weight, R, K, N, ws, gx, *grads.buffers,
                     timer=f"narrow_linear_relu_backward[{R}x{K}x{N}]")
-        if direct:
-            GradSink.delivered(ctx.params)
-            return gx, None, None
-        return gx, gw, gb
+        return (gx, *grads.handed_back())
 
 
 NARROW_MAX_IN = 16
@@ -53,8 +46,7 @@ NARROW_MAX_IN = 16
 
 def narrow_linear_relu(x, weight, bias=None):
     """relu(x W^T + b) for an input of at most 16 columns: x [..., K] -> [..., N]."""
-    if not x.is_cuda:
-        raise RuntimeError("narrow_linear_relu: only CUDA (HIP) tensors are supported — no CPU fallback")
+    _lib.require_hip("narrow_linear_relu", x)
     lead = x.shape[:-1]
     out = _NarrowLinearReLU.apply(_f32c(x).reshape(-1, x.shape[-1]), weight, bias)
     return out.view(*lead, weight.shape[0])
@@ -70,9 +62,7 @@ class _RelationHead(torch.autograd.Function):
         w = weight.reshape(-1)  # the Linear weight [1, K]: the same bytes
         _lib.launch("mpa_relation_head_forward", dev, h, w, bias, mask, R, K, ws, out,
                     timer=f"relation_head_forward[{R}x{K}]")
-        ctx.params = [p for p in (weight, bias) if p is not None]
-        ctx.has_bias = bias is not None
-        GradSink.note_use(ctx.params)
+        GradSink.register(ctx, (weight, bias))
         ctx.save_for_backward(h, w, mask, ws)
         return out
 
@@ -82,16 +72,11 @@ class _RelationHead(torch.autograd.Function):
         R, K = h.shape
         dev = h.device
         gh = torch.empty_like(h) if ctx.needs_input_grad[0] else None
-        bufs, direct = GradSink.outputs(ctx.params)
-        gw = bufs[0]
-        gb = bufs[1] if ctx.has_bias else None
+        grads = GradSink.outputs(ctx.params)
         grad_out = grad_out.contiguous()
-        _lib.launch("mpa_relation_head_backward", dev, grad_out, h, w, mask, R, K, ws, gh, gw, gb,
+        _lib.launch("mpa_relation_head_backward", dev, grad_out, h, w, mask, R, K, ws, gh, *grads.buffers,
                     timer=f"relation_head_backward[{R}x{K}]")
-        if direct:
-            GradSink.delivered(ctx.params)
-            return gh, None, None, None
-        return gh, gw, gb, None
+        return (gh, *grads.handed_back(), None)
 
 
 def relation_head_supported(width):
@@ -100,8 +85,7 @@ def relation_head_supported(width):
 
 def relation_head(h, weight, bias=None, mask=None):
     """sigmoid(h . w + b) [* mask]: h [..., K], weight [1, K] -> [...] (mask, if given, has the leading shape of h)."""
-    if not h.is_cuda:
-        raise RuntimeError("relation_head: only CUDA (HIP) tensors are supported — no CPU fallback")
+    _lib.require_hip("relation_head", h)
     lead = h.shape[:-1]
     m = None if mask is None else _f32c(mask.detach()).reshape(-1)
     return _RelationHead.apply(_f32c(h).reshape(-1, h.shape[-1]), weight, bias, m).view(*lead)
@@ -134,8 +118,7 @@ RELATION_MEAN_MAX_PARTS = 64
 
 def relation_mean(edge, rel):
     """edge [B, P, P, C], rel [B, P, P] -> [B, P, C]: sum_j edge_ij rel_ij / (sum_j rel_ij + 1e-6)."""
-    if not edge.is_cuda:
-        raise RuntimeError("relation_mean: only CUDA (HIP) tensors are supported — no CPU fallback")
+    _lib.require_hip("relation_mean", edge)
     B, P, P2, C = edge.shape
     out = _RelationMean.apply(_f32c(edge).reshape(B * P, P2, C), _f32c(rel).reshape(B * P, P2))
     return out.view(B, P, C)
@@ -169,8 +152,7 @@ def pair_rows_supported(width):
 
 def pair_rows(a, b, swap=False):
     """a, b [S, P, F] -> [S, P, P, 2F]: row (s, i, j) = [a[s, i] ; b[s, j]] (swap: [b[s, j] ; a[s, i]])."""
-    if not a.is_cuda:
-        raise RuntimeError("pair_rows: only CUDA (HIP) tensors are supported — no CPU fallback")
+    _lib.require_hip("pair_rows", a)
     return _PairRows.apply(_f32c(a), _f32c(b), bool(swap))
 
 
@@ -211,8 +193,7 @@ def merge_equal_parts(part_feats, pose_feats, part_valids, part_ids, ret_arg=Fal
     members' features: part_feats [B, P, C1], pose_feats [B, P, C2] -> the two merged tensors, in one launch, with no
     host copy of the ids (`DGLModel._merge_nodes` is the host loop it replaces; bit-equal).  Valid parts come first in
     every sample.  ret_arg: also the uint8 slot every value came from (the lowest on ties)."""
-    if not part_feats.is_cuda:
-        raise RuntimeError("merge_equal_parts: only CUDA (HIP) tensors are supported — no CPU fallback")
+    _lib.require_hip("merge_equal_parts", part_feats)
     valids = _f32c(part_valids.detach())
     ids = part_ids.detach().to(torch.int32).contiguous()
     out = _MergeEqualParts.apply(_f32c(part_feats), _f32c(pose_feats), valids, ids)

@@ -8,7 +8,7 @@ Adam step and the data-parallel all-reduce operate on — and the Function retur
 
 Safety rule: overwriting is only equivalent to accumulating when the parameter receives exactly ONE gradient
 contribution in the step and its .grad was zeroed before.  The sink therefore counts, per step, how many Function
-calls used each parameter (`note_use`, called from forward); a parameter used more than once (e.g. the pose
+calls used each parameter (`register`, called from forward); a parameter used more than once (e.g. the pose
 head under MoN sampling, base_model.py:113-148 upstream) falls back to the returned-tensor path.  `on_ready` is
 the data-parallel bucket hook (dp.BucketedGradReducer._on_grad), which AccumulateGrad would otherwise trigger.
 """
@@ -35,28 +35,62 @@ class GradSink:
 
     # ---- called by the autograd Functions ------------------------------------------------------------------
     @staticmethod
-    def note_use(params):
+    def register(ctx, params):
+        """From `forward`: keep the Parameter objects themselves (a slot may be None: an absent bias) on `ctx.params`
+        and count one use of each in this step."""
+        ctx.params = tuple(params)
         sink = GradSink.active
         if sink is not None:
-            for p in params:
-                sink.uses[id(p)] = sink.uses.get(id(p), 0) + 1
+            for p in ctx.params:
+                if p is not None:
+                    sink.uses[id(p)] = sink.uses.get(id(p), 0) + 1
 
     @staticmethod
     def outputs(params):
-        """-> (buffers, direct): the tensors the backward kernels must overwrite with d loss / d param."""
+        """From `backward`, before the launch -> the `ParamGrads` holding the tensors the kernels must overwrite with
+        d loss / d param: the parameters' own .grad when that equals accumulating (the safety rule above)."""
         sink = GradSink.active
-        if sink is not None and all(
-                sink.uses.get(id(p)) == 1 and p.is_leaf and p.grad is not None and p.grad.is_contiguous()
-                and p.grad.dtype == torch.float32 and p.grad.device == p.device for p in params):
-            return [p.grad for p in params], True
-        return [torch.empty_like(p) for p in params], False
+        if sink is not None:
+            own = []
+            for p in params:
+                g = None if p is None else p.grad  # (read once: the attribute is the costly part of this test)
+                if p is not None and not (sink.uses.get(id(p)) == 1 and p.is_leaf and g is not None and g.is_contiguous()
+                                          and g.dtype == torch.float32 and g.device == p.device):
+                    break
+                own.append(g)
+            else:
+                return ParamGrads(params, own, True)
+        return ParamGrads(params, [None if p is None else torch.empty_like(p) for p in params], False)
 
-    @staticmethod
-    def delivered(params):
+
+class ParamGrads:
+    """The parameter gradients of one backward call: `buffers` (one per parameter, None for an absent one) go to the
+    launch, `handed_back()` after it gives the entries that end `backward`'s result."""
+    __slots__ = ("params", "buffers", "direct")
+
+    def __init__(self, params, buffers, direct):
+        self.params, self.buffers, self.direct = params, buffers, direct
+
+    def handed_back(self):
+        """-> len(params) entries: the tensors for autograd to accumulate, or — written in place — None each, after
+        telling `on_ready` about every parameter."""
+        if not self.direct:
+            return tuple(self.buffers)
         sink = GradSink.active
         if sink is not None and sink.on_ready is not None:
-            for p in params:
-                sink.on_ready(p)
+            for p in self.params:
+                if p is not None:
+                    sink.on_ready(p)
+        return (None,) * len(self.params)
+
+    def accumulate(self):
+        """A parked backward ran outside autograd: add what `handed_back()` would have returned to the .grad's."""
+        for p, g in zip(self.params, self.handed_back()):
+            if g is not None:
+                if p.grad is None:
+                    p.grad = g
+                else:
+                    p.grad.add_(g)
 
 
 class DeferredBackward:

@@ -58,6 +58,15 @@ def raise_if_failed(device=None, synchronize=False):
                 "MPA_GRU=library to keep the library GRU")
 
 
+def launch_watched(name, dev, *args, timer=None):
+    """`_lib.launch` of an entry point whose blocks wait for each other: look at the pinned copy first, pass the device's
+    status word as the last argument in front of the stream, and queue the copy of the word behind the launch."""
+    raise_if_failed(dev)
+    word, host = _status(dev)
+    _lib.launch(name, dev, *args, word, timer=timer)
+    host.copy_(word, non_blocking=True)
+
+
 class _GRURecurrentFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, gi, h0, whh, bhh):
@@ -66,11 +75,8 @@ class _GRURecurrentFn(torch.autograd.Function):
         dev = gi.device
         ws = torch.empty(_lib.query("mpa_gru_workspace", D, B, T, H), dtype=torch.float32, device=dev)
         out = torch.empty((D, B, T, H), dtype=torch.float32, device=dev)
-        raise_if_failed(dev)
-        word, host = _status(dev)
-        _lib.launch("mpa_gru_forward", dev, gi, h0, whh, bhh, D, B, T, H, ws, out, word,
-                    timer=f"gru_forward[{D}x{B}x{T}x{H}]")
-        host.copy_(word, non_blocking=True)
+        launch_watched("mpa_gru_forward", dev, gi, h0, whh, bhh, D, B, T, H, ws, out,
+                       timer=f"gru_forward[{D}x{B}x{T}x{H}]")
         ctx.save_for_backward(h0, whh, out, ws)
         return out
 
@@ -83,11 +89,8 @@ class _GRURecurrentFn(torch.autograd.Function):
         gw = torch.empty_like(whh)
         gb = torch.empty((D, 3 * H), dtype=torch.float32, device=dev)
         grad_out = grad_out.contiguous()
-        raise_if_failed(dev)
-        word, host = _status(dev)
-        _lib.launch("mpa_gru_backward", dev, grad_out, h0, whh, out, D, B, T, H, ws, ggi, gw, gb, word,
-                    timer=f"gru_backward[{D}x{B}x{T}x{H}]")
-        host.copy_(word, non_blocking=True)
+        launch_watched("mpa_gru_backward", dev, grad_out, h0, whh, out, D, B, T, H, ws, ggi, gw, gb,
+                       timer=f"gru_backward[{D}x{B}x{T}x{H}]")
         return ggi, None, gw, gb
 
 
@@ -113,8 +116,7 @@ def gru_recurrent(gi, h0, whh, bhh):
     -> hidden states of every step [D, B, T, H] (torch.nn.GRU's equations).
     The initial state is DATA: `h0` is detached and takes no gradient (the callers' initial states are random draws or
     zeros); an `h0` that requires one is an error instead of a silently missing gradient."""
-    if not gi.is_cuda:
-        raise RuntimeError("gru_recurrent: only CUDA (HIP) tensors are supported — no CPU fallback")
+    _lib.require_hip("gru_recurrent", gi)
     if h0.requires_grad:
         raise RuntimeError("gru_recurrent: the backward pass does not compute the initial state's gradient — pass "
                            "h0.detach() (csrc/gru.hip treats h0 as data)")

@@ -266,14 +266,38 @@ class LossTerms(dict):
     stacked = None
 
 
+def sum_loss_rounds(per_round):
+    """The terms of a model's rounds (GNN iterations, refinement steps), each a {name: [B]} with the same names -> the
+    sums under `name`, then every round's own terms under `name_i`, round-major.  Where every round carries its terms as
+    ONE [K, B] tensor (`LossTerms.stacked`, the fused loss) those are summed (rounds - 1 launches) and `loss_function`
+    weights the [K (rounds + 1), B] concatenation directly — summing and re-stacking the terms one by one is ~100 small
+    launches per step, forward and backward."""
+    names = list(per_round[0])
+    keys = names + [f"{k}_{i}" for i in range(len(per_round)) for k in names]
+    stacks = [getattr(d, "stacked", None) for d in per_round]
+    if all(st is not None and list(st[0]) == names for st in stacks):
+        summed = stacks[0][1]
+        for st in stacks[1:]:
+            summed = summed + st[1]
+        full = torch.cat([summed] + [st[1] for st in stacks], dim=0)
+        total = LossTerms((k, full[j]) for j, k in enumerate(keys))
+        total.stacked = (tuple(keys), full)
+        return total
+    total = {k: 0.0 for k in names}
+    for i, loss_dict in enumerate(per_round):
+        for k, v in loss_dict.items():
+            total[k] = total[k] + v
+            total[f"{k}_{i}"] = v
+    return total
+
+
 def part_order(part_pcs, valids):
     """The k-d order of a batch's parts that both Chamfer searches of the fused loss run on (csrc/leaf_nn.hip,
     `mpa_assembly_order`): a function of `part_pcs` and `valids` only — not of any pose — so ONE ordering serves every
     loss evaluation of a step (the GNN iterations of DGL / RGL-NET, the min-of-N samples, both directions).  Returns a
     float32 tensor to pass as `geometric_assembly_loss(..., order=...)`, or None where the loss keeps its grid search
     (N > 2048).  Only steers speed: the loss is bit-identical with or without it."""
-    if not part_pcs.is_cuda:
-        raise RuntimeError("part_order: only CUDA (HIP) tensors are supported")
+    _lib.require_hip("part_order", part_pcs)
     B, P, N, _ = part_pcs.shape
     ne = _lib.query("mpa_assembly_order_elems", B, P, N)
     if ne == 0:
@@ -402,8 +426,7 @@ def geometric_assembly_loss(part_pcs, pred_trans, pred_rot, gt_trans, gt_rot, va
     Chamfer terms — identical results.  `order`: `part_order(part_pcs, valids)` of this batch for "leaf" / "auto" when the
     caller evaluates the loss more than once per batch (computed by the call itself when None).
     """
-    if not part_pcs.is_cuda:
-        raise RuntimeError("geometric_assembly_loss: only CUDA (HIP) tensors are supported")
+    _lib.require_hip("geometric_assembly_loss", part_pcs)
     B, P, N, _ = part_pcs.shape
     f = lambda t: t.detach().to(torch.float32).contiguous()
     if pred_rot.rot_type != gt_rot.rot_type:

@@ -74,11 +74,8 @@ class _DecoderFn(torch.autograd.Function):
         z1 = torch.empty((P, B, _Z), dtype=torch.float32, device=dev)
         y = torch.empty((P, B, _C), dtype=torch.float32, device=dev)
         mask_c = mask.contiguous() if (mask is not None and target is None) else None
-        _gru.raise_if_failed(dev)
-        word, host = _gru._status(dev)
-        _lib.launch("mpa_seq2seq_decoder_forward", dev, gi, mask_c, h0, w_ih, b_ih, w_hh, b_hh, w1, b1, w2, b2, B, P, ws,
-                    hs, z1, y, word, timer=f"seq2seq_decoder_forward[{B}x{P}]")
-        host.copy_(word, non_blocking=True)
+        _gru.launch_watched("mpa_seq2seq_decoder_forward", dev, gi, mask_c, h0, w_ih, b_ih, w_hh, b_hh, w1, b1, w2, b2,
+                            B, P, ws, hs, z1, y, timer=f"seq2seq_decoder_forward[{B}x{P}]")
         if target is None:  # free running: the inputs were the launch's own outputs (the same values)
             x = torch.cat([torch.zeros_like(y[:1]), y[:-1]], dim=0)
             if mask is not None:
@@ -109,11 +106,8 @@ def _decoder_backward(ctx, dy):
     dwhh = torch.empty_like(w_hh)
     dbhh = torch.empty((3 * _H,), dtype=torch.float32, device=dev)
     dh0 = torch.empty((B, _H), dtype=torch.float32, device=dev)
-    _gru.raise_if_failed(dev)
-    word, host = _gru._status(dev)
-    _lib.launch("mpa_seq2seq_decoder_backward", dev, dh, h0, w_hh, hs, B, P, ws, dgi, dwhh, dbhh, dh0, word,
-                timer=f"seq2seq_decoder_backward[{B}x{P}]")
-    host.copy_(word, non_blocking=True)
+    _gru.launch_watched("mpa_seq2seq_decoder_backward", dev, dh, h0, w_hh, hs, B, P, ws, dgi, dwhh, dbhh, dh0,
+                        timer=f"seq2seq_decoder_backward[{B}x{P}]")
     dgi2 = dgi.reshape(P * B, 3 * _H)
     dwih = dgi2.t() @ x.reshape(P * B, _C)
     dbih = dgi2.sum(0)
@@ -138,11 +132,8 @@ class _DecoderSelFn(torch.autograd.Function):
         hs = torch.empty((P, B, _H), dtype=torch.float32, device=dev)
         z1 = torch.empty((P, B, _Z), dtype=torch.float32, device=dev)
         y = torch.empty((P, B, _C), dtype=torch.float32, device=dev)
-        _gru.raise_if_failed(dev)
-        word, host = _gru._status(dev)
-        _lib.launch("mpa_seq2seq_decoder_forward_sel", dev, gi, mask, teacher, h0, w_ih, b_ih, w_hh, b_hh, w1, b1, w2, b2,
-                    B, P, ws, hs, z1, y, word, timer=f"seq2seq_decoder_forward[{B}x{P}]")
-        host.copy_(word, non_blocking=True)
+        _gru.launch_watched("mpa_seq2seq_decoder_forward_sel", dev, gi, mask, teacher, h0, w_ih, b_ih, w_hh, b_hh, w1, b1,
+                            w2, b2, B, P, ws, hs, z1, y, timer=f"seq2seq_decoder_forward[{B}x{P}]")
         # the step inputs behind dW_ih: the targets, or the launch's own outputs (the same values it fed back)
         xy = torch.cat([torch.zeros_like(y[:1]), y[:-1]], dim=0)
         if mask is not None:
@@ -403,10 +394,6 @@ class LSTMModel(BaseModel):
         """The counter of the device-side draws (None on host draws): `BaseModel.loss_function` begins its steps."""
         return getattr(self.seq2seq, "draw_counter", None)
 
-    def _extract_part_feats(self, part_pcs, part_valids):
-        B, P, N, _ = part_pcs.shape
-        return self.encoder.forward_parts(part_pcs.reshape(B * P, N, 3), part_valids.reshape(-1)).view(B, P, -1)
-
     def forward(self, data_dict):
         part_feats = data_dict.get("part_feats", None)
         if part_feats is None:
@@ -421,9 +408,5 @@ class LSTMModel(BaseModel):
 
     def _loss_function(self, data_dict, out_dict={}, optimizer_idx=-1):
         """One MoN sample: the part features are reused, the seq2seq (new coin, noise and masks) re-runs."""
-        pred = self.forward({"part_pcs": data_dict["part_pcs"], "part_valids": data_dict["part_valids"],
-                             "part_label": data_dict["part_label"], "instance_label": data_dict["instance_label"],
-                             "part_feats": out_dict.get("part_feats", None)})
-        loss_dict, new_out = self._calc_loss(pred, data_dict)
-        new_out["part_feats"] = pred["part_feats"]
-        return loss_dict, new_out
+        return self._sample_loss(data_dict, out_dict, ("part_pcs", "part_valids", "part_label", "instance_label"),
+                                 ("part_feats",))

@@ -96,8 +96,7 @@ class MatchSampler(torch.nn.Module):
 def linear_sum_assignment(cost: torch.Tensor, sizes: torch.Tensor | None = None) -> torch.Tensor:
     """cost [problems, ld, ld] float32 on the HIP device (sizes[i] x sizes[i] used; default the full ld) ->
     col4row [problems, ld] int32, the column assigned to each row (scipy's `col_ind`; -1 past the size)."""
-    if not cost.is_cuda:
-        raise RuntimeError("linear_sum_assignment: only CUDA (HIP) tensors are supported")
+    _lib.require_hip("linear_sum_assignment", cost)
     cost = cost.detach().to(torch.float32).contiguous()
     problems, ld, ld2 = cost.shape
     assert ld == ld2, "square problems only"
@@ -122,8 +121,7 @@ def match_parts(part_pcs, pred_trans, pred_quat, gt_trans, gt_quat, match_ids, s
     static number of group slots G = `static_groups(P)`: nothing is read back, so the call can be captured.  The
     contract on `match_ids` in that mode: no id above P // 2 — groups numbered consecutively from 1 with at least two
     members each, as `datasets.match_ids` builds them (it checks); a larger id would be left unmatched."""
-    if not part_pcs.is_cuda:
-        raise RuntimeError("match_parts: only CUDA (HIP) tensors are supported")
+    _lib.require_hip("match_parts", part_pcs)
     B, P, N, _ = part_pcs.shape
     dev = part_pcs.device
     f = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()

@@ -22,11 +22,10 @@ class _MLPLayerFn(torch.autograd.Function):
         rm, rv = running if running is not None else (None, None)
         _lib.launch("mpa_mlp_layer_forward", dev, x, x.stride(0), w, bias, gamma, beta, rm, rv, int(training),
                     float(momentum), float(eps), int(relu), R, K, N, ws, out, timer=f"mlp_layer_forward[{R}x{K}x{N}]")
-        ctx.meta = (bool(relu), bool(training), bias is not None, gamma is not None)
+        ctx.meta = (bool(relu), bool(training), gamma is not None)
         # the parameters themselves (not views of them): with a GradSink active their gradients are written straight
         # into the flat gradient buffer instead of going through one AccumulateGrad `add` launch per parameter
-        ctx.params = [p for p in (weight, bias, gamma, beta) if p is not None]
-        GradSink.note_use(ctx.params)
+        GradSink.register(ctx, (weight, bias, gamma, beta))
         ctx.save_for_backward(x, w, gamma, out, ws)
         return out
 
@@ -37,26 +36,18 @@ class _MLPLayerFn(torch.autograd.Function):
                                "same forward (retain_graph=True) is not supported — run the forward again")
         ctx.consumed = True
         x, w, gamma, out, ws = ctx.saved_tensors
-        relu, training, has_bias, has_bn = ctx.meta
+        relu, training, has_bn = ctx.meta
         if has_bn and not training:
             raise RuntimeError("MLP layer: backward is implemented for training-mode BatchNorm only")
         R, K = x.shape
         N = w.shape[0]
         dev = x.device
         gx = torch.empty((R, K), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-        bufs, direct = GradSink.outputs(ctx.params)
-        it = iter(bufs)
-        gw = next(it)
-        gb = next(it) if has_bias else None
-        gg = next(it) if has_bn else None
-        gbe = next(it) if has_bn else None
+        grads = GradSink.outputs(ctx.params)  # (weight, bias, gamma, beta): None where the layer has none
         grad_out = grad_out.contiguous()
         _lib.launch("mpa_mlp_layer_backward", dev, grad_out, x, x.stride(0), w, gamma, out, int(relu), R, K, N, ws, gx,
-                    gw, gb, gg, gbe, timer=f"mlp_layer_backward[{R}x{K}x{N}]")
-        if direct:
-            GradSink.delivered(ctx.params)
-            return gx, None, None, None, None, None, None, None, None, None
-        return gx, gw, gb, gg, gbe, None, None, None, None, None
+                    *grads.buffers, timer=f"mlp_layer_backward[{R}x{K}x{N}]")
+        return (gx, *grads.handed_back(), None, None, None, None, None)
 
 
 class _PairLayerFn(torch.autograd.Function):
@@ -73,10 +64,9 @@ class _PairLayerFn(torch.autograd.Function):
         rm, rv = running
         _lib.launch("mpa_pair_layer_forward", dev, a, b, w, bias, gamma, beta, rm, rv, int(training), float(momentum),
                     float(eps), int(relu), B, P, F, N, ws, out, timer=f"pair_layer_forward[{B}x{P}x{P}x{2 * F}x{N}]")
-        ctx.meta = (bool(relu), bool(training), bias is not None)
+        ctx.meta = (bool(relu), bool(training))
         ctx.same = a.data_ptr() == b.data_ptr() and a.shape == b.shape
-        ctx.params = [p for p in (weight, bias, gamma, beta) if p is not None]
-        GradSink.note_use(ctx.params)
+        GradSink.register(ctx, (weight, bias, gamma, beta))
         ctx.save_for_backward(a, b, w, gamma, out, ws)
         return out
 
@@ -87,7 +77,7 @@ class _PairLayerFn(torch.autograd.Function):
                                "same forward (retain_graph=True) is not supported — run the forward again")
         ctx.consumed = True
         a, b, w, gamma, out, ws = ctx.saved_tensors
-        relu, training, has_bias = ctx.meta
+        relu, training = ctx.meta
         if not training:
             raise RuntimeError("pair layer: backward is implemented for training-mode BatchNorm only")
         B, P, F = a.shape
@@ -98,20 +88,13 @@ class _PairLayerFn(torch.autograd.Function):
         same = ctx.same and ga is not None and gb is not None
         if same:
             gb = ga  # one tensor in both roles: the library adds the second half's gradient into the first's buffer
-        bufs, direct = GradSink.outputs(ctx.params)
-        it = iter(bufs)
-        gw = next(it)
-        gbias = next(it) if has_bias else None
-        gg, gbe = next(it), next(it)
+        grads = GradSink.outputs(ctx.params)  # (weight, bias, gamma, beta): None for an absent bias
         grad_out = grad_out.contiguous()
         _lib.launch("mpa_pair_layer_backward", dev, grad_out, a, b, w, gamma, out, int(relu), B, P, F, N, ws, ga, gb,
-                    gw, gbias, gg, gbe, timer=f"pair_layer_backward[{B}x{P}x{P}x{2 * F}x{N}]")
+                    *grads.buffers, timer=f"pair_layer_backward[{B}x{P}x{P}x{2 * F}x{N}]")
         if same:
             gb = None  # (already inside ga)
-        if direct:
-            GradSink.delivered(ctx.params)
-            return (ga, gb) + (None,) * 9
-        return ga, gb, gw, gbias, gg, gbe, None, None, None, None, None
+        return (ga, gb, *grads.handed_back(), None, None, None, None, None)
 
 
 def pair_layer_supported(feat, out_dim):
@@ -122,8 +105,7 @@ def pair_layer(a, b, weight, bias, bn, relu=True, training=True):
     """a, b [B, P, F] (CUDA) -> [B*P*P, N] = act(bn([a_i ; b_j] W^T + bias)), row (s, i, j) at (s*P + i)*P + j: the first
     Conv1d(k=1) + BatchNorm1d (+ ReLU) of the edge MLP over all part pairs, computed from two GEMMs over the B*P part rows
     (the pair tensor of dgl/network.py:135-144 is never built).  `weight` [N, 2F] or the Conv1d weight [N, 2F, 1]."""
-    if not a.is_cuda:
-        raise RuntimeError("pair_layer: only CUDA (HIP) tensors are supported — no CPU fallback")
+    _lib.require_hip("pair_layer", a)
     a, b = a.float().contiguous(), b.float().contiguous()
     if training:
         _count_batch(bn)
@@ -166,8 +148,7 @@ def supported(in_dim, out_dim):
 def mlp_layer(x, weight, bias=None, bn=None, relu=True, training=True):
     """x [R, K] (CUDA, fp32, rows contiguous) -> [R, N] = act(bn(x W^T + b)).  `weight` [N, K] or a Conv1d weight
     [N, K, 1]; `bn`: an nn.BatchNorm1d (its running statistics are updated in training mode) or None."""
-    if not x.is_cuda:
-        raise RuntimeError("mlp_layer: only CUDA (HIP) tensors are supported — no CPU fallback")
+    _lib.require_hip("mlp_layer", x)
     x = x.float()
     if x.stride(1) != 1 or x.stride(0) % 4 != 0:
         x = x.contiguous()

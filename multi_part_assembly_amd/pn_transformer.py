@@ -18,6 +18,8 @@ from .transformer import TransformerEncoder
 
 
 class PNTransformer(BaseModel):
+    BATCH_KEYS = ("part_pcs", "part_valids", "part_label", "instance_label")
+
     def __init__(self, cfg):
         super().__init__(cfg)
         m = cfg.model
@@ -40,13 +42,6 @@ class PNTransformer(BaseModel):
             dim += self.cfg.data.num_part_category
         return StocasticPoseRegressor(feat_dim=dim, noise_dim=self.cfg.loss.noise_dim, rot_type=self.rot_type)
 
-    def _extract_part_feats(self, part_pcs, part_valids):
-        """[B, P, N, 3] -> [B, P, C]; padded slots get zeros (network.py:59-68)."""
-        B, P, N, _ = part_pcs.shape
-        # mask in, zeros out: the valid parts are counted and compacted on the device, no host sync
-        feats = self.encoder.forward_parts(part_pcs.reshape(B * P, N, 3), part_valids.reshape(-1))
-        return feats.view(B, P, self.pc_feat_dim)
-
     def forward(self, data_dict):
         feats = data_dict.get("pre_pose_feats", None)
         if feats is None:
@@ -59,15 +54,9 @@ class PNTransformer(BaseModel):
         return {"rot": self._wrap_rotation(rot), "trans": trans, "pre_pose_feats": feats}
 
     def _loss_function(self, data_dict, out_dict={}, optimizer_idx=-1):
-        """One MoN sample: predict, then `_calc_loss`; the encoder/transformer features are cached in
-        `pre_pose_feats` because only the pose head is stochastic (network.py:106-139)."""
-        pred = self.forward({
-            "part_pcs": data_dict["part_pcs"], "part_valids": data_dict["part_valids"],
-            "part_label": data_dict["part_label"], "instance_label": data_dict["instance_label"],
-            "pre_pose_feats": out_dict.get("pre_pose_feats", None)})
-        loss_dict, new_out = self._calc_loss(pred, data_dict)
-        new_out["pre_pose_feats"] = pred["pre_pose_feats"]
-        return loss_dict, new_out
+        """One MoN sample; the encoder/transformer features are cached in `pre_pose_feats` because only the pose head
+        is stochastic (network.py:106-139)."""
+        return self._sample_loss(data_dict, out_dict, self.BATCH_KEYS, ("pre_pose_feats",))
 
 
 class PosEncoder(nn.Module):
@@ -137,28 +126,18 @@ class PNTransformerRefine(PNTransformer):
             rots.append(rot)
             transs.append(trans)
             pose = torch.cat([rot, trans], dim=-1)
-        if self.training:
-            rot, trans = self._wrap_rotation(torch.stack(rots, dim=0)), torch.stack(transs, dim=0)
-        else:
-            rot, trans = self._wrap_rotation(rots[-1]), transs[-1]
-        return {"rot": rot, "trans": trans, "pc_feats": pc_feats}
+        if not self.training:
+            return {"rot": self._wrap_rotation(rots[-1]), "trans": transs[-1], "pc_feats": pc_feats}
+        # `_iters`: the per-round predictions as they were produced, for the loss (see DGLModel._forward)
+        return {"rot": self._wrap_rotation(torch.stack(rots, dim=0)), "trans": torch.stack(transs, dim=0),
+                "pc_feats": pc_feats, "_iters": [(self._wrap_rotation(r), t) for r, t in zip(rots, transs)]}
 
     def _loss_function(self, data_dict, out_dict={}, optimizer_idx=-1):
-        pred = self.forward({"part_pcs": data_dict["part_pcs"], "part_valids": data_dict["part_valids"],
-                             "part_label": data_dict["part_label"], "instance_label": data_dict["instance_label"],
-                             "pc_feats": out_dict.get("pc_feats", None)})
+        """Loss of every round's prediction, summed (network_refine.py:131-175); `pc_feats` is reused across MoN samples."""
         if not self.training:
-            loss_dict, out = self._calc_loss(pred, data_dict)
-            out["pc_feats"] = pred["pc_feats"]
-            return loss_dict, out
-        total, out = None, {}
-        for i in range(self.refine_steps):
-            loss_dict, out = self._calc_loss({"rot": pred["rot"][i], "trans": pred["trans"][i]}, data_dict)
-            if total is None:
-                total = {k: 0.0 for k in loss_dict}
-            for k, v in loss_dict.items():
-                total[k] = total[k] + v
-                total[f"{k}_{i}"] = v
+            return self._sample_loss(data_dict, out_dict, self.BATCH_KEYS, ("pc_feats",))
+        pred = self.forward({k: data_dict[k] for k in self.BATCH_KEYS} | {"pc_feats": out_dict.get("pc_feats", None)})
+        total, out = self._rounds_loss(pred["_iters"], data_dict)
         out["pc_feats"] = pred["pc_feats"]
         return total, out
 

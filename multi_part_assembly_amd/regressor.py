@@ -30,8 +30,8 @@ class _PoseHeadFn(torch.autograd.Function):
         rot = torch.empty((M, width), dtype=torch.float32, device=dev)
         trans = torch.empty((M, 3), dtype=torch.float32, device=dev)
         _lib.launch(name + "_forward", dev, x, params, M, Fdim, ws, rot, trans, timer=f"pose_head_forward[{M}x{Fdim}]")
-        ctx.params, ctx.name = params, name
-        GradSink.note_use(params)
+        ctx.name = name
+        GradSink.register(ctx, params)
         ctx.save_for_backward(x, ws)
         return rot, trans
 
@@ -42,13 +42,10 @@ class _PoseHeadFn(torch.autograd.Function):
         M, Fdim = x.shape
         dev = x.device
         grad_x = torch.empty_like(x)
-        grads, direct = GradSink.outputs(params)
+        grads = GradSink.outputs(params)
         _lib.launch(ctx.name + "_backward", dev, grad_rot.contiguous(), grad_trans.contiguous(), x, params, M, Fdim, ws,
-                    grad_x, grads, timer=f"pose_head_backward[{M}x{Fdim}]")
-        if direct:
-            GradSink.delivered(params)
-            return (grad_x, None, *([None] * len(params)))
-        return (grad_x, None, *grads)
+                    grad_x, grads.buffers, timer=f"pose_head_backward[{M}x{Fdim}]")
+        return (grad_x, None, *grads.handed_back())
 
 
 class PoseRegressor(nn.Module):
@@ -66,8 +63,7 @@ class PoseRegressor(nn.Module):
 
     def forward(self, x):
         """x [B, C] or [B, P, C] -> (rot [.., 4] unit-normalised or [.., 6] orthonormalised, trans [.., 3])."""
-        if not x.is_cuda:
-            raise RuntimeError("PoseRegressor: only CUDA (HIP) tensors are supported — no CPU fallback")
+        _lib.require_hip("PoseRegressor", x)
         if self.native:
             lead = x.shape[:-1]
             # (any input width: the library zero-pads odd widths — labels / noise appended — to its 64-column GEMM panels)

@@ -32,8 +32,7 @@ class _TransformerFn(torch.autograd.Function):
                     int(seed), seed_dev, ws, out,
                     timer=f"transformer_forward[{B}x{P}x{D}]")
         ctx.meta = (heads, FF, L, float(dropout_p), int(seed))
-        ctx.params = params  # the Parameter objects themselves (GradSink writes into their .grad)
-        GradSink.note_use(params)
+        GradSink.register(ctx, params)  # the Parameter objects themselves (GradSink writes into their .grad)
         ctx.seed_dev = seed_dev
         ctx.save_for_backward(valid, ws)
         return out
@@ -47,14 +46,11 @@ class _TransformerFn(torch.autograd.Function):
         dev = grad_out.device
         grad_out = grad_out.contiguous()
         grad_tokens = torch.empty_like(grad_out)
-        grads, direct = GradSink.outputs(params)
+        grads = GradSink.outputs(params)
         _lib.launch("mpa_transformer_backward", dev, grad_out, valid, params, B, P, D, heads, FF, L, dropout_p, seed,
-                    ctx.seed_dev, ws, grad_tokens, grads,
+                    ctx.seed_dev, ws, grad_tokens, grads.buffers,
                     timer=f"transformer_backward[{B}x{P}x{D}]")
-        if direct:
-            GradSink.delivered(params)
-            return (grad_tokens, None, None, None, None, None, *([None] * len(params)))
-        return (grad_tokens, None, None, None, None, None, *grads)
+        return (grad_tokens, None, None, None, None, None, *grads.handed_back())
 
 
 class TransformerEncoder(nn.Module):
@@ -124,8 +120,7 @@ class TransformerEncoder(nn.Module):
         """tokens [B, N, C]; valid_masks [B, N] bool (True = real part), or the float validity matrix itself (a part is
         real iff its entry == 1: the kernels apply the reference's `part_valids == 1` themselves, which spares the
         compare and the cast), or None -> [B, N, C]."""
-        if not tokens.is_cuda:
-            raise RuntimeError("TransformerEncoder: only CUDA (HIP) tensors are supported — no CPU fallback")
+        _lib.require_hip("TransformerEncoder", tokens)
         if valid_masks is not None:
             assert valid_masks.shape == tokens.shape[:2]
         if not self.native or tokens.shape[1] > 64:

@@ -47,8 +47,7 @@ def pose_apply(pc, quat, trans=None, mask=None, fill=0.0):
     Parts with mask == 0 have their points replaced by `fill` before the transform (the padded-part
     fill of shape_cd_loss, reference utils/loss.py:173-175).  fp32, CUDA tensors only.
     """
-    if not pc.is_cuda:
-        raise RuntimeError("pose_apply: only CUDA (HIP) tensors are supported")
+    _lib.require_hip("pose_apply", pc)
     lead = pc.shape[:-2]
     if quat.shape[:-1] != lead or quat.shape[-1] != 4 or pc.shape[-1] != 3:
         raise RuntimeError(f"pose_apply: shape mismatch pc {tuple(pc.shape)} quat {tuple(quat.shape)}")
@@ -91,8 +90,7 @@ class _PoseApplyRmat(torch.autograd.Function):
 def pose_apply_rmat(pc, rmat, trans=None, mask=None, fill=0.0):
     """`pose_apply` with rotation matrices: pc [..., N, 3], rmat [..., 3, 3], trans [..., 3] | None, mask [...] | None.
     Each output is (r_i0 x + r_i1 y) + r_i2 z (+ t_i), the reference's `r @ v[..., None]` (transforms.py:155-172)."""
-    if not pc.is_cuda:
-        raise RuntimeError("pose_apply_rmat: only CUDA (HIP) tensors are supported")
+    _lib.require_hip("pose_apply_rmat", pc)
     lead = pc.shape[:-2]
     if rmat.shape[:-2] != lead or rmat.shape[-2:] != (3, 3) or pc.shape[-1] != 3:
         raise RuntimeError(f"pose_apply_rmat: shape mismatch pc {tuple(pc.shape)} rmat {tuple(rmat.shape)}")
