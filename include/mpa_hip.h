@@ -607,6 +607,46 @@ int mpa_grad_clip_workspace(int64_t* bytes);
 int mpa_grad_clip_coef(const float* grad, int64_t numel, float max_norm, const float* grad_scale_dev,
                        float grad_scale, void* ws, float* coef, void* stream);
 
+/* ---- Guarded optimiser step: a non-finite gradient or a failed launch skips the step ON THE DEVICE -----------------
+ * Stands where Lightning's GradScaler stands in the reference's documented `--fp16` runs (docs/model.md:76,95,123): a
+ * step whose gradients hold an inf or NaN is dropped, not applied.  Opt-in; the unguarded entry points above are
+ * untouched.  No allocation, no synchronisation, launch configurations depend on sizes only (capturable).
+ *
+ * mpa_step_guard: ONE pass over `grad` (mpa_grad_clip_coef's two-stage double sum, same operations in the same order,
+ * which also finds the smallest flat index of a NaN / +-inf element) and ONE one-wave launch whose lane 0 writes
+ *   hyper[5], hyper[6]: for a finite gradient and max_norm > 0 the exact bits mpa_grad_clip_coef writes; max_norm <= 0
+ *                       = no clipping: hyper[5] = 1, hyper[6] still the norm; non-finite gradient: 1 and +inf;
+ *   the verdict:        bit 0 = some element of `grad` is NaN or +-inf (decided from the double sum of squares, which is
+ *                       finite exactly when every element is: 2^31 squares of the largest float stay in range — 3e38
+ *                       does not trip); bit 1 = `launch_status` is non-NULL and *launch_status != 0;
+ *   the step advance:   ONLY for verdict 0, what mpa_adam_step_dev's advance does to hyper[1], hyper[2], hyper[4].
+ * `guard`: eight int32 DEVICE words owned by the caller (zero them to start counting)
+ *   [0] this call's verdict   [1] steps applied   [2] steps skipped   [3] skipped in a row (0 after an applied step)
+ *   [4] flat index of the first non-finite element of the most recent skipped step, -1 if the status word alone
+ *   [5] 1-based attempt number ([1] + [2]) of the most recent skipped step, 0 if none   [6] OR of all verdicts   [7] 0.
+ * numel = 0 (grad may be NULL) gives verdict 0 unless the status word is raised; numel < 2^31.  `ws` =
+ * mpa_step_guard_workspace bytes, 8-byte aligned; `grad` 16-byte aligned.  Restated in numpy by
+ * multi_part_assembly_amd/guard_ref.py.
+ *
+ * mpa_adam_step_guarded: mpa_adam_step_dev WITHOUT its advance launch, behind mpa_step_guard: guard[0] != 0 -> every
+ * block returns before its first store (parameters, moments and `hyper` keep their bits); otherwise the same update on
+ * the same operands, bit-equal to mpa_adam_step_dev.
+ *
+ * mpa_guard_mark: one tiny launch in front of a data-parallel all-reduce: *launch_status != 0 -> grad[0] = quiet NaN,
+ * else nothing is touched.  A rank-local failure so becomes a non-finite reduced gradient, and with it the same verdict,
+ * on every rank, without another collective.
+ *
+ * What the guard does NOT protect: forward-side state of a skipped step (BatchNorm running statistics, dropout-seed
+ * positions, device draw counters) is not rolled back. */
+int mpa_step_guard_workspace(int64_t* bytes);
+int mpa_step_guard(const float* grad, int64_t numel, float max_norm, const float* grad_scale_dev, float grad_scale,
+                   const int32_t* launch_status, void* ws, float* hyper, int32_t* guard,
+                   float beta1, float beta2, void* stream);
+int mpa_adam_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t numel,
+                          const float* hyper, float beta1, float beta2, float eps, float weight_decay,
+                          int decoupled_weight_decay, const float* decay_mask, const int32_t* guard, void* stream);
+int mpa_guard_mark(const int32_t* launch_status, float* grad, int64_t numel, void* stream);
+
 /* ---- GT <-> prediction matching of equivalent parts (semantic datasets) --------------------------------------
  * Replaces BaseModel._linear_sum_assignment / _match_parts (multi_part_assembly/models/modules/base_model.py:
  * 150-238: p x p Chamfer cost matrix on n = 100 sub-sampled points, scipy.optimize.linear_sum_assignment on the

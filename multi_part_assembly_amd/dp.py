@@ -39,6 +39,7 @@ class BucketedGradReducer:
             first += size
         self.pending = []
         self.enabled = True  # False: hooks and finish() issue no collective (bench.py: the step time without them)
+        self.before_reduce = None  # callable(bucket index), run on the stream in front of that bucket's collective
         self._seen = set()
         self._owner = {}
         idx = 0
@@ -60,6 +61,8 @@ class BucketedGradReducer:
         bucket = self.buckets[self._owner[param]]
         bucket["ready"] += 1
         if bucket["ready"] == bucket["count"]:
+            if self.before_reduce is not None:
+                self.before_reduce(self._owner[param])
             self.pending.append(dist.all_reduce(bucket["slice"], op=dist.ReduceOp.SUM,
                                                 group=self.group, async_op=True))
 
@@ -67,8 +70,10 @@ class BucketedGradReducer:
         """Issue collectives for buckets whose hooks did not all fire (parameters unused in this
         step), wait for everything, reset.  Returns the scale (1/world) still to be applied."""
         if self.world > 1 and self.enabled:
-            for bucket in self.buckets:
+            for b, bucket in enumerate(self.buckets):
                 if bucket["ready"] != bucket["count"]:
+                    if self.before_reduce is not None:
+                        self.before_reduce(b)
                     self.pending.append(dist.all_reduce(bucket["slice"], op=dist.ReduceOp.SUM,
                                                         group=self.group, async_op=True))
                 bucket["ready"] = 0

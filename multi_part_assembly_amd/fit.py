@@ -102,7 +102,7 @@ def resume(trainer, ckpt_dir):
 
 
 def fit(trainer, train_producer, sampler, val_batches=None, epochs=None, val_every=None, ckpt_dir=None, keep=5,
-        monitor="val/part_acc", log_every=50, on_log=None, max_steps=None):
+        monitor="val/part_acc", log_every=50, on_log=None, max_steps=None, skip_limit=None):
     """Train from the epoch a preceding `resume` returned (0 otherwise) up to `epochs` (default `cfg.exp.num_epochs`).
 
     Per epoch e: `set_epoch(e)` on trainer and sampler; `train_step(train_producer.batch(idx))` for every index batch of
@@ -115,7 +115,24 @@ def fit(trainer, train_producer, sampler, val_batches=None, epochs=None, val_eve
 
     `max_steps`: stop after that many steps of this call as a preemption would — `last.pt` then holds the position
     inside the epoch, and a resumed run continues with the batches this one would have seen.  Returns the history: one
-    dict per finished epoch (`epoch`, `lr`, `train/loss`, the validation metrics where they ran)."""
+    dict per finished epoch (`epoch`, `lr`, `train/loss`, the validation metrics where they ran).
+
+    With a guarded trainer (`Trainer(guard_step=True)`: non-finite or failed steps are skipped on the device) every
+    `log_every` record also carries `grad_norm` (the last step's; inf for a skipped non-finite one), `skipped` and
+    `skipped_in_a_row`, read in the SAME device read as the running loss; `skip_limit`: RuntimeError with the
+    optimiser's `guard_report` text at a log read that finds `skipped_in_a_row >= skip_limit`."""
+    guarded = bool(getattr(trainer, "guard_step", False))
+    if skip_limit is not None and not guarded:
+        raise ValueError("fit: skip_limit needs a guarded trainer (Trainer(guard_step=True) / cfg.optimizer.skip_nonfinite)")
+
+    def read(acc):
+        """The one device read of a log interval: (running loss, the guard's figures or {})."""
+        if not guarded:
+            return float(acc.item()), {}
+        opt = trainer.optimizer
+        v = torch.cat([acc.detach().reshape(1).double(), opt.grad_norm().double(),
+                       opt.guard_words()[2:4].double()]).tolist()
+        return v[0], {"grad_norm": v[1], "skipped": int(v[2]), "skipped_in_a_row": int(v[3])}
     cfg = getattr(trainer, "cfg", None) or getattr(getattr(trainer, "model", None), "cfg", None)
     if epochs is None:
         epochs = cfg.exp.num_epochs
@@ -175,9 +192,16 @@ def fit(trainer, train_producer, sampler, val_batches=None, epochs=None, val_eve
             acc_steps += 1
             steps_run += 1
             if log_every and sampler.next_step % log_every == 0:
-                loss_sum, loss_steps, acc, acc_steps = loss_sum + float(acc.item()), loss_steps + acc_steps, None, 0
+                value, guard_figures = read(acc)
+                loss_sum, loss_steps, acc, acc_steps = loss_sum + value, loss_steps + acc_steps, None, 0
                 if on_log is not None:
-                    on_log({"epoch": epoch, "step": sampler.next_step, "lr": lr, "train/loss": loss_sum / loss_steps})
+                    on_log({"epoch": epoch, "step": sampler.next_step, "lr": lr, "train/loss": loss_sum / loss_steps,
+                            **guard_figures})
+                if skip_limit is not None and guard_figures["skipped_in_a_row"] >= skip_limit:
+                    report = trainer.optimizer.guard_report(getattr(trainer, "flat", None))
+                    raise RuntimeError(f"fit: {guard_figures['skipped_in_a_row']} optimiser steps skipped in a row "
+                                       f"(skip_limit {skip_limit}) at epoch {epoch}, step {sampler.next_step}: "
+                                       + report["text"])
             if max_steps is not None and steps_run >= max_steps:
                 break
         if acc is not None:  # the epoch's (or the interrupted epoch's) one read

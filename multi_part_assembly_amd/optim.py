@@ -81,10 +81,17 @@ class FusedAdam:
     travels as a kernel argument) only when they change.
 
     `decay_mask`: optional flat 1/0 tensor (see `decay_mask_for`).  `clip_grad`: global-norm clipping of the
-    (mean) gradient, the reference's `gradient_clip_val` (scripts/train.py:90)."""
+    (mean) gradient, the reference's `gradient_clip_val` (scripts/train.py:90).
+
+    `guard=True`: `step_dev()` looks at the gradient first (csrc/adam.hip mpa_step_guard: one pass that is also the
+    clipping's norm) and SKIPS the step on the device — parameters, moments, step count and bias corrections keep their
+    bits — when the gradient holds a NaN or an inf, or when `launch_status` (an int32 device word, e.g. the GRU launches'
+    status word) is raised.  What the reference gets from Lightning's GradScaler in its `--fp16` runs.  Eight device
+    words count what happened (`guard_words()`, `guard_report()`); forward-side state of a skipped step (BatchNorm
+    running statistics, dropout-seed positions) is not rolled back."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 decoupled_weight_decay=None, decay_mask=None, clip_grad=None):
+                 decoupled_weight_decay=None, decay_mask=None, clip_grad=None, guard=False, launch_status=None):
         self.flat = params if isinstance(params, FlatBuffers) else FlatBuffers(params)
         self.params = self.flat.params
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
@@ -101,6 +108,10 @@ class FusedAdam:
         self.exp_avg = torch.zeros_like(self.flat_param)
         self.exp_avg_sq = torch.zeros_like(self.flat_param)
         self._hyper_dev, self._uploaded = None, (None, None)
+        self.guard, self.launch_status = bool(guard), launch_status
+        # the eight guard words live from construction on (a checkpoint may be loaded before the first step)
+        self._guard_dev = torch.zeros(8, dtype=torch.int32, device=self.flat_param.device) if self.guard else None
+        self._guard_ws = None
 
     def zero_grad(self):
         self.flat.zero_grad()
@@ -114,6 +125,12 @@ class FusedAdam:
             self._hyper_dev = torch.zeros(8, dtype=torch.float32, device=dev)
             self._hyper_dev[5] = 1.0  # clip coefficient: no clipping
             self._set_device_step(self._step_count)
+        self._ensure_guard_ws()
+
+    def _ensure_guard_ws(self):
+        if self.guard and self._guard_ws is None:
+            self._guard_ws = torch.empty(_lib.query("mpa_step_guard_workspace") // 4, dtype=torch.int32,
+                                         device=self.flat_param.device)
 
     @property
     def step_count(self):
@@ -149,6 +166,18 @@ class FusedAdam:
         """[clip coefficient +] step-count advance + Adam update, all on the stream (safe to capture in a HIP
         graph: every launch argument is constant across replays)."""
         dev = self.flat_param.device
+        if self.guard:
+            # pass + verdict / coefficient / advance, then the update that returns at once behind a non-zero verdict
+            # (clipping off: one launch more than advance + update; clipping on: one fewer than its four)
+            self._clip_written = bool(self.clip_grad)  # (the verdict kernel rewrites the coefficient in every step)
+            self._ensure_guard_ws()
+            _lib.launch("mpa_step_guard", dev, self.flat_grad, self.numel, float(self.clip_grad or 0.0),
+                        self._hyper_dev.data_ptr() + 12, 1.0, self.launch_status, self._guard_ws, self._hyper_dev,
+                        self._guard_dev, float(self.betas[0]), float(self.betas[1]))
+            _lib.launch("mpa_adam_step_guarded", dev, self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq,
+                        self.numel, self._hyper_dev, float(self.betas[0]), float(self.betas[1]), float(self.eps),
+                        float(self.weight_decay), int(self.decoupled), self.decay_mask, self._guard_dev)
+            return
         if not self.clip_grad and self._clip_written:  # clipping was switched off: back to "no clipping"
             self._hyper_dev[5:6].fill_(1.0)
             self._clip_written = False
@@ -167,14 +196,66 @@ class FusedAdam:
         self.prepare_hyper()
         self.step_dev()
 
+    # ---- the guard's eight words ----------------------------------------------------------------------------------------
+    def guard_words(self):
+        """The eight int32 guard words (include/mpa_hip.h, guard_ref.WORDS) as a DEVICE tensor: no synchronisation."""
+        if not self.guard:
+            raise RuntimeError("FusedAdam.guard_words: the optimiser was built with guard=False")
+        return self._guard_dev
+
+    def grad_norm(self):
+        """hyper[6] as a one-element DEVICE view: the norm of the last step's (scaled) gradient, +inf for a non-finite
+        one.  Written by every guarded step (by the clipping alone without the guard)."""
+        self._ensure_hyper()
+        return self._hyper_dev[6:7]
+
+    def guard_report(self, flat=None):
+        """One device read: the words by name, plus `parameter` (index into `flat.params`), `shape` and `element` of the
+        tensor owning `first_bad_index` (resolved through `FlatBuffers.offsets`; None when the last skip was the status
+        word's alone, or nothing was skipped) and a one-line `text`."""
+        from .guard_ref import LAUNCH_FAILED, NONFINITE, describe
+        flat = flat if flat is not None else self.flat
+        rep = describe(self.guard_words().tolist())
+        rep.update(parameter=None, shape=None, element=None)
+        idx = rep["first_bad_index"]
+        if rep["skipped"] and idx >= 0:
+            k = max(i for i, off in enumerate(flat.offsets) if off <= idx)
+            rep.update(parameter=k, shape=tuple(flat.params[k].shape), element=idx - flat.offsets[k])
+        if not rep["skipped"]:
+            rep["text"] = f"{rep['applied']} steps applied, none skipped"
+        else:
+            why = []
+            if rep["verdicts_or"] & NONFINITE:
+                why.append("non-finite gradient")
+            if rep["verdicts_or"] & LAUNCH_FAILED:
+                why.append("raised launch status word")
+            where = (f"first non-finite gradient element: flat index {idx} = element {rep['element']} of parameter "
+                     f"{rep['parameter']} (shape {rep['shape']})") if rep["parameter"] is not None else \
+                "the launch status word alone"
+            rep["text"] = (f"{rep['applied']} steps applied, {rep['skipped']} skipped ({' / '.join(why)} seen), "
+                           f"{rep['skipped_in_a_row']} in a row; last skipped attempt {rep['last_skipped_attempt']}: {where}")
+        return rep
+
     def state_dict(self):
-        return {"step": self.step_count, "lr": self.lr, "exp_avg": self.exp_avg.clone(),
-                "exp_avg_sq": self.exp_avg_sq.clone()}
+        state = {"step": self.step_count, "lr": self.lr, "exp_avg": self.exp_avg.clone(),
+                 "exp_avg_sq": self.exp_avg_sq.clone()}
+        if self.guard:
+            # the host mirror counts ATTEMPTS once steps can be skipped: the applied count is the device's (one read, at
+            # a checkpoint, which synchronises anyway)
+            if self._hyper_dev is not None:
+                state["step"] = int(self._hyper_dev[4:5].view(torch.int32).item())
+            state["guard"] = self._guard_dev.clone()
+        return state
 
     def load_state_dict(self, state):
         self.step_count, self.lr = state["step"], state["lr"]  # (the setter re-synchronises the device counter)
         self.exp_avg.copy_(state["exp_avg"])
         self.exp_avg_sq.copy_(state["exp_avg_sq"])
+        if self.guard:  # (a checkpoint without the words: counting starts at zero)
+            if state.get("guard") is not None:
+                self._guard_dev.copy_(state["guard"])
+            else:
+                self._guard_dev.zero_()
 
 
 def cosine_warmup_lr(total_epochs, warmup_epochs, max_lr, min_lr):

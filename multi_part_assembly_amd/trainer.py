@@ -26,6 +26,7 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
+from . import _lib
 from . import gru as _gru
 from .gradsink import DeferredBackward, GradSink
 from .dp import BucketedGradReducer, broadcast_from_rank0, bucket_sizes_for, ordered_parameters
@@ -33,7 +34,14 @@ from .optim import FlatBuffers, FusedAdam, cosine_warmup_lr, decay_mask_for
 
 
 class Trainer:
-    def __init__(self, model, cfg=None, process_group=None, use_graph=False, graph_warmup=3):
+    def __init__(self, model, cfg=None, process_group=None, use_graph=False, graph_warmup=3, guard_step=None):
+        """`guard_step` (None: `cfg.optimizer.skip_nonfinite`, False where the key is absent — no preset sets it): every
+        optimiser step is guarded on the device (optim.FusedAdam `guard=True`): a step whose reduced gradient holds a
+        NaN or an inf, or behind which the GRU launches' status word is raised, is skipped — parameters, moments and
+        the step count keep their bits — and counted.  Forward-side state of a skipped step (BatchNorm running
+        statistics, `num_batches_tracked`, dropout-seed positions, device draw counters) is NOT rolled back; a NaN born
+        in the forward pass reaches the running statistics, which is why a guarded `state_dict()` refuses non-finite
+        parameters and buffers."""
         self.model = model
         if use_graph and getattr(model, "semantic", False) and getattr(model, "match_sample", "host") != "device":
             # identical-part matching draws its point sample on the host every step (base_model._match_parts; reference
@@ -65,11 +73,15 @@ class Trainer:
         self.cfg = cfg
         opt = cfg.optimizer
         self.flat = FlatBuffers(ordered_parameters(model))
+        self.guard_step = bool(opt.get("skip_nonfinite", False) if guard_step is None else guard_step)
+        dev = self.flat.flat_param.device
+        # the status word the guard reads is the one the GRU launches raise (allocated here: before any capture)
+        status = _gru.prepare(dev)[0] if self.guard_step and dev.type == "cuda" else None
         # weight decay > 0 -> AdamW with biases / normalisation weights exempt (base_model.py:394-404); clip_grad ->
         # global-norm clipping of the averaged gradient (scripts/train.py:90 gradient_clip_val)
         self.optimizer = FusedAdam(self.flat, lr=opt.lr, weight_decay=opt.weight_decay,
                                    decay_mask=decay_mask_for(model, self.flat) if opt.weight_decay > 0 else None,
-                                   clip_grad=opt.get("clip_grad", None))
+                                   clip_grad=opt.get("clip_grad", None), guard=self.guard_step, launch_status=status)
         self.schedule = None
         if opt.lr_scheduler:
             total = cfg.exp.num_epochs
@@ -84,12 +96,13 @@ class Trainer:
         self.reducer = BucketedGradReducer(self.flat, bucket_sizes_for(model, self.flat), process_group)
         if use_graph:
             self.reducer.enabled = False
+        elif self.guard_step and self.world > 1:
+            self.reducer.before_reduce = self._mark_before_bucket
         self._graph_b = None
         self.sink = GradSink(on_ready=self.reducer._on_grad if not use_graph and self.world > 1 else None)
         # buffers the step allocates lazily (the GRU launches' status word + its pinned copy, the loss's side stream)
         # exist BEFORE a capture can see them: a pinned allocation is illegal under capture and a device word born there
         # would live in the graph's private pool
-        dev = self.flat.flat_param.device
         if dev.type == "cuda":
             _gru.prepare(dev)
             for mod in model.modules():
@@ -110,6 +123,39 @@ class Trainer:
             self._failed = True
             raise
 
+    # ---- guarded steps -------------------------------------------------------------------------------------------------
+    def _mark_failed_launch(self):
+        """Data parallel, in front of the all-reduce of the bucket holding element 0: a status word raised on THIS rank
+        becomes a NaN in the reduced gradient of every rank, which then all reach the same verdict (no extra collective)."""
+        opt = self.optimizer
+        _lib.launch("mpa_guard_mark", self.flat.flat_grad.device, opt.launch_status, self.flat.flat_grad, self.flat.numel)
+
+    def _mark_before_bucket(self, bucket):
+        if bucket == 0:  # (FlatBuffers order: the first bucket starts at element 0)
+            self._mark_failed_launch()
+
+    def _refuse_nonfinite_state(self):
+        """Guarded trainers only, at checkpoints: a NaN / inf in a parameter (one mpa_step_guard pass over the flat
+        parameters against scratch words) or in a buffer (the forward side is not guarded) must not reach a file."""
+        flat, opt = self.flat.flat_param, self.optimizer
+        if not flat.is_cuda:
+            return
+        opt._ensure_hyper()
+        hyper = torch.zeros(8, dtype=torch.float32, device=flat.device)
+        words = torch.zeros(8, dtype=torch.int32, device=flat.device)
+        _lib.launch("mpa_step_guard", flat.device, flat, self.flat.numel, 0.0, None, 1.0, None, opt._guard_ws, hyper, words,
+                    float(opt.betas[0]), float(opt.betas[1]))
+        verdict, _, _, _, idx = words[:5].tolist()
+        if verdict:
+            k = max(i for i, off in enumerate(self.flat.offsets) if off <= idx)
+            raise RuntimeError(f"Trainer.state_dict: parameter {k} (shape {tuple(self.flat.params[k].shape)}) holds a "
+                               f"non-finite value at element {idx - self.flat.offsets[k]}; restore a checkpoint with "
+                               "load_state_dict first")
+        for name, buf in self.model.named_buffers():
+            if buf.is_floating_point() and not bool(torch.isfinite(buf).all()):
+                raise RuntimeError(f"Trainer.state_dict: buffer {name} holds a non-finite value (forward-side state of a "
+                                   "skipped step is not rolled back); restore a checkpoint with load_state_dict first")
+
     def state_dict(self):
         """Model + optimiser state for a checkpoint; refuses (RuntimeError) if a launch behind the current parameters
         gave up — now, or at any `check_health` since the parameters were last loaded.  Besides "model", "optimizer" and
@@ -119,6 +165,8 @@ class Trainer:
             raise RuntimeError("Trainer.state_dict: an earlier check_health reported a launch that gave up; the parameters "
                                "behind it are undefined — restore a checkpoint with load_state_dict first")
         self.check_health(synchronize=True)
+        if self.guard_step:
+            self._refuse_nonfinite_state()
         return {"model": self.model.state_dict(), "optimizer": self.optimizer.state_dict()
                 if hasattr(self.optimizer, "state_dict") else None, "epoch": self.epoch,
                 # position of every dropout-seed stream (transformer.TransformerEncoder._next_seed), in module order: a
@@ -178,7 +226,7 @@ class Trainer:
         return dist.get_rank(self.group) if dist.is_initialized() else 0
 
     def fit(self, train_producer, sampler, val_batches=None, epochs=None, val_every=None, ckpt_dir=None, keep=5,
-            monitor="val/part_acc", log_every=50, on_log=None, max_steps=None):
+            monitor="val/part_acc", log_every=50, on_log=None, max_steps=None, skip_limit=None):
         """The epoch loop (fit.fit has the contract): order of the epoch from `sampler` (sampler.EpochSampler), batches
         from `train_producer`, the schedule, validation every `val_every` epochs, the best `keep` checkpoints by
         `monitor` plus `last.pt` in `ckpt_dir`.  Continues from the epoch a preceding `resume` returned.  Returns the
@@ -186,7 +234,7 @@ class Trainer:
         from . import fit as _fit
         return _fit.fit(self, train_producer, sampler, val_batches=val_batches, epochs=epochs, val_every=val_every,
                         ckpt_dir=ckpt_dir, keep=keep, monitor=monitor, log_every=log_every, on_log=on_log,
-                        max_steps=max_steps)
+                        max_steps=max_steps, skip_limit=skip_limit)
 
     def resume(self, ckpt_dir):
         """Load `ckpt_dir/last.pt` if it exists (model, optimiser, schedule, seed positions now; sampler position, producer
@@ -275,8 +323,12 @@ class Trainer:
         encoder's bucket behind it."""
         buckets = self.reducer.buckets
         assert len(buckets) <= 2, "the two-graph overlap reduces only the first and the last bucket"
+        if self.guard_step and len(buckets) > 1:
+            self._mark_failed_launch()  # (bucket 0 holds element 0)
         first = dist.all_reduce(buckets[0]["slice"], group=self.group, async_op=True) if len(buckets) > 1 else None
         run_second_half()
+        if self.guard_step and len(buckets) == 1:
+            self._mark_failed_launch()
         last = dist.all_reduce(buckets[-1]["slice"], group=self.group, async_op=True)
         if first is not None:
             first.wait()
@@ -290,6 +342,8 @@ class Trainer:
                 self._eager_steps += 1
                 loss = self._fwd_bwd(self._tensor_items(data_dict))
                 if self.world > 1:
+                    if self.guard_step:
+                        self._mark_failed_launch()
                     dist.all_reduce(self.flat.flat_grad, group=self.group)
                 self.check_health()
                 self.optimizer.prepare_hyper()
@@ -309,6 +363,8 @@ class Trainer:
             if self._graph_b is not None:
                 self._reduce_buckets_around(self._graph_b.replay)
             else:  # nothing was deferred (an encoder outside the fused kernels): one all-reduce behind the replay
+                if self.guard_step:
+                    self._mark_failed_launch()
                 dist.all_reduce(self.flat.flat_grad, group=self.group)
             self.check_health()  # before the (uncaptured) optimiser step consumes the gradients
             self.optimizer.step_dev()

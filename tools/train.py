@@ -2,6 +2,7 @@
 
   python tools/train.py --preset pn_transformer_everyday --data-dir data/breaking_bad --data-fn everyday.train.txt \\
       --val-fn everyday.val.txt [--category Bottle] [--epochs 400] [--graph] [--ckpt-dir ckpt] [--resume]
+  python tools/train.py --preset pn_transformer_everyday --skip-nonfinite --skip-limit 20 ...  (bad steps skipped on the device)
   python tools/train.py --preset pn_transformer_everyday --repulsion 0.01 1.0 ...   (the opt-in repulsion term: THRE W)
   python tools/train.py --preset lstm_everyday --lstm-draws device --graph ...      (B-LSTM captured: its draws on the device)
   python tools/train.py --preset dgl_partnet_chair --data-dir data/partnet --data-fn Chair.train.npy --val-fn Chair.val.npy
@@ -52,6 +53,11 @@ def parser():
     ap.add_argument("--monitor", default="val/part_acc")
     ap.add_argument("--log-every", type=int, default=50)
     ap.add_argument("--max-steps", type=int, default=-1, help="stop after this many steps, leaving last.pt to resume from")
+    ap.add_argument("--skip-nonfinite", action="store_true",
+                    help="cfg.optimizer.skip_nonfinite: skip, on the device, every optimiser step whose gradient holds a NaN "
+                         "or an inf or behind which a launch gave up (parameters, moments and step count keep their bits)")
+    ap.add_argument("--skip-limit", type=int, default=-1, metavar="N",
+                    help="with --skip-nonfinite: stop at a log line that finds N steps skipped in a row")
     ap.add_argument("--seed", type=int, default=0)
     return ap
 
@@ -63,6 +69,8 @@ def parse_args(argv=None):
         ap.error("--data-dir and --data-fn are needed unless --synthetic is given")
     if args.resume and not args.ckpt_dir:
         ap.error("--resume needs --ckpt-dir")
+    if args.skip_limit > 0 and not args.skip_nonfinite:
+        ap.error("--skip-limit needs --skip-nonfinite")
     return args
 
 
@@ -127,6 +135,8 @@ def configure(args):
     if args.repulsion is not None:
         cfg.loss.use_repulsion_loss = True
         cfg.loss.repulsion_thre, cfg.loss.repulsion_loss_w = args.repulsion
+    if args.skip_nonfinite:
+        cfg.optimizer.skip_nonfinite = True
     return cfg
 
 
@@ -170,7 +180,8 @@ def main(argv=None):
             print(f"resuming at epoch {start}", flush=True)
     history = trainer.fit(train, sampler, val_batches=val_batches, val_every=args.val_every if args.val_every > 0 else None,
                           ckpt_dir=args.ckpt_dir or None, monitor=args.monitor, log_every=args.log_every, on_log=log,
-                          max_steps=args.max_steps if args.max_steps > 0 else None)
+                          max_steps=args.max_steps if args.max_steps > 0 else None,
+                          skip_limit=args.skip_limit if args.skip_limit > 0 else None)
     if rank == 0:
         print(f"done: {len(history)} epochs in the history", flush=True)
     if world > 1:
