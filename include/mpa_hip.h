@@ -636,8 +636,25 @@ int mpa_grad_clip_coef(const float* grad, int64_t numel, float max_norm, const f
  * else nothing is touched.  A rank-local failure so becomes a non-finite reduced gradient, and with it the same verdict,
  * on every rank, without another collective.
  *
- * What the guard does NOT protect: forward-side state of a skipped step (BatchNorm running statistics, dropout-seed
- * positions, device draw counters) is not rolled back. */
+ * mpa_guard_commit: behind mpa_step_guard (and the update), ONE launch over two caller-owned byte ranges of equal size,
+ * `live` (every module buffer of the model, optim.BufferSlab) and `shadow` (their bits at the end of the last applied
+ * step).  guard[0] == 0 (the step was applied): shadow <- live; guard[0] != 0 (the step was skipped): live <- shadow.
+ * The verdict is read from device memory by every block with one uniform load, never passed by value: a captured launch
+ * takes the right direction on every replay.  A bitwise copy of `bytes` bytes in 16-byte units (one 16-byte load and
+ * one 16-byte store per unit, grid-stride): NaN payloads, -0 and int64 counters pass through unchanged, and nothing
+ * outside the two ranges is written.  bytes % 16 == 0, both ranges 16-byte aligned and disjoint; bytes == 0 is a no-op
+ * without a launch (the ranges may then be NULL).  `guard` NULL or misaligned, a NULL range with bytes > 0, a misaligned
+ * or overlapping range, a negative size or one that is no multiple of 16: MPA_EINVAL, nothing is launched.  Restated by
+ * guard_ref.commit.
+ *
+ * What a skipped step leaves behind.  With mpa_guard_commit behind every guarded step (Trainer(guard_buffers=True)) every
+ * module buffer — BatchNorm running statistics, num_batches_tracked, whatever else a module registers — has the bits it
+ * had before the skipped step.  Without it they keep what the skipped step's forward wrote.  Never rolled back, and
+ * harmless: the dropout-seed positions (host counters; the skipped step's masks are spent, the next step draws fresh
+ * ones), the matching and seq2seq draw counters (rewritten from the host counter in front of every step) and the
+ * producers' counters (the data stream is outside the step).  The remaining hole: a step whose gradient is finite while a
+ * statistic overflowed to inf is APPLIED, and the statistic is committed; only the checkpoint's refusal of non-finite
+ * buffers catches that one. */
 int mpa_step_guard_workspace(int64_t* bytes);
 int mpa_step_guard(const float* grad, int64_t numel, float max_norm, const float* grad_scale_dev, float grad_scale,
                    const int32_t* launch_status, void* ws, float* hyper, int32_t* guard,
@@ -646,6 +663,7 @@ int mpa_adam_step_guarded(float* param, const float* grad, float* exp_avg, float
                           const float* hyper, float beta1, float beta2, float eps, float weight_decay,
                           int decoupled_weight_decay, const float* decay_mask, const int32_t* guard, void* stream);
 int mpa_guard_mark(const int32_t* launch_status, float* grad, int64_t numel, void* stream);
+int mpa_guard_commit(const int32_t* guard, void* live, void* shadow, int64_t bytes, void* stream);
 
 /* ---- GT <-> prediction matching of equivalent parts (semantic datasets) --------------------------------------
  * Replaces BaseModel._linear_sum_assignment / _match_parts (multi_part_assembly/models/modules/base_model.py:

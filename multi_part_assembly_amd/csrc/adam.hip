@@ -245,6 +245,19 @@ __global__ void guard_mark_kernel(const int* __restrict__ launch_status, float* 
   if (launch_status[0] != 0) grad[0] = __uint_as_float(0x7fc00000u);  // quiet NaN
 }
 
+// mpa_guard_commit: the verdict is one plain load of the same word in every lane (uniform across the grid, as in
+// adam_guarded_kernel) and picks the DIRECTION of a bitwise copy in 16-byte units: applied step, shadow <- live; skipped
+// step, live <- shadow.  uint4, not float4: the bytes are counters and flags as well as statistics.
+constexpr int kCommitBlocks = 512;
+__global__ __launch_bounds__(kThreads) void guard_commit_kernel(const int* __restrict__ guard, uint4* live, uint4* shadow,
+                                                                long long units) {
+  const bool skipped = guard[0] != 0;
+  const uint4* __restrict__ src = skipped ? shadow : live;
+  uint4* __restrict__ dst = skipped ? live : shadow;
+  const long long stride = (long long)gridDim.x * kThreads;
+  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < units; i += stride) dst[i] = src[i];
+}
+
 }  // namespace
 
 extern "C" int mpa_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
@@ -377,4 +390,21 @@ extern "C" int mpa_guard_mark(const int32_t* launch_status, float* grad, int64_t
   MPA_REQUIRE(((uintptr_t)launch_status | (uintptr_t)grad) % 4 == 0, "guard_mark: misaligned word");
   hipLaunchKernelGGL(guard_mark_kernel, dim3(1), dim3(1), 0, mpa::as_stream(stream), (const int*)launch_status, grad);
   return mpa::check_launch("guard_mark");
+}
+
+extern "C" int mpa_guard_commit(const int32_t* guard, void* live, void* shadow, int64_t bytes, void* stream) {
+  MPA_REQUIRE(guard != nullptr, "guard_commit: null pointer (the guard words)");
+  MPA_REQUIRE((uintptr_t)guard % 4 == 0, "guard_commit: misaligned word");
+  MPA_REQUIRE(bytes >= 0 && bytes % 16 == 0, "guard_commit: bytes must be a non-negative multiple of 16");
+  if (bytes == 0) return MPA_OK;
+  MPA_REQUIRE(live && shadow, "guard_commit: null pointer");
+  MPA_REQUIRE(((uintptr_t)live | (uintptr_t)shadow) % 16 == 0, "guard_commit: buffers must be 16-byte aligned");
+  const uintptr_t a = (uintptr_t)live, b = (uintptr_t)shadow;
+  MPA_REQUIRE(a + (uintptr_t)bytes <= b || b + (uintptr_t)bytes <= a, "guard_commit: the two ranges overlap");
+  const long long units = bytes / 16;
+  long long blocks = (units + kThreads - 1) / kThreads;
+  if (blocks > kCommitBlocks) blocks = kCommitBlocks;
+  hipLaunchKernelGGL(guard_commit_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, mpa::as_stream(stream),
+                     (const int*)guard, static_cast<uint4*>(live), static_cast<uint4*>(shadow), units);
+  return mpa::check_launch("guard_commit");
 }

@@ -8,6 +8,9 @@ gets the first half from Lightning's GradScaler in its documented `--fp16` runs 
 `sum_of_squares` walks the gradient in the kernel's order (512 blocks of 256 threads, a float4 per thread and grid
 stride, a three-element tail, a binary tree per block, the blocks added in index order), so the coefficient and the norm
 come out with the device's bits: every operation is one IEEE double operation (a float's square is exact in double).
+
+`commit` restates mpa_guard_commit, the buffer rollback behind the verdict (optim.BufferSlab): an applied step makes the
+live bytes the shadow, a skipped one makes the shadow the live bytes; `run_steps` carries a slab through a sequence of steps.
 """
 from __future__ import annotations
 
@@ -127,6 +130,36 @@ def guard_mark(launch_status, grad):
     """mpa_guard_mark: a raised status word becomes a quiet NaN in element 0 of the gradient."""
     if launch_status != 0:
         grad[0] = np.float32(np.nan)
+
+
+COMMIT_BLOCKS, COMMIT_UNIT = 512, 16  # kCommitBlocks of csrc/adam.hip (blocks of THREADS threads), bytes per unit
+
+
+def commit(verdict, live, shadow):
+    """mpa_guard_commit on two numpy byte arrays of equal size: returns (live, shadow) after the call, as new arrays.
+    verdict == 0 (the step was applied): shadow <- live; anything else (skipped): live <- shadow.  Bit for bit."""
+    live, shadow = np.asarray(live), np.asarray(shadow)
+    if live.dtype != np.uint8 or shadow.dtype != np.uint8 or live.ndim != 1 or live.shape != shadow.shape:
+        raise ValueError("guard_ref.commit: two one-dimensional uint8 arrays of equal size")
+    if live.size % COMMIT_UNIT:
+        raise ValueError("guard_ref.commit: the size must be a multiple of 16 bytes")
+    keep = shadow if int(verdict) != 0 else live
+    return keep.copy(), keep.copy()
+
+
+def run_steps(steps, state, live, shadow, hyper=None, guard=None, max_norm=0.0, scale=1.0):
+    """A sequence of guarded steps that carries a buffer slab: `steps` = [(grad, launch_status, forward_bytes)], where
+    `forward_bytes` is what the step's forward leaves in the live slab before the verdict is known.  `state` = (param,
+    exp_avg, exp_avg_sq), updated in place.  Returns (live, shadow, verdicts)."""
+    hyper = new_hyper() if hyper is None else hyper
+    guard = np.zeros(8, dtype=np.int32) if guard is None else guard
+    verdicts = []
+    for grad, status, forward_bytes in steps:
+        live = np.asarray(forward_bytes, dtype=np.uint8).copy()
+        verdicts.append(step_guard(grad, max_norm, scale, status, hyper, guard))
+        adam_step_guarded(state[0], grad, state[1], state[2], hyper, guard)
+        live, shadow = commit(guard[0], live, shadow)
+    return live, shadow, verdicts
 
 
 def describe(words):

@@ -55,6 +55,82 @@ class FlatBuffers:
         self.flat_grad.zero_()
 
 
+class BufferSlab:
+    """Re-homes every module buffer of a model (`model.buffers()`: BatchNorm running statistics, the int64
+    `num_batches_tracked` scalars, whatever else a module registers, non-persistent ones included; a buffer shared by
+    several modules once) as a view of ONE byte slab `live`, each buffer on a 16-byte boundary with zero padding, beside
+    a `shadow` slab of the same size that starts as a copy.  What csrc/adam.hip mpa_guard_commit works on: behind an
+    applied step shadow <- live, behind a skipped one live <- shadow, so a skipped step leaves every buffer with the bits
+    it had before the step.  Kernels that write running statistics take the buffers as tensors and so write into the
+    slab; a captured step bakes the slab's addresses in, which is why the slab has to exist before the first capture.
+
+    `names`, `offsets`, `sizes` (bytes) describe the layout.  Device-agnostic like FlatBuffers: on host tensors
+    `commit` is `guard_ref.commit` on the slab.  A model without buffers gives a slab of zero bytes."""
+
+    ALIGN = 16
+
+    def __init__(self, model):
+        self.model = model
+        named = list(model.named_buffers())  # (remove_duplicate: a shared buffer appears once, under its first name)
+        dev = named[0][1].device if named else next((p.device for p in model.parameters()), torch.device("cpu"))
+        self.names, self.offsets, self.sizes, total = [], [], [], 0
+        for name, b in named:
+            if b.device != dev:
+                raise RuntimeError(f"BufferSlab: buffer {name} lives on {b.device}, the slab on {dev}")
+            self.names.append(name)
+            self.offsets.append(total)
+            self.sizes.append(b.numel() * b.element_size())
+            total += (self.sizes[-1] + self.ALIGN - 1) // self.ALIGN * self.ALIGN
+        self.nbytes = total
+        self.live = torch.zeros(total, dtype=torch.uint8, device=dev)
+        self._layout = []  # (name, dtype, shape) per slot, for check()
+        with torch.no_grad():
+            for (name, b), off, size in zip(named, self.offsets, self.sizes):
+                view = self.live[off:off + size].view(b.dtype).view(b.shape)
+                view.copy_(b)
+                b.data = view
+                self._layout.append((name, b.dtype, tuple(b.shape)))
+        self.shadow = self.live.clone()
+        self.check()
+
+    def refresh(self):
+        """shadow <- live: the current buffers become what a skipped step rolls back to (after a checkpoint was loaded)."""
+        self.shadow.copy_(self.live)
+
+    def commit(self, guard):
+        """mpa_guard_commit on the slab behind the verdict `guard[0]` (`guard`: the optimiser's guard words on the slab's
+        device); on host tensors its restatement."""
+        if self.nbytes == 0:
+            return
+        if self.live.is_cuda:
+            _lib.launch("mpa_guard_commit", self.live.device, guard, self.live, self.shadow, self.nbytes)
+            return
+        from .guard_ref import commit
+        live, shadow = commit(int(guard[0]), self.live.numpy(), self.shadow.numpy())
+        self.live.copy_(torch.from_numpy(live))
+        self.shadow.copy_(torch.from_numpy(shadow))
+
+    def check(self):
+        """RuntimeError naming the buffer if a buffer of the model no longer is its view of the slab (after
+        `model.to(...)`, `.float()` / `.double()`, or a module that registered a buffer anew): a rollback would then
+        restore memory nobody reads."""
+        slots = {name: (off, dtype, shape) for (name, dtype, shape), off in zip(self._layout, self.offsets)}
+        base = self.live.data_ptr()
+        now = dict(self.model.named_buffers())
+        for name in slots:
+            if name not in now:
+                raise RuntimeError(f"BufferSlab: buffer {name} left the model after the slab was built")
+        for name, b in now.items():
+            if name not in slots:
+                raise RuntimeError(f"BufferSlab: buffer {name} was registered after the slab was built; build the trainer "
+                                   "after the model is complete")
+            off, dtype, shape = slots[name]
+            moved = b.numel() > 0 and b.data_ptr() != base + off
+            if moved or b.dtype != dtype or tuple(b.shape) != shape or b.device != self.live.device:
+                raise RuntimeError(f"BufferSlab: buffer {name} no longer lives in the slab (model.to(...), .float() or a "
+                                   "re-registered buffer after the trainer was built?); a skipped step could not roll it back")
+
+
 def decay_mask_for(model, flat: "FlatBuffers"):
     """1/0 per element of the flat parameter buffer: the reference's AdamW parameter groups (utils/utils.py:90-125
     `filter_wd_parameters`) exempt every bias and the weights of normalisation layers from weight decay."""
@@ -87,11 +163,20 @@ class FusedAdam:
     clipping's norm) and SKIPS the step on the device — parameters, moments, step count and bias corrections keep their
     bits — when the gradient holds a NaN or an inf, or when `launch_status` (an int32 device word, e.g. the GRU launches'
     status word) is raised.  What the reference gets from Lightning's GradScaler in its `--fp16` runs.  Eight device
-    words count what happened (`guard_words()`, `guard_report()`); forward-side state of a skipped step (BatchNorm
-    running statistics, dropout-seed positions) is not rolled back."""
+    words count what happened (`guard_words()`, `guard_report()`).
+
+    `guard_state` (a `BufferSlab`, needs `guard=True`): `step_dev()` issues mpa_guard_commit on the slab directly behind
+    the guarded update, so a skipped step also leaves every module buffer (BatchNorm running statistics,
+    `num_batches_tracked`, ...) with the bits it had before the step, and an applied step makes the current ones the
+    state to return to.  Without it the buffers keep what the skipped step's forward wrote.  Host-side counters
+    (dropout-seed positions, draw counters, the producers') are never rolled back: the skipped step's draws are spent
+    and the next step draws fresh ones."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 decoupled_weight_decay=None, decay_mask=None, clip_grad=None, guard=False, launch_status=None):
+                 decoupled_weight_decay=None, decay_mask=None, clip_grad=None, guard=False, launch_status=None,
+                 guard_state=None):
+        if guard_state is not None and not guard:
+            raise ValueError("FusedAdam: guard_state (the buffer slab a skipped step rolls back) needs guard=True")
         self.flat = params if isinstance(params, FlatBuffers) else FlatBuffers(params)
         self.params = self.flat.params
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
@@ -108,7 +193,7 @@ class FusedAdam:
         self.exp_avg = torch.zeros_like(self.flat_param)
         self.exp_avg_sq = torch.zeros_like(self.flat_param)
         self._hyper_dev, self._uploaded = None, (None, None)
-        self.guard, self.launch_status = bool(guard), launch_status
+        self.guard, self.launch_status, self.guard_state = bool(guard), launch_status, guard_state
         # the eight guard words live from construction on (a checkpoint may be loaded before the first step)
         self._guard_dev = torch.zeros(8, dtype=torch.int32, device=self.flat_param.device) if self.guard else None
         self._guard_ws = None
@@ -177,6 +262,9 @@ class FusedAdam:
             _lib.launch("mpa_adam_step_guarded", dev, self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq,
                         self.numel, self._hyper_dev, float(self.betas[0]), float(self.betas[1]), float(self.eps),
                         float(self.weight_decay), int(self.decoupled), self.decay_mask, self._guard_dev)
+            slab = self.guard_state
+            if slab is not None and slab.nbytes:  # applied: shadow <- live; skipped: live <- shadow (same verdict word)
+                _lib.launch("mpa_guard_commit", dev, self._guard_dev, slab.live, slab.shadow, slab.nbytes)
             return
         if not self.clip_grad and self._clip_written:  # clipping was switched off: back to "no clipping"
             self._hyper_dev[5:6].fill_(1.0)

@@ -30,18 +30,33 @@ from . import _lib
 from . import gru as _gru
 from .gradsink import DeferredBackward, GradSink
 from .dp import BucketedGradReducer, broadcast_from_rank0, bucket_sizes_for, ordered_parameters
-from .optim import FlatBuffers, FusedAdam, cosine_warmup_lr, decay_mask_for
+from .optim import BufferSlab, FlatBuffers, FusedAdam, cosine_warmup_lr, decay_mask_for
 
 
 class Trainer:
-    def __init__(self, model, cfg=None, process_group=None, use_graph=False, graph_warmup=3, guard_step=None):
+    def __init__(self, model, cfg=None, process_group=None, use_graph=False, graph_warmup=3, guard_step=None,
+                 guard_buffers=None):
         """`guard_step` (None: `cfg.optimizer.skip_nonfinite`, False where the key is absent — no preset sets it): every
         optimiser step is guarded on the device (optim.FusedAdam `guard=True`): a step whose reduced gradient holds a
         NaN or an inf, or behind which the GRU launches' status word is raised, is skipped — parameters, moments and
-        the step count keep their bits — and counted.  Forward-side state of a skipped step (BatchNorm running
-        statistics, `num_batches_tracked`, dropout-seed positions, device draw counters) is NOT rolled back; a NaN born
-        in the forward pass reaches the running statistics, which is why a guarded `state_dict()` refuses non-finite
-        parameters and buffers."""
+        the step count keep their bits — and counted.
+
+        `guard_buffers` (None: `cfg.optimizer.skip_rollback_buffers`, False where absent — no preset sets it; needs a
+        guarded step): a skipped step also rolls back every module buffer.  The buffers are re-homed here into one
+        byte slab (optim.BufferSlab, `self.buffer_slab`) with a shadow beside it, and one more launch behind every
+        guarded update (csrc/adam.hip mpa_guard_commit) copies live -> shadow after an applied step and shadow -> live
+        after a skipped one, decided on the device by the guard's verdict — eager, warm-up, captured and data-parallel
+        steps alike (every rank rolls back its own per-rank statistics on the common verdict).  The run then equals,
+        buffers included, one that never saw the skipped batch.  The model must not be moved or cast afterwards
+        (`BufferSlab.check()` runs here, at the capture and in `state_dict()`).
+
+        Without `guard_buffers` forward-side state of a skipped step (BatchNorm running statistics,
+        `num_batches_tracked`) is NOT rolled back: a NaN born in the forward pass reaches the running statistics.
+        Never rolled back, and harmless: the dropout-seed positions (host counters; the skipped step's masks are spent,
+        the next step draws fresh ones), the matching and seq2seq draw counters (rewritten from the host counter in
+        front of every step) and the producers' counters (the data stream is outside the step).  The remaining hole: a
+        step whose gradient is finite while a statistic overflowed to inf is applied and the statistic committed — which
+        is why a guarded `state_dict()` still refuses non-finite parameters and buffers."""
         self.model = model
         if use_graph and getattr(model, "semantic", False) and getattr(model, "match_sample", "host") != "device":
             # identical-part matching draws its point sample on the host every step (base_model._match_parts; reference
@@ -74,14 +89,21 @@ class Trainer:
         opt = cfg.optimizer
         self.flat = FlatBuffers(ordered_parameters(model))
         self.guard_step = bool(opt.get("skip_nonfinite", False) if guard_step is None else guard_step)
+        self.guard_buffers = bool(opt.get("skip_rollback_buffers", False) if guard_buffers is None else guard_buffers)
+        if self.guard_buffers and not self.guard_step:
+            raise ValueError("Trainer: guard_buffers=True (cfg.optimizer.skip_rollback_buffers) rolls back the buffers of "
+                             "a SKIPPED step and so needs guard_step=True (cfg.optimizer.skip_nonfinite)")
         dev = self.flat.flat_param.device
+        # the buffers move into their slab now: the model is on its device and nothing has been captured yet
+        self.buffer_slab = BufferSlab(model) if self.guard_buffers else None
         # the status word the guard reads is the one the GRU launches raise (allocated here: before any capture)
         status = _gru.prepare(dev)[0] if self.guard_step and dev.type == "cuda" else None
         # weight decay > 0 -> AdamW with biases / normalisation weights exempt (base_model.py:394-404); clip_grad ->
         # global-norm clipping of the averaged gradient (scripts/train.py:90 gradient_clip_val)
         self.optimizer = FusedAdam(self.flat, lr=opt.lr, weight_decay=opt.weight_decay,
                                    decay_mask=decay_mask_for(model, self.flat) if opt.weight_decay > 0 else None,
-                                   clip_grad=opt.get("clip_grad", None), guard=self.guard_step, launch_status=status)
+                                   clip_grad=opt.get("clip_grad", None), guard=self.guard_step, launch_status=status,
+                                   guard_state=self.buffer_slab)
         self.schedule = None
         if opt.lr_scheduler:
             total = cfg.exp.num_epochs
@@ -90,6 +112,8 @@ class Trainer:
         self.epoch = 0
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         broadcast_from_rank0(self.flat, model, process_group)
+        if self.buffer_slab is not None:
+            self.buffer_slab.refresh()  # (rank 0's buffers arrived in place: they are the state to return to)
         self.group = process_group
         # eager: bucket hooks fire during backward; graph mode: the same two buckets, reduced between / behind the two
         # graphs (the reducer only provides the bucket slices there: its hooks are switched off)
@@ -124,6 +148,22 @@ class Trainer:
             raise
 
     # ---- guarded steps -------------------------------------------------------------------------------------------------
+    def _health_and_step(self, step):
+        """`check_health` and the optimiser step of a path that issues it outside a graph.  Without `guard_buffers` the look comes
+        first: a launch that gave up must not reach the parameters (csrc/gru.hip's status word), and a raise leaves the
+        step untaken.  With `guard_buffers` the step comes first.  `check_health` raises on the PINNED copy of the status
+        word, and only that raise clears the device word, so the guard behind it still reads the word raised: verdict 2,
+        the update returns at its first load and the buffers are rolled back — then the look reports the failure.  That
+        is what the captured step does (its guard and commit run inside the graph, the report follows the replay), and
+        it keeps the rule whole: the buffers are rolled back on every path on which the guard gave a non-zero verdict.
+        Raising first would leave that step's statistics folded in with no verdict ever written."""
+        if self.buffer_slab is None:
+            self.check_health()
+            step()
+        else:
+            step()
+            self.check_health()
+
     def _mark_failed_launch(self):
         """Data parallel, in front of the all-reduce of the bucket holding element 0: a status word raised on THIS rank
         becomes a NaN in the reduced gradient of every rank, which then all reach the same verdict (no extra collective)."""
@@ -153,8 +193,9 @@ class Trainer:
                                "load_state_dict first")
         for name, buf in self.model.named_buffers():
             if buf.is_floating_point() and not bool(torch.isfinite(buf).all()):
-                raise RuntimeError(f"Trainer.state_dict: buffer {name} holds a non-finite value (forward-side state of a "
-                                   "skipped step is not rolled back); restore a checkpoint with load_state_dict first")
+                raise RuntimeError(f"Trainer.state_dict: buffer {name} holds a non-finite value (buffers are rolled back "
+                                   "behind a skipped step only with guard_buffers=True, and never behind an applied one); "
+                                   "restore a checkpoint with load_state_dict first")
 
     def state_dict(self):
         """Model + optimiser state for a checkpoint; refuses (RuntimeError) if a launch behind the current parameters
@@ -165,6 +206,8 @@ class Trainer:
             raise RuntimeError("Trainer.state_dict: an earlier check_health reported a launch that gave up; the parameters "
                                "behind it are undefined — restore a checkpoint with load_state_dict first")
         self.check_health(synchronize=True)
+        if self.buffer_slab is not None:
+            self.buffer_slab.check()
         if self.guard_step:
             self._refuse_nonfinite_state()
         return {"model": self.model.state_dict(), "optimizer": self.optimizer.state_dict()
@@ -184,9 +227,11 @@ class Trainer:
         freshly built `use_graph=True` trainer starts with its eager warm-up steps, whose seeds travel by value."""
         if "state_dict" in state and "model" not in state:
             self.model.load_state_dict(state["state_dict"])
+            self._refresh_buffer_shadow()
             self._failed = False
             return
         self.model.load_state_dict(state["model"])
+        self._refresh_buffer_shadow()
         if state.get("optimizer") is not None:
             self.optimizer.load_state_dict(state["optimizer"])
         if self.schedule is not None:
@@ -202,6 +247,13 @@ class Trainer:
             for m, c in zip(seeded, calls):
                 m._calls = int(c)
         self._failed = False
+
+    def _refresh_buffer_shadow(self):
+        """Behind a load of the model's buffers (copied in place, so they stay views of the slab): the loaded statistics,
+        not the ones from before the load, are what a skipped step returns to."""
+        if self.buffer_slab is not None:
+            self.buffer_slab.check()
+            self.buffer_slab.refresh()
 
     def evaluate(self, batches, prefix="val"):
         """One evaluation pass over `batches` (evaluate.Evaluator on this trainer's model and process group): the
@@ -263,6 +315,8 @@ class Trainer:
         return loss.detach() if loss_out is None else loss_out
 
     def _capture(self, data_dict):
+        if self.buffer_slab is not None:
+            self.buffer_slab.check()  # the graph bakes the buffers' addresses in: they must be the slab's
         self._static_batch = {k: v.clone() for k, v in self._tensor_items(data_dict).items()}
         self._loss_buf = torch.zeros((), dtype=torch.float32, device=self.flat.flat_param.device)
         self._graph = torch.cuda.CUDAGraph()
@@ -345,9 +399,7 @@ class Trainer:
                     if self.guard_step:
                         self._mark_failed_launch()
                     dist.all_reduce(self.flat.flat_grad, group=self.group)
-                self.check_health()
-                self.optimizer.prepare_hyper()
-                self.optimizer.step_dev()
+                self._health_and_step(self.optimizer.step)
                 return loss
             torch.cuda.synchronize()
             self._capture(data_dict)
@@ -366,8 +418,7 @@ class Trainer:
                 if self.guard_step:
                     self._mark_failed_launch()
                 dist.all_reduce(self.flat.flat_grad, group=self.group)
-            self.check_health()  # before the (uncaptured) optimiser step consumes the gradients
-            self.optimizer.step_dev()
+            self._health_and_step(self.optimizer.step_dev)  # (the optimiser step is not captured here)
         # the captured status copy refreshes the pinned word on every replay: a replay that gave up is reported here, at
         # the latest one replay later (the copy is asynchronous), and the word is cleared so that later replays run
         self.check_health()
@@ -386,6 +437,5 @@ class Trainer:
                 one = self._one = torch.ones((), dtype=loss.dtype, device=loss.device)
             loss.backward(one)
         self.optimizer.grad_scale = self.reducer.finish()
-        self.check_health()  # a launch that gave up must not reach the parameters (csrc/gru.hip's status word)
-        self.optimizer.step()
+        self._health_and_step(self.optimizer.step)
         return loss.detach()

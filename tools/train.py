@@ -3,6 +3,7 @@
   python tools/train.py --preset pn_transformer_everyday --data-dir data/breaking_bad --data-fn everyday.train.txt \\
       --val-fn everyday.val.txt [--category Bottle] [--epochs 400] [--graph] [--ckpt-dir ckpt] [--resume]
   python tools/train.py --preset pn_transformer_everyday --skip-nonfinite --skip-limit 20 ...  (bad steps skipped on the device)
+  python tools/train.py --preset pn_transformer_everyday --skip-nonfinite --rollback-buffers ...  (and their BatchNorm statistics undone)
   python tools/train.py --preset pn_transformer_everyday --repulsion 0.01 1.0 ...   (the opt-in repulsion term: THRE W)
   python tools/train.py --preset lstm_everyday --lstm-draws device --graph ...      (B-LSTM captured: its draws on the device)
   python tools/train.py --preset dgl_partnet_chair --data-dir data/partnet --data-fn Chair.train.npy --val-fn Chair.val.npy
@@ -58,6 +59,9 @@ def parser():
                          "or an inf or behind which a launch gave up (parameters, moments and step count keep their bits)")
     ap.add_argument("--skip-limit", type=int, default=-1, metavar="N",
                     help="with --skip-nonfinite: stop at a log line that finds N steps skipped in a row")
+    ap.add_argument("--rollback-buffers", action="store_true",
+                    help="with --skip-nonfinite: cfg.optimizer.skip_rollback_buffers: a skipped step also rolls back every "
+                         "module buffer (BatchNorm running statistics, num_batches_tracked) on the device")
     ap.add_argument("--seed", type=int, default=0)
     return ap
 
@@ -71,6 +75,8 @@ def parse_args(argv=None):
         ap.error("--resume needs --ckpt-dir")
     if args.skip_limit > 0 and not args.skip_nonfinite:
         ap.error("--skip-limit needs --skip-nonfinite")
+    if args.rollback_buffers and not args.skip_nonfinite:
+        ap.error("--rollback-buffers needs --skip-nonfinite")
     return args
 
 
@@ -137,6 +143,8 @@ def configure(args):
         cfg.loss.repulsion_thre, cfg.loss.repulsion_loss_w = args.repulsion
     if args.skip_nonfinite:
         cfg.optimizer.skip_nonfinite = True
+    if args.rollback_buffers:
+        cfg.optimizer.skip_rollback_buffers = True
     return cfg
 
 
