@@ -665,6 +665,47 @@ int mpa_adam_step_guarded(float* param, const float* grad, float* exp_avg, float
 int mpa_guard_mark(const int32_t* launch_status, float* grad, int64_t numel, void* stream);
 int mpa_guard_commit(const int32_t* guard, void* live, void* shadow, int64_t bytes, void* stream);
 
+/* ---- Exponential moving average of the weights (csrc/weight_average.hip; opt-in) ------------------------------
+ * The reference keeps one copy of the weights; this adds the averaged copy of timm's ModelEmaV2 /
+ * torch.optim.swa_utils.AveragedModel, kept on the device: e <- e + (1 - d)(p - e) behind every APPLIED optimiser step.
+ *
+ * mpa_ema_update: ONE launch over both state ranges of a model.
+ *   (a) `param` (read) and `ema` (read / written): `numel` float32 elements of the flat parameter buffer; numel % 4 == 0,
+ *       both 16-byte aligned and disjoint.
+ *   (b) `live` (read) and `ema_state` (read / written): `state_bytes` bytes of the buffer slab (optim.BufferSlab);
+ *       state_bytes % 16 == 0, both 16-byte aligned and disjoint.  `segments`: DEVICE table of `num_segments` int64
+ *       triples {byte offset, byte size, kind}, one per buffer, `segments_host` the same table in host memory (read
+ *       during the call, which is how the table is checked without touching the device; the caller keeps the two
+ *       equal).  A segment's slot is [offset, offset + size rounded up to 16); slots start on 16-byte boundaries, ascend,
+ *       do not overlap and lie inside the slab.  kind 1: `size` / 4 float32 words averaged like the parameters
+ *       (size % 4 == 0); kind 0: copied bit for bit (int64 counters, flags).  The slot's bytes behind `size` are copied
+ *       too (BufferSlab pads with zeros).  Nothing outside the slots is written; a zero-size segment writes nothing.
+ *       state_bytes == 0 or num_segments == 0 is legal (the pointers may then be NULL).  One block walks one segment:
+ *       meant for slabs of many small buffers (BatchNorm statistics), not for one buffer of many megabytes.
+ *   `hyper`: the optimiser's eight device words (mpa_adam_step_dev); t = the int32 in hyper[4], read by the kernel BEHIND
+ *   this step's advance, so t >= 1.  Every operation below is one rounded float32 operation, no FMA contraction:
+ *       a = (float)t;   q = (1 + a) / (10 + a);   d = warmup ? fminf(decay, q) : decay;   c = 1 - d
+ *       e = e + c * (p - e)                         (non-finite values propagate as IEEE 754 says)
+ *   0 <= decay < 1; warmup 0 / 1.  `guard`: the eight guard words of mpa_step_guard, or NULL; guard[0] != 0 -> every
+ *   block returns before its first store (the average of a skipped step keeps its bits).  Verdict and step count are
+ *   read from device memory by every block with one uniform load each, never passed by value: a captured launch follows
+ *   them on every replay.  Grid-stride, 16 bytes per lane per access, no atomics, no LDS, bit-identical from run to run.
+ *   MPA_EINVAL, with nothing launched: a null `hyper`, a null range of non-zero size, a misaligned pointer, numel < 0 or
+ *   numel % 4, state_bytes < 0 or state_bytes % 16, decay outside [0, 1) or NaN, overlapping ranges, a segment that is
+ *   not 16-byte aligned, leaves the slab, overlaps its predecessor or has an unknown kind.
+ *
+ * mpa_ema_swap: bitwise exchange, in 16-byte units and ONE launch, of `param` <-> `ema` (`param_bytes` bytes) and
+ *   `live` <-> `ema_state` (`state_bytes` bytes).  Two calls give every bit back, NaN payloads and padding included.  Sizes
+ *   are non-negative multiples of 16 (zero in either pair, or both, is legal: the pair's pointers may be NULL); ranges
+ *   16-byte aligned and pairwise disjoint, else MPA_EINVAL.  It is how averaged weights are put in front of the model:
+ *   parameters and buffers stay views of the same memory.
+ * Restated in numpy by multi_part_assembly_amd/ema_ref.py. */
+int mpa_ema_update(const float* param, float* ema, int64_t numel, const void* live, void* ema_state, int64_t state_bytes,
+                   const int64_t* segments_host, const int64_t* segments, int64_t num_segments, const float* hyper,
+                   float decay, int warmup, const int32_t* guard, void* stream);
+int mpa_ema_swap(void* param, void* ema, int64_t param_bytes, void* live, void* ema_state, int64_t state_bytes,
+                 void* stream);
+
 /* ---- GT <-> prediction matching of equivalent parts (semantic datasets) --------------------------------------
  * Replaces BaseModel._linear_sum_assignment / _match_parts (multi_part_assembly/models/modules/base_model.py:
  * 150-238: p x p Chamfer cost matrix on n = 100 sub-sampled points, scipy.optimize.linear_sum_assignment on the

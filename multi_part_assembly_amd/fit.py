@@ -102,7 +102,7 @@ def resume(trainer, ckpt_dir):
 
 
 def fit(trainer, train_producer, sampler, val_batches=None, epochs=None, val_every=None, ckpt_dir=None, keep=5,
-        monitor="val/part_acc", log_every=50, on_log=None, max_steps=None, skip_limit=None):
+        monitor="val/part_acc", log_every=50, on_log=None, max_steps=None, skip_limit=None, val_weights=None):
     """Train from the epoch a preceding `resume` returned (0 otherwise) up to `epochs` (default `cfg.exp.num_epochs`).
 
     Per epoch e: `set_epoch(e)` on trainer and sampler; `train_step(train_producer.batch(idx))` for every index batch of
@@ -120,8 +120,19 @@ def fit(trainer, train_producer, sampler, val_batches=None, epochs=None, val_eve
     With a guarded trainer (`Trainer(guard_step=True)`: non-finite or failed steps are skipped on the device) every
     `log_every` record also carries `grad_norm` (the last step's; inf for a skipped non-finite one), `skipped` and
     `skipped_in_a_row`, read in the SAME device read as the running loss; `skip_limit`: RuntimeError with the
-    optimiser's `guard_report` text at a log read that finds `skipped_in_a_row >= skip_limit`."""
+    optimiser's `guard_report` text at a log read that finds `skipped_in_a_row >= skip_limit`.
+
+    `val_weights`: "live" or "ema" — which weights the validation passes (and so the `monitor` ranking) see; None means
+    "ema" for a trainer that keeps a weight average (`Trainer(ema_decay=...)`) and "live" otherwise.  The record of an
+    epoch that validated says which under "val/weights".  The checkpoints carry the average (`Trainer.state_dict`)."""
     guarded = bool(getattr(trainer, "guard_step", False))
+    averaging = getattr(trainer, "average", None) is not None
+    if val_weights is None:
+        val_weights = "ema" if averaging else "live"
+    if val_weights not in ("live", "ema"):
+        raise ValueError(f"fit: val_weights must be 'live' or 'ema', got {val_weights!r}")
+    if val_weights == "ema" and not averaging:
+        raise ValueError("fit: val_weights='ema' needs a trainer that averages (Trainer(ema_decay=...) / cfg.optimizer.ema_decay)")
     if skip_limit is not None and not guarded:
         raise ValueError("fit: skip_limit needs a guarded trainer (Trainer(guard_step=True) / cfg.optimizer.skip_nonfinite)")
 
@@ -213,7 +224,11 @@ def fit(trainer, train_producer, sampler, val_batches=None, epochs=None, val_eve
             return history
         record = {"epoch": epoch, "lr": lr, "train/loss": loss_sum / max(loss_steps, 1)}
         if val_every and val_batches is not None and (epoch + 1) % val_every == 0:
-            record.update(trainer.evaluate(val_batches() if callable(val_batches) else val_batches))
+            batches = val_batches() if callable(val_batches) else val_batches
+            # (a trainer that knows nothing of `weights` is only ever asked for its live weights, positionally as before)
+            record.update(trainer.evaluate(batches) if val_weights == "live" else
+                          trainer.evaluate(batches, weights=val_weights))
+            record["val/weights"] = val_weights
         history.append(record)
         if on_log is not None:
             on_log(record)

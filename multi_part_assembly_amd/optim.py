@@ -131,6 +131,126 @@ class BufferSlab:
                                    "re-registered buffer after the trainer was built?); a skipped step could not roll it back")
 
 
+class WeightAverage:
+    """An exponential moving average of a model's weights beside the live ones (csrc/weight_average.hip; timm's
+    ModelEmaV2 / torch.optim.swa_utils.AveragedModel): `ema_param`, a second flat buffer, and `ema_state`, a second byte
+    slab, both starting as copies of the current state.  `update` averages behind an optimiser step — one launch,
+    coefficient from the device step count `hyper[4]`, nothing written behind a non-zero guard verdict; `decay` in
+    [0, 1), `warmup`: d = min(decay, (1 + t) / (10 + t)).  float32 buffers are averaged, every other buffer (the int64
+    `num_batches_tracked`) is copied.  `swap` exchanges live and averaged bits in place (`swapped` says which are in
+    front): parameters and buffers stay views of the same memory, so kernels, GradSink and captured graphs see the
+    averaged values with no re-homing.  Device-agnostic like FlatBuffers and BufferSlab: on host tensors the methods
+    run the restatement `ema_ref`."""
+
+    def __init__(self, flat, slab, decay, warmup=True):
+        import ctypes
+        from .ema_ref import KIND_COPY, KIND_F32, check_segments
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:  # (false for a NaN)
+            raise ValueError(f"WeightAverage: decay must lie in [0, 1), got {decay}")
+        if slab.live.device != flat.flat_param.device:
+            raise RuntimeError("WeightAverage: the flat parameters and the buffer slab live on different devices")
+        self.flat, self.slab, self.decay, self.warmup = flat, slab, decay, bool(warmup)
+        self.ema_param = flat.flat_param.clone()
+        self.ema_state = slab.live.clone()
+        self.segments = [(off, size, KIND_F32 if dtype == torch.float32 else KIND_COPY)
+                         for (_, dtype, _), off, size in zip(slab._layout, slab.offsets, slab.sizes)]
+        check_segments(self.segments, slab.nbytes)
+        words = [w for seg in self.segments for w in seg]
+        self._table_host = (ctypes.c_int64 * len(words))(*words) if words else None
+        self._table_dev = torch.tensor(words, dtype=torch.int64, device=flat.flat_param.device) if words else None
+        self.swapped = False
+
+    def _refuse_swapped(self, what):
+        if self.swapped:
+            raise RuntimeError(f"WeightAverage.{what}: the averaged weights are swapped in (swap() back first)")
+
+    def update_args(self, hyper, guard):
+        """The arguments of mpa_ema_update behind the device (what `FusedAdam.step_dev` launches)."""
+        return (self.flat.flat_param, self.ema_param, self.flat.numel, self.slab.live, self.ema_state, self.slab.nbytes,
+                self._table_host, self._table_dev, len(self.segments), hyper, self.decay, int(self.warmup), guard)
+
+    def update(self, hyper, guard=None):
+        """ema <- ema + c (current - ema) behind the step whose count `hyper[4]` holds (`hyper`: the optimiser's eight
+        words; `guard`: its guard words or None)."""
+        self._refuse_swapped("update")
+        if self.ema_param.is_cuda:
+            _lib.launch("mpa_ema_update", self.ema_param.device, *self.update_args(hyper, guard))
+            return
+        from .ema_ref import update
+        t = int(hyper[4:5].view(torch.int32)[0])
+        ema, state = update(0 if guard is None else int(guard[0]), t, self.decay, self.warmup,
+                            self.flat.flat_param.detach().numpy(), self.ema_param.numpy(), self.slab.live.numpy(),
+                            self.ema_state.numpy(), self.segments)
+        self.ema_param.copy_(torch.from_numpy(ema))
+        self.ema_state.copy_(torch.from_numpy(state))
+
+    def swap(self):
+        """Exchange live and averaged weights, bit for bit, in one launch."""
+        param, live = self.flat.flat_param, self.slab.live
+        if param.is_cuda:
+            _lib.launch("mpa_ema_swap", param.device, param, self.ema_param, self.flat.numel * 4, live, self.ema_state,
+                        self.slab.nbytes)
+        else:
+            with torch.no_grad():
+                for a, b in ((param, self.ema_param), (live, self.ema_state)):
+                    keep = a.clone()
+                    a.copy_(b)
+                    b.copy_(keep)
+        self.swapped = not self.swapped
+
+    def reset(self):
+        """average <- current weights (after a checkpoint without an average was loaded)."""
+        self._refuse_swapped("reset")
+        with torch.no_grad():
+            self.ema_param.copy_(self.flat.flat_param)
+            self.ema_state.copy_(self.slab.live)
+
+    def _slots(self, model):
+        """state_dict key -> ("param", offset, tensor) | ("buffer", offset, tensor) for what the average holds."""
+        flat_off = {id(p): off for p, off in zip(self.flat.params, self.flat.offsets)}
+        first = dict(model.named_buffers())
+        slab_off = {id(first[name]): off for name, off in zip(self.slab.names, self.slab.offsets) if name in first}
+        slots = {}
+        for key, p in model.named_parameters(remove_duplicate=False):
+            if id(p) in flat_off:
+                slots[key] = ("param", flat_off[id(p)], p)
+        for key, b in model.named_buffers(remove_duplicate=False):
+            if id(b) in slab_off:
+                slots[key] = ("buffer", slab_off[id(b)], b)
+        return slots
+
+    def _view(self, kind, off, like):
+        if kind == "param":
+            return self.ema_param[off:off + like.numel()].view_as(like)
+        return self.ema_state[off:off + like.numel() * like.element_size()].view(like.dtype).view(like.shape)
+
+    def averaged_state_dict(self, model):
+        """A dict shaped like `model.state_dict()` (same keys, same order) of CLONES, built without swapping: trainable
+        parameters from the averaged flat buffer, buffers from the averaged slab, everything else (parameters with
+        requires_grad=False) from the model."""
+        self._refuse_swapped("averaged_state_dict")
+        slots = self._slots(model)
+        out = type(model.state_dict())()
+        for key, value in model.state_dict().items():
+            slot = slots.get(key)
+            out[key] = (self._view(*slot) if slot is not None else value).detach().clone()
+        return out
+
+    def load_averaged_state_dict(self, state, model):
+        """Inverse of `averaged_state_dict`: every key the average holds is copied in; a missing one is a KeyError.
+        Entries the average does not hold (frozen parameters) are ignored."""
+        self._refuse_swapped("load_averaged_state_dict")
+        slots = self._slots(model)
+        wanted = [k for k in model.state_dict() if k in slots]
+        missing = [k for k in wanted if k not in state]
+        if missing:
+            raise KeyError(f"WeightAverage.load_averaged_state_dict: missing {missing[:3]}{'...' if len(missing) > 3 else ''}")
+        with torch.no_grad():
+            for key in wanted:
+                self._view(*slots[key]).copy_(state[key])
+
+
 def decay_mask_for(model, flat: "FlatBuffers"):
     """1/0 per element of the flat parameter buffer: the reference's AdamW parameter groups (utils/utils.py:90-125
     `filter_wd_parameters`) exempt every bias and the weights of normalisation layers from weight decay."""
@@ -170,11 +290,15 @@ class FusedAdam:
     `num_batches_tracked`, ...) with the bits it had before the step, and an applied step makes the current ones the
     state to return to.  Without it the buffers keep what the skipped step's forward wrote.  Host-side counters
     (dropout-seed positions, draw counters, the producers') are never rolled back: the skipped step's draws are spent
-    and the next step draws fresh ones."""
+    and the next step draws fresh ones.
+
+    `average` (a `WeightAverage` over the same flat buffer; may be assigned after construction): `step_dev()` issues
+    mpa_ema_update as its LAST launch — behind the update, and behind mpa_guard_commit where that runs — with the guard words
+    when `guard=True`, so the average of a skipped step keeps its bits.  One launch more per step, none without it."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  decoupled_weight_decay=None, decay_mask=None, clip_grad=None, guard=False, launch_status=None,
-                 guard_state=None):
+                 guard_state=None, average=None):
         if guard_state is not None and not guard:
             raise ValueError("FusedAdam: guard_state (the buffer slab a skipped step rolls back) needs guard=True")
         self.flat = params if isinstance(params, FlatBuffers) else FlatBuffers(params)
@@ -194,6 +318,7 @@ class FusedAdam:
         self.exp_avg_sq = torch.zeros_like(self.flat_param)
         self._hyper_dev, self._uploaded = None, (None, None)
         self.guard, self.launch_status, self.guard_state = bool(guard), launch_status, guard_state
+        self.average = average
         # the eight guard words live from construction on (a checkpoint may be loaded before the first step)
         self._guard_dev = torch.zeros(8, dtype=torch.int32, device=self.flat_param.device) if self.guard else None
         self._guard_ws = None
@@ -248,8 +373,13 @@ class FusedAdam:
             self._uploaded = (float(self.lr), float(self.grad_scale))
 
     def step_dev(self):
-        """[clip coefficient +] step-count advance + Adam update, all on the stream (safe to capture in a HIP
-        graph: every launch argument is constant across replays)."""
+        """[clip coefficient +] step-count advance + Adam update [+ weight average], all on the stream (safe to capture
+        in a HIP graph: every launch argument is constant across replays)."""
+        self._update_dev()
+        if self.average is not None:  # last: behind the advance of the step count and the commit of the buffers
+            _lib.launch("mpa_ema_update", self.flat_param.device, *self.average.update_args(self._hyper_dev, self._guard_dev))
+
+    def _update_dev(self):
         dev = self.flat_param.device
         if self.guard:
             # pass + verdict / coefficient / advance, then the update that returns at once behind a non-zero verdict

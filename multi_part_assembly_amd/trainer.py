@@ -23,6 +23,8 @@ GPU-bound, so the replay is only ~2 % faster than eager launches; eager stays th
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 import torch.distributed as dist
 
@@ -30,13 +32,23 @@ from . import _lib
 from . import gru as _gru
 from .gradsink import DeferredBackward, GradSink
 from .dp import BucketedGradReducer, broadcast_from_rank0, bucket_sizes_for, ordered_parameters
-from .optim import BufferSlab, FlatBuffers, FusedAdam, cosine_warmup_lr, decay_mask_for
+from .optim import BufferSlab, FlatBuffers, FusedAdam, WeightAverage, cosine_warmup_lr, decay_mask_for
 
 
 class Trainer:
     def __init__(self, model, cfg=None, process_group=None, use_graph=False, graph_warmup=3, guard_step=None,
-                 guard_buffers=None):
-        """`guard_step` (None: `cfg.optimizer.skip_nonfinite`, False where the key is absent — no preset sets it): every
+                 guard_buffers=None, ema_decay=None, ema_warmup=None):
+        """`ema_decay` (None: `cfg.optimizer.ema_decay`, off where the key is absent — no preset sets it) in [0, 1): an
+        exponential moving average of the weights is kept on the device (optim.WeightAverage, `self.average`): one more
+        launch (csrc/weight_average.hip mpa_ema_update) as the last of every optimiser step — eager, warm-up, captured
+        and data-parallel steps alike — averages the flat parameters and every float32 buffer and copies the other
+        buffers; `ema_warmup` (None: `cfg.optimizer.ema_warmup`, True where absent) starts with a small decay,
+        min(decay, (1 + t) / (10 + t)) over the applied steps t.  A skipped step (`guard_step`) leaves the average's bits
+        alone.  The buffers move into one byte slab for it (`self.buffer_slab`, as for `guard_buffers`, which shares
+        the slab), so the model must not be moved or cast afterwards.  `averaged_weights()` puts the average in front of
+        the model, `evaluate(weights="ema")` evaluates it, `state_dict()` carries it under "ema".
+
+        `guard_step` (None: `cfg.optimizer.skip_nonfinite`, False where the key is absent — no preset sets it): every
         optimiser step is guarded on the device (optim.FusedAdam `guard=True`): a step whose reduced gradient holds a
         NaN or an inf, or behind which the GRU launches' status word is raised, is skipped — parameters, moments and
         the step count keep their bits — and counted.
@@ -94,8 +106,14 @@ class Trainer:
             raise ValueError("Trainer: guard_buffers=True (cfg.optimizer.skip_rollback_buffers) rolls back the buffers of "
                              "a SKIPPED step and so needs guard_step=True (cfg.optimizer.skip_nonfinite)")
         dev = self.flat.flat_param.device
-        # the buffers move into their slab now: the model is on its device and nothing has been captured yet
-        self.buffer_slab = BufferSlab(model) if self.guard_buffers else None
+        ema_decay = opt.get("ema_decay", None) if ema_decay is None else ema_decay
+        self.ema_warmup = bool(opt.get("ema_warmup", True) if ema_warmup is None else ema_warmup)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        if self.ema_decay is not None and not 0.0 <= self.ema_decay < 1.0:
+            raise ValueError(f"Trainer: ema_decay (cfg.optimizer.ema_decay) must lie in [0, 1), got {ema_decay}")
+        # the buffers move into their slab now: the model is on its device and nothing has been captured yet (the weight
+        # average needs them as one range too; only `guard_buffers` hands the slab to the optimiser for the rollback)
+        self.buffer_slab = BufferSlab(model) if self.guard_buffers or self.ema_decay is not None else None
         # the status word the guard reads is the one the GRU launches raise (allocated here: before any capture)
         status = _gru.prepare(dev)[0] if self.guard_step and dev.type == "cuda" else None
         # weight decay > 0 -> AdamW with biases / normalisation weights exempt (base_model.py:394-404); clip_grad ->
@@ -103,7 +121,7 @@ class Trainer:
         self.optimizer = FusedAdam(self.flat, lr=opt.lr, weight_decay=opt.weight_decay,
                                    decay_mask=decay_mask_for(model, self.flat) if opt.weight_decay > 0 else None,
                                    clip_grad=opt.get("clip_grad", None), guard=self.guard_step, launch_status=status,
-                                   guard_state=self.buffer_slab)
+                                   guard_state=self.buffer_slab if self.guard_buffers else None)
         self.schedule = None
         if opt.lr_scheduler:
             total = cfg.exp.num_epochs
@@ -114,6 +132,11 @@ class Trainer:
         broadcast_from_rank0(self.flat, model, process_group)
         if self.buffer_slab is not None:
             self.buffer_slab.refresh()  # (rank 0's buffers arrived in place: they are the state to return to)
+        # the average starts as a copy of rank 0's weights, like the weights themselves
+        self.average = WeightAverage(self.flat, self.buffer_slab, self.ema_decay, self.ema_warmup) \
+            if self.ema_decay is not None else None
+        self.optimizer.average = self.average
+        self._ema_warned = False
         self.group = process_group
         # eager: bucket hooks fire during backward; graph mode: the same two buckets, reduced between / behind the two
         # graphs (the reducer only provides the bucket slices there: its hooks are switched off)
@@ -157,7 +180,7 @@ class Trainer:
         is what the captured step does (its guard and commit run inside the graph, the report follows the replay), and
         it keeps the rule whole: the buffers are rolled back on every path on which the guard gave a non-zero verdict.
         Raising first would leave that step's statistics folded in with no verdict ever written."""
-        if self.buffer_slab is None:
+        if not self.guard_buffers:
             self.check_health()
             step()
         else:
@@ -177,25 +200,36 @@ class Trainer:
     def _refuse_nonfinite_state(self):
         """Guarded trainers only, at checkpoints: a NaN / inf in a parameter (one mpa_step_guard pass over the flat
         parameters against scratch words) or in a buffer (the forward side is not guarded) must not reach a file."""
-        flat, opt = self.flat.flat_param, self.optimizer
-        if not flat.is_cuda:
+        opt = self.optimizer
+        if not self.flat.flat_param.is_cuda:
             return
         opt._ensure_hyper()
-        hyper = torch.zeros(8, dtype=torch.float32, device=flat.device)
-        words = torch.zeros(8, dtype=torch.int32, device=flat.device)
-        _lib.launch("mpa_step_guard", flat.device, flat, self.flat.numel, 0.0, None, 1.0, None, opt._guard_ws, hyper, words,
-                    float(opt.betas[0]), float(opt.betas[1]))
-        verdict, _, _, _, idx = words[:5].tolist()
-        if verdict:
-            k = max(i for i, off in enumerate(self.flat.offsets) if off <= idx)
-            raise RuntimeError(f"Trainer.state_dict: parameter {k} (shape {tuple(self.flat.params[k].shape)}) holds a "
-                               f"non-finite value at element {idx - self.flat.offsets[k]}; restore a checkpoint with "
-                               "load_state_dict first")
+
+        def refuse_flat(flat, whose):
+            hyper = torch.zeros(8, dtype=torch.float32, device=flat.device)
+            words = torch.zeros(8, dtype=torch.int32, device=flat.device)
+            _lib.launch("mpa_step_guard", flat.device, flat, self.flat.numel, 0.0, None, 1.0, None, opt._guard_ws, hyper,
+                        words, float(opt.betas[0]), float(opt.betas[1]))
+            verdict, _, _, _, idx = words[:5].tolist()
+            if verdict:
+                k = max(i for i, off in enumerate(self.flat.offsets) if off <= idx)
+                raise RuntimeError(f"Trainer.state_dict: {whose}parameter {k} (shape {tuple(self.flat.params[k].shape)}) "
+                                   f"holds a non-finite value at element {idx - self.flat.offsets[k]}; restore a "
+                                   "checkpoint with load_state_dict first")
+
+        refuse_flat(self.flat.flat_param, "")
         for name, buf in self.model.named_buffers():
             if buf.is_floating_point() and not bool(torch.isfinite(buf).all()):
                 raise RuntimeError(f"Trainer.state_dict: buffer {name} holds a non-finite value (buffers are rolled back "
                                    "behind a skipped step only with guard_buffers=True, and never behind an applied one); "
                                    "restore a checkpoint with load_state_dict first")
+        if self.average is not None:  # the average of an applied step follows the weights, non-finite ones included
+            refuse_flat(self.average.ema_param, "the weight average of ")
+            state = self.average.ema_state
+            for name, (off, size, kind) in zip(self.buffer_slab.names, self.average.segments):
+                if kind == 1 and not bool(torch.isfinite(state[off:off + size].view(torch.float32)).all()):
+                    raise RuntimeError(f"Trainer.state_dict: the weight average of buffer {name} holds a non-finite "
+                                       "value; restore a checkpoint with load_state_dict first")
 
     def state_dict(self):
         """Model + optimiser state for a checkpoint; refuses (RuntimeError) if a launch behind the current parameters
@@ -205,16 +239,31 @@ class Trainer:
         if getattr(self, "_failed", False):
             raise RuntimeError("Trainer.state_dict: an earlier check_health reported a launch that gave up; the parameters "
                                "behind it are undefined — restore a checkpoint with load_state_dict first")
+        if self.average is not None and self.average.swapped:
+            raise RuntimeError("Trainer.state_dict: the averaged weights are swapped in (inside averaged_weights()); "
+                               "\"model\" would hold the average and \"ema\" the live weights")
         self.check_health(synchronize=True)
         if self.buffer_slab is not None:
             self.buffer_slab.check()
         if self.guard_step:
             self._refuse_nonfinite_state()
-        return {"model": self.model.state_dict(), "optimizer": self.optimizer.state_dict()
-                if hasattr(self.optimizer, "state_dict") else None, "epoch": self.epoch,
-                # position of every dropout-seed stream (transformer.TransformerEncoder._next_seed), in module order: a
-                # resumed run then draws the masks the uninterrupted one would have drawn
-                "dropout_calls": [m._calls for m in self.model.modules() if hasattr(m, "advance_seed")]}
+        model_state = self.model.state_dict()
+        if self.buffer_slab is not None:
+            # buffers of several types are views of ONE byte slab, which `torch.save` refuses ("view the same data as
+            # different types"): the checkpoint takes copies of them
+            slab_views = {id(b) for b in self.model.buffers()}
+            for key, b in self.model.named_buffers(remove_duplicate=False):
+                if key in model_state and id(b) in slab_views:
+                    model_state[key] = model_state[key].clone()
+        state = {"model": model_state, "optimizer": self.optimizer.state_dict()
+                 if hasattr(self.optimizer, "state_dict") else None, "epoch": self.epoch,
+                 # position of every dropout-seed stream (transformer.TransformerEncoder._next_seed), in module order: a
+                 # resumed run then draws the masks the uninterrupted one would have drawn
+                 "dropout_calls": [m._calls for m in self.model.modules() if hasattr(m, "advance_seed")]}
+        if self.average is not None:  # "model" loads into a model as it is (tools/evaluate.py --weights ema)
+            state["ema"] = {"decay": self.average.decay, "warmup": self.average.warmup,
+                            "model": self.average.averaged_state_dict(self.model)}
+        return state
 
     def load_state_dict(self, state):
         """Inverse of `state_dict()`: model weights and buffers (copied in place: the parameters stay views of the flat
@@ -225,13 +274,17 @@ class Trainer:
         The dropout-seed positions are host counters; the device word a captured step reads its seed from is not
         restored here because `train_step` rewrites it from the counter (`advance_seed`) in front of every replay, and a
         freshly built `use_graph=True` trainer starts with its eager warm-up steps, whose seeds travel by value."""
+        if self.average is not None and self.average.swapped:
+            raise RuntimeError("Trainer.load_state_dict: the averaged weights are swapped in (inside averaged_weights())")
         if "state_dict" in state and "model" not in state:
             self.model.load_state_dict(state["state_dict"])
             self._refresh_buffer_shadow()
+            self._load_average(None)
             self._failed = False
             return
         self.model.load_state_dict(state["model"])
         self._refresh_buffer_shadow()
+        self._load_average(state.get("ema"))
         if state.get("optimizer") is not None:
             self.optimizer.load_state_dict(state["optimizer"])
         if self.schedule is not None:
@@ -255,9 +308,49 @@ class Trainer:
             self.buffer_slab.check()
             self.buffer_slab.refresh()
 
-    def evaluate(self, batches, prefix="val"):
+    def _load_average(self, ema):
+        """Behind a load of the model: the average of before the load never stays.  With the checkpoint's "ema" entry it
+        is restored (entries the entry lacks, such as non-persistent buffers, are the loaded weights'); without one it
+        becomes the loaded weights, with one warning per trainer.  A trainer without averaging ignores the entry; the
+        checkpoint's decay and warm-up are informational, the trainer's own hold."""
+        if self.average is None:
+            return
+        self.average.reset()
+        if ema is not None:
+            self.average.load_averaged_state_dict(ema["model"], self.model)
+        elif not self._ema_warned:
+            import warnings
+            self._ema_warned = True
+            warnings.warn("Trainer.load_state_dict: the checkpoint holds no weight average (\"ema\"); the average restarts "
+                          "from the loaded weights")
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """Inside the block the model computes with the averaged weights and buffers (one bitwise exchange in, one out,
+        also when the block raises); `train_step` and `state_dict` refuse meanwhile."""
+        if self.average is None:
+            raise RuntimeError("Trainer.averaged_weights: weight averaging is off (Trainer(ema_decay=...) / "
+                               "cfg.optimizer.ema_decay)")
+        if self.average.swapped:
+            raise RuntimeError("Trainer.averaged_weights: the averaged weights are swapped in already")
+        self.average.swap()
+        try:
+            yield self.model
+        finally:
+            self.average.swap()
+
+    def evaluate(self, batches, prefix="val", weights="live"):
         """One evaluation pass over `batches` (evaluate.Evaluator on this trainer's model and process group): the
-        batch-size-weighted averages as floats.  Touches neither the optimiser nor the dropout seeds of training."""
+        batch-size-weighted averages as floats.  Touches neither the optimiser nor the dropout seeds of training.
+        `weights="ema"`: the pass runs inside `averaged_weights()`."""
+        if weights not in ("live", "ema"):
+            raise ValueError(f"Trainer.evaluate: weights must be 'live' or 'ema', got {weights!r}")
+        if weights == "ema":
+            if self.average is None:
+                raise RuntimeError("Trainer.evaluate: weights='ema' needs weight averaging (Trainer(ema_decay=...) / "
+                                   "cfg.optimizer.ema_decay)")
+            with self.averaged_weights():
+                return self.evaluate(batches, prefix=prefix)
         from .evaluate import Evaluator
         ev = getattr(self, "_evaluator", None)
         if ev is None:
@@ -278,7 +371,7 @@ class Trainer:
         return dist.get_rank(self.group) if dist.is_initialized() else 0
 
     def fit(self, train_producer, sampler, val_batches=None, epochs=None, val_every=None, ckpt_dir=None, keep=5,
-            monitor="val/part_acc", log_every=50, on_log=None, max_steps=None, skip_limit=None):
+            monitor="val/part_acc", log_every=50, on_log=None, max_steps=None, skip_limit=None, val_weights=None):
         """The epoch loop (fit.fit has the contract): order of the epoch from `sampler` (sampler.EpochSampler), batches
         from `train_producer`, the schedule, validation every `val_every` epochs, the best `keep` checkpoints by
         `monitor` plus `last.pt` in `ckpt_dir`.  Continues from the epoch a preceding `resume` returned.  Returns the
@@ -286,7 +379,7 @@ class Trainer:
         from . import fit as _fit
         return _fit.fit(self, train_producer, sampler, val_batches=val_batches, epochs=epochs, val_every=val_every,
                         ckpt_dir=ckpt_dir, keep=keep, monitor=monitor, log_every=log_every, on_log=on_log,
-                        max_steps=max_steps, skip_limit=skip_limit)
+                        max_steps=max_steps, skip_limit=skip_limit, val_weights=val_weights)
 
     def resume(self, ckpt_dir):
         """Load `ckpt_dir/last.pt` if it exists (model, optimiser, schedule, seed positions now; sampler position, producer
@@ -426,6 +519,9 @@ class Trainer:
 
     def train_step(self, data_dict, batch_idx=0):
         """One optimiser step on this rank's shard; returns the (detached) scalar loss tensor."""
+        if self.average is not None and self.average.swapped:
+            raise RuntimeError("Trainer.train_step: the averaged weights are swapped in (inside averaged_weights()); a "
+                               "step would train the average")
         if self.use_graph:
             return self._graph_step(data_dict)
         self.model.train()

@@ -3,7 +3,7 @@
 
   python tools/evaluate.py --preset pn_transformer_everyday --weight ckpt.pt --data-dir data/breaking_bad \\
       --data-fn everyday.val.txt [--category Bottle | --category all] [--min-num-part 2] [--max-num-part 20]
-      [--connectivity] [--encoder pointnet2_ssg [--pointnet2-eval fused]]
+      [--connectivity] [--encoder pointnet2_ssg [--pointnet2-eval fused]] [--weights ema]
 
 `--preset` names a function of multi_part_assembly_amd.config; `--weight` a file written by `torch.save` holding either
 `Trainer.state_dict()`, a Lightning-style `{"state_dict": ...}` or a bare model state dict (not needed for the identity
@@ -25,8 +25,21 @@ from multi_part_assembly_amd.evaluate import Evaluator, evaluate_categories, for
 from multi_part_assembly_amd.pn_transformer import build_model  # noqa: E402
 
 
-def load_weights(model, path, device):
-    state = torch.load(path, map_location=device)
+def averaged_entry(state, path):
+    """The averaged model state of a `Trainer.state_dict()` checkpoint (`ckpt["ema"]["model"]`); SystemExit if it has none."""
+    ema = state.get("ema") if isinstance(state, dict) else None
+    if not (isinstance(ema, dict) and isinstance(ema.get("model"), dict)):
+        raise SystemExit(f"--weights ema: {path} holds no weight average (no \"ema\" entry: it was written by a run "
+                         "without tools/train.py --ema, or is not a Trainer.state_dict() checkpoint)")
+    return ema["model"]
+
+
+def load_weights(model, path, device, weights="live"):
+    # (weights_only=False: a checkpoint of `Trainer.fit` also holds the run's generator states, numpy's among them)
+    state = torch.load(path, map_location=device, weights_only=False)
+    if weights == "ema":
+        model.load_state_dict(averaged_entry(state, path))
+        return
     for key in ("model", "state_dict"):
         if isinstance(state, dict) and key in state and isinstance(state[key], dict):
             state = state[key]
@@ -60,6 +73,9 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--preset", required=True)
     ap.add_argument("--weight", default="")
+    ap.add_argument("--weights", choices=("live", "ema"), default="live",
+                    help="which weights of the checkpoint to evaluate: the trained ones, or the exponential moving average "
+                         "a run with tools/train.py --ema keeps beside them")
     ap.add_argument("--data-dir", required=True)
     ap.add_argument("--data-fn", required=True)
     ap.add_argument("--category", default="")
@@ -93,7 +109,7 @@ def main(argv=None):
     device = torch.device("cuda:0")
     model = build_model(cfg).to(device)
     if args.weight:
-        load_weights(model, args.weight, device)
+        load_weights(model, args.weight, device, args.weights)
     elif cfg.model.name != "identity":
         raise SystemExit("please provide --weight (only the identity baseline needs none)")
     evaluator = Evaluator(model)

@@ -4,6 +4,7 @@
       --val-fn everyday.val.txt [--category Bottle] [--epochs 400] [--graph] [--ckpt-dir ckpt] [--resume]
   python tools/train.py --preset pn_transformer_everyday --skip-nonfinite --skip-limit 20 ...  (bad steps skipped on the device)
   python tools/train.py --preset pn_transformer_everyday --skip-nonfinite --rollback-buffers ...  (and their BatchNorm statistics undone)
+  python tools/train.py --preset pn_transformer_everyday --ema DECAY [--no-ema-warmup] ...  (averaged weights kept, validated, saved)
   python tools/train.py --preset pn_transformer_everyday --repulsion 0.01 1.0 ...   (the opt-in repulsion term: THRE W)
   python tools/train.py --preset lstm_everyday --lstm-draws device --graph ...      (B-LSTM captured: its draws on the device)
   python tools/train.py --preset dgl_partnet_chair --data-dir data/partnet --data-fn Chair.train.npy --val-fn Chair.val.npy
@@ -62,6 +63,13 @@ def parser():
     ap.add_argument("--rollback-buffers", action="store_true",
                     help="with --skip-nonfinite: cfg.optimizer.skip_rollback_buffers: a skipped step also rolls back every "
                          "module buffer (BatchNorm running statistics, num_batches_tracked) on the device")
+    ap.add_argument("--ema", type=float, default=None, metavar="DECAY",
+                    help="cfg.optimizer.ema_decay in [0, 1): keep an exponential moving average of the weights on the device; "
+                         "validation and the checkpoint ranking then use it, and the checkpoints carry it (tools/evaluate.py "
+                         "--weights ema); no default exists")
+    ap.add_argument("--no-ema-warmup", action="store_true",
+                    help="with --ema: cfg.optimizer.ema_warmup = False, the decay is DECAY from the first step instead of "
+                         "min(DECAY, (1 + t) / (10 + t))")
     ap.add_argument("--seed", type=int, default=0)
     return ap
 
@@ -77,6 +85,10 @@ def parse_args(argv=None):
         ap.error("--skip-limit needs --skip-nonfinite")
     if args.rollback_buffers and not args.skip_nonfinite:
         ap.error("--rollback-buffers needs --skip-nonfinite")
+    if args.ema is not None and not 0.0 <= args.ema < 1.0:
+        ap.error("--ema DECAY must lie in [0, 1)")
+    if args.no_ema_warmup and args.ema is None:
+        ap.error("--no-ema-warmup needs --ema")
     return args
 
 
@@ -145,6 +157,10 @@ def configure(args):
         cfg.optimizer.skip_nonfinite = True
     if args.rollback_buffers:
         cfg.optimizer.skip_rollback_buffers = True
+    if args.ema is not None:
+        cfg.optimizer.ema_decay = args.ema
+        if args.no_ema_warmup:
+            cfg.optimizer.ema_warmup = False
     return cfg
 
 

@@ -24,10 +24,18 @@ from multi_part_assembly_amd.pn_transformer import build_model  # noqa: E402
 from multi_part_assembly_amd.trainer import Trainer  # noqa: E402
 
 
-def load_checkpoint(model, cfg, path, device):
+def load_checkpoint(model, cfg, path, device, weights="live"):
     """`Trainer.load_state_dict` on what `torch.save` wrote: `Trainer.state_dict()`, a Lightning-style `{"state_dict":
-    ...}`, or a bare model state dict."""
-    state = torch.load(path, map_location=device)
+    ...}`, or a bare model state dict.  `weights="ema"`: the checkpoint's weight average (`ckpt["ema"]["model"]`, written
+    by a run with tools/train.py --ema) goes into the model instead; SystemExit if the checkpoint has none."""
+    # (weights_only=False: a checkpoint of `Trainer.fit` also holds the run's generator states, numpy's among them)
+    state = torch.load(path, map_location=device, weights_only=False)
+    if weights == "ema":
+        ema = state.get("ema") if isinstance(state, dict) else None
+        if not (isinstance(ema, dict) and isinstance(ema.get("model"), dict)):
+            raise SystemExit(f"--weights ema: {path} holds no weight average (no \"ema\" entry: it was written by a run "
+                             "without tools/train.py --ema, or is not a Trainer.state_dict() checkpoint)")
+        state = ema["model"]
     if not (isinstance(state, dict) and ("model" in state or "state_dict" in state)):
         state = {"state_dict": state}
     Trainer(model, cfg).load_state_dict(state)
@@ -92,6 +100,9 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--preset", required=True)
     ap.add_argument("--weight", default="")
+    ap.add_argument("--weights", choices=("live", "ema"), default="live",
+                    help="which weights of the checkpoint to export with: the trained ones, or the exponential moving "
+                         "average a run with tools/train.py --ema keeps beside them")
     ap.add_argument("--data-dir", required=True)
     ap.add_argument("--data-fn", required=True)
     ap.add_argument("--category", default="")
@@ -126,7 +137,7 @@ def main(argv=None):
     device = torch.device("cuda:0")
     model = build_model(cfg).to(device)
     if args.weight:
-        load_checkpoint(model, cfg, args.weight, device)
+        load_checkpoint(model, cfg, args.weight, device, args.weights)
     elif cfg.model.name != "identity":
         raise SystemExit("please provide --weight (only the identity baseline needs none)")
     folders = datasets.read_fracture_list(args.data_dir, args.data_fn, args.category, cfg.data.min_num_part,
