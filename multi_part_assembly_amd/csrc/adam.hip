@@ -180,19 +180,27 @@ __global__ __launch_bounds__(kThreads) void grad_sqnorm_find_kernel(const float*
   grad_sqnorm<true>(grad, n, partial, first_bad);
 }
 
+// the clipping of both step forms: from the gradient's sum of squares, the norm of the (already scaled) mean gradient and
+// the quotient that is the coefficient where it lies below 1 (torch.nn.utils.clip_grad_norm_), all in double
+__device__ __forceinline__ void clip_coef(double s, const float* __restrict__ scale_dev, float scale, float max_norm,
+                                          double& c, double& norm) {
+  const double k = scale_dev != nullptr ? (double)scale_dev[0] : (double)scale;
+  norm = __builtin_sqrt(s) * k;
+  c = (double)max_norm / (norm + 1e-6);
+}
+
 __global__ void grad_clip_coef_kernel(const double* __restrict__ partial, int blocks, float max_norm,
                                       const float* __restrict__ scale_dev, float scale, float* __restrict__ coef) {
   double s = 0.0;
   for (int b = 0; b < blocks; ++b) s += partial[b];
-  const double k = scale_dev != nullptr ? (double)scale_dev[0] : (double)scale;
-  const double norm = __builtin_sqrt(s) * k;                       // norm of the (already scaled) mean gradient
-  const double c = (double)max_norm / (norm + 1e-6);               // torch.nn.utils.clip_grad_norm_
+  double c, norm;
+  clip_coef(s, scale_dev, scale, max_norm, c, norm);
   coef[0] = c < 1.0 ? (float)c : 1.0f;
   coef[1] = (float)norm;
 }
 
-// mpa_step_guard's second launch (one wave, lane 0 decides): the coefficient exactly as grad_clip_coef_kernel computes it, the
-// verdict, the eight guard words, and — for an accepted step only — adam_advance
+// mpa_step_guard's second launch (one wave, lane 0 decides): the coefficient exactly as grad_clip_coef_kernel computes it
+// (clip_coef), the verdict, the eight guard words, and — for an accepted step only — adam_advance
 constexpr int kVerdictLanes = 64;
 __global__ __launch_bounds__(kVerdictLanes) void step_guard_verdict_kernel(const double* __restrict__ partial, const int* __restrict__ first_bad,
                                           int blocks, float max_norm, const float* __restrict__ scale_dev, float scale,
@@ -220,9 +228,8 @@ __global__ __launch_bounds__(kVerdictLanes) void step_guard_verdict_kernel(const
     hyper[5] = 1.0f;
     hyper[6] = __uint_as_float(0x7f800000u);  // "not finite", whichever of NaN / inf the sum came out as
   } else {
-    const double k = scale_dev != nullptr ? (double)scale_dev[0] : (double)scale;
-    const double norm = __builtin_sqrt(s) * k;
-    const double c = (double)max_norm / (norm + 1e-6);
+    double c, norm;
+    clip_coef(s, scale_dev, scale, max_norm, c, norm);
     hyper[5] = max_norm > 0.0f && c < 1.0 ? (float)c : 1.0f;
     hyper[6] = (float)norm;
   }
@@ -258,6 +265,26 @@ __global__ __launch_bounds__(kThreads) void guard_commit_kernel(const int* __res
   for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < units; i += stride) dst[i] = src[i];
 }
 
+// host side of the three update entry points: the arguments that travel by value (lr, grad_scale and both bias corrections
+// are zero here: mpa_adam_step fills them in, the other two read them from `hyper` on the device) and the grid
+AdamArgs adam_args(float beta1, float beta2, float eps, float weight_decay, int decoupled) {
+  AdamArgs a;
+  a.lr = a.bc1 = a.bc2_sqrt = a.grad_scale = 0.0f;
+  a.beta1 = beta1;
+  a.beta2 = beta2;
+  a.eps = eps;
+  a.weight_decay = weight_decay;
+  a.decoupled = decoupled;
+  return a;
+}
+
+dim3 adam_grid(int64_t numel) {
+  long long blocks = (numel / 4 + kThreads - 1) / kThreads;
+  if (blocks < 1) blocks = 1;
+  if (blocks > 2048) blocks = 2048;
+  return dim3((unsigned)blocks);
+}
+
 }  // namespace
 
 extern "C" int mpa_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
@@ -269,21 +296,13 @@ extern "C" int mpa_adam_step(float* param, const float* grad, float* exp_avg, fl
   MPA_REQUIRE(param && grad && exp_avg && exp_avg_sq, "adam_step: null pointer");
   MPA_REQUIRE(((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) % 16 == 0,
               "adam_step: buffers must be 16-byte aligned");
-  AdamArgs a;
+  AdamArgs a = adam_args(beta1, beta2, eps, weight_decay, decoupled_weight_decay);
   a.lr = lr;
-  a.beta1 = beta1;
-  a.beta2 = beta2;
-  a.eps = eps;
-  a.weight_decay = weight_decay;
-  a.decoupled = decoupled_weight_decay;
   a.grad_scale = grad_scale;
   // bias corrections in double, as torch computes them on the host
   a.bc1 = (float)(1.0 - __builtin_pow((double)beta1, (double)step));
   a.bc2_sqrt = (float)__builtin_sqrt(1.0 - __builtin_pow((double)beta2, (double)step));
-  long long blocks = (numel / 4 + kThreads - 1) / kThreads;
-  if (blocks < 1) blocks = 1;
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, mpa::as_stream(stream),
+  hipLaunchKernelGGL(adam_kernel, adam_grid(numel), dim3(kThreads), 0, mpa::as_stream(stream),
                      param, grad, exp_avg, exp_avg_sq, (long long)numel, a, (const float*)nullptr, decay_mask);
   return mpa::check_launch("adam_step");
 }
@@ -297,19 +316,10 @@ extern "C" int mpa_adam_step_dev(float* param, const float* grad, float* exp_avg
   MPA_REQUIRE(param && grad && exp_avg && exp_avg_sq && hyper, "adam_step_dev: null pointer");
   MPA_REQUIRE(((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) % 16 == 0,
               "adam_step_dev: buffers must be 16-byte aligned");
-  AdamArgs a;
-  a.lr = a.bc1 = a.bc2_sqrt = a.grad_scale = 0.0f;  // taken from `hyper` on the device
-  a.beta1 = beta1;
-  a.beta2 = beta2;
-  a.eps = eps;
-  a.weight_decay = weight_decay;
-  a.decoupled = decoupled_weight_decay;
-  long long blocks = (numel / 4 + kThreads - 1) / kThreads;
-  if (blocks < 1) blocks = 1;
-  if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, mpa::as_stream(stream), hyper, beta1, beta2);
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, mpa::as_stream(stream),
-                     param, grad, exp_avg, exp_avg_sq, (long long)numel, a, (const float*)hyper, decay_mask);
+  hipLaunchKernelGGL(adam_kernel, adam_grid(numel), dim3(kThreads), 0, mpa::as_stream(stream),
+                     param, grad, exp_avg, exp_avg_sq, (long long)numel,
+                     adam_args(beta1, beta2, eps, weight_decay, decoupled_weight_decay), (const float*)hyper, decay_mask);
   return mpa::check_launch("adam_step_dev");
 }
 
@@ -369,18 +379,9 @@ extern "C" int mpa_adam_step_guarded(float* param, const float* grad, float* exp
   MPA_REQUIRE(((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) % 16 == 0,
               "adam_step_guarded: buffers must be 16-byte aligned");
   MPA_REQUIRE(((uintptr_t)hyper | (uintptr_t)guard) % 4 == 0, "adam_step_guarded: misaligned word");
-  AdamArgs a;
-  a.lr = a.bc1 = a.bc2_sqrt = a.grad_scale = 0.0f;  // taken from `hyper` on the device
-  a.beta1 = beta1;
-  a.beta2 = beta2;
-  a.eps = eps;
-  a.weight_decay = weight_decay;
-  a.decoupled = decoupled_weight_decay;
-  long long blocks = (numel / 4 + kThreads - 1) / kThreads;  // (mpa_adam_step_dev's configuration)
-  if (blocks < 1) blocks = 1;
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(adam_guarded_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, mpa::as_stream(stream),
-                     param, grad, exp_avg, exp_avg_sq, (long long)numel, a, hyper, decay_mask, (const int*)guard);
+  hipLaunchKernelGGL(adam_guarded_kernel, adam_grid(numel), dim3(kThreads), 0, mpa::as_stream(stream),
+                     param, grad, exp_avg, exp_avg_sq, (long long)numel,
+                     adam_args(beta1, beta2, eps, weight_decay, decoupled_weight_decay), hyper, decay_mask, (const int*)guard);
   return mpa::check_launch("adam_step_guarded");
 }
 

@@ -50,6 +50,11 @@ class FlatBuffers:
         """[start, end) element range covering parameters first..last (inclusive indices)."""
         return self.offsets[first], self.offsets[last] + (self.params[last].numel() + 3) // 4 * 4
 
+    def owner(self, index):
+        """(k, shape, element) of the last parameter whose offset is <= `index` (in the padding: element >= its numel)."""
+        k = max(i for i, off in enumerate(self.offsets) if off <= index)
+        return k, tuple(self.params[k].shape), index - self.offsets[k]
+
     def zero_grad(self):
         """One memset; gradients stay views of the flat buffer (never set to None)."""
         self.flat_grad.zero_()
@@ -97,14 +102,15 @@ class BufferSlab:
         """shadow <- live: the current buffers become what a skipped step rolls back to (after a checkpoint was loaded)."""
         self.shadow.copy_(self.live)
 
-    def commit(self, guard):
-        """mpa_guard_commit on the slab behind the verdict `guard[0]` (`guard`: the optimiser's guard words on the slab's
-        device); on host tensors its restatement."""
-        if self.nbytes == 0:
-            return
-        if self.live.is_cuda:
+    def launch_commit(self, guard):
+        """mpa_guard_commit behind the verdict `guard[0]`, always launched (`FusedAdam.step_dev`) unless the slab is empty."""
+        if self.nbytes:
             _lib.launch("mpa_guard_commit", self.live.device, guard, self.live, self.shadow, self.nbytes)
-            return
+
+    def commit(self, guard):
+        """`launch_commit` (`guard`: the optimiser's guard words on the slab's device); on host tensors its restatement."""
+        if self.live.is_cuda or not self.nbytes:
+            return self.launch_commit(guard)
         from .guard_ref import commit
         live, shadow = commit(int(guard[0]), self.live.numpy(), self.shadow.numpy())
         self.live.copy_(torch.from_numpy(live))
@@ -165,18 +171,18 @@ class WeightAverage:
         if self.swapped:
             raise RuntimeError(f"WeightAverage.{what}: the averaged weights are swapped in (swap() back first)")
 
-    def update_args(self, hyper, guard):
-        """The arguments of mpa_ema_update behind the device (what `FusedAdam.step_dev` launches)."""
-        return (self.flat.flat_param, self.ema_param, self.flat.numel, self.slab.live, self.ema_state, self.slab.nbytes,
-                self._table_host, self._table_dev, len(self.segments), hyper, self.decay, int(self.warmup), guard)
+    def launch_update(self, hyper, guard):
+        """mpa_ema_update, wherever the tensors live (what `FusedAdam.step_dev` issues; the package's one launch of it)."""
+        _lib.launch("mpa_ema_update", self.ema_param.device, self.flat.flat_param, self.ema_param, self.flat.numel,
+                    self.slab.live, self.ema_state, self.slab.nbytes, self._table_host, self._table_dev, len(self.segments),
+                    hyper, self.decay, int(self.warmup), guard)
 
     def update(self, hyper, guard=None):
         """ema <- ema + c (current - ema) behind the step whose count `hyper[4]` holds (`hyper`: the optimiser's eight
         words; `guard`: its guard words or None)."""
         self._refuse_swapped("update")
         if self.ema_param.is_cuda:
-            _lib.launch("mpa_ema_update", self.ema_param.device, *self.update_args(hyper, guard))
-            return
+            return self.launch_update(hyper, guard)
         from .ema_ref import update
         t = int(hyper[4:5].view(torch.int32)[0])
         ema, state = update(0 if guard is None else int(guard[0]), t, self.decay, self.warmup,
@@ -335,12 +341,14 @@ class FusedAdam:
             self._hyper_dev = torch.zeros(8, dtype=torch.float32, device=dev)
             self._hyper_dev[5] = 1.0  # clip coefficient: no clipping
             self._set_device_step(self._step_count)
-        self._ensure_guard_ws()
+        if self.guard:
+            self.guard_workspace()
 
-    def _ensure_guard_ws(self):
-        if self.guard and self._guard_ws is None:
+    def guard_workspace(self):  # (mpa_step_guard's partial sums and first-bad indices, allocated on first use)
+        if self._guard_ws is None:
             self._guard_ws = torch.empty(_lib.query("mpa_step_guard_workspace") // 4, dtype=torch.int32,
                                          device=self.flat_param.device)
+        return self._guard_ws
 
     @property
     def step_count(self):
@@ -377,7 +385,7 @@ class FusedAdam:
         in a HIP graph: every launch argument is constant across replays)."""
         self._update_dev()
         if self.average is not None:  # last: behind the advance of the step count and the commit of the buffers
-            _lib.launch("mpa_ema_update", self.flat_param.device, *self.average.update_args(self._hyper_dev, self._guard_dev))
+            self.average.launch_update(self._hyper_dev, self._guard_dev)
 
     def _update_dev(self):
         dev = self.flat_param.device
@@ -385,16 +393,14 @@ class FusedAdam:
             # pass + verdict / coefficient / advance, then the update that returns at once behind a non-zero verdict
             # (clipping off: one launch more than advance + update; clipping on: one fewer than its four)
             self._clip_written = bool(self.clip_grad)  # (the verdict kernel rewrites the coefficient in every step)
-            self._ensure_guard_ws()
             _lib.launch("mpa_step_guard", dev, self.flat_grad, self.numel, float(self.clip_grad or 0.0),
-                        self._hyper_dev.data_ptr() + 12, 1.0, self.launch_status, self._guard_ws, self._hyper_dev,
+                        self._hyper_dev.data_ptr() + 12, 1.0, self.launch_status, self.guard_workspace(), self._hyper_dev,
                         self._guard_dev, float(self.betas[0]), float(self.betas[1]))
             _lib.launch("mpa_adam_step_guarded", dev, self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq,
                         self.numel, self._hyper_dev, float(self.betas[0]), float(self.betas[1]), float(self.eps),
                         float(self.weight_decay), int(self.decoupled), self.decay_mask, self._guard_dev)
-            slab = self.guard_state
-            if slab is not None and slab.nbytes:  # applied: shadow <- live; skipped: live <- shadow (same verdict word)
-                _lib.launch("mpa_guard_commit", dev, self._guard_dev, slab.live, slab.shadow, slab.nbytes)
+            if self.guard_state is not None:  # applied: shadow <- live; skipped: live <- shadow (same verdict word)
+                self.guard_state.launch_commit(self._guard_dev)
             return
         if not self.clip_grad and self._clip_written:  # clipping was switched off: back to "no clipping"
             self._hyper_dev[5:6].fill_(1.0)
@@ -427,9 +433,19 @@ class FusedAdam:
         self._ensure_hyper()
         return self._hyper_dev[6:7]
 
+    def first_nonfinite(self, flat_tensor):
+        """The smallest index of a NaN / inf in `flat_tensor` (on the device, of the flat buffers' length) or None: one
+        mpa_step_guard pass against scratch words — the optimiser's own count and words stay — and one device read."""
+        dev = flat_tensor.device
+        hyper, words = torch.zeros(8, dtype=torch.float32, device=dev), torch.zeros(8, dtype=torch.int32, device=dev)
+        _lib.launch("mpa_step_guard", dev, flat_tensor, self.numel, 0.0, None, 1.0, None, self.guard_workspace(), hyper,
+                    words, float(self.betas[0]), float(self.betas[1]))
+        verdict, _, _, _, idx = words[:5].tolist()
+        return idx if verdict else None
+
     def guard_report(self, flat=None):
         """One device read: the words by name, plus `parameter` (index into `flat.params`), `shape` and `element` of the
-        tensor owning `first_bad_index` (resolved through `FlatBuffers.offsets`; None when the last skip was the status
+        tensor owning `first_bad_index` (resolved through `FlatBuffers.owner`; None when the last skip was the status
         word's alone, or nothing was skipped) and a one-line `text`."""
         from .guard_ref import LAUNCH_FAILED, NONFINITE, describe
         flat = flat if flat is not None else self.flat
@@ -437,8 +453,7 @@ class FusedAdam:
         rep.update(parameter=None, shape=None, element=None)
         idx = rep["first_bad_index"]
         if rep["skipped"] and idx >= 0:
-            k = max(i for i, off in enumerate(flat.offsets) if off <= idx)
-            rep.update(parameter=k, shape=tuple(flat.params[k].shape), element=idx - flat.offsets[k])
+            rep.update(zip(("parameter", "shape", "element"), flat.owner(idx)))
         if not rep["skipped"]:
             rep["text"] = f"{rep['applied']} steps applied, none skipped"
         else:

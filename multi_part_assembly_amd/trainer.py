@@ -24,6 +24,7 @@ GPU-bound, so the replay is only ~2 % faster than eager launches; eager stays th
 from __future__ import annotations
 
 import contextlib
+import warnings
 
 import torch
 import torch.distributed as dist
@@ -33,6 +34,35 @@ from . import gru as _gru
 from .gradsink import DeferredBackward, GradSink
 from .dp import BucketedGradReducer, broadcast_from_rank0, bucket_sizes_for, ordered_parameters
 from .optim import BufferSlab, FlatBuffers, FusedAdam, WeightAverage, cosine_warmup_lr, decay_mask_for
+
+
+def graph_refusal(model):
+    """The first reason why a step of `model` cannot be captured into a HIP graph (it keeps its launches eager), or None."""
+    name = type(model).__name__
+    table = (
+        # identical-part matching draws its point sample on the host every step (base_model._match_parts; reference
+        # base_model.py:196-238): a captured step would replay ONE draw for ever, and the capture itself would hit the
+        # host copy of the match ids.  With cfg.loss.match_sample = "device" the draw is a kernel reading its counter from
+        # device memory (matching.MatchSampler) and the step is captured.
+        (getattr(model, "semantic", False) and getattr(model, "match_sample", "host") != "device",
+         "models with semantic part matching (the matching's point sample is drawn on the host every step)"),
+        # B-LSTM draws its teacher-forcing coin and its decoder noise on the host in every forward (lstm.py; reference
+        # b_lstm/seq2seq.py:177-178,212-220): a captured step would replay ONE draw for ever.
+        (getattr(model, "host_draws_per_forward", False),
+         f"{name} (its teacher-forcing coin and decoder noise are drawn on the host every forward)"),
+        # the PointNet++ encoder compacts the valid parts on the host in every forward (pointnet2.py: BatchNorm must
+        # see valid parts only): the synchronisation is illegal under capture.
+        (any(getattr(mod, "host_sync_per_forward", False) for mod in model.modules()),
+         f"{name} (its encoder synchronises with the host in every forward to compact the valid parts)"),
+    )
+    return next((reason for holds, reason in table if holds), None)
+
+
+# `Trainer._refuse_swapped`: what each refusal adds behind "the averaged weights are swapped in"
+_SWAPPED = {"state_dict": " (inside averaged_weights()); \"model\" would hold the average and \"ema\" the live weights",
+            "load_state_dict": " (inside averaged_weights())",
+            "train_step": " (inside averaged_weights()); a step would train the average",
+            "averaged_weights": " already"}
 
 
 class Trainer:
@@ -70,31 +100,15 @@ class Trainer:
         step whose gradient is finite while a statistic overflowed to inf is applied and the statistic committed — which
         is why a guarded `state_dict()` still refuses non-finite parameters and buffers."""
         self.model = model
-        if use_graph and getattr(model, "semantic", False) and getattr(model, "match_sample", "host") != "device":
-            # identical-part matching draws its point sample on the host every step (base_model._match_parts; reference
-            # base_model.py:196-238): a captured step would replay ONE draw for ever, and the capture itself would hit the
-            # host copy of the match ids.  Such models keep their launches eager; with cfg.loss.match_sample = "device"
-            # the draw is a kernel reading its counter from device memory (matching.MatchSampler) and the step is captured.
-            import warnings
-            warnings.warn("Trainer: use_graph=True is not available for models with semantic part matching (the matching's "
-                          "point sample is drawn on the host every step); running eager launches")
-            use_graph = False
-        if use_graph and getattr(model, "host_draws_per_forward", False):
-            # B-LSTM draws its teacher-forcing coin and its decoder noise on the host in every forward (lstm.py; reference
-            # b_lstm/seq2seq.py:177-178,212-220): a captured step would replay ONE draw for ever.  Eager launches instead.
-            import warnings
-            warnings.warn(f"Trainer: use_graph=True is not available for {type(model).__name__} (its teacher-forcing coin "
-                          "and decoder noise are drawn on the host every forward); running eager launches")
-            use_graph = False
-        if use_graph and any(getattr(mod, "host_sync_per_forward", False) for mod in model.modules()):
-            # the PointNet++ encoder compacts the valid parts on the host in every forward (pointnet2.py: BatchNorm must
-            # see valid parts only): the synchronisation is illegal under capture.  Eager launches instead.
-            import warnings
-            warnings.warn(f"Trainer: use_graph=True is not available for {type(model).__name__} (its encoder synchronises "
-                          "with the host in every forward to compact the valid parts); running eager launches")
+        refusal = graph_refusal(model) if use_graph else None
+        if refusal is not None:
+            warnings.warn(f"Trainer: use_graph=True is not available for {refusal}; running eager launches")
             use_graph = False
         self.use_graph, self.graph_warmup = use_graph, graph_warmup
         self._fit_pending = None  # what `resume` read for the next `fit` (fit.py)
+        self._failed = False    # sticky: a `check_health` reported a launch that gave up (cleared by load_state_dict)
+        self._one = None        # d loss / d loss, kept: autograd would fill a fresh ones_like every step
+        self._evaluator = None  # built by the first `evaluate`
         self._graph, self._static_batch, self._static_loss, self._eager_steps = None, None, None, 0
         cfg = cfg if cfg is not None else model.cfg
         self.cfg = cfg
@@ -197,24 +211,22 @@ class Trainer:
         if bucket == 0:  # (FlatBuffers order: the first bucket starts at element 0)
             self._mark_failed_launch()
 
+    def _refuse_swapped(self, what):
+        if self.average is not None and self.average.swapped:
+            raise RuntimeError(f"Trainer.{what}: the averaged weights are swapped in{_SWAPPED[what]}")
+
     def _refuse_nonfinite_state(self):
         """Guarded trainers only, at checkpoints: a NaN / inf in a parameter (one mpa_step_guard pass over the flat
         parameters against scratch words) or in a buffer (the forward side is not guarded) must not reach a file."""
-        opt = self.optimizer
         if not self.flat.flat_param.is_cuda:
             return
-        opt._ensure_hyper()
 
         def refuse_flat(flat, whose):
-            hyper = torch.zeros(8, dtype=torch.float32, device=flat.device)
-            words = torch.zeros(8, dtype=torch.int32, device=flat.device)
-            _lib.launch("mpa_step_guard", flat.device, flat, self.flat.numel, 0.0, None, 1.0, None, opt._guard_ws, hyper,
-                        words, float(opt.betas[0]), float(opt.betas[1]))
-            verdict, _, _, _, idx = words[:5].tolist()
-            if verdict:
-                k = max(i for i, off in enumerate(self.flat.offsets) if off <= idx)
-                raise RuntimeError(f"Trainer.state_dict: {whose}parameter {k} (shape {tuple(self.flat.params[k].shape)}) "
-                                   f"holds a non-finite value at element {idx - self.flat.offsets[k]}; restore a "
+            idx = self.optimizer.first_nonfinite(flat)
+            if idx is not None:
+                k, shape, element = self.flat.owner(idx)
+                raise RuntimeError(f"Trainer.state_dict: {whose}parameter {k} (shape {shape}) "
+                                   f"holds a non-finite value at element {element}; restore a "
                                    "checkpoint with load_state_dict first")
 
         refuse_flat(self.flat.flat_param, "")
@@ -236,12 +248,10 @@ class Trainer:
         gave up — now, or at any `check_health` since the parameters were last loaded.  Besides "model", "optimizer" and
         "epoch" the dictionary carries "dropout_calls": the position of every dropout-seed stream, which
         `load_state_dict` needs to continue a run with the masks the uninterrupted run draws (optional on loading)."""
-        if getattr(self, "_failed", False):
+        if self._failed:
             raise RuntimeError("Trainer.state_dict: an earlier check_health reported a launch that gave up; the parameters "
                                "behind it are undefined — restore a checkpoint with load_state_dict first")
-        if self.average is not None and self.average.swapped:
-            raise RuntimeError("Trainer.state_dict: the averaged weights are swapped in (inside averaged_weights()); "
-                               "\"model\" would hold the average and \"ema\" the live weights")
+        self._refuse_swapped("state_dict")
         self.check_health(synchronize=True)
         if self.buffer_slab is not None:
             self.buffer_slab.check()
@@ -255,8 +265,7 @@ class Trainer:
             for key, b in self.model.named_buffers(remove_duplicate=False):
                 if key in model_state and id(b) in slab_views:
                     model_state[key] = model_state[key].clone()
-        state = {"model": model_state, "optimizer": self.optimizer.state_dict()
-                 if hasattr(self.optimizer, "state_dict") else None, "epoch": self.epoch,
+        state = {"model": model_state, "optimizer": self.optimizer.state_dict(), "epoch": self.epoch,
                  # position of every dropout-seed stream (transformer.TransformerEncoder._next_seed), in module order: a
                  # resumed run then draws the masks the uninterrupted one would have drawn
                  "dropout_calls": [m._calls for m in self.model.modules() if hasattr(m, "advance_seed")]}
@@ -274,8 +283,7 @@ class Trainer:
         The dropout-seed positions are host counters; the device word a captured step reads its seed from is not
         restored here because `train_step` rewrites it from the counter (`advance_seed`) in front of every replay, and a
         freshly built `use_graph=True` trainer starts with its eager warm-up steps, whose seeds travel by value."""
-        if self.average is not None and self.average.swapped:
-            raise RuntimeError("Trainer.load_state_dict: the averaged weights are swapped in (inside averaged_weights())")
+        self._refuse_swapped("load_state_dict")
         if "state_dict" in state and "model" not in state:
             self.model.load_state_dict(state["state_dict"])
             self._refresh_buffer_shadow()
@@ -319,7 +327,6 @@ class Trainer:
         if ema is not None:
             self.average.load_averaged_state_dict(ema["model"], self.model)
         elif not self._ema_warned:
-            import warnings
             self._ema_warned = True
             warnings.warn("Trainer.load_state_dict: the checkpoint holds no weight average (\"ema\"); the average restarts "
                           "from the loaded weights")
@@ -331,8 +338,7 @@ class Trainer:
         if self.average is None:
             raise RuntimeError("Trainer.averaged_weights: weight averaging is off (Trainer(ema_decay=...) / "
                                "cfg.optimizer.ema_decay)")
-        if self.average.swapped:
-            raise RuntimeError("Trainer.averaged_weights: the averaged weights are swapped in already")
+        self._refuse_swapped("averaged_weights")
         self.average.swap()
         try:
             yield self.model
@@ -352,14 +358,12 @@ class Trainer:
             with self.averaged_weights():
                 return self.evaluate(batches, prefix=prefix)
         from .evaluate import Evaluator
-        ev = getattr(self, "_evaluator", None)
-        if ev is None:
+        if self._evaluator is None:
             group = self.group  # (None in a multi-rank job means the default group, as everywhere in this class)
             if group is None and self.world > 1:
                 group = dist.group.WORLD
-            ev = self._evaluator = Evaluator(self.model, process_group=group,
-                                             health=lambda: self.check_health(synchronize=True))
-        return ev.run(batches, prefix=prefix)
+            self._evaluator = Evaluator(self.model, process_group=group, health=lambda: self.check_health(synchronize=True))
+        return self._evaluator.run(batches, prefix=prefix)
 
     def set_epoch(self, epoch):
         self.epoch = epoch
@@ -398,13 +402,18 @@ class Trainer:
     def _tensor_items(self, data_dict):
         return {k: v for k, v in data_dict.items() if isinstance(v, torch.Tensor)}
 
-    def _fwd_bwd(self, batch, loss_out=None):
+    def _fwd_bwd(self, batch, loss_out=None, batch_idx=0):
+        """zero_grad, forward, backward of the eager (the reducer's hooks fire inside), warm-up and one-graph captured steps."""
+        # (the two-graph data-parallel capture spells them itself, in `_capture`: it is cut inside backward)
         self.optimizer.zero_grad()
         with self.sink:  # HIP backward kernels write straight into the flat gradient buffer
-            loss = self.model.training_step(batch, 0)
+            loss = self.model.training_step(batch, batch_idx)
             if loss_out is not None:  # graph mode: the loss is copied out before backward recycles memory
                 loss_out.copy_(loss.detach())
-            loss.backward()
+            # d loss / d loss, kept across steps (with a warm-up step it exists before the capture)
+            if self._one is None or self._one.device != loss.device or self._one.dtype != loss.dtype:
+                self._one = torch.ones((), dtype=loss.dtype, device=loss.device)
+            loss.backward(self._one)
         return loss.detach() if loss_out is None else loss_out
 
     def _capture(self, data_dict):
@@ -465,21 +474,31 @@ class Trainer:
                                        "outside the last gradient bucket (an encoder module outside model.encoder?); "
                                        "use use_graph=False for this model")
 
-    def _reduce_buckets_around(self, run_second_half):
-        """bucket 0 (everything but the encoder) is reduced WHILE `run_second_half` (the encoder's backward) runs; the
-        encoder's bucket behind it."""
+    def _reduce_grad(self, second_half=None):
+        """The gradient's sum over the ranks on the paths without the reducer's hooks.  No `second_half` (the warm-up step;
+        a replay with nothing deferred): the whole flat gradient in one blocking call.  With it (the second graph, the
+        encoder's backward): bucket 0 is reduced WHILE it runs, the encoder's bucket behind it."""
+        # (never per bucket without it: a ring's summation order may depend on the slice.  A guarded step marks in front of
+        # the first collective of either form: the one whose slice holds element 0)
+        if self.world == 1:
+            return
         buckets = self.reducer.buckets
-        assert len(buckets) <= 2, "the two-graph overlap reduces only the first and the last bucket"
-        if self.guard_step and len(buckets) > 1:
-            self._mark_failed_launch()  # (bucket 0 holds element 0)
-        first = dist.all_reduce(buckets[0]["slice"], group=self.group, async_op=True) if len(buckets) > 1 else None
-        run_second_half()
-        if self.guard_step and len(buckets) == 1:
+        overlap = second_half is not None and len(buckets) > 1
+        if second_half is not None:
+            assert len(buckets) <= 2, "the two-graph overlap reduces only the first and the last bucket"
+            if not overlap:  # one bucket: nothing to run it under
+                second_half()
+        if self.guard_step:
             self._mark_failed_launch()
-        last = dist.all_reduce(buckets[-1]["slice"], group=self.group, async_op=True)
-        if first is not None:
-            first.wait()
-        last.wait()
+        if second_half is None:
+            dist.all_reduce(self.flat.flat_grad, group=self.group)
+            return
+        pending = [dist.all_reduce(buckets[0]["slice"], group=self.group, async_op=True)]
+        if overlap:
+            second_half()
+            pending.append(dist.all_reduce(buckets[-1]["slice"], group=self.group, async_op=True))
+        for work in pending:
+            work.wait()
 
     def _graph_step(self, data_dict):
         self.model.train()
@@ -488,10 +507,7 @@ class Trainer:
             if self._eager_steps < self.graph_warmup:  # let allocator / library state settle first
                 self._eager_steps += 1
                 loss = self._fwd_bwd(self._tensor_items(data_dict))
-                if self.world > 1:
-                    if self.guard_step:
-                        self._mark_failed_launch()
-                    dist.all_reduce(self.flat.flat_grad, group=self.group)
+                self._reduce_grad()
                 self._health_and_step(self.optimizer.step)
                 return loss
             torch.cuda.synchronize()
@@ -505,12 +521,8 @@ class Trainer:
                 mod.advance_seed()
         self._graph.replay()
         if self.world > 1:
-            if self._graph_b is not None:
-                self._reduce_buckets_around(self._graph_b.replay)
-            else:  # nothing was deferred (an encoder outside the fused kernels): one all-reduce behind the replay
-                if self.guard_step:
-                    self._mark_failed_launch()
-                dist.all_reduce(self.flat.flat_grad, group=self.group)
+            # (no second graph: nothing was deferred — an encoder outside the fused kernels — and one all-reduce follows)
+            self._reduce_grad(self._graph_b.replay if self._graph_b is not None else None)
             self._health_and_step(self.optimizer.step_dev)  # (the optimiser step is not captured here)
         # the captured status copy refreshes the pinned word on every replay: a replay that gave up is reported here, at
         # the latest one replay later (the copy is asynchronous), and the word is cleared so that later replays run
@@ -519,19 +531,11 @@ class Trainer:
 
     def train_step(self, data_dict, batch_idx=0):
         """One optimiser step on this rank's shard; returns the (detached) scalar loss tensor."""
-        if self.average is not None and self.average.swapped:
-            raise RuntimeError("Trainer.train_step: the averaged weights are swapped in (inside averaged_weights()); a "
-                               "step would train the average")
+        self._refuse_swapped("train_step")
         if self.use_graph:
             return self._graph_step(data_dict)
         self.model.train()
-        self.optimizer.zero_grad()
-        with self.sink:  # HIP backward kernels write straight into the flat gradient buffer
-            loss = self.model.training_step(data_dict, batch_idx)
-            one = getattr(self, "_one", None)  # d loss / d loss, kept: autograd would fill a fresh ones_like every step
-            if one is None or one.device != loss.device or one.dtype != loss.dtype:
-                one = self._one = torch.ones((), dtype=loss.dtype, device=loss.device)
-            loss.backward(one)
+        loss = self._fwd_bwd(data_dict, batch_idx=batch_idx)  # (the reducer's hooks fire inside)
         self.optimizer.grad_scale = self.reducer.finish()
         self._health_and_step(self.optimizer.step)
-        return loss.detach()
+        return loss

@@ -3,24 +3,17 @@ restatement (`guard_ref`, the specification the kernels are tested against in te
 hand-written sequences, the configuration key and the tool's flags, `fit`'s records / `skip_limit` / checkpoint round trip
 with a stub trainer, and the launches `FusedAdam.step_dev` issues with the guard off (today's) and on."""
 import ctypes
-import importlib.util
-import os
 
 import numpy as np
 import pytest
 import torch
 
-from multi_part_assembly_amd import _build, _lib, config, fit as fit_mod, guard_ref
+from multi_part_assembly_amd import _lib, fit as fit_mod, guard_ref
 from multi_part_assembly_amd.optim import FlatBuffers, FusedAdam
 from multi_part_assembly_amd.sampler import EpochSampler
+from trainer_cases import StubProducer, StubTrainer, bits_i32 as _bits, built, optimizer_presets, record, tiny_cfg, tool as _tool  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("mpa_step_guard_workspace", "mpa_step_guard", "mpa_adam_step_guarded", "mpa_guard_mark")
-
-
-@pytest.fixture(scope="module")
-def built():
-    return _build.build()
 
 
 # ---- 1. the boundary ---------------------------------------------------------------------------------------------------------
@@ -68,10 +61,6 @@ def test_argument_refusals_need_no_gpu(built):
 # ---- 2. the restatement ------------------------------------------------------------------------------------------------------
 def _grad(n, seed=0):
     return np.random.RandomState(seed).randn(n).astype(np.float32)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.int32).copy()
 
 
 def test_reference_words_over_a_hand_written_sequence():
@@ -179,28 +168,15 @@ def test_reference_skipped_update_is_the_identity_and_an_applied_one_is_adam():
 
 # ---- 3. configuration and tool ---------------------------------------------------------------------------------------------
 def test_no_preset_sets_the_key_and_it_reads_false_by_default():
-    import inspect
-    presets = [f for name, f in inspect.getmembers(config, inspect.isfunction)
-               if not name.startswith("_") and not inspect.signature(f).parameters and f.__module__ == config.__name__]
-    seen = 0
-    for preset in presets:
-        cfg = preset()
-        if "optimizer" in cfg:
-            seen += 1
-            assert "skip_nonfinite" not in cfg.optimizer
-            assert cfg.optimizer.get("skip_nonfinite", False) is False
-    assert seen >= 10
-
-
-def _train_tool():
-    spec = importlib.util.spec_from_file_location("train_tool", os.path.join(ROOT, "tools", "train.py"))
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
-    return tool
+    cfgs = optimizer_presets()
+    assert len(cfgs) >= 10
+    for cfg in cfgs:
+        assert "skip_nonfinite" not in cfg.optimizer
+        assert cfg.optimizer.get("skip_nonfinite", False) is False
 
 
 def test_train_tool_flags():
-    tool = _train_tool()
+    tool = _tool("train")
     base = ["--preset", "pn_transformer_everyday", "--synthetic"]
     args = tool.parse_args(base)
     assert args.skip_nonfinite is False and args.skip_limit == -1
@@ -215,10 +191,7 @@ def test_train_tool_flags():
 def test_trainer_reads_the_key_with_a_default():
     from multi_part_assembly_amd.pn_transformer import build_model
     from multi_part_assembly_amd.trainer import Trainer
-    cfg = config.pn_transformer_everyday()
-    cfg.model.pc_feat_dim, cfg.model.transformer_heads = 64, 4
-    cfg.model.transformer_feat_dim, cfg.model.transformer_layers = 128, 1
-    cfg.data.max_num_part = 3
+    cfg = tiny_cfg()
     off = Trainer(build_model(cfg), cfg)
     assert off.guard_step is False and off.optimizer.guard is False and off.reducer.before_reduce is None
     cfg.optimizer.skip_nonfinite = True
@@ -228,71 +201,6 @@ def test_trainer_reads_the_key_with_a_default():
 
 
 # ---- 4. fit with a stub trainer ---------------------------------------------------------------------------------------------
-class StubOptimizer:
-    """Guard words and norm as host tensors, scripted per step: step k is skipped when k is in `skip`."""
-
-    lr = 0.5
-
-    def __init__(self):
-        self.words = torch.zeros(8, dtype=torch.int32)
-        self.norm = torch.zeros(1)
-
-    def grad_norm(self):
-        return self.norm
-
-    def guard_words(self):
-        return self.words
-
-    def guard_report(self, flat=None):
-        return {"text": f"stub report: {int(self.words[2])} skipped"}
-
-    def state_dict(self):
-        return {"step": int(self.words[1]), "guard": self.words.clone()}
-
-    def load_state_dict(self, state):
-        self.words.copy_(state["guard"])
-
-
-class StubTrainer:
-    static_batch, guard_step = None, True
-
-    def __init__(self, skip=()):
-        self.optimizer, self.skip, self.steps, self.epoch = StubOptimizer(), set(skip), 0, 0
-
-    def set_epoch(self, epoch):
-        self.epoch = epoch
-
-    def train_step(self, batch):
-        self.steps += 1
-        w = self.optimizer.words
-        if self.steps in self.skip:
-            w[2] += 1
-            w[3] += 1
-            self.optimizer.norm[0] = float("inf")
-        else:
-            w[1] += 1
-            w[3] = 0
-            self.optimizer.norm[0] = float(self.steps)
-        return torch.tensor(1.0)
-
-    def check_health(self):
-        pass
-
-    def state_dict(self):
-        return {"model": {}, "optimizer": self.optimizer.state_dict(), "epoch": self.epoch}
-
-    def load_state_dict(self, state):
-        self.optimizer.load_state_dict(state["optimizer"])
-        self.epoch = state["epoch"]
-
-
-class StubProducer:
-    batch_counter = 0
-
-    def batch(self, indices):
-        return {"idx": indices}
-
-
 def test_fit_records_carry_the_guard_figures(tmp_path):
     trainer, logged = StubTrainer(skip={2, 3, 5}), []
     fit_mod.fit(trainer, StubProducer(), EpochSampler(12, 2, device="cpu"), epochs=1, log_every=2, on_log=logged.append,
@@ -303,13 +211,13 @@ def test_fit_records_carry_the_guard_figures(tmp_path):
                                                                                       (6.0, 3, 0)]
     assert all(type(r["skipped"]) is int and type(r["grad_norm"]) is float for r in steps)
     # the words survive the checkpoint: a fresh trainer resumes with them
-    fresh = StubTrainer()
+    fresh = StubTrainer(skip=())  # (an empty script: guarded, no step skipped; without `skip` the stub is unguarded)
     assert fit_mod.resume(fresh, str(tmp_path)) == 1
     assert fresh.optimizer.words.tolist() == [0, 3, 3, 0, 0, 0, 0, 0]
 
 
 def test_an_unguarded_trainer_keeps_the_record_keys_and_refuses_a_skip_limit():
-    trainer, logged = StubTrainer(), []
+    trainer, logged = StubTrainer(skip=()), []  # (built guarded, as above; switched off on the next line)
     trainer.guard_step = False
     fit_mod.fit(trainer, StubProducer(), EpochSampler(4, 2, device="cpu"), epochs=1, log_every=1, on_log=logged.append)
     assert [set(r) for r in logged if "step" in r] == [{"epoch", "step", "lr", "train/loss"}] * 2
@@ -364,8 +272,7 @@ def test_guard_report_names_the_owning_parameter():
 def test_step_dev_launches_with_the_guard_off_are_todays(monkeypatch, built, clip):
     """Recorded on a stub `_lib.launch` (host tensors, nothing runs): guard off = the launches and arguments of before;
     guard on = pass + verdict in front of the guarded update, the status word passed through."""
-    calls = []
-    monkeypatch.setattr(_lib, "launch", lambda name, dev, *args, **kw: calls.append((name, args)))
+    calls = record(monkeypatch)
     params = [torch.nn.Parameter(torch.zeros(6))]
     status = torch.zeros(1, dtype=torch.int32)
     for guard in (False, True):

@@ -7,19 +7,18 @@ Then the trainer: a poisoned batch between two clean ones leaves parameters, mom
 twin that never took the poisoned optimiser step, eager and captured; a raised status word skips the step; a checkpoint
 refuses non-finite state; two gloo ranks reach one verdict from a status word raised on one of them."""
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
 from multi_part_assembly_amd import _lib, guard_ref
+from trainer_cases import (BT, NT, PT, batches as _batches, i32 as _i32, model as _model, opt_state, rank_setup, run_two_ranks,
+                           trainer as _trainer)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STRIDE = guard_ref.BLOCKS * guard_ref.THREADS * 4  # elements one sweep of the pass covers
 SIZES = [0, 1, 3, 4, 5, 1023, 1024, 1025, STRIDE - 1, STRIDE, STRIDE + 1, STRIDE + 3, 2 * STRIDE + 1]
 B1, B2 = 0.9, 0.999
@@ -65,10 +64,6 @@ def _grad(n, seed=0):
 
 def _dev(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _i32(t):
-    return t.detach().view(torch.int32).cpu().clone()
 
 
 @pytest.fixture(scope="module")
@@ -321,50 +316,8 @@ def test_guard_mark_writes_element_zero_only_and_only_when_raised(cuda_device, f
 
 
 # ---- 3. the trainer -------------------------------------------------------------------------------------------------------------
-BT, PT, NT = 2, 3, 64
-
-
-def _model(dev):
-    from multi_part_assembly_amd import config
-    from multi_part_assembly_amd.pn_transformer import build_model
-    cfg = config.pn_transformer_everyday()
-    cfg.model.pc_feat_dim, cfg.model.transformer_heads = 64, 4
-    cfg.model.transformer_feat_dim, cfg.model.transformer_layers = 128, 2
-    cfg.data.max_num_part = PT
-    torch.manual_seed(7)
-    model = build_model(cfg)
-    for m in model.modules():
-        if isinstance(m, torch.nn.Dropout):
-            m.p = 0.0
-        if isinstance(m, torch.nn.MultiheadAttention):
-            m.dropout = 0.0
-    return model.to(dev), cfg
-
-
-def _trainer(dev, **kw):
-    from multi_part_assembly_amd.trainer import Trainer
-    model, cfg = _model(dev)
-    return Trainer(model, cfg, **kw)
-
-
-def _batches(dev):
-    """clean, poisoned, clean: the NaN sits in one sample's `part_trans`, which enters the loss only."""
-    from multi_part_assembly_amd import synthetic
-    out = []
-    for seed in (60, 61, 62):
-        batch = synthetic.make_batch(BT, PT, NT, preset="everyday", seed=seed, device=dev)
-        batch.pop("num_parts")
-        out.append(batch)
-    clean2 = {k: v.clone() for k, v in out[1].items()}
-    out[1]["part_trans"][1, 0, 1] = float("nan")
-    return out, clean2
-
-
 def _opt_state(trainer):
-    torch.cuda.synchronize()
-    opt = trainer.optimizer
-    return [_i32(trainer.flat.flat_param), _i32(opt.exp_avg), _i32(opt.exp_avg_sq)], \
-        int(opt._hyper_dev[4:5].view(torch.int32).item())
+    return opt_state(trainer, _i32)  # (int32 words)
 
 
 @pytest.fixture(scope="module")
@@ -503,9 +456,7 @@ def _rank_main(rank, port, out_dir):
     ranks, then the status word raised on rank 1 ONLY in front of the next step."""
     import torch.distributed as dist
     from multi_part_assembly_amd import gru, synthetic
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    dev = torch.device("cuda", 0)
-    dist.init_process_group("gloo", rank=rank, world_size=2)
+    dev = rank_setup(rank, port)
     out = {}
     for mode, use_graph in (("eager", False), ("graph", True)):
         t = _trainer(dev, guard_step=True, use_graph=use_graph, graph_warmup=1)
@@ -532,16 +483,7 @@ def _rank_main(rank, port, out_dir):
 
 
 def test_two_ranks_reach_one_verdict_from_a_status_word_raised_on_one(cuda_device):
-    from test_dp_gpu import _free_port
-    port = _free_port()
-    with tempfile.TemporaryDirectory() as out_dir:
-        env = dict(os.environ, PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, "tests"), os.environ.get("PYTHONPATH", "")]))
-        procs = [subprocess.Popen(["timeout", "-k", "10", "240", sys.executable, os.path.abspath(__file__), str(r), str(port),
-                                   out_dir], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-                 for r in range(2)]
-        logs = [p.communicate()[0] for p in procs]
-        assert [p.returncode for p in procs] == [0, 0], "\n".join(logs)
-        got = [torch.load(os.path.join(out_dir, f"rank{r}.pt")) for r in range(2)]
+    got = run_two_ranks(__file__)
     for mode in ("eager", "graph"):
         a, b = got[0][mode], got[1][mode]
         assert a["graph"] == b["graph"] == (mode == "graph")

@@ -3,23 +3,15 @@ apply / skip / skip / apply sequences, the layout of `optim.BufferSlab` and its 
 (FusedAdam, Trainer, tools/train.py, and mpa_guard_commit's through `_lib`), and the launches of a step with the switch
 off (the parent's) and on (exactly one more, mpa_guard_commit)."""
 import ctypes
-import importlib.util
-import os
 
 import numpy as np
 import pytest
 import torch
 import torch.nn as nn
 
-from multi_part_assembly_amd import _build, _lib, config, guard_ref
+from multi_part_assembly_amd import _lib, guard_ref
 from multi_part_assembly_amd.optim import BufferSlab, FlatBuffers, FusedAdam
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def built():
-    return _build.build()
+from trainer_cases import built, optimizer_presets, record as _record, tiny_cfg as _tiny_cfg, tool as _tool  # noqa: F401
 
 
 def _bytes(n, seed):
@@ -206,23 +198,7 @@ def test_slab_edge_cases():
 
 
 # ---- 3. refusals -----------------------------------------------------------------------------------------------------------------
-def _tiny_cfg():
-    cfg = config.pn_transformer_everyday()
-    cfg.model.pc_feat_dim, cfg.model.transformer_heads = 64, 4
-    cfg.model.transformer_feat_dim, cfg.model.transformer_layers = 128, 1
-    cfg.data.max_num_part = 3
-    return cfg
-
-
-def _train_tool():
-    spec = importlib.util.spec_from_file_location("train_tool", os.path.join(ROOT, "tools", "train.py"))
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
-    return tool
-
-
 def test_python_side_refusals_and_the_configuration_key():
-    import inspect
     from multi_part_assembly_amd.pn_transformer import build_model
     from multi_part_assembly_amd.trainer import Trainer
     slab = BufferSlab(_small())
@@ -245,12 +221,10 @@ def test_python_side_refusals_and_the_configuration_key():
     on.model.double()
     with pytest.raises(RuntimeError, match="no longer lives in the slab"):
         on.state_dict()
-    presets = [f for name, f in inspect.getmembers(config, inspect.isfunction)
-               if not name.startswith("_") and not inspect.signature(f).parameters and f.__module__ == config.__name__]
-    with_optimizer = [p() for p in presets if "optimizer" in p()]
+    with_optimizer = optimizer_presets()
     assert len(with_optimizer) >= 10 and all("skip_rollback_buffers" not in c.optimizer for c in with_optimizer)
     # the tool
-    tool = _train_tool()
+    tool = _tool("train")
     base = ["--preset", "pn_transformer_everyday", "--synthetic"]
     args = tool.parse_args(base + ["--skip-nonfinite"])
     assert args.rollback_buffers is False and "skip_rollback_buffers" not in tool.configure(args).optimizer
@@ -303,12 +277,6 @@ def test_entry_point_is_declared_and_refuses_bad_arguments_without_a_gpu(built):
 
 
 # ---- 4. the launches of a step --------------------------------------------------------------------------------------------------
-def _record(monkeypatch):
-    calls = []
-    monkeypatch.setattr(_lib, "launch", lambda name, dev, *args, **kw: calls.append((name, args)))
-    return calls
-
-
 @pytest.mark.parametrize("clip", [None, 1.0])
 def test_trainer_step_launches_switch_off_are_the_parents_and_on_is_one_more(monkeypatch, built, clip):
     """Recorded on a stub `_lib.launch` (host tensors, nothing runs)."""

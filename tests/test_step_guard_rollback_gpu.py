@@ -9,55 +9,26 @@ count equal to those of a twin that never saw the batch, eager and captured, for
 the switch off; a statistic that went non-finite in a skipped step is undone; a raised status word rolls back; a loaded
 checkpoint is what a skipped step returns to; two gloo ranks roll back their own statistics on the common verdict."""
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
 from multi_part_assembly_amd import _lib, guard_ref
+from trainer_cases import (BT, NT, PT, Zoned, batches as _batches, buffers as _buffers, opt_state, random_bytes as _random_bytes,
+                           rank_setup, run_two_ranks, trainer as _trainer, u8 as _bits)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 UNIT = guard_ref.COMMIT_UNIT
 BLOCK = guard_ref.THREADS * UNIT                  # bytes one block copies per sweep
 SWEEP = guard_ref.COMMIT_BLOCKS * BLOCK           # bytes one sweep of the full grid covers
 SIZES = [16, 32, 16 * 63, 16 * 64, 16 * 65, BLOCK - UNIT, BLOCK, BLOCK + UNIT, SWEEP - UNIT, SWEEP, SWEEP + UNIT,
          2 * SWEEP + BLOCK + UNIT]
-ZONE, SENTINEL = 256, 0xA5
 
 
 # ---- 1. the kernel ---------------------------------------------------------------------------------------------------------------
-def _random_bytes(n, seed):
-    """Random bits: NaN payloads, infinities, denormals and -0 are among the float32 words."""
-    a = np.random.RandomState(seed).randint(0, 256, size=n).astype(np.uint8)
-    if n >= 32:
-        a[:32].view(np.uint32)[:] = [0x7FC00001, 0xFFC12345, 0x7F800000, 0xFF800000, 0x00000001, 0x80000001, 0x80000000,
-                                     0x7FA00000]
-    return a
-
-
-class Zoned:
-    """A slab on the device between two sentinel-filled guard zones."""
-
-    def __init__(self, host, dev):
-        self.n = host.size
-        self.buf = torch.full((ZONE + self.n + ZONE,), SENTINEL, dtype=torch.uint8, device=dev)
-        self.slab = self.buf[ZONE:ZONE + self.n]
-        self.slab.copy_(torch.from_numpy(host))
-        assert self.slab.data_ptr() % 16 == 0 or self.n == 0
-
-    def words(self):
-        return self.slab.cpu().numpy().view(np.int32)
-
-    def zones_intact(self):
-        z = self.buf.cpu()
-        return bool((z[:ZONE] == SENTINEL).all()) and bool((z[ZONE + self.n:] == SENTINEL).all())
-
-
 def _commit(dev, word, live, shadow, n):
     _lib.launch("mpa_guard_commit", dev, word, live, shadow, n)
 
@@ -72,7 +43,7 @@ def test_commit_equals_the_restatement_bit_for_bit(cuda_device, n):
         runs = []
         for _ in range(2):
             live, shadow = Zoned(live_h, cuda_device), Zoned(shadow_h, cuda_device)
-            _commit(cuda_device, word, live.slab, shadow.slab, n)
+            _commit(cuda_device, word, live.mid, shadow.mid, n)
             torch.cuda.synchronize()
             got = (live.words(), shadow.words())
             assert np.array_equal(got[0], want_live.view(np.int32)), (n, verdict, "live")
@@ -89,16 +60,16 @@ def test_commit_of_zero_bytes_succeeds_without_a_launch_and_touches_nothing(cuda
     live, shadow = Zoned(host, cuda_device), Zoned(_random_bytes(64, 4), cuda_device)
     before = (live.buf.clone(), shadow.buf.clone())
     _commit(cuda_device, word, None, None, 0)              # NULL ranges
-    _commit(cuda_device, word, live.slab, shadow.slab, 0)  # and real ones
+    _commit(cuda_device, word, live.mid, shadow.mid, 0)  # and real ones
     torch.cuda.synchronize()
     assert torch.equal(live.buf, before[0]) and torch.equal(shadow.buf, before[1])
     # refusals on real device pointers: nothing is launched, nothing is written
-    for args, why in (((live.slab[8:], shadow.slab, 16), "aligned"), ((live.slab, live.slab[16:], 32), "overlap"),
-                      ((live.slab, shadow.slab, 24), "multiple of 16"), ((live.slab, None, 16), "null")):
+    for args, why in (((live.mid[8:], shadow.mid, 16), "aligned"), ((live.mid, live.mid[16:], 32), "overlap"),
+                      ((live.mid, shadow.mid, 24), "multiple of 16"), ((live.mid, None, 16), "null")):
         with pytest.raises(_lib.MpaError, match=why):
             _commit(cuda_device, word, *args)
     with pytest.raises(_lib.MpaError, match="null"):
-        _commit(cuda_device, None, live.slab, shadow.slab, 16)
+        _commit(cuda_device, None, live.mid, shadow.mid, 16)
     torch.cuda.synchronize()
     assert torch.equal(live.buf, before[0]) and torch.equal(shadow.buf, before[1])
 
@@ -110,18 +81,18 @@ def test_a_captured_commit_takes_the_direction_of_the_word_at_each_replay(cuda_d
     word = torch.zeros(8, dtype=torch.int32, device=cuda_device)
     eager = (Zoned(start, cuda_device), Zoned(start, cuda_device))
     graph = (Zoned(start, cuda_device), Zoned(start, cuda_device))
-    _commit(cuda_device, word, eager[0].slab, eager[1].slab, n)  # (the code object loads outside the capture)
+    _commit(cuda_device, word, eager[0].mid, eager[1].mid, n)  # (the code object loads outside the capture)
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g, capture_error_mode="thread_local"):
-        _commit(cuda_device, word, graph[0].slab, graph[1].slab, n)
+        _commit(cuda_device, word, graph[0].mid, graph[1].mid, n)
     ref_live, ref_shadow = start.copy(), start.copy()
     for fwd, verdict in zip(forwards, (0, 1, 0)):
         word[0] = verdict
         for live, _ in (eager, graph):
-            live.slab.copy_(torch.from_numpy(fwd))
+            live.mid.copy_(torch.from_numpy(fwd))
         g.replay()
-        _commit(cuda_device, word, eager[0].slab, eager[1].slab, n)
+        _commit(cuda_device, word, eager[0].mid, eager[1].mid, n)
         torch.cuda.synchronize()
         ref_live, ref_shadow = guard_ref.commit(verdict, fwd, ref_shadow)
         for k, want in enumerate((ref_live, ref_shadow)):
@@ -132,62 +103,8 @@ def test_a_captured_commit_takes_the_direction_of_the_word_at_each_replay(cuda_d
 
 
 # ---- 2. the trainer -------------------------------------------------------------------------------------------------------------
-BT, PT, NT = 2, 3, 64
-
-
-def _model(dev, family="pn"):
-    from multi_part_assembly_amd import config
-    from multi_part_assembly_amd.pn_transformer import build_model
-    if family == "pn":
-        cfg = config.pn_transformer_everyday()
-        cfg.model.pc_feat_dim, cfg.model.transformer_heads = 64, 4
-        cfg.model.transformer_feat_dim, cfg.model.transformer_layers = 128, 2
-    else:  # dgl: its node and edge MLPs' BatchNorm layers are those of csrc/mlp.hip
-        cfg = config.dgl_everyday()
-    cfg.data.max_num_part = PT
-    torch.manual_seed(7)
-    model = build_model(cfg)
-    for m in model.modules():
-        if isinstance(m, torch.nn.Dropout):
-            m.p = 0.0
-        if isinstance(m, torch.nn.MultiheadAttention):
-            m.dropout = 0.0
-    return model.to(dev), cfg
-
-
-def _trainer(dev, family="pn", **kw):
-    from multi_part_assembly_amd.trainer import Trainer
-    model, cfg = _model(dev, family)
-    return Trainer(model, cfg, **kw)
-
-
-def _batches(dev):
-    """clean, poisoned, clean: the NaN sits in one sample's `part_trans`, which enters the loss only."""
-    from multi_part_assembly_amd import synthetic
-    out = []
-    for seed in (60, 61, 62):
-        batch = synthetic.make_batch(BT, PT, NT, preset="everyday", seed=seed, device=dev)
-        batch.pop("num_parts")
-        out.append(batch)
-    clean2 = {k: v.clone() for k, v in out[1].items()}
-    out[1]["part_trans"][1, 0, 1] = float("nan")
-    return out, clean2
-
-
-def _bits(t):
-    return t.detach().reshape(-1).contiguous().view(torch.uint8).cpu().clone()
-
-
-def _buffers(trainer):
-    torch.cuda.synchronize()
-    return {name: _bits(b) for name, b in trainer.model.named_buffers()}
-
-
 def _opt_state(trainer):
-    torch.cuda.synchronize()
-    opt = trainer.optimizer
-    return [_bits(trainer.flat.flat_param), _bits(opt.exp_avg), _bits(opt.exp_avg_sq)], \
-        int(opt._hyper_dev[4:5].view(torch.int32).item())
+    return opt_state(trainer, _bits)  # (bytes)
 
 
 def _assert_buffers_equal(got, want, what=""):
@@ -369,9 +286,7 @@ def _rank_main(rank, port, out_dir):
     ranks, then the status word raised on rank 1 ONLY in front of the next step."""
     import torch.distributed as dist
     from multi_part_assembly_amd import gru, synthetic
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    dev = torch.device("cuda", 0)
-    dist.init_process_group("gloo", rank=rank, world_size=2)
+    dev = rank_setup(rank, port)
     out = {}
     for mode, use_graph in (("eager", False), ("graph", True)):
         t = _trainer(dev, guard_step=True, guard_buffers=True, use_graph=use_graph, graph_warmup=1)
@@ -396,16 +311,7 @@ def _rank_main(rank, port, out_dir):
 
 
 def test_two_ranks_roll_back_their_own_buffers_on_the_common_verdict(cuda_device):
-    from test_dp_gpu import _free_port
-    port = _free_port()
-    with tempfile.TemporaryDirectory() as out_dir:
-        env = dict(os.environ, PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, "tests"), os.environ.get("PYTHONPATH", "")]))
-        procs = [subprocess.Popen(["timeout", "-k", "10", "240", sys.executable, os.path.abspath(__file__), str(r), str(port),
-                                   out_dir], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-                 for r in range(2)]
-        logs = [p.communicate()[0] for p in procs]
-        assert [p.returncode for p in procs] == [0, 0], "\n".join(logs)
-        got = [torch.load(os.path.join(out_dir, f"rank{r}.pt")) for r in range(2)]
+    got = run_two_ranks(__file__)
     for mode in ("eager", "graph"):
         a, b = got[0][mode], got[1][mode]
         assert a["graph"] == b["graph"] == (mode == "graph")

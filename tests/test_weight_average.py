@@ -3,8 +3,6 @@ segment kinds, swap), `optim.WeightAverage` on host tensors, the argument refusa
 through `_lib` and of the Python layer, the launches of a step with the switch off (the parent's) and on (exactly one
 more, mpa_ema_update, last), `fit`'s `val_weights`, the checkpoint rules and the three tools' flags."""
 import ctypes
-import importlib.util
-import os
 import warnings
 
 import numpy as np
@@ -12,20 +10,12 @@ import pytest
 import torch
 import torch.nn as nn
 
-from multi_part_assembly_amd import _build, _lib, config, ema_ref
+from multi_part_assembly_amd import _lib, ema_ref
 from multi_part_assembly_amd.optim import BufferSlab, FlatBuffers, FusedAdam, WeightAverage
+from trainer_cases import (StubProducer, StubSampler, StubTrainer, bits_bytes as _bits, built, cpu_trainer as _trainer,  # noqa: F401
+                           optimizer_presets, record as _record, tiny_cfg as _tiny_cfg, tool as _tool)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
-
-
-@pytest.fixture(scope="module")
-def built():
-    return _build.build()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint8).tobytes()
 
 
 # ---- 1. the restatement ------------------------------------------------------------------------------------------------------
@@ -161,15 +151,6 @@ def test_swap_twice_is_the_identity_on_random_bits():
 
 
 # ---- 2. WeightAverage on host tensors -------------------------------------------------------------------------------------------
-def _tiny_cfg(preset="pn_transformer_everyday"):
-    cfg = getattr(config, preset)()
-    if preset.startswith("pn_transformer"):
-        cfg.model.pc_feat_dim, cfg.model.transformer_heads = 64, 4
-        cfg.model.transformer_feat_dim, cfg.model.transformer_layers = 128, 1
-    cfg.data.max_num_part = 3
-    return cfg
-
-
 def _hyper(step):
     h = torch.zeros(8)
     h[4:5].view(torch.int32).fill_(step)
@@ -311,16 +292,7 @@ def test_entry_points_are_declared_and_refuse_bad_arguments_without_a_gpu(built)
 
 
 # ---- 4. the Python layer's refusals, the configuration keys ---------------------------------------------------------------------------
-def _trainer(**kw):
-    from multi_part_assembly_amd.pn_transformer import build_model
-    from multi_part_assembly_amd.trainer import Trainer
-    cfg = _tiny_cfg()
-    torch.manual_seed(1)
-    return Trainer(build_model(cfg), cfg, **kw), cfg
-
-
 def test_trainer_switch_configuration_and_refusals():
-    import inspect
     from multi_part_assembly_amd.pn_transformer import build_model
     from multi_part_assembly_amd.trainer import Trainer
     off, cfg = _trainer()
@@ -368,20 +340,12 @@ def test_trainer_switch_configuration_and_refusals():
             raise KeyError("inside")
     assert not on.average.swapped and torch.equal(on.flat.flat_param, live)
     # no preset sets the keys
-    presets = [f for name, f in inspect.getmembers(config, inspect.isfunction)
-               if not name.startswith("_") and not inspect.signature(f).parameters and f.__module__ == config.__name__]
-    with_optimizer = [p() for p in presets if "optimizer" in p()]
+    with_optimizer = optimizer_presets()
     assert len(with_optimizer) >= 10
     assert all("ema_decay" not in c.optimizer and "ema_warmup" not in c.optimizer for c in with_optimizer)
 
 
 # ---- 5. the launches of a step -----------------------------------------------------------------------------------------------------
-def _record(monkeypatch):
-    calls = []
-    monkeypatch.setattr(_lib, "launch", lambda name, dev, *args, **kw: calls.append((name, args)))
-    return calls
-
-
 @pytest.mark.parametrize("clip", [None, 1.0])
 def test_step_launches_switch_off_are_the_parents_and_on_is_one_more(monkeypatch, built, clip):
     """Recorded on a stub `_lib.launch` (host tensors, nothing runs)."""
@@ -428,59 +392,6 @@ def test_a_bare_optimiser_takes_the_average_too(monkeypatch, built):
 
 
 # ---- 6. fit -------------------------------------------------------------------------------------------------------------------------
-class StubSampler:
-    def __init__(self):
-        self.epoch, self.next_step = 0, 0
-
-    def set_epoch(self, epoch):
-        self.epoch, self.next_step = epoch, 0
-
-    def __len__(self):
-        return 2
-
-    def __iter__(self):
-        while self.next_step < 2:
-            self.next_step += 1
-            yield self.next_step
-
-    def state_dict(self):
-        return {"epoch": self.epoch, "next_step": self.next_step}
-
-    def load_state_dict(self, s):
-        self.epoch, self.next_step = s["epoch"], s["next_step"]
-
-
-class StubProducer:
-    def batch(self, idx):
-        return idx
-
-
-class StubTrainer:
-    """What fit needs, and an `evaluate` that records the weights it was asked for."""
-
-    def __init__(self, average):
-        self.optimizer = type("O", (), {"lr": 1e-3})()
-        self.static_batch, self._fit_pending, self.asked = None, None, []
-        if average is not None:
-            self.average = average
-
-    def set_epoch(self, epoch):
-        pass
-
-    def train_step(self, batch):
-        return torch.tensor(1.0)
-
-    def check_health(self):
-        pass
-
-    def evaluate(self, batches, prefix="val", weights="live"):
-        self.asked.append(weights)
-        return {"val/part_acc": 0.5}
-
-    def state_dict(self):
-        return {"model": {}}
-
-
 class OldStubTrainer(StubTrainer):
     """A trainer from before the average: its `evaluate` takes the batches only."""
 
@@ -556,13 +467,6 @@ def test_checkpoint_keys_and_load_rules(tmp_path):
 
 
 # ---- 8. the tools -------------------------------------------------------------------------------------------------------------------
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(f"tools_{name}_ema", os.path.join(ROOT, "tools", f"{name}.py"))
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
-    return tool
-
-
 def test_train_tool_flags():
     tool = _tool("train")
     base = ["--preset", "pn_transformer_everyday", "--synthetic"]

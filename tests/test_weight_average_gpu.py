@@ -18,23 +18,22 @@ alone, checkpoints and `resume` carry it, two ranks agree, and the tools run end
 import os
 import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
 from multi_part_assembly_amd import _lib, ema_ref
+from trainer_cases import (BT, NT, PT, ROOT, SENTINEL, Zoned, batch as _batch, model as _model, random_bytes as _random_bytes,
+                           rank_setup, run_two_ranks, trainer as _trainer)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 UNIT = ema_ref.UNIT
 WAVE = 64 * UNIT
 BLOCK = ema_ref.THREADS * UNIT
 SWEEP = ema_ref.BLOCKS * BLOCK
 SIZES = [0, UNIT, 2 * UNIT, WAVE - UNIT, WAVE, WAVE + UNIT, BLOCK - UNIT, BLOCK, BLOCK + UNIT, SWEEP - UNIT, SWEEP, SWEEP + UNIT]
-ZONE, SENTINEL = 256, 0xA5
 STEPS = (1, 9, 10, 1000)
 K0, K1 = ema_ref.KIND_COPY, ema_ref.KIND_F32
 # float32 (20 B in a 32 B slot), int64, uint8 x 3, one float in a 16 B slot, an empty buffer, a gap of 32 bytes nobody
@@ -45,16 +44,6 @@ MIXED_BYTES = 112 + BLOCK + 2 * UNIT + BLOCK + 48
 
 
 # ---- 1. the kernels --------------------------------------------------------------------------------------------------------------
-def _random_bytes(n, seed):
-    """Random bits: about one float32 word in 256 is a NaN or an infinity and one in 256 a denormal; the first words are
-    fixed special values."""
-    a = np.random.RandomState(seed).randint(0, 256, size=n).astype(np.uint8)
-    if n >= 32:
-        a[:32].view(np.uint32)[:] = [0x7FC00001, 0xFFC12345, 0x7F800000, 0xFF800000, 0x00000001, 0x80000001, 0x80000000,
-                                     0x7FA00000]
-    return a
-
-
 def _slab_bytes(segments, nbytes, seed):
     """Random bits inside the segments, zero padding (BufferSlab's layout), SENTINEL in bytes no slot owns."""
     s = np.full(nbytes, SENTINEL, dtype=np.uint8)
@@ -63,24 +52,6 @@ def _slab_bytes(segments, nbytes, seed):
         s[off:off + (size + UNIT - 1) // UNIT * UNIT] = 0
         s[off:off + size] = rng.randint(0, 256, size=size)
     return s
-
-
-class Zoned:
-    """Bytes on the device between two sentinel-filled guard zones."""
-
-    def __init__(self, host, dev):
-        self.n = host.size
-        self.buf = torch.full((ZONE + self.n + ZONE,), SENTINEL, dtype=torch.uint8, device=dev)
-        self.mid = self.buf[ZONE:ZONE + self.n]
-        self.mid.copy_(torch.from_numpy(host))
-        assert self.mid.data_ptr() % 16 == 0
-
-    def bytes(self):
-        return self.mid.cpu().numpy()
-
-    def zones_intact(self):
-        z = self.buf.cpu()
-        return bool((z[:ZONE] == SENTINEL).all()) and bool((z[ZONE + self.n:] == SENTINEL).all())
 
 
 def _tables(segments, dev):
@@ -262,41 +233,7 @@ def test_a_captured_update_follows_the_device_step_word(cuda_device):
 
 
 # ---- 2. the trainer -------------------------------------------------------------------------------------------------------------
-BT, PT, NT = 2, 3, 64
 DECAY = 0.9
-
-
-def _model(dev, family="pn"):
-    from multi_part_assembly_amd import config
-    from multi_part_assembly_amd.pn_transformer import build_model
-    if family == "pn":
-        cfg = config.pn_transformer_everyday()
-        cfg.model.pc_feat_dim, cfg.model.transformer_heads = 64, 4
-        cfg.model.transformer_feat_dim, cfg.model.transformer_layers = 128, 2
-    else:
-        cfg = config.dgl_everyday()
-    cfg.data.max_num_part = PT
-    torch.manual_seed(7)
-    model = build_model(cfg)
-    for m in model.modules():
-        if isinstance(m, torch.nn.Dropout):
-            m.p = 0.0
-        if isinstance(m, torch.nn.MultiheadAttention):
-            m.dropout = 0.0
-    return model.to(dev), cfg
-
-
-def _trainer(dev, family="pn", **kw):
-    from multi_part_assembly_amd.trainer import Trainer
-    model, cfg = _model(dev, family)
-    return Trainer(model, cfg, **kw)
-
-
-def _batch(dev, seed):
-    from multi_part_assembly_amd import synthetic
-    batch = synthetic.make_batch(BT, PT, NT, preset="everyday", seed=seed, device=dev)
-    batch.pop("num_parts")
-    return batch
 
 
 def _average(t):
@@ -449,9 +386,7 @@ def test_checkpoint_round_trip_and_resume_inside_a_run(cuda_device, tmp_path):
 def _rank_main(rank, port, out_dir):
     """One rank of the two-rank run (started as a program, under its own time limit): three steps on different shards."""
     import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    dev = torch.device("cuda", 0)
-    dist.init_process_group("gloo", rank=rank, world_size=2)
+    dev = rank_setup(rank, port)
     out = {}
     for mode, use_graph in (("eager", False), ("graph", True)):
         t = _trainer(dev, ema_decay=DECAY, use_graph=use_graph, graph_warmup=1)
@@ -464,16 +399,7 @@ def _rank_main(rank, port, out_dir):
 
 
 def test_two_ranks_end_with_identical_averaged_parameters(cuda_device):
-    from test_dp_gpu import _free_port
-    port = _free_port()
-    with tempfile.TemporaryDirectory() as out_dir:
-        env = dict(os.environ, PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, "tests"), os.environ.get("PYTHONPATH", "")]))
-        procs = [subprocess.Popen(["timeout", "-k", "10", "240", sys.executable, os.path.abspath(__file__), str(r), str(port),
-                                   out_dir], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-                 for r in range(2)]
-        logs = [p.communicate()[0] for p in procs]
-        assert [p.returncode for p in procs] == [0, 0], "\n".join(logs)
-        got = [torch.load(os.path.join(out_dir, f"rank{r}.pt"), weights_only=False) for r in range(2)]
+    got = run_two_ranks(__file__, weights_only=False)  # (numpy arrays among the results)
     for mode in ("eager", "graph"):
         a, b = got[0][mode], got[1][mode]
         assert a["graph"] == b["graph"] == (mode == "graph")

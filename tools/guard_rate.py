@@ -126,7 +126,7 @@ def main():
 
     def guard_alone(i):
         _lib.launch("mpa_step_guard", dev, opt.flat_grad, opt.numel, float(args.clip), opt._hyper_dev.data_ptr() + 12, 1.0,
-                    opt.launch_status, opt._guard_ws, opt._hyper_dev, opt._guard_dev, 0.9, 0.999)
+                    opt.launch_status, opt.guard_workspace(), opt._hyper_dev, opt.guard_words(), 0.9, 0.999)
 
     def clip_alone(i):
         _lib.launch("mpa_grad_clip_coef", dev, plain.flat_grad, plain.numel, float(args.clip),
