@@ -1,10 +1,8 @@
 """csrc/assemble.hip on the device: `assemble_clouds` against the reference's recorded `sample_assembly` and the numpy
 restatement (tests/assembly_ref.py), `pose_meshes` against the float64 restatement, `BaseModel.sample_assembly` against
 its composition from `forward` + `transform_pc` + masking, a captured call, and tools/visualize.py end to end."""
-import importlib.util
 import os
 import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -19,6 +17,7 @@ from multi_part_assembly_amd import assemble, config, datasets, synthetic  # noq
 from multi_part_assembly_amd.pn_transformer import build_model  # noqa: E402
 from multi_part_assembly_amd.rotation import Rotation3D  # noqa: E402
 from multi_part_assembly_amd.transforms import transform_pc  # noqa: E402
+from tool_loader import load_tool  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -384,14 +383,6 @@ def test_mesh_pose_parts_leaves_other_slots_alone(cuda_device, mesh_case):
 
 
 # ---- the tool -----------------------------------------------------------------------------------------------------------------
-def load_tool(name):
-    path = Path(__file__).resolve().parents[1] / "tools" / f"{name}.py"
-    spec = importlib.util.spec_from_file_location(f"tool_{name}", path)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_visualize_tool_end_to_end(cuda_device, tmp_path):
     """tools/visualize.py on 6 synthetic shapes written as fracture folders, an untrained model, --vis 2."""
     vis = load_tool("visualize")

@@ -2,8 +2,6 @@
 force, its tie rule, structure and threshold edge, the invariant that the ground-truth poses score a connectivity accuracy
 of exactly 1 on a generated table, and the host-side plumbing (ABI table, argument checks, the new data key, the metrics
 of a geometry model, the tools' arguments).  No GPU: the wrapper's host path runs the restatement."""
-import importlib.util
-import os
 import warnings
 
 import numpy as np
@@ -14,8 +12,8 @@ from multi_part_assembly_amd import _lib, contacts, contacts_ref, datasets, eval
 from multi_part_assembly_amd.base_model import BaseModel
 from multi_part_assembly_amd.evaluate import PAPER_METRICS, evaluate_categories, format_table
 from multi_part_assembly_amd.rotation import Rotation3D, quat_to_matrix
+from tool_loader import load_tool as _tool
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
 
 
@@ -333,13 +331,6 @@ def test_category_table_shows_connectivity_only_when_asked_and_present():
 
 
 # ---- the tools' arguments -----------------------------------------------------------------------------------------------------
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(f"tools_{name}", os.path.join(ROOT, "tools", f"{name}.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_tools_parse_their_arguments():
     rate = _tool("contact_rate")
     args = rate.parse_args([])

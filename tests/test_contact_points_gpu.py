@@ -1,7 +1,6 @@
 """csrc/contact_points.hip against its numpy restatement, bit for bit on all three outputs, at the edges of its envelope,
 on both sides of its prune, eager and captured — and the table's way through the producers, the stores, the metrics and
 the evaluation tool."""
-import importlib.util
 import os
 import warnings
 
@@ -13,10 +12,10 @@ from multi_part_assembly_amd import assemble, config, contacts, contacts_ref, da
 from multi_part_assembly_amd.evaluate import Evaluator
 from multi_part_assembly_amd.pn_transformer import build_model
 from multi_part_assembly_amd.rotation import Rotation3D, quat_to_matrix
+from tool_loader import load_tool
 from test_contact_points import check_structure, duplicated_case, lattice_case, make_case
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(120)]
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
 
 
@@ -314,9 +313,7 @@ def test_evaluate_tool_with_connectivity(cuda_device, tmp_path, capsys):
             assemble.write_obj(os.path.join(folder, f"piece_{k}.obj"), v[f])
     with open(os.path.join(root, "everyday.val.txt"), "w") as fh:
         fh.write("everyday/Bottle/s0\neveryday/Bottle/s1\n")
-    spec = importlib.util.spec_from_file_location("tools_evaluate_ca", os.path.join(ROOT, "tools", "evaluate.py"))
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
+    tool = load_tool("evaluate")
     base = ["--preset", "identity_everyday", "--data-dir", root, "--data-fn", "everyday.val.txt", "--max-num-part", "4"]
     tool.main(base)
     plain = dict(kv.split(": ") for kv in capsys.readouterr().out.strip().split("; "))

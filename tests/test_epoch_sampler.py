@@ -3,9 +3,7 @@ oracle of tests/test_epoch_order_gpu.py), its sharding against torch's `Distribu
 counts and resume state, the argument contract of the new entry points, the bookkeeping of `fit.fit` with a stub trainer,
 and tools/train.py's argument parser."""
 import ctypes
-import importlib.util
 import os
-import pathlib
 
 import numpy as np
 import pytest
@@ -15,8 +13,7 @@ from torch.utils.data import DistributedSampler
 from multi_part_assembly_amd import _build, _lib, fit as fit_mod, sampler_ref
 from multi_part_assembly_amd.sampler import EpochSampler
 from test_mesh_store import philox4x32_10
-
-ROOT = pathlib.Path(__file__).resolve().parents[1]
+from tool_loader import load_tool
 
 
 @pytest.fixture(scope="module")
@@ -317,15 +314,8 @@ def test_rng_states_travel_with_the_checkpoint(tmp_path):
 
 
 # ---- 6. the tool's arguments ------------------------------------------------------------------------------------------------
-def _tool():
-    spec = importlib.util.spec_from_file_location("train_tool", ROOT / "tools" / "train.py")
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_train_tool_arguments():
-    tool = _tool()
+    tool = load_tool("train")
     a = tool.parse_args(["--preset", "pn_transformer_everyday", "--synthetic", "--epochs", "2"])
     assert a.synthetic and a.epochs == 2 and not a.graph and not a.resume and a.ckpt_dir == "" and a.log_every == 50
     a = tool.parse_args(["--preset", "dgl_partnet_chair", "--data-dir", "d", "--data-fn", "Chair.train.npy", "--val-fn",

@@ -18,6 +18,7 @@ from multi_part_assembly_amd.chamfer import chamfer_distance  # noqa: E402
 from multi_part_assembly_amd.pn_transformer import build_model  # noqa: E402
 from multi_part_assembly_amd.rotation import Rotation3D  # noqa: E402
 from multi_part_assembly_amd.transforms import transform_pc  # noqa: E402
+from tool_loader import load_tool  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -199,20 +200,11 @@ def test_out_of_envelope_takes_the_composition_with_one_warning(cuda_device, mon
         assert torch.equal(got[f"rot_{m}"], eval_utils.rot_metrics(r, r, valids, m))
 
 
-def _metric_launches():
-    import importlib.util
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "eval_rate.py")
-    spec = importlib.util.spec_from_file_location("tools_eval_rate", path)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod.metric_launches
-
-
 def test_fused_calc_metrics_is_at_most_three_launches_plus_one_for_connectivity(cuda_device):
     """Device kernels of one `_calc_metrics` call, counted by the profiler (tools/eval_rate.py): the fused path is the two
     kernels of mpa_assembly_metrics, plus mpa_connectivity_acc on semantic data with contacts — and no memcpy / memset."""
     from multi_part_assembly_amd import synthetic
-    count = _metric_launches()
+    count = load_tool("eval_rate").metric_launches
     cfg = config.pn_transformer_everyday()
     cfg.model.transformer_layers, cfg.data.max_num_part = 2, 6
     torch.manual_seed(0)

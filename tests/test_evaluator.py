@@ -17,6 +17,7 @@ from multi_part_assembly_amd import config
 from multi_part_assembly_amd.base_model import BaseModel
 from multi_part_assembly_amd.evaluate import PAPER_METRICS, Evaluator, evaluate_categories, format_table
 from multi_part_assembly_amd.trainer import Trainer
+from tool_loader import load_tool
 
 
 class Stub(nn.Module):
@@ -224,15 +225,6 @@ def _fracture_tree(root):
         fh.write("everyday/Bottle/s1\neveryday/Cup/s2\neveryday/Cup/missing\n")
 
 
-def _evaluate_tool():
-    import importlib.util
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "evaluate.py")
-    spec = importlib.util.spec_from_file_location("tools_evaluate", path)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_data_list_expands_shape_folders_and_skips_part_counts_out_of_range(tmp_path):
     """The split files name SHAPE folders; their `fractured_*` / `mode_*` sub-folders are the samples, and a fracture with
     too few or too many parts is skipped without an error (reference geometry_data.py:48-71)."""
@@ -246,7 +238,7 @@ def test_data_list_expands_shape_folders_and_skips_part_counts_out_of_range(tmp_
     assert sorted(datasets.read_fracture_list(root, "everyday.val.txt", "Cup", 1, 1)) == ["everyday/Cup/s2/fractured_0"]
     assert datasets.read_fracture_list(root, "everyday.val.txt", "Bott", 2, 20) == []  # a whole path component, not a prefix
 
-    tool = _evaluate_tool()
+    tool = load_tool("evaluate")
     args = type("Args", (), {"data_dir": root, "data_fn": "everyday.val.txt"})()
     cfg = config.pn_transformer_everyday()
     cfg.data.min_num_part, cfg.data.max_num_part = 2, 4

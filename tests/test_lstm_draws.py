@@ -2,8 +2,6 @@
 seq2seq_draw_ref.py, the oracle of tests/test_lstm_draws_gpu.py) — its Philox against the plain-int one, the statistics of
 coin, mask and noise — the `cfg.model.lstm_draws` key, and the argument contract of the two new entry points."""
 import ctypes
-import importlib.util
-import pathlib
 
 import numpy as np
 import pytest
@@ -11,9 +9,9 @@ import torch
 
 from multi_part_assembly_amd import _build, _lib, config, lstm, matching, seq2seq_draw_ref as ref
 from multi_part_assembly_amd.pn_transformer import build_model
+from tool_loader import load_tool
 from test_mesh_store import philox4x32_10
 
-ROOT = pathlib.Path(__file__).resolve().parents[1]
 LSTM_PRESETS = ("lstm_everyday", "lstm_artifact", "lstm_partnet_chair")
 
 
@@ -158,9 +156,7 @@ def test_device_mode_never_falls_back_to_host_draws():
 
 
 def test_train_tool_takes_the_key():
-    spec = importlib.util.spec_from_file_location("tools_train_lstm_draws", ROOT / "tools" / "train.py")
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    mod = load_tool("train")
     args = mod.parse_args(["--preset", "lstm_everyday", "--synthetic", "--lstm-draws", "device"])
     assert args.lstm_draws == "device"
     assert mod.parse_args(["--preset", "lstm_everyday", "--synthetic"]).lstm_draws is None

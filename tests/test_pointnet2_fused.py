@@ -4,8 +4,6 @@ float64 records of tests/golden/pointnet2_ssg.npz, the routing of `PointNet2SSG.
 tools' flag, and the argument contract of the three entry points of csrc/pointnet2_sa_mlp.hip."""
 import copy
 import ctypes
-import importlib.util
-import pathlib
 import warnings
 
 import numpy as np
@@ -21,8 +19,8 @@ from multi_part_assembly_amd import pointnet2_utils as pu
 from multi_part_assembly_amd.encoder import DGCNN, PointNet
 from multi_part_assembly_amd.pn_transformer import build_model
 from multi_part_assembly_amd.pointnet2 import PointNet2SSG, PointnetSAModule
+from tool_loader import load_tool as _tool
 
-ROOT = pathlib.Path(__file__).resolve().parents[1]
 PRESETS = ["pn_transformer_everyday", "pn_transformer_refine_everyday", "global_everyday", "dgl_everyday",
            "rgl_net_everyday", "lstm_everyday"]
 
@@ -190,13 +188,6 @@ def test_other_encoders_ignore_the_key(arch, cls):
     cfg.model.pointnet2_eval = "fused"
     model = build_model(cfg)
     assert isinstance(model.encoder, cls) and not hasattr(model.encoder, "eval_mlp")
-
-
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(f"tools_{name}_pointnet2_eval", ROOT / "tools" / f"{name}.py")
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def test_tools_take_the_flag():

@@ -3,7 +3,6 @@ float64 restatement under the bars of tests/anchored.py (r32 = the float32 libra
 comes from the library's own distance to float64, never from the kernel), its structural contract, the pack kernel, the
 encoder on the fixture, `forward_parts`, stale weights, memory, and the evaluation pass end to end."""
 import copy
-import importlib.util
 import os
 
 import numpy as np
@@ -18,9 +17,9 @@ from multi_part_assembly_amd.evaluate import Evaluator
 from multi_part_assembly_amd.pn_transformer import build_model
 from multi_part_assembly_amd.pointnet2 import PointNet2SSG
 from multi_part_assembly_amd.trainer import Trainer
+from tool_loader import load_tool
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def dev_call(mlp, xyz, new_xyz, feats, idx, device, out=None):
@@ -321,9 +320,7 @@ def test_evaluator_with_the_knob_on(cuda_device, preset, capsys):
 
 
 def test_evaluate_tool_runs_to_a_table(cuda_device, tmp_path, capsys, monkeypatch):
-    spec = importlib.util.spec_from_file_location("tools_evaluate_fused", os.path.join(ROOT, "tools", "evaluate.py"))
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
+    tool = load_tool("evaluate")
     shapes = synthetic.make_fracture_meshes(7, 4, [2, 3, 2, 3], 40)
     folders = []
     for s, parts in enumerate(shapes):

@@ -2,8 +2,6 @@
 float64 brute force, its diagonal constant, the exactness of the bounding-box prune, a sample without a valid part, the
 ABI's refusals, the host path of `loss.repulsion_cd_loss(fused=True)`, and the configuration keys of the model term."""
 import ctypes
-import importlib.util
-import os
 import warnings
 
 import numpy as np
@@ -13,8 +11,8 @@ import torch
 from multi_part_assembly_amd import _build, _lib, config, eval_utils
 from multi_part_assembly_amd import loss as loss_mod
 from multi_part_assembly_amd import repulsion_ref as rr
+from tool_loader import load_tool
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
 
 
@@ -329,9 +327,7 @@ def test_term_needs_its_threshold_and_weight(monkeypatch):
 
 
 def test_train_tool_sets_the_three_keys():
-    spec = importlib.util.spec_from_file_location("tools_train_repulsion", os.path.join(ROOT, "tools", "train.py"))
-    train = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(train)
+    train = load_tool("train")
     base = ["--preset", "pn_transformer_everyday", "--synthetic"]
     cfg = train.configure(train.parse_args(base))
     assert "use_repulsion_loss" not in cfg.loss and cfg.loss == config.pn_transformer_everyday().loss

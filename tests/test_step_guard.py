@@ -11,7 +11,8 @@ import torch
 from multi_part_assembly_amd import _lib, fit as fit_mod, guard_ref
 from multi_part_assembly_amd.optim import FlatBuffers, FusedAdam
 from multi_part_assembly_amd.sampler import EpochSampler
-from trainer_cases import StubProducer, StubTrainer, bits_i32 as _bits, built, optimizer_presets, record, tiny_cfg, tool as _tool  # noqa: F401
+from tool_loader import load_tool as _tool
+from trainer_cases import StubProducer, StubTrainer, bits_i32 as _bits, built, optimizer_presets, record, tiny_cfg  # noqa: F401
 
 NEW = ("mpa_step_guard_workspace", "mpa_step_guard", "mpa_adam_step_guarded", "mpa_guard_mark")
 

@@ -11,7 +11,8 @@ import torch.nn as nn
 
 from multi_part_assembly_amd import _lib, guard_ref
 from multi_part_assembly_amd.optim import BufferSlab, FlatBuffers, FusedAdam
-from trainer_cases import built, optimizer_presets, record as _record, tiny_cfg as _tiny_cfg, tool as _tool  # noqa: F401
+from tool_loader import load_tool as _tool
+from trainer_cases import built, optimizer_presets, record as _record, tiny_cfg as _tiny_cfg  # noqa: F401
 
 
 def _bytes(n, seed):

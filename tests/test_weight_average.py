@@ -13,7 +13,8 @@ import torch.nn as nn
 from multi_part_assembly_amd import _lib, ema_ref
 from multi_part_assembly_amd.optim import BufferSlab, FlatBuffers, FusedAdam, WeightAverage
 from trainer_cases import (StubProducer, StubSampler, StubTrainer, bits_bytes as _bits, built, cpu_trainer as _trainer,  # noqa: F401
-                           optimizer_presets, record as _record, tiny_cfg as _tiny_cfg, tool as _tool)
+                           optimizer_presets, record as _record, tiny_cfg as _tiny_cfg)
+from tool_loader import load_tool as _tool
 
 f32 = np.float32
 

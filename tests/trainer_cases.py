@@ -1,8 +1,7 @@
 """The one rig of the trainer-tail tests (guarded step, buffer rollback, weight average; tests/test_step_guard*.py,
 tests/test_step_guard_rollback*.py, tests/test_weight_average*.py): the tiny model per family, the trainer factory, the
-clean / poisoned / clean batches, bit views, random bytes between guard zones, the launch recorder, the tool loader, the
+clean / poisoned / clean batches, bit views, random bytes between guard zones, the launch recorder, the
 `fit` stubs and the two-rank launcher.  A plain module, imported by the test files (and by their rank programs)."""
-import importlib.util
 import inspect
 import os
 import subprocess
@@ -146,7 +145,7 @@ class Zoned:
         return bool((z[:ZONE] == SENTINEL).all()) and bool((z[ZONE + self.n:] == SENTINEL).all())
 
 
-# ---- launches, presets, tools -----------------------------------------------------------------------------------------------------
+# ---- launches, presets ------------------------------------------------------------------------------------------------------------
 def record(monkeypatch):
     """`_lib.launch` replaced by a recorder (host tensors, nothing runs): the list of (name, args) it fills."""
     calls = []
@@ -159,13 +158,6 @@ def optimizer_presets():
     made = [f() for name, f in inspect.getmembers(config, inspect.isfunction)
             if not name.startswith("_") and not inspect.signature(f).parameters and f.__module__ == config.__name__]
     return [cfg for cfg in made if "optimizer" in cfg]
-
-
-def tool(name):
-    spec = importlib.util.spec_from_file_location(f"tools_{name}_rig", os.path.join(ROOT, "tools", f"{name}.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 # ---- fit with stubs -----------------------------------------------------------------------------------------------------------------

@@ -16,37 +16,17 @@ model's forwards are excluded from both arms: the poses are given.  One JSON lin
 
 GPU only:  python tools/assembly_rate.py [--calls 10] [--windows 5] [--out profiles/r12_assembly_rate.json]"""
 import argparse
-import importlib.util
-import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rate_rig as rig  # noqa: E402  (puts the repository root on sys.path)
 from multi_part_assembly_amd import assemble, config, datasets, synthetic  # noqa: E402
 from multi_part_assembly_amd.rotation import Rotation3D  # noqa: E402
 from multi_part_assembly_amd.transforms import transform_pc  # noqa: E402
-
-
-def representative_parts(seed):
-    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
-    bench = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(bench)
-    return bench.representative_parts("everyday", seed)
-
-
-def window(fn, calls):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(calls):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / calls
 
 
 def coloured_rows_on_host(posed_shape, valid_row, palette):
@@ -125,7 +105,7 @@ def main():
     dev = torch.device("cuda:0")
     B, P, N, S = 32, 20, 1000, 5
     result = {"B": B, "P": P, "N": N, "sample_iter": S, "calls_per_window": args.calls, "windows": args.windows}
-    batch = synthetic.make_batch(B, P, N, seed=1234, device=dev, num_parts=representative_parts(1234))
+    batch = rig.c2_batches(dev, 1, B=B, P=P, N=N, keep_num_parts=True)[0]
     result["valid_parts"] = int(sum(batch["num_parts"]))
     g = torch.Generator().manual_seed(0)
     quat = torch.nn.functional.normalize(torch.randn(S, B, P, 4, generator=g), dim=-1).to(dev)
@@ -145,22 +125,14 @@ def main():
     assert all(np.array_equal(x, y) for x, y in zip(a[0], b[0]))
     assert all(np.array_equal(x, y) for xs, ys in zip(a[1], b[1]) for x, y in zip(xs, ys))
     result["arms_agree_bitwise"] = True
-    arms = {"ref": ref, "fused": fused, "fused_device": launch}
-    for fn in arms.values():
-        window(fn, 2)
-    times = {k: [] for k in arms}
-    for _ in range(args.windows):
-        for k, fn in arms.items():
-            times[k].append(window(fn, args.calls))
-    for k, v in times.items():
-        result[f"clouds_ms_{k}"] = round(statistics.median(v), 4)
-        result[f"clouds_ms_{k}_windows"] = [round(t, 4) for t in v]
-    for k in ("ref", "fused"):
-        result[f"clouds_{k}_launches"], result[f"clouds_{k}_copies"], result[f"clouds_{k}_host_syncs"] = census(arms[k])
+    arms = {"ref": lambda i: ref(), "fused": lambda i: fused(), "fused_device": lambda i: launch()}
+    rig.report(result, rig.alternate(arms, args.calls, args.windows, 2), key="clouds_ms_{name}")
+    for k, fn in (("ref", ref), ("fused", fused)):
+        result[f"clouds_{k}_launches"], result[f"clouds_{k}_copies"], result[f"clouds_{k}_host_syncs"] = census(fn)
     result["clouds_bytes_used"] = int(24 * (S + 1) * N * result["valid_parts"])
     result["clouds_bytes_copied"] = int(out.packed.numel())
 
-    shapes = synthetic.make_fracture_meshes(77, B, representative_parts(1234), 5000)
+    shapes = synthetic.make_fracture_meshes(77, B, rig.representative_parts(1234), 5000)
     store = datasets.MeshStore.from_arrays(shapes, max_num_part=P)
     prod = datasets.DeviceGeometryProducer(store, num_points=N, max_num_part=P, device=dev)
     slots = prod.slot_parts(list(range(B)))
@@ -179,20 +151,10 @@ def main():
     mesh_numpy = lambda: mesh_algebra_numpy(store, slots.reshape(-1), g_rmat, g_t, p_rmat, p_t)
     x, y = mesh_fused(), mesh_numpy()
     result["mesh_max_abs_diff"] = float(max(np.abs(p - q).max() for p, q in zip(x, y)))
-    marms = {"fused": mesh_fused, "numpy": mesh_numpy}
-    mtimes = {k: [] for k in marms}
-    for _ in range(args.windows):
-        for k, fn in marms.items():
-            mtimes[k].append(window(fn, max(1, args.calls // 5)))
-    for k, v in mtimes.items():
-        result[f"mesh_ms_{k}"] = round(statistics.median(v), 4)
-        result[f"mesh_ms_{k}_windows"] = [round(t, 4) for t in v]
+    marms = {"fused": lambda i: mesh_fused(), "numpy": lambda i: mesh_numpy()}  # warmed up by the comparison above
+    rig.report(result, rig.alternate(marms, max(1, args.calls // 5), args.windows, 0), key="mesh_ms_{name}")
     result["mesh_fused_launches"], result["mesh_fused_copies"], result["mesh_fused_host_syncs"] = census(mesh_fused)
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as fh:
-            fh.write(line + "\n")
+    rig.emit(result, args.out)
 
 
 if __name__ == "__main__":

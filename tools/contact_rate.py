@@ -15,36 +15,16 @@ library operators, B = 32, P = 20, N = 1000, part counts of `bench.representativ
 
 GPU only:  python tools/contact_rate.py [--calls 10] [--windows 5] [--out profiles/r14_contact_rate.json]"""
 import argparse
-import importlib.util
-import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rate_rig as rig  # noqa: E402  (puts the repository root on sys.path)
 from multi_part_assembly_amd import contacts, synthetic  # noqa: E402
 from multi_part_assembly_amd.rotation import Rotation3D  # noqa: E402
 from multi_part_assembly_amd.transforms import transform_pc  # noqa: E402
-
-
-def representative_parts(seed):
-    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
-    bench = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(bench)
-    return bench.representative_parts("everyday", seed)
-
-
-def window(fn, calls):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(calls):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / calls
 
 
 def cdist_table(part_pcs, valids, rot, trans, thre=0.01, pairs_per_step=8):
@@ -85,7 +65,7 @@ def main(argv=None):
     dev = torch.device("cuda:0")
     B, P, N = args.batch, args.parts, args.points
     result = {"B": B, "P": P, "N": N, "thre": args.thre, "calls_per_window": args.calls, "windows": args.windows}
-    parts = representative_parts(1234)
+    parts = rig.representative_parts(1234)
     parts = [min(P, parts[b % len(parts)]) for b in range(B)]
     batch = synthetic.make_batch(B, P, N, seed=1234, device=dev, num_parts=parts)
     part_pcs, valids, trans = batch["part_pcs"], batch["part_valids"], batch["part_trans"]
@@ -94,33 +74,22 @@ def main(argv=None):
     out3 = (torch.empty_like(out1[0]), torch.empty((B, P, P), dtype=torch.float32, device=dev),
             torch.empty((B, P, P), dtype=torch.int32, device=dev))
     arms = {
-        "operator": lambda: contacts.contact_points(part_pcs, valids, rot, trans, thre=args.thre, out=out1),
-        "operator_full": lambda: contacts.contact_points(part_pcs, valids, rot, trans, thre=args.thre, return_dist=True,
-                                                         return_index=True, out=out3),
-        "cdist": lambda: cdist_table(part_pcs, valids, rot, trans, thre=args.thre),
+        "operator": lambda i: contacts.contact_points(part_pcs, valids, rot, trans, thre=args.thre, out=out1),
+        "operator_full": lambda i: contacts.contact_points(part_pcs, valids, rot, trans, thre=args.thre, return_dist=True,
+                                                           return_index=True, out=out3),
+        "cdist": lambda i: cdist_table(part_pcs, valids, rot, trans, thre=args.thre),
     }
-    table = arms["operator"]().clone()
-    full = arms["operator_full"]()[0]
-    yard = arms["cdist"]()
+    table = arms["operator"](0).clone()
+    full = arms["operator_full"](0)[0]
+    yard = arms["cdist"](0)
     result["operator_arms_agree_bitwise"] = bool(torch.equal(table, full))
     result["flags_differ"] = int((table[..., 0] != yard[..., 0]).sum().item())
     result["real_pairs"] = int(sum(p * (p - 1) // 2 for p in parts))
     result["contacts"] = int(table[..., 0].sum().item()) // 2
     result["pair_evaluations_full"] = result["real_pairs"] * N * N
-    for fn in arms.values():
-        window(fn, 2)
-    times = {k: [] for k in arms}
-    for _ in range(args.windows):
-        for k, fn in arms.items():
-            times[k].append(window(fn, args.calls if k != "cdist" else max(1, args.calls // 5)))
-    for k, v in times.items():
-        result[f"ms_{k}"] = round(statistics.median(v), 4)
-        result[f"ms_{k}_windows"] = [round(t, 4) for t in v]
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as fh:
-            fh.write(line + "\n")
+    calls = {k: args.calls if k != "cdist" else max(1, args.calls // 5) for k in arms}
+    rig.report(result, rig.alternate(arms, calls, args.windows, 2), key="ms_{name}")
+    rig.emit(result, args.out)
 
 
 if __name__ == "__main__":

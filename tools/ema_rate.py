@@ -18,53 +18,22 @@ every optimiser step) on the c2 configuration: pn_transformer, everyday preset, 
 
 GPU only:  python tools/ema_rate.py [--steps 30] [--windows 5] [--decay 0.999]"""
 import argparse
-import importlib.util
-import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from multi_part_assembly_amd import _lib, config, synthetic  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rate_rig as rig  # noqa: E402  (puts the repository root on sys.path)
+from multi_part_assembly_amd import _lib, config  # noqa: E402
 from multi_part_assembly_amd.pn_transformer import build_model  # noqa: E402
 from multi_part_assembly_amd.trainer import Trainer  # noqa: E402
 
 KERNELS = {"mpa_grad_clip_coef": 2, "mpa_adam_step_dev": 2, "mpa_ema_update": 1}
 
 
-def representative_parts(seed):
-    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
-    bench = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(bench)
-    return bench.representative_parts("everyday", seed)
-
-
-def window(fn, steps):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for i in range(steps):
-        fn(i)
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / steps
-
-
 def arm_name(ema, graph):
     return f"ema_{'on' if ema else 'off'}_{'graph' if graph else 'eager'}"
-
-
-def optimizer_launches(optimizer):
-    """Kernels behind the library calls of one `step_dev` (recorded, nothing runs)."""
-    names, real = [], _lib.launch
-    _lib.launch = lambda name, dev, *a, **k: names.append(name)
-    try:
-        optimizer.step_dev()
-    finally:
-        _lib.launch = real
-    return sum(KERNELS[n] for n in names)
 
 
 def main():
@@ -72,13 +41,11 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--decay", type=float, default=0.999, help="any value in [0, 1): the cost does not depend on it")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r21_ema_rate.json"))
+    ap.add_argument("--out", default=os.path.join(rig.ROOT, "profiles", "r21_ema_rate.json"))
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     B, P, N = 32, 20, 1000
-    batches = [{k: v for k, v in synthetic.make_batch(B, P, N, seed=1234 + i, device=dev,
-                                                      num_parts=representative_parts(1234 + i)).items() if k != "num_parts"}
-               for i in range(4)]
+    batches = rig.c2_batches(dev, 4, B=B, P=P, N=N)
 
     def make(ema, graph):
         torch.manual_seed(0)
@@ -95,7 +62,7 @@ def main():
         torch.cuda.reset_peak_memory_stats(dev)
         base = torch.cuda.memory_allocated(dev)
         trainer = make(ema, False)
-        window(step(trainer), 3)
+        rig.window(step(trainer), 3)
         result[f"peak_memory_{'on' if ema else 'off'}_bytes"] = torch.cuda.max_memory_allocated(dev) - base
         if ema:
             result["average_bytes"] = trainer.average.ema_param.numel() * 4 + trainer.average.ema_state.numel()
@@ -104,21 +71,15 @@ def main():
 
     arms = {(ema, graph): make(ema, graph) for graph in (False, True) for ema in (False, True)}
     result["numel"] = arms[(True, False)].flat.numel
-    for trainer in arms.values():  # warm-up: code objects, lazily built buffers, the capture (3 eager steps, then replays)
-        window(step(trainer), 6)
-    times = {key: [] for key in arms}
-    for _ in range(args.windows):  # alternating windows in one process
-        for key, trainer in arms.items():
-            times[key].append(window(step(trainer), args.steps))
-    for key, trainer in arms.items():
-        name = arm_name(*key)
-        result[f"{name}_ms"] = round(statistics.median(times[key]), 4)
-        result[f"{name}_ms_windows"] = [round(t, 4) for t in times[key]]
-        result[f"{name}_optimizer_launches"] = optimizer_launches(trainer.optimizer)
-    result["ema_off_spread_ms"] = {arm_name(*k)[8:]: round(max(t) - min(t), 4) for k, t in times.items() if not k[0]}
-    result["ema_on_minus_off_ms"] = {
-        arm_name(*k)[7:]: round(statistics.median(t) - statistics.median(times[(False, k[1])]), 4)
-        for k, t in times.items() if k[0]}
+    # warm-up of 6: code objects, lazily built buffers, the capture (3 eager steps, then replays)
+    timed = rig.alternate({key: step(trainer) for key, trainer in arms.items()}, args.steps, args.windows, 6)
+    rig.report(result, {arm_name(*key): v for key, v in timed.items()})
+    for key, trainer in arms.items():  # kernels behind the library calls of one `step_dev`
+        names = rig.recorded_launches(trainer.optimizer.step_dev)
+        result[f"{arm_name(*key)}_optimizer_launches"] = sum(KERNELS[n] for n in names)
+    result["ema_off_spread_ms"] = {arm_name(*k)[8:]: round(max(ts) - min(ts), 4) for k, (_, ts) in timed.items() if not k[0]}
+    result["ema_on_minus_off_ms"] = {arm_name(*k)[7:]: round(med - timed[(False, k[1])][0], 4)
+                                     for k, (med, _) in timed.items() if k[0]}
 
     # the three kernels alone, on the model's own flat buffer (copies: a trainer's weights stay what they are)
     on = arms[(True, False)]
@@ -142,19 +103,11 @@ def main():
                     0.999, 1e-8, 0.0, 0, None)
 
     for name, fn in (("ema_update", update_alone), ("ema_swap", swap_alone), ("adam_step_dev", adam_alone)):
-        window(fn, 20)
-        ws = [window(fn, calls) for _ in range(args.windows)]
-        result[f"{name}_alone_ms"] = round(statistics.median(ws), 5)
-        result[f"{name}_alone_ms_windows"] = [round(t, 5) for t in ws]
+        rig.report(result, rig.alternate({name: fn}, calls, args.windows, 20), key="{name}_alone_ms", digits=5)
     result["ema_update_bytes"] = 12 * on.flat.numel + 3 * slab.nbytes
     result["ema_update_gbps"] = round(result["ema_update_bytes"] / (result["ema_update_alone_ms"] * 1e-3) / 1e9, 1)
     result["ema_update_not_slower_than_adam"] = result["ema_update_alone_ms"] <= result["adam_step_dev_alone_ms"]
-    line = json.dumps(result)
-    if args.out:
-        os.makedirs(os.path.dirname(args.out), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
-    print(line)
+    rig.emit(result, args.out)
 
 
 if __name__ == "__main__":

@@ -11,11 +11,10 @@
 
 The batch and epoch arms are host clocks around windows that end in a device synchronise, divided by the calls in the window;
 the arms of a group run in alternating windows after a warm-up of every arm, and the median of the windows is reported with
-the windows beside it (the protocol of tools/partnet_producer_rate.py).
+the windows beside it (the protocol of tools/rate_rig.py).
 
 GPU only:  python tools/epoch_rate.py [--windows 5] [--batches 100] [--shapes 256] [--out FILE]"""
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -23,14 +22,12 @@ import sys
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rate_rig as rig  # noqa: E402  (puts the repository root on sys.path)
 from multi_part_assembly_amd import _lib, config, datasets, sampler_ref, synthetic  # noqa: E402
 from multi_part_assembly_amd.pn_transformer import build_model  # noqa: E402
 from multi_part_assembly_amd.sampler import EpochSampler  # noqa: E402
 from multi_part_assembly_amd.trainer import Trainer  # noqa: E402
-from partnet_producer_rate import alternate, report  # noqa: E402
 
 B, P, N = 32, 20, 1000
 
@@ -64,17 +61,14 @@ def main():
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("epoch_rate: needs the GPU (a host timing says nothing about the device path)")
+    rig.require_gpu("epoch_rate")
     dev = torch.device("cuda:0")
     out = {"tool": "epoch_rate", "device": torch.cuda.get_device_name(0), "B": B, "P": P, "N": N, "shapes": args.shapes,
            "faces_per_part": args.faces, "windows": args.windows, "calls_per_window": args.batches, "order": {}}
 
     # ---- (a) the order of an epoch ----
     for S in (1000, 40000, sampler_ref.MAX_SHAPES):
-        med, ts = order_ms(dev, S, args.order_reps, args.windows)
-        out["order"][f"S{S}_ms"] = round(med, 4)
-        out["order"][f"S{S}_ms_windows"] = [round(t, 4) for t in ts]
+        rig.report(out, {f"S{S}": order_ms(dev, S, args.order_reps, args.windows)}, group="order")
 
     # ---- (b) a geometry batch from host indices and from device indices ----
     counts = np.random.RandomState(args.seed).randint(2, P + 1, size=args.shapes).tolist()
@@ -85,8 +79,7 @@ def main():
     index_tensors = [torch.tensor(ix, dtype=torch.int64, device=dev) for ix in index_lists]
     arms = {"host_idx": lambda i: prod.batch(index_lists[i % 64], batch_counter=i),
             "device_idx": lambda i: prod.batch(index_tensors[i % 64], batch_counter=i)}
-    calls = {"host_idx": args.batches, "device_idx": args.batches}
-    report(out, "batch", alternate(arms, calls, args.windows, {"host_idx": 10, "device_idx": 10}))
+    rig.report(out, rig.alternate(arms, args.batches, args.windows, 10), group="batch")
     prod.check()
 
     # ---- (c) an epoch of c2 steps: fit against the hand-written loop ----
@@ -109,20 +102,13 @@ def main():
             trainers["hand"].check_health()
             loss.item()
 
-    result = alternate({"fit": fit_epoch, "hand": hand_epoch}, {"fit": args.epochs, "hand": args.epochs}, args.windows,
-                       {"fit": 1, "hand": 1})
+    result = rig.alternate({"fit": fit_epoch, "hand": hand_epoch}, args.epochs, args.windows, 1)
     out["epoch"] = {"steps": steps, "epochs_per_window": args.epochs}
-    for arm, (med, ts) in result.items():
-        out["epoch"][f"{arm}_ms"] = round(med / steps, 4)
-        out["epoch"][f"{arm}_ms_windows"] = [round(t / steps, 4) for t in ts]
+    per_step = {arm: (med / steps, [t / steps for t in ts]) for arm, (med, ts) in result.items()}  # a call is an epoch
+    rig.report(out, per_step, group="epoch")
     for t in trainers.values():
         t.check_health(synchronize=True)
-    line = json.dumps(out)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(line + "\n")
+    rig.emit(out, args.out)
 
 
 if __name__ == "__main__":

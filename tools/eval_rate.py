@@ -11,35 +11,15 @@
 
 GPU only:  python tools/eval_rate.py [--batches 30] [--windows 5]"""
 import argparse
-import importlib.util
-import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rate_rig as rig  # noqa: E402  (puts the repository root on sys.path)
 from multi_part_assembly_amd import config, synthetic  # noqa: E402
 from multi_part_assembly_amd.pn_transformer import build_model  # noqa: E402
-
-
-def representative_parts(seed):
-    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
-    bench = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(bench)
-    return bench.representative_parts("everyday", seed)
-
-
-def window(fn, batches):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for i in range(batches):
-        fn(i)
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / batches
 
 
 def metric_launches(model, batch, fused):
@@ -90,17 +70,8 @@ def measure(model, batches, args):
                 model.validation_step(batches[i % len(batches)], i)
         return fn
 
-    for fused in (False, True):  # warm-up of both paths
-        window(step(fused), 5)
-    times = {False: [], True: []}
-    for _ in range(args.windows):  # alternating windows in one process
-        for fused in (False, True):
-            times[fused].append(window(step(fused), args.batches))
+    rig.report(out, rig.alternate({"off": step(False), "on": step(True)}, args.batches, args.windows, 5), key="ms_{name}")
     model.fused_metrics = False
-    out["ms_off"] = round(statistics.median(times[False]), 4)
-    out["ms_on"] = round(statistics.median(times[True]), 4)
-    out["ms_off_windows"] = [round(t, 4) for t in times[False]]
-    out["ms_on_windows"] = [round(t, 4) for t in times[True]]
     out["launches_off"], _, out["copies_off"] = metric_launches(model, batches[0], False)
     out["launches_on"], out["kernels_on"], out["copies_on"] = metric_launches(model, batches[0], True)
     return out
@@ -117,9 +88,7 @@ def main():
     result = {"B": B, "P": P, "N": N, "batches_per_window": args.batches, "windows": args.windows}
 
     model = build_model(config.pn_transformer_everyday()).to(dev)
-    batches = [synthetic.make_batch(B, P, N, seed=1234 + i, device=dev, num_parts=representative_parts(1234 + i))
-               for i in range(2)]
-    for k, v in measure(model, batches, args).items():
+    for k, v in measure(model, rig.c2_batches(dev, 2, B=B, P=P, N=N, keep_num_parts=True), args).items():
         result[f"c2_{k}"] = v
 
     cfg = config.global_partnet_chair()
@@ -137,7 +106,7 @@ def main():
     args.batches = max(3, args.batches // 3)
     for k, v in measure(model, batches, args).items():
         result[f"global_{k}"] = v
-    print(json.dumps(result))
+    rig.emit(result, None)
 
 
 if __name__ == "__main__":

@@ -10,8 +10,6 @@ pn_transformer, everyday preset, B = 32, P = 20, N = 1000, part counts of `bench
 Every figure is a host clock around a window that ends in a device synchronise, after a warm-up, divided by the number
 of batches in the window.  GPU only:  python tools/geometry_producer_rate.py [--batches 200] [--host-batches 1]"""
 import argparse
-import importlib.util
-import json
 import os
 import sys
 import tempfile
@@ -20,18 +18,11 @@ import time
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rate_rig as rig  # noqa: E402  (puts the repository root on sys.path)
 from multi_part_assembly_amd import config, datasets, synthetic  # noqa: E402
 from multi_part_assembly_amd.pn_transformer import build_model  # noqa: E402
 from multi_part_assembly_amd.trainer import Trainer  # noqa: E402
-
-
-def representative_parts(seed):
-    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
-    bench = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(bench)
-    return bench.representative_parts("everyday", seed)
 
 
 def write_obj_folders(root, shapes):
@@ -47,16 +38,9 @@ def write_obj_folders(root, shapes):
     return data_list
 
 
-def window(fn, batches, warmup):
-    """ms per call of fn(i) over `batches` calls, the window closed by a synchronise."""
-    for i in range(warmup):
-        fn(i)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for i in range(batches):
-        fn(warmup + i)
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / batches
+def single(fn, batches, warmup):
+    """ms per call of one window of `batches` calls of fn(i), after `warmup` untimed calls (a rig.alternate of one arm)."""
+    return rig.alternate({"arm": fn}, batches, 1, warmup)["arm"][0]
 
 
 def main():
@@ -68,12 +52,11 @@ def main():
     ap.add_argument("--faces", type=int, default=5000, help="triangles per part")
     ap.add_argument("--seed", type=int, default=1234)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("geometry_producer_rate: needs a GPU (a host timing says nothing about the device path)")
+    rig.require_gpu("geometry_producer_rate")
     dev = torch.device("cuda:0")
     cfg = config.pn_transformer_everyday()
     B, P, N = 32, cfg.data.max_num_part, cfg.data.num_pc_points
-    parts = representative_parts(args.seed)
+    parts = rig.representative_parts(args.seed)
     shapes = synthetic.make_fracture_meshes(args.seed, B, parts, args.faces)
     indices = list(range(B))
 
@@ -94,25 +77,25 @@ def main():
             host_obj = datasets.GeometryBatchProducer(
                 num_points=N, max_num_part=P, data_keys=cfg.data.data_keys, device=dev, data_list=data_list,
                 sampler=datasets.ObjSurfaceSampler(tmp, num_points=N, max_num_part=P))
-            a_ms = window(lambda i: host_obj.batch(indices), args.host_batches, 0)
+            a_ms = single(lambda i: host_obj.batch(indices), args.host_batches, 0)
         parsed = dict(zip(data_list, shapes))
         host_parsed = datasets.GeometryBatchProducer(
             num_points=N, max_num_part=P, data_keys=cfg.data.data_keys, device=dev, data_list=data_list,
             sampler=lambda rel: np.stack([datasets.sample_surface(v, f, N) for v, f in parsed[rel]]))
-        b_ms = window(lambda i: host_parsed.batch(indices), args.host_batches, 0)
+        b_ms = single(lambda i: host_parsed.batch(indices), args.host_batches, 0)
 
-    c_ms = window(lambda i: device.batch(indices), args.batches, args.warmup)
-    d_ms = window(lambda i: trainer.train_step(fixed), args.batches, args.warmup)
-    e_ms = window(lambda i: trainer.train_step(device.batch(indices)), args.batches, args.warmup)
-    c2_ms = window(lambda i: device.batch(indices), args.batches, args.warmup)  # again: the spread of (c)
+    c_ms = single(lambda i: device.batch(indices), args.batches, args.warmup)
+    d_ms = single(lambda i: trainer.train_step(fixed), args.batches, args.warmup)
+    e_ms = single(lambda i: trainer.train_step(device.batch(indices)), args.batches, args.warmup)
+    c2_ms = single(lambda i: device.batch(indices), args.batches, args.warmup)  # again: the spread of (c)
     trainer.check_health(synchronize=True)
-    print(json.dumps({
+    rig.emit({
         "tool": "geometry_producer_rate", "device": torch.cuda.get_device_name(0), "B": B, "P": P, "N": N,
         "valid_parts": int(sum(parts)), "faces_per_part": int(store.part_face_off[1]), "store_bytes": int(store.nbytes),
         "store_pack_s": round(pack_s, 3), "batches": args.batches, "host_batches": args.host_batches,
         "a_host_obj_ms": a_ms and round(a_ms, 1), "b_host_parsed_ms": b_ms and round(b_ms, 1), "c_device_ms": round(c_ms, 4),
         "c_device_ms_repeat": round(c2_ms, 4), "d_step_ms": round(d_ms, 4), "e_device_and_step_ms": round(e_ms, 4),
-        "launch": "eager"}))
+        "launch": "eager"}, None)
 
 
 if __name__ == "__main__":

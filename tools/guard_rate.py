@@ -21,18 +21,14 @@ rollback arm is the guard-on arm beside it.
 
 GPU only:  python tools/guard_rate.py [--steps 30] [--windows 5] [--clip 1.0]"""
 import argparse
-import importlib.util
-import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from multi_part_assembly_amd import _lib, config, synthetic  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rate_rig as rig  # noqa: E402  (puts the repository root on sys.path)
+from multi_part_assembly_amd import _lib, config  # noqa: E402
 from multi_part_assembly_amd.pn_transformer import build_model  # noqa: E402
 from multi_part_assembly_amd.trainer import Trainer  # noqa: E402
 
@@ -41,35 +37,8 @@ KERNELS = {"mpa_grad_clip_coef": 2, "mpa_adam_step_dev": 2, "mpa_step_guard": 2,
 GUARDS = ("off", "on", "rollback")
 
 
-def representative_parts(seed):
-    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
-    bench = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(bench)
-    return bench.representative_parts("everyday", seed)
-
-
-def window(fn, steps):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for i in range(steps):
-        fn(i)
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / steps
-
-
 def arm_name(guard, graph, clip):
     return f"guard_{guard}_{'graph' if graph else 'eager'}_{'clip' if clip else 'noclip'}"
-
-
-def optimizer_launches(optimizer):
-    """Kernels behind the library calls of one `step_dev` (recorded, nothing runs)."""
-    names, real = [], _lib.launch
-    _lib.launch = lambda name, dev, *a, **k: names.append(name)
-    try:
-        optimizer.step_dev()
-    finally:
-        _lib.launch = real
-    return sum(KERNELS[n] for n in names)
 
 
 def main():
@@ -80,9 +49,7 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     B, P, N = 32, 20, 1000
-    batches = [{k: v for k, v in synthetic.make_batch(B, P, N, seed=1234 + i, device=dev,
-                                                      num_parts=representative_parts(1234 + i)).items() if k != "num_parts"}
-               for i in range(4)]
+    batches = rig.c2_batches(dev, 4, B=B, P=P, N=N)
     arms = {}
     for clip in (False, True):
         for graph in (False, True):
@@ -99,25 +66,20 @@ def main():
     def step(trainer):
         return lambda i: trainer.train_step(batches[i % len(batches)])
 
-    for trainer in arms.values():  # warm-up: code objects, lazily built buffers, the capture (3 eager steps, then replays)
-        window(step(trainer), 6)
-    times = {key: [] for key in arms}
-    for _ in range(args.windows):  # alternating windows in one process
-        for key, trainer in arms.items():
-            times[key].append(window(step(trainer), args.steps))
+    # warm-up of 6: code objects, lazily built buffers, the capture (3 eager steps, then replays)
+    timed = rig.alternate({key: step(trainer) for key, trainer in arms.items()}, args.steps, args.windows, 6)
+    rig.report(result, {arm_name(*key): v for key, v in timed.items()})
     for key, trainer in arms.items():
         name = arm_name(*key)
-        result[f"{name}_ms"] = round(statistics.median(times[key]), 4)
-        result[f"{name}_ms_windows"] = [round(t, 4) for t in times[key]]
-        result[f"{name}_optimizer_launches"] = optimizer_launches(trainer.optimizer)
+        # kernels behind the library calls of one `step_dev`
+        result[f"{name}_optimizer_launches"] = sum(KERNELS[n] for n in rig.recorded_launches(trainer.optimizer.step_dev))
         if key[0] != "off":
             words = trainer.optimizer.guard_words().tolist()
             result[f"{name}_applied_skipped"] = words[1:3]
-    result["guard_off_spread_ms"] = {arm_name(*k)[10:]: round(max(t) - min(t), 4) for k, t in times.items()
+    result["guard_off_spread_ms"] = {arm_name(*k)[10:]: round(max(ts) - min(ts), 4) for k, (_, ts) in timed.items()
                                      if k[0] == "off"}
-    result["rollback_minus_guard_on_ms"] = {
-        arm_name(*k)[15:]: round(statistics.median(t) - statistics.median(times[("on",) + k[1:]]), 4)
-        for k, t in times.items() if k[0] == "rollback"}
+    result["rollback_minus_guard_on_ms"] = {arm_name(*k)[15:]: round(med - timed[("on",) + k[1:]][0], 4)
+                                            for k, (med, _) in timed.items() if k[0] == "rollback"}
 
     # the guard's two launches alone, at the model's numel
     opt = arms[("on", False, True)].optimizer
@@ -150,11 +112,8 @@ def main():
 
     for name, fn in (("step_guard", guard_alone), ("grad_clip_coef", clip_alone), ("adam_step_dev", adam_alone),
                      ("guard_commit", commit_alone)):
-        window(fn, 20)
-        ws = [window(fn, calls) for _ in range(args.windows)]
-        result[f"{name}_alone_ms"] = round(statistics.median(ws), 5)
-        result[f"{name}_alone_ms_windows"] = [round(t, 5) for t in ws]
-    print(json.dumps(result))
+        rig.report(result, rig.alternate({name: fn}, calls, args.windows, 20), key="{name}_alone_ms", digits=5)
+    rig.emit(result, None)
 
 
 if __name__ == "__main__":

@@ -18,17 +18,15 @@ of one step of each.  GPU only:  python tools/lstm_step.py [--steps 20]
 
   python tools/lstm_step.py --draws [--steps 10] [--windows 5] [--models everyday,partnet] [--arms a,b,c]"""
 import argparse
-import json
 import os
-import statistics
 import sys
-import time
 import warnings
 
 import torch
 from torch.utils._python_dispatch import TorchDispatchMode
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rate_rig as rig  # noqa: E402  (puts the repository root on sys.path)
 from multi_part_assembly_amd import config, synthetic  # noqa: E402
 from multi_part_assembly_amd.pn_transformer import build_model  # noqa: E402
 from multi_part_assembly_amd.trainer import Trainer  # noqa: E402
@@ -56,15 +54,6 @@ def _draws_arm(name, arm, dev, P):
         cfg.model.lstm_draws = "device"
     torch.manual_seed(0)
     return Trainer(build_model(cfg).to(dev), cfg, use_graph=arm == "c", graph_warmup=2)
-
-
-def _window(trainer, batches, steps):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for i in range(steps):
-        trainer.train_step(batches[i % len(batches)], i)
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / steps
 
 
 def _forward_launches(trainer, batch):
@@ -107,21 +96,19 @@ def measure_draws(name, dev, args):
     for b in batches:
         b.pop("num_parts", None)
     trainers = {arm: _draws_arm(name, arm, dev, P) for arm in args.arms}
-    for tr in trainers.values():  # warm-up of every arm: first launches, allocator, the capture of arm c
-        _window(tr, batches, 4)
-    times = {arm: [] for arm in trainers}
-    for _ in range(args.windows):
-        for arm, tr in trainers.items():
-            times[arm].append(_window(tr, batches, args.steps))
+
+    def step(tr):
+        return lambda i: tr.train_step(batches[i % len(batches)], i)
+
+    # warm-up of every arm: first launches, allocator, the capture of arm c
+    timed = rig.alternate({arm: step(tr) for arm, tr in trainers.items()}, args.steps, args.windows, 4)
     out = {"B": B, "P": P, "N": N, "steps_per_window": args.steps, "sample_iter": trainers[args.arms[0]].model.sample_iter}
-    for arm, ts in times.items():
-        out[f"{arm}_ms"] = round(statistics.median(ts), 4)
-        out[f"{arm}_ms_windows"] = [round(t, 4) for t in ts]
+    rig.report(out, timed)
     if "c" in trainers:
         out["c_captured"] = trainers["c"]._graph is not None
-    if "a" in times:
-        out["spread_a"] = round(max(times["a"]) - min(times["a"]), 4)
-        if "b" in times:
+    if "a" in timed:
+        out["spread_a"] = round(max(timed["a"][1]) - min(timed["a"][1]), 4)
+        if "b" in timed:
             out["b_not_slower"] = out["b_ms"] <= out["a_ms"] + out["spread_a"]
     for arm in ("a", "b"):
         if arm in trainers:
@@ -139,7 +126,7 @@ def main_draws(args):
     for name in args.models.split(","):
         result[name] = measure_draws(name, dev, args)
     result["draw_us"] = round(_draw_us(dev, 32, 20), 3)
-    print(json.dumps(result))
+    rig.emit(result, None)
 
 
 def main():
@@ -153,8 +140,7 @@ def main():
     ap.add_argument("--no-counts", action="store_true", help="skip the op / launch counts (under an outside profiler)")
     ap.add_argument("--paths", default="hip,library", help="comma-separated subset of hip,library")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("lstm_step: needs the GPU (a host timing says nothing about the step)")
+    rig.require_gpu("lstm_step")
     if args.draws:
         args.steps = 10 if args.steps is None else args.steps
         return main_draws(args)

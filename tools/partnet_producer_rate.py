@@ -12,13 +12,12 @@
                              graph, ten replays between two HIP events, per launch; with the bytes a launch moves by the
                              formula in gather.traffic_formula, and their ratio
 
-Every other *_ms is a host clock around a window that ends in a device synchronise, divided by the calls
-in the window; the arms of a group run in alternating windows after a warm-up of every arm (captures included); the median
-of the windows is reported, the windows themselves beside it.  Another set of indices every batch.
+Every other *_ms is the median of the arm's windows, the windows themselves beside it: the arms of a group run in
+alternating windows after a warm-up of every arm (captures included), the protocol of tools/rate_rig.py.  Another set of
+indices every batch.
 
 GPU only:  python tools/partnet_producer_rate.py [--windows 5] [--batches 100] [--host-batches 10] [--out FILE]"""
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -28,8 +27,8 @@ import time
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rate_rig as rig  # noqa: E402  (puts the repository root on sys.path)
 from multi_part_assembly_amd import config, datasets, synthetic  # noqa: E402
 from multi_part_assembly_amd.pn_transformer import build_model  # noqa: E402
 from multi_part_assembly_amd.trainer import Trainer  # noqa: E402
@@ -37,32 +36,6 @@ from multi_part_assembly_amd.trainer import Trainer  # noqa: E402
 PRESETS = {"global": config.global_partnet_chair, "dgl": config.dgl_partnet_chair}
 B, P, N = 32, 20, 1000
 REPS = 50  # gather launches in the graph that gather.event_ms times
-
-
-def window(fn, calls, start=0):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for i in range(calls):
-        fn(start + i)
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / calls
-
-
-def alternate(arms, calls, windows, warmup):
-    """arms: name -> fn(i); calls: name -> calls per window.  -> name -> (median ms, [window ms])."""
-    for name, fn in arms.items():
-        window(fn, warmup[name])
-    times = {name: [] for name in arms}
-    for w in range(windows):
-        for name, fn in arms.items():
-            times[name].append(window(fn, calls[name], start=warmup[name] + w * calls[name]))
-    return {name: (statistics.median(ts), ts) for name, ts in times.items()}
-
-
-def report(out, group, result):
-    for name, (med, ts) in result.items():
-        out.setdefault(group, {})[f"{name}_ms"] = round(med, 4)
-        out[group][f"{name}_ms_windows"] = [round(t, 4) for t in ts]
 
 
 def main():
@@ -75,8 +48,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("partnet_producer_rate: needs the GPU (a host timing says nothing about the device path)")
+    rig.require_gpu("partnet_producer_rate")
     dev = torch.device("cuda:0")
     t0 = time.perf_counter()
     store = synthetic.make_partnet_like_store(args.shapes, max_parts=P, num_points=N, seed=args.seed)
@@ -105,7 +77,7 @@ def main():
                 "device": lambda i: device.batch(pick(index_lists, i)),
                 "device_idx": lambda i: device.batch(pick(index_tensors, i))}
         calls = {"host": args.host_batches, "device": args.batches, "device_idx": args.batches}
-        report(out, "producer", alternate(arms, calls, args.windows, {"host": 2, "device": 10, "device_idx": 10}))
+        rig.report(out, rig.alternate(arms, calls, args.windows, {"host": 2, "device": 10, "device_idx": 10}), group="producer")
         out["producer"]["device_below_host"] = out["producer"]["device_ms"] < out["producer"]["host_ms"]
 
         # ---- the gather launch between two events, against the bytes it moves ----
@@ -173,20 +145,13 @@ def main():
                     "host_fed": lambda i: trainers["host_fed"].train_step(m_host.batch(pick(index_lists, i))),
                     "device_fed": device_fed}
             calls = {"alone": args.batches, "host_fed": args.host_batches, "device_fed": args.batches}
-            result = alternate(arms, calls, args.windows, {"alone": 5, "host_fed": 2, "device_fed": 5})
-            step = {"data_keys": list(mkeys)}
-            for arm, (med, ts) in result.items():
-                step[f"{arm}_ms"] = round(med, 4)
-                step[f"{arm}_ms_windows"] = [round(t, 4) for t in ts]
-            out["step"][name] = step
+            out["step"][name] = {"data_keys": list(mkeys)}
+            rig.report(out["step"], rig.alternate(arms, calls, args.windows, {"alone": 5, "host_fed": 2, "device_fed": 5}),
+                       group=name)
             for t in trainers.values():
                 t.check_health(synchronize=True)
             m_dev.check()
-    line = json.dumps(out)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as fh:
-            fh.write(line + "\n")
+    rig.emit(out, args.out)
 
 
 if __name__ == "__main__":

@@ -13,29 +13,17 @@ points (352: the valid parts of a B = 32 everyday batch), its two evaluation pat
 
 GPU only:  python tools/pointnet2_eval_rate.py [--clouds 352] [--calls 5] [--windows 5] [--out FILE]"""
 import argparse
-import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 import torch.nn.functional as F
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rate_rig as rig  # noqa: E402  (puts the repository root on sys.path)
 from multi_part_assembly_amd import pointnet2_fused as fused  # noqa: E402
 from multi_part_assembly_amd import pointnet2_utils as pu  # noqa: E402
 from multi_part_assembly_amd.pointnet2 import PointNet2SSG  # noqa: E402
-
-
-def window(fn, calls):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(calls):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / calls
 
 
 def parse_args(argv=None):
@@ -85,27 +73,17 @@ def main(argv=None):
     result = {"clouds": M, "points": 1000, "calls_per_window": args.calls, "windows": args.windows}
     outs = {}
     for k in ("library", "fused"):
-        window(arms[k], 1)
+        arms[k]()
+        torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats(dev)
         base = torch.cuda.memory_allocated(dev)
         outs[k] = arms[k]()
         torch.cuda.synchronize()
         result[f"peak_mib_{k}"] = round((torch.cuda.max_memory_allocated(dev) - base) / 2 ** 20, 1)
     result["max_rel_diff"] = float((outs["fused"] - outs["library"]).abs().max() / outs["library"].abs().max())
-    for fn in arms.values():
-        window(fn, 1)
-    times = {k: [] for k in arms}
-    for _ in range(args.windows):
-        for k, fn in arms.items():
-            times[k].append(window(fn, args.calls))
-    for k, v in times.items():
-        result[f"ms_{k}"] = round(statistics.median(v), 4)
-        result[f"ms_{k}_windows"] = [round(t, 4) for t in v]
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as fh:
-            fh.write(line + "\n")
+    timed = rig.alternate({k: lambda i, fn=fn: fn() for k, fn in arms.items()}, args.calls, args.windows, 1)
+    rig.report(result, timed, key="ms_{name}")
+    rig.emit(result, args.out)
 
 
 if __name__ == "__main__":

@@ -12,26 +12,14 @@ JSON line:
 
 GPU only:  python tools/pointnet2_interp_rate.py [--clouds 352] [--calls 5] [--windows 5] [--out FILE]"""
 import argparse
-import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rate_rig as rig  # noqa: E402  (puts the repository root on sys.path)
 from multi_part_assembly_amd import pointnet2_utils as pu  # noqa: E402
-
-
-def window(fn, calls):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(calls):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / calls
 
 
 def three_nn_torch(unknown, known):
@@ -86,27 +74,15 @@ def main(argv=None):
         result[f"interp_bwd_m{m}_torch_agrees"] = bool((interp_bwd_torch(grad, idx, weight, m) - back).abs().max()
                                                        <= 1e-5 * back.abs().max())
         arms.update({
-            f"three_nn_m{m}": lambda known=known: pu.three_nn(unknown, known),
-            f"three_nn_m{m}_torch": lambda known=known: three_nn_torch(unknown, known),
-            f"interp_fwd_m{m}": lambda a=(feat, idx, weight): pu._interpolate_forward(*a),
-            f"interp_fwd_m{m}_torch": lambda a=(feat, idx, weight): interp_torch(*a),
-            f"interp_bwd_m{m}": lambda a=(grad, idx, weight, m): pu._interpolate_backward(*a),
-            f"interp_bwd_m{m}_torch": lambda a=(grad, idx, weight, m): interp_bwd_torch(*a),
+            f"three_nn_m{m}": lambda i, known=known: pu.three_nn(unknown, known),
+            f"three_nn_m{m}_torch": lambda i, known=known: three_nn_torch(unknown, known),
+            f"interp_fwd_m{m}": lambda i, a=(feat, idx, weight): pu._interpolate_forward(*a),
+            f"interp_fwd_m{m}_torch": lambda i, a=(feat, idx, weight): interp_torch(*a),
+            f"interp_bwd_m{m}": lambda i, a=(grad, idx, weight, m): pu._interpolate_backward(*a),
+            f"interp_bwd_m{m}_torch": lambda i, a=(grad, idx, weight, m): interp_bwd_torch(*a),
         })
-    for fn in arms.values():
-        window(fn, 1)
-    times = {k: [] for k in arms}
-    for _ in range(args.windows):
-        for k, fn in arms.items():
-            times[k].append(window(fn, args.calls))
-    for k, v in times.items():
-        result[f"ms_{k}"] = round(statistics.median(v), 4)
-        result[f"ms_{k}_windows"] = [round(t, 4) for t in v]
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as fh:
-            fh.write(line + "\n")
+    rig.report(result, rig.alternate(arms, args.calls, args.windows, 1), key="ms_{name}")
+    rig.emit(result, args.out)
 
 
 if __name__ == "__main__":

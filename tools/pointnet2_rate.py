@@ -14,27 +14,15 @@ composed from library operators, and of the encoder's forward + backward.  One J
 
 GPU only:  python tools/pointnet2_rate.py [--clouds 352] [--parts 88] [--calls 5] [--windows 5] [--out FILE]"""
 import argparse
-import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rate_rig as rig  # noqa: E402  (puts the repository root on sys.path)
 from multi_part_assembly_amd import pointnet2_utils as pu  # noqa: E402
 from multi_part_assembly_amd.pointnet2 import PointNet2SSG  # noqa: E402
-
-
-def window(fn, calls):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(calls):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / calls
 
 
 def fps_torch(xyz, npoint):
@@ -100,51 +88,40 @@ def main(argv=None):
               "ball_torch_agrees": bool(torch.equal(ball_torch(0.2, 64, xyz1, xyz2), ball1)),
               "group_torch_agrees": bool(torch.equal(group_torch(f2, ball2), pu.grouping_operation(f2, ball2)))}
     arms = {
-        "fps_sa1": lambda: pu.furthest_point_sample(xyz1, 512),
-        "fps_sa2": lambda: pu.furthest_point_sample(xyz2, 128),
-        "fps_sa1_torch": lambda: fps_torch(xyz1, 512),
-        "fps_sa2_torch": lambda: fps_torch(xyz2, 128),
-        "ball_sa1": lambda: pu.ball_query(0.2, 64, xyz1, xyz2),
-        "ball_sa2": lambda: pu.ball_query(0.4, 64, xyz2, xyz3),
-        "ball_sa1_torch": lambda: ball_torch(0.2, 64, xyz1, xyz2),
-        "ball_sa2_torch": lambda: ball_torch(0.4, 64, xyz2, xyz3),
-        "group_fwd_sa1": lambda: pu._group_forward(f1, ball1),
-        "group_fwd_sa2": lambda: pu._group_forward(f2, ball2),
-        "group_fwd_sa1_torch": lambda: group_torch(f1, ball1),
-        "group_fwd_sa2_torch": lambda: group_torch(f2, ball2),
-        "group_bwd_sa1": lambda: pu._group_backward(g1, ball1, 1000),
-        "group_bwd_sa2": lambda: pu._group_backward(g2, ball2, 512),
-        "group_bwd_sa1_torch": lambda: group_bwd_torch(g1, ball1, 1000),
-        "group_bwd_sa2_torch": lambda: group_bwd_torch(g2, ball2, 512),
+        "fps_sa1": lambda i: pu.furthest_point_sample(xyz1, 512),
+        "fps_sa2": lambda i: pu.furthest_point_sample(xyz2, 128),
+        "fps_sa1_torch": lambda i: fps_torch(xyz1, 512),
+        "fps_sa2_torch": lambda i: fps_torch(xyz2, 128),
+        "ball_sa1": lambda i: pu.ball_query(0.2, 64, xyz1, xyz2),
+        "ball_sa2": lambda i: pu.ball_query(0.4, 64, xyz2, xyz3),
+        "ball_sa1_torch": lambda i: ball_torch(0.2, 64, xyz1, xyz2),
+        "ball_sa2_torch": lambda i: ball_torch(0.4, 64, xyz2, xyz3),
+        "group_fwd_sa1": lambda i: pu._group_forward(f1, ball1),
+        "group_fwd_sa2": lambda i: pu._group_forward(f2, ball2),
+        "group_fwd_sa1_torch": lambda i: group_torch(f1, ball1),
+        "group_fwd_sa2_torch": lambda i: group_torch(f2, ball2),
+        "group_bwd_sa1": lambda i: pu._group_backward(g1, ball1, 1000),
+        "group_bwd_sa2": lambda i: pu._group_backward(g2, ball2, 512),
+        "group_bwd_sa1_torch": lambda i: group_bwd_torch(g1, ball1, 1000),
+        "group_bwd_sa2_torch": lambda i: group_bwd_torch(g2, ball2, 512),
     }
     enc = PointNet2SSG(128).to(dev).train()
     parts = xyz1[:args.parts].contiguous()
     w = torch.randn(args.parts, 128, device=dev, generator=g)
 
-    def encoder_step():
+    def encoder_step(i):
         enc.zero_grad(set_to_none=True)
         (enc(parts) * w).sum().backward()
 
     arms["encoder_fwd_bwd"] = encoder_step
-    slow = ("fps_sa1_torch", "fps_sa2_torch")
-    for k, fn in arms.items():
-        window(fn, 1)
+    rig.window(encoder_step, 1)  # the peak is a warmed-up step's
     torch.cuda.reset_peak_memory_stats(dev)
     base = torch.cuda.memory_allocated(dev)
-    window(encoder_step, 1)
+    rig.window(encoder_step, 1)
     result["encoder_peak_mib"] = round((torch.cuda.max_memory_allocated(dev) - base) / 2 ** 20, 1)
-    times = {k: [] for k in arms}
-    for _ in range(args.windows):
-        for k, fn in arms.items():
-            times[k].append(window(fn, 1 if k in slow else args.calls))
-    for k, v in times.items():
-        result[f"ms_{k}"] = round(statistics.median(v), 4)
-        result[f"ms_{k}_windows"] = [round(t, 4) for t in v]
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as fh:
-            fh.write(line + "\n")
+    calls = {k: 1 if k in ("fps_sa1_torch", "fps_sa2_torch") else args.calls for k in arms}  # the torch loops are slow
+    rig.report(result, rig.alternate(arms, calls, args.windows, 1), key="ms_{name}")
+    rig.emit(result, args.out)
 
 
 if __name__ == "__main__":

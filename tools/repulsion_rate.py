@@ -17,48 +17,17 @@ benchmark's synthetic batch with the part counts of `bench.representative_parts`
 
 GPU only:  python tools/repulsion_rate.py [--calls 5] [--windows 5] [--thre 0.01 0.05] [--out profiles/r18_repulsion_rate.json]"""
 import argparse
-import importlib.util
-import json
 import os
-import statistics
 import sys
-import time
 import warnings
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rate_rig as rig  # noqa: E402  (puts the repository root on sys.path)
 from multi_part_assembly_amd import config, synthetic  # noqa: E402
 from multi_part_assembly_amd import loss as L  # noqa: E402
 from multi_part_assembly_amd.transforms import transform_pc  # noqa: E402
-
-
-def representative_parts(seed):
-    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
-    bench = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(bench)
-    return bench.representative_parts("everyday", seed)
-
-
-def window(fn, calls):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(calls):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / calls
-
-
-def alternate(arms, windows, calls):
-    """{arm: (median ms, [window ms])} of callables timed in alternating windows after a warm-up window each."""
-    for fn in arms.values():
-        window(fn, 2)
-    times = {k: [] for k in arms}
-    for _ in range(windows):
-        for k, fn in arms.items():
-            times[k].append(window(fn, calls))
-    return {k: (round(statistics.median(v), 4), [round(t, 4) for t in v]) for k, v in times.items()}
 
 
 def peak_mb(fn):
@@ -66,7 +35,7 @@ def peak_mb(fn):
     torch.cuda.empty_cache()
     rest = torch.cuda.memory_allocated()
     torch.cuda.reset_peak_memory_stats()
-    fn()
+    fn(0)
     torch.cuda.synchronize()
     return round((torch.cuda.max_memory_allocated() - rest) / 2 ** 20, 1)
 
@@ -96,8 +65,8 @@ def cell(posed, valids, thre, args):
         loss = L.repulsion_cd_loss(x, valids, thre, fused=fused)
         return torch.autograd.grad((loss * w).sum(), x)[0]
 
-    arms = {"composed_fwd": lambda: fwd(False), "fused_fwd": lambda: fwd(True),
-            "composed_fwdbwd": lambda: fwdbwd(False), "fused_fwdbwd": lambda: fwdbwd(True)}
+    arms = {"composed_fwd": lambda i: fwd(False), "fused_fwd": lambda i: fwd(True),
+            "composed_fwdbwd": lambda i: fwdbwd(False), "fused_fwdbwd": lambda i: fwdbwd(True)}
     res = {"thre": thre}
     a, b = fwd(True), fwd(False)
     res["rel_diff"] = float(((a - b).abs().max() / b.abs().max()).item())
@@ -105,8 +74,7 @@ def cell(posed, valids, thre, args):
     v = valids == 1
     res["pairs"] = {"valid": int(sum(int(n) * (int(n) - 1) // 2 for n in v.sum(1).tolist())),
                     "searched": int((flag > 0).sum().item()), "hinged": int((flag == 2).sum().item())}
-    for k, (med, wins) in alternate(arms, args.windows, args.calls).items():
-        res[f"ms_{k}"], res[f"ms_{k}_windows"] = med, wins
+    rig.report(res, rig.alternate(arms, args.calls, args.windows, 2), key="ms_{name}")
     res["peak_mb_composed"], res["peak_mb_fused"] = peak_mb(arms["composed_fwdbwd"]), peak_mb(arms["fused_fwdbwd"])
     res["fused_wins"] = bool(res["ms_fused_fwd"] <= res["ms_composed_fwd"] and res["ms_fused_fwdbwd"] <= res["ms_composed_fwdbwd"]
                              and res["peak_mb_fused"] < res["peak_mb_composed"])
@@ -128,8 +96,9 @@ def step_arms(batch, thre, args, dev):
             return Trainer(build_model(cfg).to(dev), cfg)
 
     plain, term = trainer(False), trainer(True)
-    arms = {"step": lambda: plain.train_step(batch), "step_with_term": lambda: term.train_step(batch)}
-    return {f"ms_{k}": v for k, v in alternate(arms, args.windows, max(args.calls, 10)).items()}
+    arms = {"step": lambda i: plain.train_step(batch), "step_with_term": lambda i: term.train_step(batch)}
+    timed = rig.alternate(arms, max(args.calls, 10), args.windows, 2)
+    return {f"ms_{k}": (round(med, 4), [round(t, 4) for t in ts]) for k, (med, ts) in timed.items()}  # a pair per arm
 
 
 def main(argv=None):
@@ -137,7 +106,7 @@ def main(argv=None):
     dev = torch.device("cuda:0")
     B, P, N = args.batch, args.parts, args.points
     result = {"B": B, "P": P, "N": N, "calls_per_window": args.calls, "windows": args.windows, "cells": {}}
-    parts = representative_parts(1234)
+    parts = rig.representative_parts(1234)
     parts = [min(P, parts[b % len(parts)]) for b in range(B)]
     batch = synthetic.make_batch(B, P, N, seed=1234, device=dev, num_parts=parts)
     pcs, valids = batch["part_pcs"], batch["part_valids"]
@@ -149,11 +118,7 @@ def main(argv=None):
     result["fused_wins_every_cell"] = all(c["fused_wins"] for c in result["cells"].values())
     if not args.no_step:
         result["step"] = step_arms(batch, float(args.thre[0]), args, dev)
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as fh:
-            fh.write(line + "\n")
+    rig.emit(result, args.out)
 
 
 if __name__ == "__main__":

@@ -10,16 +10,14 @@ from __future__ import annotations
 
 import argparse
 import gc
-import json
+import os
 import sys
 import time
-from pathlib import Path
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
+import torch
 
-import torch  # noqa: E402
-
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rate_rig as rig  # noqa: E402  (puts the repository root on sys.path)
 import bench  # noqa: E402
 from multi_part_assembly_amd.pn_transformer import build_model  # noqa: E402
 from multi_part_assembly_amd.trainer import Trainer  # noqa: E402
@@ -64,9 +62,9 @@ def main():
             ms, loss = run(rot_type, batches, args.steps, args.warmup, dev)
             best[rot_type] = min(best[rot_type], ms)
             losses[rot_type] = loss
-    print(json.dumps({"workload": "c2", "steps": args.steps, "warmup": args.warmup, "repeats": args.repeats,
-                      "quat_ms_per_step": best["quat"], "rmat_ms_per_step": best["rmat"],
-                      "rmat_over_quat": best["rmat"] / best["quat"], "final_loss": losses}))
+    rig.emit({"workload": "c2", "steps": args.steps, "warmup": args.warmup, "repeats": args.repeats,
+              "quat_ms_per_step": best["quat"], "rmat_ms_per_step": best["rmat"],
+              "rmat_over_quat": best["rmat"] / best["quat"], "final_loss": losses}, None)
 
 
 if __name__ == "__main__":

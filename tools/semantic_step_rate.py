@@ -13,16 +13,13 @@
 
 GPU only:  python tools/semantic_step_rate.py [--steps 10] [--windows 5] [--models global,dgl,rgl_net,c1] [--arms a,b,c]"""
 import argparse
-import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rate_rig as rig  # noqa: E402  (puts the repository root on sys.path)
 from multi_part_assembly_amd import config, synthetic  # noqa: E402
 from multi_part_assembly_amd.pn_transformer import build_model  # noqa: E402
 from multi_part_assembly_amd.trainer import Trainer  # noqa: E402
@@ -43,15 +40,6 @@ def make_arm(name, arm, dev, P):
     return Trainer(model, cfg, use_graph=arm == "c", graph_warmup=2)
 
 
-def window(trainer, batches, steps):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for i in range(steps):
-        trainer.train_step(batches[i % len(batches)], i)
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / steps
-
-
 def measure(name, dev, args):
     if name == "c1":
         B, P, N = 4, 2, 1000
@@ -63,23 +51,21 @@ def measure(name, dev, args):
         b.pop("num_parts", None)
     steps = args.steps * (8 if name == "c1" else 1)  # a window of a fraction of a second measures the clock
     trainers = {arm: make_arm(name, arm, dev, P) for arm in args.arms}
-    for tr in trainers.values():  # warm-up of every arm: first launches, allocator, the capture of arm c
-        window(tr, batches, 4)
-    times = {arm: [] for arm in trainers}
-    for _ in range(args.windows):
-        for arm, tr in trainers.items():
-            times[arm].append(window(tr, batches, steps))
+
+    def step(tr):
+        return lambda i: tr.train_step(batches[i % len(batches)], i)
+
+    # warm-up of every arm: first launches, allocator, the capture of arm c
+    timed = rig.alternate({arm: step(tr) for arm, tr in trainers.items()}, steps, args.windows, 4)
     out = {"B": B, "P": P, "N": N, "steps_per_window": steps,
            "valid_parts": int(sum(float(b["part_valids"].sum()) for b in batches) / len(batches)),
            "groups": int(sum(float(b["match_ids"].max(dim=1)[0].sum()) for b in batches) / len(batches))}
-    for arm, ts in times.items():
-        out[f"{arm}_ms"] = round(statistics.median(ts), 4)
-        out[f"{arm}_ms_windows"] = [round(t, 4) for t in ts]
+    rig.report(out, timed)
     if "c" in trainers:
         out["c_captured"] = trainers["c"]._graph is not None
-    if "a" in times:
-        out["spread_a"] = round(max(times["a"]) - min(times["a"]), 4)
-        if "b" in times:
+    if "a" in timed:
+        out["spread_a"] = round(max(timed["a"][1]) - min(timed["a"][1]), 4)
+        if "b" in timed:
             out["b_not_slower"] = out["b_ms"] <= out["a_ms"] + out["spread_a"]
     return out
 
@@ -92,13 +78,12 @@ def main():
     ap.add_argument("--arms", default="a,b,c")
     args = ap.parse_args()
     args.arms = [a for a in args.arms.split(",") if a]
-    if not torch.cuda.is_available():
-        raise SystemExit("semantic_step_rate: needs the GPU (a host timing says nothing about the step)")
+    rig.require_gpu("semantic_step_rate")
     dev = torch.device("cuda:0")
     result = {"windows": args.windows}
     for name in args.models.split(","):
         result[name] = measure(name, dev, args)
-    print(json.dumps(result))
+    rig.emit(result, None)
 
 
 if __name__ == "__main__":
