@@ -706,6 +706,26 @@ int mpa_ema_update(const float* param, float* ema, int64_t numel, const void* li
 int mpa_ema_swap(void* param, void* ema, int64_t param_bytes, void* live, void* ema_state, int64_t state_bytes,
                  void* stream);
 
+/* ---- Gradient accumulation (csrc/grad_accumulate.hip; opt-in) -------------------------------------------------
+ * One optimiser step over a WINDOW of several micro-batches, Lightning's `accumulate_grad_batches`.  The HIP backward
+ * kernels overwrite their slices of the flat gradient, so the window's sum is kept in a second flat buffer of the same
+ * length, the accumulator, by ONE streaming launch behind every micro-batch's backward:
+ *   mode 0 FIRST  acc[i]  = grad[i]            (a copy; the accumulator's old content is never read; 8 B per element)
+ *   mode 1 ADD    acc[i]  = acc[i] + grad[i]   (12 B)
+ *   mode 2 LAST   grad[i] = acc[i] + grad[i]   (12 B; the sum lands in the flat GRADIENT, so the all-reduce, mpa_guard_mark,
+ *                                               mpa_step_guard, the clipping, the Adam kernels, mpa_guard_commit and
+ *                                               mpa_ema_update run unchanged on the buffer they already know)
+ * A window of k >= 2 micro-batches is FIRST, ADD x (k - 2), LAST and leaves ((g0 + g1) + g2) + ... in `grad`; a window of
+ * one micro-batch needs no call.  The mean (1 / k, and 1 / world) is the optimiser's grad_scale.  Every addition is one
+ * rounded fp32 operation, denormals are kept, the buffer a mode does not write keeps its bytes.
+ *   `mode` is taken by value when `mode_dev` is NULL; otherwise the launch reads the int32 DEVICE word `mode_dev` (one
+ *   uniform load), so a launch captured in a graph follows the word on every replay; a word outside 0..2 writes nothing.
+ *   Grid: a float4 per lane, grid-stride, at most 2048 blocks of 256; no LDS, no scratch.  numel == 0: success, no launch.
+ *   MPA_EINVAL: numel < 0 or numel % 4, a NULL or not 16-byte aligned buffer when numel > 0, overlapping buffers, `mode`
+ *   outside 0..2 when mode_dev is NULL, a misaligned mode_dev.
+ * Restated in numpy by multi_part_assembly_amd/accum_ref.py. */
+int mpa_grad_accumulate(float* grad, float* acc, int64_t numel, int mode, const int32_t* mode_dev, void* stream);
+
 /* ---- GT <-> prediction matching of equivalent parts (semantic datasets) --------------------------------------
  * Replaces BaseModel._linear_sum_assignment / _match_parts (multi_part_assembly/models/modules/base_model.py:
  * 150-238: p x p Chamfer cost matrix on n = 100 sub-sampled points, scipy.optimize.linear_sum_assignment on the

@@ -118,6 +118,7 @@ SIGNATURES: dict[str, tuple] = {
     "mpa_guard_commit": (_INT, [_P, _P, _P, _I64, _P]),
     "mpa_ema_update": (_INT, [_P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _P, _F32, _INT, _P, _P]),
     "mpa_ema_swap": (_INT, [_P, _P, _I64, _P, _P, _I64, _P]),
+    "mpa_grad_accumulate": (_INT, [_P, _P, _I64, _INT, _P, _P]),
     "mpa_quat_to_rmat": (_INT, [_P, _I64, _P, _P]),
     "mpa_assembly_loss_forward_rmat": (_INT, [_P] * 6 + [_I64, _I64, _I64, _INT, _INT, _P, _P, _P, _P]),
     "mpa_assembly_loss_forward_rmat_timed": (_INT, [_P] * 6 + [_I64, _I64, _I64, _INT, _INT, _P, _P, _P, _P, _P]),

@@ -122,11 +122,19 @@ def fit(trainer, train_producer, sampler, val_batches=None, epochs=None, val_eve
     `skipped_in_a_row`, read in the SAME device read as the running loss; `skip_limit`: RuntimeError with the
     optimiser's `guard_report` text at a log read that finds `skipped_in_a_row >= skip_limit`.
 
+    With a trainer that accumulates (`Trainer(accumulate=K)`, K > 1) every `train_step` is a micro-batch: `log_every`,
+    `max_steps`, `step` and the sampler's position count micro-batches, `train/loss` stays the mean of the micro-batch
+    losses, and `skip_limit` counts optimiser steps in a row (the guard's own word).  The epoch's last batch is passed with
+    `close_window=True`, so no window spans two epochs and the learning rate of a step is one epoch's.  A run stopped by
+    `max_steps` inside a window writes the open window (`Trainer.state_dict` carries its sum) and the resumed run
+    continues it.
+
     `val_weights`: "live" or "ema" — which weights the validation passes (and so the `monitor` ranking) see; None means
     "ema" for a trainer that keeps a weight average (`Trainer(ema_decay=...)`) and "live" otherwise.  The record of an
     epoch that validated says which under "val/weights".  The checkpoints carry the average (`Trainer.state_dict`)."""
     guarded = bool(getattr(trainer, "guard_step", False))
     averaging = getattr(trainer, "average", None) is not None
+    windows = getattr(trainer, "accumulate", 1) > 1  # (a trainer that knows nothing of windows is called as before)
     if val_weights is None:
         val_weights = "ema" if averaging else "live"
     if val_weights not in ("live", "ema"):
@@ -194,7 +202,10 @@ def fit(trainer, train_producer, sampler, val_batches=None, epochs=None, val_eve
         for idx in sampler:
             static = trainer.static_batch if takes_out else None
             batch = train_producer.batch(idx, out=static) if static is not None else train_producer.batch(idx)
-            loss = trainer.train_step(batch)
+            if windows:  # no window spans two epochs: the epoch's last batch closes the one it is in
+                loss = trainer.train_step(batch, close_window=sampler.next_step >= len(sampler))
+            else:
+                loss = trainer.train_step(batch)
             trainer.check_health()
             if acc is None:
                 acc = loss.detach().clone()

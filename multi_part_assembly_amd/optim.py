@@ -257,6 +257,87 @@ class WeightAverage:
                 self._view(*slots[key]).copy_(state[key])
 
 
+class GradAccumulator:
+    """The sum of a window of micro-batch gradients beside the flat gradient (csrc/grad_accumulate.hip; Lightning's
+    `accumulate_grad_batches`): `acc`, a second flat buffer allocated here (before any capture), `mode_word`, the int32
+    device word a captured launch reads its mode from (written with `fill_`, as the learning rate is; `IDLE` = 3 writes
+    nothing), and `window`, the number of micro-batches the open window holds.  Behind the backward of every micro-batch
+    `launch_add(closing)` issues the package's one launch of mpa_grad_accumulate — FIRST, ADD, ..., LAST (`accum_ref.mode_at`),
+    none for a window that closes at its first micro-batch — and returns the window's size when it closed it, so the
+    flat gradient then holds the window's sum and the caller takes the step with `grad_scale = 1 / (world * size)`.
+    Device-agnostic like FlatBuffers: on host tensors `add` runs the restatement `accum_ref`."""
+
+    IDLE = 3
+
+    def __init__(self, flat):
+        self.flat = flat
+        self.acc = torch.zeros_like(flat.flat_grad)
+        self.mode_word = torch.full((1,), self.IDLE, dtype=torch.int32, device=flat.flat_grad.device)
+        self.window = 0
+
+    def _advance(self, closing):
+        from .accum_ref import mode_at
+        mode = mode_at(self.window, closing)
+        self.window += 1
+        size = self.window
+        if closing:
+            self.window = 0
+        return mode, (size if closing else None)
+
+    def launch(self, mode=None):
+        """mpa_grad_accumulate, wherever the tensors live: `mode` by value, or (None) from `mode_word`."""
+        _lib.launch("mpa_grad_accumulate", self.acc.device, self.flat.flat_grad, self.acc, self.flat.numel,
+                    0 if mode is None else int(mode), self.mode_word if mode is None else None)
+
+    def launch_add(self, closing):
+        """The micro-batch whose gradient the flat buffer holds joins the window (one launch, by value; none for a window
+        of one).  Returns the window's size if `closing`, else None."""
+        mode, size = self._advance(closing)
+        if mode is not None:
+            self.launch(mode)
+        return size
+
+    def write_mode(self, closing):
+        """`launch_add` for a captured launch: only the mode word is written (IDLE for a window of one); the replay of
+        the graph that holds `launch()` does the rest."""
+        mode, size = self._advance(closing)
+        self.mode_word.fill_(self.IDLE if mode is None else mode)
+        return size
+
+    def add(self, closing):
+        """`launch_add`; on host tensors its restatement."""
+        if self.acc.is_cuda:
+            return self.launch_add(closing)
+        from .accum_ref import accumulate
+        mode, size = self._advance(closing)
+        if mode is not None:
+            grad, acc = accumulate(mode, self.flat.flat_grad.detach().numpy(), self.acc.numpy())
+            self.flat.flat_grad.copy_(torch.from_numpy(grad))
+            self.acc.copy_(torch.from_numpy(acc))
+        return size
+
+    def drop(self):
+        """Forget the open window (its sum holds undefined gradients): the next micro-batch starts one with FIRST."""
+        self.window = 0
+
+    def state_dict(self, every):
+        return {"every": int(every), "window": self.window, "grad": self.acc.clone() if self.window else None}
+
+    def load_state_dict(self, state, every):
+        """A missing entry (None) means an empty window; an open window saved under another `every` is refused."""
+        window = int(state["window"]) if state is not None else 0
+        if window and int(state["every"]) != int(every):
+            raise RuntimeError(f"GradAccumulator.load_state_dict: the checkpoint holds an open window of {window} "
+                               f"micro-batches taken with accumulate = {state['every']}, this trainer has accumulate = "
+                               f"{every}; finish the window first or build the trainer with the checkpoint's value")
+        if window:
+            if window >= int(every) or state.get("grad") is None:
+                raise RuntimeError(f"GradAccumulator.load_state_dict: an open window of {window} micro-batches needs its "
+                                   f"sum and accumulate > {window}")
+            self.acc.copy_(state["grad"])
+        self.window = window
+
+
 def decay_mask_for(model, flat: "FlatBuffers"):
     """1/0 per element of the flat parameter buffer: the reference's AdamW parameter groups (utils/utils.py:90-125
     `filter_wd_parameters`) exempt every bias and the weights of normalisation layers from weight decay."""
@@ -281,6 +362,9 @@ class FusedAdam:
     neither eager steps nor HIP-graph replays upload per-step scalars from the host — a host that runs steps ahead
     of the GPU cannot corrupt a queued update.  Learning rate and grad_scale are written with `fill_` (the value
     travels as a kernel argument) only when they change.
+
+    `grad_scale`: what the flat gradient, a SUM, is multiplied by inside the update: 1 / world for the mean over the ranks,
+    1 / (world * k) behind a window of k accumulated micro-batches (`GradAccumulator`); it travels through `hyper[3]`.
 
     `decay_mask`: optional flat 1/0 tensor (see `decay_mask_for`).  `clip_grad`: global-norm clipping of the
     (mean) gradient, the reference's `gradient_clip_val` (scripts/train.py:90).

@@ -20,6 +20,11 @@ data on replay — what an earlier revision of this note blamed on a library GEM
 between replays is read from device memory that the host refreshes before each replay: the optimiser's step
 scalars (csrc/adam.hip keeps the step count on the device) and the dropout seeds (`advance_seed`).  The step is
 GPU-bound, so the replay is only ~2 % faster than eager launches; eager stays the default of bench.py.
+
+With `accumulate=K` > 1 (opt-in) a `train_step` is one micro-batch of a window of K: zero_grad, forward, backward and one
+launch that keeps the window's sum beside the flat gradient (csrc/grad_accumulate.hip); the call that closes the window runs
+the tail above once, on the mean.  Captured, that micro-step is ONE graph whatever K, and the tail follows it as eager
+launches; data parallel, only the closing call issues a collective, one for the whole flat gradient.
 """
 from __future__ import annotations
 
@@ -33,7 +38,7 @@ from . import _lib
 from . import gru as _gru
 from .gradsink import DeferredBackward, GradSink
 from .dp import BucketedGradReducer, broadcast_from_rank0, bucket_sizes_for, ordered_parameters
-from .optim import BufferSlab, FlatBuffers, FusedAdam, WeightAverage, cosine_warmup_lr, decay_mask_for
+from .optim import BufferSlab, FlatBuffers, FusedAdam, GradAccumulator, WeightAverage, cosine_warmup_lr, decay_mask_for
 
 
 def graph_refusal(model):
@@ -67,8 +72,23 @@ _SWAPPED = {"state_dict": " (inside averaged_weights()); \"model\" would hold th
 
 class Trainer:
     def __init__(self, model, cfg=None, process_group=None, use_graph=False, graph_warmup=3, guard_step=None,
-                 guard_buffers=None, ema_decay=None, ema_warmup=None):
-        """`ema_decay` (None: `cfg.optimizer.ema_decay`, off where the key is absent — no preset sets it) in [0, 1): an
+                 guard_buffers=None, ema_decay=None, ema_warmup=None, accumulate=None):
+        """`accumulate` (None: `cfg.optimizer.accumulate_grad_batches`, 1 where the key is absent — no preset sets it; an
+        integer >= 1): an optimiser step is taken over a WINDOW of that many micro-batches, Lightning's
+        `accumulate_grad_batches`.  `train_step` then runs one micro-batch per call — zero_grad, forward, backward, each
+        moving BatchNorm statistics, seed positions and draw counters as a step does — and one more launch behind its
+        backward (csrc/grad_accumulate.hip mpa_grad_accumulate, optim.GradAccumulator, `self.accumulator`) keeps the
+        window's sum in a second flat buffer; the call that closes the window (the K-th, or an earlier one given
+        `close_window=True`) leaves the sum in the flat gradient and runs the step's tail once: all-reduce, guard, update,
+        commit, average, on the MEAN over the micro-batches actually in the window and over the ranks
+        (`grad_scale = 1 / (world * k)`).  `self.window` is the number of micro-batches in the open window.  With 1 every
+        launch, collective and result is that of a trainer built without the argument.  The guard judges the window's
+        sum: one poisoned micro-batch skips the whole window, and with `guard_buffers` every buffer returns to its bits
+        from before the WINDOW (the commit runs at optimiser steps only).  Data parallel: a micro-batch that does not
+        close the window issues no collective, the closing one reduces the whole flat gradient in one blocking call (the
+        overlap of the bucket all-reduces with backward is given up, there are K times fewer collectives).
+
+        `ema_decay` (None: `cfg.optimizer.ema_decay`, off where the key is absent — no preset sets it) in [0, 1): an
         exponential moving average of the weights is kept on the device (optim.WeightAverage, `self.average`): one more
         launch (csrc/weight_average.hip mpa_ema_update) as the last of every optimiser step — eager, warm-up, captured
         and data-parallel steps alike — averages the flat parameters and every float32 buffer and copies the other
@@ -114,6 +134,14 @@ class Trainer:
         self.cfg = cfg
         opt = cfg.optimizer
         self.flat = FlatBuffers(ordered_parameters(model))
+        every = opt.get("accumulate_grad_batches", 1) if accumulate is None else accumulate
+        if isinstance(every, bool) or not isinstance(every, int) or every < 1:
+            raise ValueError("Trainer: accumulate (cfg.optimizer.accumulate_grad_batches) must be an integer >= 1, got "
+                             f"{every!r}")
+        self.accumulate = every
+        # the window's sum lives beside the flat gradient from now on: before any capture
+        self.accumulator = GradAccumulator(self.flat) if every > 1 else None
+        self.micro_batches = 0  # micro-batches this trainer has run (`optimizer.step_count` counts optimiser steps)
         self.guard_step = bool(opt.get("skip_nonfinite", False) if guard_step is None else guard_step)
         self.guard_buffers = bool(opt.get("skip_rollback_buffers", False) if guard_buffers is None else guard_buffers)
         if self.guard_buffers and not self.guard_step:
@@ -155,12 +183,15 @@ class Trainer:
         # eager: bucket hooks fire during backward; graph mode: the same two buckets, reduced between / behind the two
         # graphs (the reducer only provides the bucket slices there: its hooks are switched off)
         self.reducer = BucketedGradReducer(self.flat, bucket_sizes_for(model, self.flat), process_group)
-        if use_graph:
+        # accumulate > 1: no bucket hooks either — a micro-batch that does not close its window issues no collective, the
+        # closing one reduces the whole flat gradient behind the window's sum (`_reduce_grad`)
+        hooks = not use_graph and self.accumulate == 1
+        if not hooks:
             self.reducer.enabled = False
         elif self.guard_step and self.world > 1:
             self.reducer.before_reduce = self._mark_before_bucket
         self._graph_b = None
-        self.sink = GradSink(on_ready=self.reducer._on_grad if not use_graph and self.world > 1 else None)
+        self.sink = GradSink(on_ready=self.reducer._on_grad if hooks and self.world > 1 else None)
         # buffers the step allocates lazily (the GRU launches' status word + its pinned copy, the loss's side stream)
         # exist BEFORE a capture can see them: a pinned allocation is illegal under capture and a device word born there
         # would live in the graph's private pool
@@ -175,14 +206,26 @@ class Trainer:
         """RuntimeError if a cooperative launch of this step (csrc/gru.hip) gave up: its outputs, and every gradient
         behind them, are undefined.  Without `synchronize` the answer covers every launch whose status copy has already
         arrived (a plain read of pinned memory: this runs after every step and replay); with it — in front of
-        checkpoints and evaluation reports — every launch issued so far."""
+        checkpoints and evaluation reports — every launch issued so far.
+
+        A guarded trainer with an open window (`accumulate` > 1) does not look unless `synchronize`: the look clears the
+        status word as it reports, and the word has to stay raised until the guard gives the window's verdict."""
+        if self.guard_step and self.window > 0 and not synchronize:
+            return
         try:
             _gru.raise_if_failed(self.flat.flat_param.device, synchronize=synchronize)
         except RuntimeError:
             # sticky: raise_if_failed clears the status word as it reports, so a caller that catches this error and goes
             # on would otherwise get a clean bill of health — and a checkpoint — for parameters behind a failed launch
             self._failed = True
+            if self.accumulator is not None:  # the open window's sum holds undefined gradients: no later step applies it
+                self.accumulator.drop()
             raise
+
+    @property
+    def window(self):
+        """The number of micro-batches in the open window (0: the next `train_step` starts one)."""
+        return self.accumulator.window if self.accumulator is not None else 0
 
     # ---- guarded steps -------------------------------------------------------------------------------------------------
     def _health_and_step(self, step):
@@ -272,7 +315,19 @@ class Trainer:
         if self.average is not None:  # "model" loads into a model as it is (tools/evaluate.py --weights ema)
             state["ema"] = {"decay": self.average.decay, "warmup": self.average.warmup,
                             "model": self.average.averaged_state_dict(self.model)}
+        # the open window: a run stopped inside one continues with the sum of the micro-batches it has seen
+        state["accumulate"] = self.accumulator.state_dict(self.accumulate) if self.accumulator is not None else \
+            {"every": 1, "window": 0, "grad": None}
         return state
+
+    def _load_window(self, entry):
+        """Behind a load of the model: the checkpoint's open window (None: an empty one).  An open window saved under
+        another `accumulate` is a RuntimeError — its sum cannot be closed by this trainer's rule."""
+        if self.accumulator is not None:
+            self.accumulator.load_state_dict(entry, self.accumulate)
+        elif entry is not None and int(entry["window"]):
+            raise RuntimeError(f"Trainer.load_state_dict: the checkpoint holds an open window of {entry['window']} "
+                               f"micro-batches taken with accumulate = {entry['every']}, this trainer has accumulate = 1")
 
     def load_state_dict(self, state):
         """Inverse of `state_dict()`: model weights and buffers (copied in place: the parameters stay views of the flat
@@ -284,6 +339,7 @@ class Trainer:
         restored here because `train_step` rewrites it from the counter (`advance_seed`) in front of every replay, and a
         freshly built `use_graph=True` trainer starts with its eager warm-up steps, whose seeds travel by value."""
         self._refuse_swapped("load_state_dict")
+        self._load_window(state.get("accumulate"))  # (first: its refusal leaves the trainer as it was)
         if "state_dict" in state and "model" not in state:
             self.model.load_state_dict(state["state_dict"])
             self._refresh_buffer_shadow()
@@ -529,9 +585,81 @@ class Trainer:
         self.check_health()
         return self._static_loss
 
-    def train_step(self, data_dict, batch_idx=0):
-        """One optimiser step on this rank's shard; returns the (detached) scalar loss tensor."""
+    # ---- gradient accumulation ------------------------------------------------------------------------------------------
+    def _capture_micro(self, data_dict):
+        """The ONE graph of a captured trainer with `accumulate` > 1, whatever the window's length and position: zero_grad,
+        forward, backward and the accumulate launch reading its mode from the device word.  The tail stays outside, as the
+        data-parallel path keeps its optimiser step outside its graphs."""
+        if self.buffer_slab is not None:
+            self.buffer_slab.check()
+        acc = self.accumulator
+        acc.mode_word.fill_(acc.IDLE)
+        acc.launch()  # (writes nothing; the kernel's code object is loaded outside the capture whatever the warm-up ran)
+        self._static_batch = {k: v.clone() for k, v in self._tensor_items(data_dict).items()}
+        self._loss_buf = torch.zeros((), dtype=torch.float32, device=self.flat.flat_param.device)
+        self._graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._graph, capture_error_mode="thread_local"):
+            self._static_loss = self._fwd_bwd(self._static_batch, self._loss_buf)
+            acc.launch()
+
+    def _replay_micro(self, data_dict, closing):
+        if self._graph is None:
+            torch.cuda.synchronize()
+            self._capture_micro(data_dict)
+        for k, v in self._tensor_items(data_dict).items():
+            if v.data_ptr() != self._static_batch[k].data_ptr():
+                self._static_batch[k].copy_(v, non_blocking=True)
+        # the host writes the mode in front of the replay; a window of one micro-batch replays the launch idle (mode 3
+        # returns at its first load) rather than keeping a second graph without it
+        size = self.accumulator.write_mode(closing)
+        for mod in self.model.modules():
+            if hasattr(mod, "advance_seed"):
+                mod.advance_seed()
+        self._graph.replay()
+        return self._static_loss, size
+
+    def _micro_step(self, data_dict, batch_idx, close_window):
+        """One micro-batch of a trainer with `accumulate` > 1; the tail behind the one that closes the window."""
+        acc = self.accumulator
+        closing = bool(close_window) or acc.window + 1 >= self.accumulate
+        self.model.train()
+        try:
+            replay = self.use_graph and (self._graph is not None or self._eager_steps >= self.graph_warmup)
+            if replay:
+                loss, size = self._replay_micro(data_dict, closing)
+            else:
+                if self.use_graph:
+                    self._eager_steps += 1
+                    loss = self._fwd_bwd(self._tensor_items(data_dict))
+                else:
+                    loss = self._fwd_bwd(data_dict, batch_idx=batch_idx)
+                size = acc.launch_add(closing)
+            if not closing:
+                # unguarded: a launch that gave up is reported at its micro-batch, and `check_health` drops the window;
+                # guarded: the word stays raised for the window's verdict (`check_health` does not look meanwhile)
+                self.check_health()
+                return loss
+            # the flat gradient holds the window's sum: the tail of a step, on the mean over its micro-batches and the ranks
+            self.optimizer.grad_scale = 1.0 / (self.world * size)
+            self._reduce_grad()
+            self._health_and_step(self.optimizer.step)
+            if replay:
+                self.check_health()
+            return loss
+        except BaseException:
+            acc.drop()
+            raise
+
+    def train_step(self, data_dict, batch_idx=0, close_window=None):
+        """One optimiser step on this rank's shard; returns the (detached) scalar loss tensor.
+
+        With `accumulate` > 1: one MICRO-BATCH, whose loss is returned; the window closes, and the optimiser step is
+        taken, when it holds `accumulate` micro-batches or earlier with `close_window=True` (the epoch's last batch in
+        `fit`).  `close_window` means nothing to a trainer with `accumulate` = 1, whose every call is a step."""
         self._refuse_swapped("train_step")
+        self.micro_batches += 1
+        if self.accumulate > 1:
+            return self._micro_step(data_dict, batch_idx, close_window)
         if self.use_graph:
             return self._graph_step(data_dict)
         self.model.train()

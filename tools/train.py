@@ -5,6 +5,7 @@
   python tools/train.py --preset pn_transformer_everyday --skip-nonfinite --skip-limit 20 ...  (bad steps skipped on the device)
   python tools/train.py --preset pn_transformer_everyday --skip-nonfinite --rollback-buffers ...  (and their BatchNorm statistics undone)
   python tools/train.py --preset pn_transformer_everyday --ema DECAY [--no-ema-warmup] ...  (averaged weights kept, validated, saved)
+  python tools/train.py --preset pn_transformer_everyday --accumulate K ...         (one optimiser step per K batches, on their mean)
   python tools/train.py --preset pn_transformer_everyday --repulsion 0.01 1.0 ...   (the opt-in repulsion term: THRE W)
   python tools/train.py --preset lstm_everyday --lstm-draws device --graph ...      (B-LSTM captured: its draws on the device)
   python tools/train.py --preset dgl_partnet_chair --data-dir data/partnet --data-fn Chair.train.npy --val-fn Chair.val.npy
@@ -70,6 +71,10 @@ def parser():
     ap.add_argument("--no-ema-warmup", action="store_true",
                     help="with --ema: cfg.optimizer.ema_warmup = False, the decay is DECAY from the first step instead of "
                          "min(DECAY, (1 + t) / (10 + t))")
+    ap.add_argument("--accumulate", type=int, default=None, metavar="K",
+                    help="cfg.optimizer.accumulate_grad_batches: one optimiser step per K batches, on the mean of their "
+                         "gradients (BatchNorm statistics per batch, as K ranks would keep them); --batch-size, --log-every "
+                         "and --max-steps then count micro-batches, and an epoch's last window may be shorter")
     ap.add_argument("--seed", type=int, default=0)
     return ap
 
@@ -89,6 +94,8 @@ def parse_args(argv=None):
         ap.error("--ema DECAY must lie in [0, 1)")
     if args.no_ema_warmup and args.ema is None:
         ap.error("--no-ema-warmup needs --ema")
+    if args.accumulate is not None and args.accumulate < 1:
+        ap.error("--accumulate K must be at least 1")
     return args
 
 
@@ -161,6 +168,8 @@ def configure(args):
         cfg.optimizer.ema_decay = args.ema
         if args.no_ema_warmup:
             cfg.optimizer.ema_warmup = False
+    if args.accumulate is not None:
+        cfg.optimizer.accumulate_grad_batches = args.accumulate
     return cfg
 
 
@@ -207,7 +216,9 @@ def main(argv=None):
                           max_steps=args.max_steps if args.max_steps > 0 else None,
                           skip_limit=args.skip_limit if args.skip_limit > 0 else None)
     if rank == 0:
-        print(f"done: {len(history)} epochs in the history", flush=True)
+        steps = f"; {trainer.micro_batches} micro-batches in {trainer.optimizer.step_count} optimiser steps" \
+            if trainer.accumulate > 1 else ""
+        print(f"done: {len(history)} epochs in the history{steps}", flush=True)
     if world > 1:
         dist.destroy_process_group()
 
